@@ -6,6 +6,13 @@ A step = one ps_run over one batch of synthetic publishes of the workload
 topology already resident in HBM.  Prints ONE JSON line (rank 0).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the line's headline figure needs and no more: set-up,
+warm-up, the K timed steps, the outputs of the last timed step when
+--dump-outputs is given (psengine/dump.py), the line.  --full adds every other
+leg to the line: the roofline pass (instrumented steps), sustained throughput,
+the general path, the CPU baselines, and with N > 1 the other decompositions.
 
 N > 1 runs one process per GPU: under torch.distributed.run (WORLD_SIZE must
 equal --gpus), or, started without a launcher, bench.py starts that launcher
@@ -30,6 +37,7 @@ sys.path.insert(0, os.path.join(REPO, "go-libp2p-pubsub_amd"))
 
 import psengine as PE  # noqa: E402
 from psengine import workloads as WL  # noqa: E402
+from psengine.dump import dump_outputs  # noqa: E402
 
 METRIC = "deliveries/sec (peer×msg) at 1M peers, 1/2/4/8 GPU; % of HBM roofline"
 TRAFFIC_FILE = os.path.join(REPO, "profiles", "pmc_traffic.json")
@@ -320,6 +328,8 @@ def bench_cfg5(args):
     log(f"[bench] cfg5: {wl.n_peers} peers, {wl.topics[0].join_order.size} initial members, "
         f"setup {time.perf_counter() - t0:.1f}s")
 
+    pub = {}  # "first": id of the first message of the last batch published
+
     def churn(b):
         leave, join = plan[b]
         tc = time.perf_counter()
@@ -330,7 +340,7 @@ def bench_cfg5(args):
         tl = time.perf_counter()
         eng.join(0, join, check=False)
         tj = time.perf_counter()
-        eng.publish(wl.msg_topics)
+        pub["first"] = eng.publish(wl.msg_topics)
         return tl - tc, tj - tl
 
     def step(b):
@@ -365,14 +375,9 @@ def bench_cfg5(args):
     tot += st.deliveries
     run_gpu += st.run_ms
     wall = time.perf_counter() - t0
-    gpu_ms = []  # device span of the blocking instrumented batches (init start .. reduce end)
-
-    def blocking(it=iter(range(args.warmup + args.steps, args.warmup + args.steps + 3))):
-        st_b = step(next(it))[0]
-        gpu_ms.append(st_b.run_ms)
-        return st_b
-
-    per, st = instrumented(eng, blocking, 3)
+    if args.dump_outputs:
+        # the last timed batch: its counters and rows, and the tree its churn left
+        dump_outputs(args.dump_outputs, eng, st, pub["first"], wl.n_msgs, extra={"parents": eng.parents(0)})
     out = {
         "metric": METRIC + " [cfg5 end to end]",
         "value": tot / wall,
@@ -387,7 +392,6 @@ def bench_cfg5(args):
                                   "join_host": join_s * 1e3 / args.steps,
                                   "ps_run_async_host": run_host / args.steps,
                                   "ps_wait": wait_s * 1e3 / args.steps,
-                                  "ps_run_gpu": sum(gpu_ms) / len(gpu_ms),
                                   "window_span_pipelined": run_gpu / args.steps,
                                   "note": "ps_run_async_host = rebuild + plan + launch + lazy prune of the batch "
                                           "(host wall inside the call); its propagation overlaps the next "
@@ -396,11 +400,21 @@ def bench_cfg5(args):
                                           "window_span_pipelined = the same stamps in the timed pipelined "
                                           "batches, where a window's counter reduce rides in the next batch's "
                                           "first launch (after that batch's host churn)"},
-        "roofline": roofline_of(per),
-        "last_step": {"deliveries": st.deliveries, "rounds": st.rounds, "host_ms": st.host_ms,
-                      "run_ms": st.run_ms},
     }
-    if not args.no_cpu:
+    if args.full:
+        gpu_ms = []  # device span of the blocking instrumented batches (init start .. reduce end)
+
+        def blocking(it=iter(range(args.warmup + args.steps, args.warmup + args.steps + 3))):
+            st_b = step(next(it))[0]
+            gpu_ms.append(st_b.run_ms)
+            return st_b
+
+        per, st = instrumented(eng, blocking, 3)
+        out["breakdown_ms_per_step"]["ps_run_gpu"] = sum(gpu_ms) / len(gpu_ms)
+        out["roofline"] = roofline_of(per)
+    out["last_step"] = {"deliveries": st.deliveries, "rounds": st.rounds, "host_ms": st.host_ms,
+                        "run_ms": st.run_ms}
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline_cfg5(wl, plan, args.cpu_budget)
     print(json.dumps(out), flush=True)
     eng.close()
@@ -511,14 +525,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg3", choices=sorted(DESCR))
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debug)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (its counters, sampled "
+                         "delivered sets, the seen digest: psengine/dump.py) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the roofline pass (instrumented steps), sustained "
+                         "throughput, the general path, the CPU baselines, and with N > 1 the other "
+                         "decompositions; the --no-* options and --sustain choose among these legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-budget", type=float, default=10.0)
     ap.add_argument("--sustain", type=float, default=8.0,
-                    help="seconds of back-to-back pipelined steps after the timed region (one GPU; "
+                    help="--full: seconds of back-to-back pipelined steps after the timed region (one GPU; "
                          "reported under 'sustained', not in value); 0 skips")
     ap.add_argument("--no-check", action="store_true", help="skip delivery assertions (experiments)")
     ap.add_argument("--no-general", action="store_true",
-                    help="skip the general-path leg (staggered starts, compaction mode)")
+                    help="--full: skip the general-path leg (staggered starts, compaction mode)")
     ap.add_argument("--general-only", action="store_true",
                     help="run only the general-path leg and print it as the JSON line (its PMC passes)")
     ap.add_argument("--force-dist", action="store_true",
@@ -576,8 +597,10 @@ def main():
     log(f"[bench] {wl.name}: {wl.n_peers} peers, {len(wl.topics)} topics, {sum(sizes)} "
         f"subscriptions, {wl.n_msgs} msgs, setup {time.perf_counter() - t0:.1f}s")
 
+    pub = {}  # "first": id of the first message of the last batch published
+
     def step():
-        eng.publish(wl.msg_topics)
+        pub["first"] = eng.publish(wl.msg_topics)
         return eng.run()
 
     if args.general_only:
@@ -591,14 +614,14 @@ def main():
         batch's kernels run; every batch completes inside the call."""
         out = []
         if n:
-            eng.publish(wl.msg_topics)
+            pub["first"] = eng.publish(wl.msg_topics)
         for i in range(n):
             eng.run_async()
             # batch i + 1 published while batches i - 1 and i run, so the wait
             # below returns straight into its enqueue (cfg2 35.3 -> 34.9 us,
             # cfg3 0.870 -> 0.864 ms/step: profiles/r06/ab/publish_ahead.txt)
             if i + 1 < n:
-                eng.publish(wl.msg_topics)
+                pub["first"] = eng.publish(wl.msg_topics)
             if i:
                 out.append(eng.wait())
         if n:
@@ -617,10 +640,13 @@ def main():
     tot_deliv = sum(st.deliveries for st in sts)
     assert args.no_check or tot_deliv == deliv_expected * args.steps
     value = tot_deliv / wall
-    per, st = instrumented(eng, step, max(3, min(args.steps, 5)))
-    assert args.no_check or st.deliveries == deliv_expected
-    kernel = max(per, key=lambda k: (per[k][1], per[k][0]))
-    traffic, traffic_src = pmc_traffic(kernel, wl.name)
+    st = sts[-1]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, st, pub["first"], wl.n_msgs)
+    if args.full:
+        # (the last instrumented step stands for the last step in the line below)
+        per, st = instrumented(eng, step, max(3, min(args.steps, 5)))
+        assert args.no_check or st.deliveries == deliv_expected
     pair_gbs = value * PAIR_BYTES / 1e9
     out = {
         "metric": METRIC,
@@ -641,7 +667,6 @@ def main():
                    "parallelism": "1 GPU",
                    "steps_issue": "blocking ps_run" if args.sync else
                    "pipelined ps_run_async/ps_wait (<= 2 batches in flight)"},
-        "roofline": roofline_of(per, traffic, traffic_src),
         # SURVEY.md §8d's (peer,msg)-pair formulation: the HBM rate a pair-frontier
         # engine would need for this delivery rate.  A model figure, NOT bandwidth
         # this engine moves; compare roofline.frac, not this, with the peak.
@@ -655,16 +680,19 @@ def main():
                  "prefix_rounds": st.prefix_rounds, "flood_rounds": st.flood_rounds,
                  "overlapped_windows_timed": overlapped_timed},
         "last_step": {"rounds": st.rounds, "windows": st.windows, "flood_rounds": st.flood_rounds,
-                      "run_ms": st.run_ms,
-                      "expand_ms": st.expand_ms, "host_ms": st.host_ms,
+                      "run_ms": st.run_ms, "host_ms": st.host_ms,
                       "edge_words": st.edge_words,
                       "frontier_per_round": st.as_dict()["frontier_per_round"],
                       "deliveries_per_round": st.as_dict()["deliveries_per_round"],
-                      "mbytes_per_round": [round(x / 1e6, 1) for x in st.as_dict()["expand_bytes_per_round"]],
-                      "expand_us_per_round": [round(x * 1e3, 1) for x in
-                                              st.as_dict()["expand_ms_per_round"]]},
+                      "mbytes_per_round": [round(x / 1e6, 1) for x in st.as_dict()["expand_bytes_per_round"]]},
     }
-    if args.sustain > 0:
+    if args.full:
+        # per-kernel device times, from the instrumented steps
+        kernel = max(per, key=lambda k: (per[k][1], per[k][0]))
+        out["roofline"] = roofline_of(per, *pmc_traffic(kernel, wl.name))
+        out["last_step"]["expand_ms"] = st.expand_ms
+        out["last_step"]["expand_us_per_round"] = [round(x * 1e3, 1) for x in st.as_dict()["expand_ms_per_round"]]
+    if args.full and args.sustain > 0:
         # the same pipelined steps back to back for a few seconds after the
         # timed region: sustained throughput, and device activity long enough
         # for a utilisation sampler polling every few seconds to see
@@ -677,9 +705,9 @@ def main():
         assert args.no_check or deliv_sus == deliv_expected * n_sus
         out["sustained"] = {"value": deliv_sus / wall_sus, "unit": "deliveries/s", "steps": n_sus,
                             "seconds": wall_sus, "ms_per_step": wall_sus * 1e3 / n_sus}
-    if not args.no_general and not args.no_check:
+    if args.full and not args.no_general and not args.no_check:
         out["general_path"] = general_path(eng, wl, deliv_expected, max(20, min(args.steps, 100)))
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(eng, wl, sizes, args.cpu_budget, deliv_expected)
     print(json.dumps(out), flush=True)
     eng.close()

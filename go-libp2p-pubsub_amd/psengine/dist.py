@@ -17,7 +17,8 @@ workload: the same topology, N x the messages (each rank holds 1/N of every
 tree, so it moves as many row words as one GPU does at N=1); "strong" runs
 the N=1 workload unchanged.
 
-Beside the partitioned run (the JSON line's value), two legs time SURVEY.md
+Beside the partitioned run (the JSON line's value), bench.py --full adds the
+roofline pass and two legs that time SURVEY.md
 §8e's other decompositions on the same ranks: the other partition
 (`subtree_partition` beside the peer-hash headline: cross edges only above
 level L, so almost no exchange) and `message_sharded`: every rank holds the
@@ -34,6 +35,7 @@ import time
 
 from . import MODE_KERNEL, PART_PEER, PART_SUBTREE, Engine, device_count, ipc_group_id, load, unique_id
 from . import workloads as WL
+from .dump import dump_outputs
 
 
 def env_ranks():
@@ -137,8 +139,10 @@ def bench_main(args, descr: dict, metric: str):
     tdev = None
     part = PART_SUBTREE if getattr(args, "partition", "peer") == "subtree" else PART_PEER
     ipc_mode = getattr(args, "ipc_mode", "inplace")
-    out = partitioned(args, dist, dev, rank, world, descr, metric, part, transport, ipc_mode, tdev)
-    if shared and world > 1:
+    full = getattr(args, "full", False)  # bench.py --full: the legs beside the headline run
+    out = partitioned(args, dist, dev, rank, world, descr, metric, part, transport, ipc_mode, tdev,
+                      dump=getattr(args, "dump_outputs", None))
+    if full and shared and world > 1:
         # N ranks sharing one GPU against one rank doing the same N x messages
         # alone: the cost of the partition and its exchange on one device
         one = one_rank_reference(args, dev, world) if rank == 0 else None
@@ -148,7 +152,7 @@ def bench_main(args, descr: dict, metric: str):
                                  "note": f"{world} processes on one GPU, each owning 1/{world} of every tree, "
                                          f"against one engine disseminating the same {world} x messages alone"}
         dist.barrier()
-    if world > 1 and not shared and transport == "rccl" and getattr(args, "ipc_leg", False):
+    if full and world > 1 and not shared and transport == "rccl" and getattr(args, "ipc_leg", False):
         # the same partition with the owners' rows read in place over xGMI peer
         # mappings (IPC transport, PS_DIST_F_INPLACE): no records shipped
         # (opt-in: never run across separate GPUs on this pool's one-GPU boxes)
@@ -160,7 +164,7 @@ def bench_main(args, descr: dict, metric: str):
             print(f"[bench] rank {rank}: ipc_in_place leg failed: {exc!r}", file=sys.stderr, flush=True)
             if rank == 0:
                 out["ipc_in_place"] = {"error": repr(exc)}
-    if world > 1 and not shared and not getattr(args, "no_message_leg", False):
+    if full and world > 1 and not shared and not getattr(args, "no_message_leg", False):
         # the decompositions SURVEY.md §8e allows beside the mandated peer hash,
         # on the same ranks: level-L subtrees (cross edges only above level L)
         # and message sharding (replicated topology, no exchange)
@@ -193,14 +197,16 @@ def bench_main(args, descr: dict, metric: str):
 
 
 def partitioned(args, dist, dev, rank: int, world: int, descr: dict, metric: str, part: int,
-                transport: str = "rccl", ipc_mode: str = "inplace", tdev=None):
+                transport: str = "rccl", ipc_mode: str = "inplace", tdev=None, dump=None):
     """The node-partitioned run: every rank owns a hash (PART_PEER) or
     subtree (PART_SUBTREE) share of every tree; the frontier rows that cross
     ranks are exchanged each round over the engine's RCCL communicator, or
     (transport "ipc", one process per rank on one node) read through IPC
     mappings of the other ranks' buffers: the owners' rows in place
     (ipc_mode "inplace"), the senders' records in place ("zc") or copied
-    ("copy").  Returns the bench JSON object on rank 0 (None elsewhere)."""
+    ("copy").  Returns the bench JSON object on rank 0 (None elsewhere).
+    dump: a directory for the outputs of the last timed step, each rank its
+    own nodes' share (psengine/dump.py, names ending in _rank<r>)."""
     local = int(dev)
     wl = workload(args, world)
     scaling = getattr(args, "scaling", "weak") if world > 1 else "weak"
@@ -219,8 +225,10 @@ def partitioned(args, dist, dev, rank: int, world: int, descr: dict, metric: str
         print(f"[bench] {wl.name} on {world} GPUs ({pname} partition), setup {time.perf_counter() - t0:.1f}s",
               file=sys.stderr, flush=True)
 
+    pub = {}  # "first": id of the first message of the last batch published
+
     def step():
-        eng.publish(wl.msg_topics)
+        pub["first"] = eng.publish(wl.msg_topics)
         return eng.run()
 
     for _ in range(args.warmup):
@@ -239,33 +247,36 @@ def partitioned(args, dist, dev, rank: int, world: int, descr: dict, metric: str
         # pipelined like bench.py: batch k + 1 is published and enqueued (its
         # RCCL exchanges included, stream-ordered) while batch k runs
         for i in range(args.steps):
-            eng.publish(wl.msg_topics)
+            pub["first"] = eng.publish(wl.msg_topics)
             eng.run_async()
             if i:
                 local_deliv += eng.wait().deliveries
         if args.steps:
-            local_deliv += eng.wait().deliveries
+            st = eng.wait()
+            local_deliv += st.deliveries
     dist.barrier()
     elapsed = time.perf_counter() - t0
     wall, total = job_totals(dist, elapsed, local_deliv, tdev)
-    # roofline pass: HIP events around every hot-kernel launch (untimed above)
-    eng.set_time_kernels(True)
-    bytes_, exp_ms, launches = 0, 0.0, 0
-    for _ in range(3):
-        st = step()
-        bytes_ += st.expand_bytes
-        exp_ms += st.expand_ms
-        launches += st.expand_launches
-    eng.set_time_kernels(False)
-    _, tot_bytes = job_totals(dist, 0.0, bytes_, tdev)
-    slow_exp_ms, _ = job_totals(dist, exp_ms, 0, tdev)
+    if dump and args.steps:
+        dump_outputs(dump, eng, st, pub["first"], wl.n_msgs, suffix=f"_rank{rank}", ranks=world)
+    full = getattr(args, "full", False)
+    if full:
+        # roofline pass: HIP events around every hot-kernel launch (untimed above)
+        eng.set_time_kernels(True)
+        bytes_, exp_ms, launches = 0, 0.0, 0
+        for _ in range(3):
+            st = step()
+            bytes_ += st.expand_bytes
+            exp_ms += st.expand_ms
+            launches += st.expand_launches
+        eng.set_time_kernels(False)
+        _, tot_bytes = job_totals(dist, 0.0, bytes_, tdev)
+        slow_exp_ms, _ = job_totals(dist, exp_ms, 0, tdev)
     if not args.no_check:
         assert total == expected * args.steps, (total, expected * args.steps)
     out = None
     if rank == 0:
         value = total / wall
-        # per GPU: the job's expand bytes over the slowest rank's expand time / N
-        achieved = tot_bytes / max(1e-12, slow_exp_ms * 1e-3) / 1e9 / world
         out = {
             "metric": metric,
             "value": value,
@@ -287,10 +298,6 @@ def partitioned(args, dist, dev, rank: int, world: int, descr: dict, metric: str
                            f"IPC transport ({ipc_mode}: "
                            + {"inplace": "owners' rows read in place", "zc": "senders' records read in place",
                               "copy": "records copied"}[ipc_mode] + "), device-flag ordered rounds")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": None,
-                         "kernel": MODE_KERNEL.get(st.expand_mode, "k_expand"),
-                         "note": "per-GPU: job expand bytes / slowest rank's expand time / N"},
             "last_step_rank0": {"rounds": st.rounds, "run_ms": st.run_ms,
                                 "expand_ms": st.expand_ms, "host_ms": st.host_ms,
                                 "xchg_path": {0: "none", 1: "zero-copy", 2: "copy", 3: "in-place"}.get(int(st.xchg_path)),
@@ -298,6 +305,13 @@ def partitioned(args, dist, dev, rank: int, world: int, descr: dict, metric: str
                                 "max_rounds_per_launch": st.plan_max_rounds},
             "plan_opts": eng.plan_opts(),
         }
+        if full:
+            # per GPU: the job's expand bytes over the slowest rank's expand time / N
+            achieved = tot_bytes / max(1e-12, slow_exp_ms * 1e-3) / 1e9 / world
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                               "frac": achieved / 8000.0, "traffic": None,
+                               "kernel": MODE_KERNEL.get(st.expand_mode, "k_expand"),
+                               "note": "per-GPU: job expand bytes / slowest rank's expand time / N"}
     eng.close()
     return out
 

@@ -70,6 +70,68 @@ def test_pmc_traffic_matches_kernel_and_workload():
         assert bench.pmc_traffic(x["kernel"], x["workload"] + "_other")[0] is None
 
 
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs draws the same messages and peers on every run, and the
+    sampled delivered sets stay under 48 MB as float32 at any workload size."""
+    import numpy as np
+    from psengine import dump as D
+
+    for n_msgs, n_peers in ((100_000, 1_000_000), (1000, 1 << 24), (3, 16)):
+        m1, p1 = D.sample(n_msgs, n_peers)
+        m2, p2 = D.sample(n_msgs, n_peers)
+        assert np.array_equal(m1, m2) and m1.shape[0] == min(D.SAMPLE_MSGS, n_msgs)
+        assert np.unique(m1).shape == m1.shape and m1.max() < n_msgs
+        if n_peers <= D.SAMPLE_PEERS:
+            assert p1 is None and p2 is None
+        else:
+            assert np.array_equal(p1, p2) and p1.shape[0] == D.SAMPLE_PEERS and p1.max() < n_peers
+        width = n_peers if p1 is None else p1.shape[0]
+        assert m1.shape[0] * width * 4 <= 48_000_000
+    # the ranks of a multi-process run share the budget, and draw alike
+    m4, p4 = D.sample(100_000, 1_000_000, ranks=4)
+    assert p4.shape[0] == D.SAMPLE_PEERS // 4 and np.array_equal(m4, D.sample(100_000, 1_000_000)[0])
+
+
+def test_dump_outputs_files(tmp_path):
+    """dump_outputs on a stand-in engine: float arrays named as documented,
+    the digest exact in its 16-bit limbs, a message of an earlier window
+    marked -1, the caller's extra arrays and the rank suffix kept."""
+    import numpy as np
+    from psengine import dump as D
+
+    n = 100
+
+    class Eng:
+        n_peers = n
+
+        def seen_digest(self):
+            return 0xFEDCBA9876543210
+
+        def delivered(self, msg):
+            if msg == 1000 + int(D.sample(20, n)[0][0]):
+                raise PE.EngineError(-8, "message not in the last window")
+            return (np.arange(n) % 3 == msg % 3).astype(np.uint8)
+
+    st = PE.Stats()
+    st.deliveries, st.duplicates, st.rounds, st.windows = 1234, 0, 3, 1
+    st.deliveries_per_round[1], st.deliveries_per_round[2], st.deliveries_per_round[3] = 1000, 200, 34
+    D.dump_outputs(str(tmp_path), Eng(), st, 1000, 20, suffix="_rank1", extra={"parents": np.arange(n)})
+    got = {f: np.load(tmp_path / f) for f in bench.os.listdir(tmp_path)}
+    assert set(got) == {k + "_rank1.npy" for k in (
+        "counters", "deliveries_per_round", "frontier_per_round", "seen_digest", "sample_messages",
+        "sample_peers", "delivered_sample", "delivered_counts", "parents")}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["counters_rank1.npy"].tolist() == [1234, 0, 3, 1]
+    assert got["deliveries_per_round_rank1.npy"][:5].tolist() == [0, 1000, 200, 34, 0]
+    assert sum(int(x) << (16 * i) for i, x in enumerate(got["seen_digest_rank1.npy"])) == 0xFEDCBA9876543210
+    msgs = got["sample_messages_rank1.npy"].astype(int)
+    deliv = got["delivered_sample_rank1.npy"]
+    assert deliv.shape == (8, n) and (deliv[0] == -1).all() and got["delivered_counts_rank1.npy"][0] == -1
+    for k in range(1, 8):
+        assert np.array_equal(deliv[k], (np.arange(n) % 3 == (1000 + msgs[k]) % 3).astype(np.float32))
+        assert got["delivered_counts_rank1.npy"][k] == deliv[k].sum()
+
+
 def _args(**kw):
     base = dict(gpus=1, workload="cfg3")
     base.update(kw)

@@ -166,7 +166,7 @@ def test_bench_two_processes_on_one_gpu():
         pytest.skip("every rank has a GPU of its own: bench.py takes RCCL")
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--workload", "cfg4", "--scale", "0.05",
-           "--steps", "3", "--warmup", "1", "--no-cpu"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-cpu"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=150, cwd=repo)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

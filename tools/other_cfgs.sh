@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 for W in cfg4 cfg5; do
   echo "[other_cfgs] $W $(date +%T)"
-  timeout -k 10 400 python -u bench.py --workload $W --steps 10 --warmup 2 > "$OUT/bench_$W.json" 2> "$OUT/bench_$W.err"
+  timeout -k 10 400 python -u bench.py --full --workload $W --steps 10 --warmup 2 > "$OUT/bench_$W.json" 2> "$OUT/bench_$W.err"
   cut -c1-300 "$OUT/bench_$W.json"
 done
 echo "[other_cfgs] loopback $(date +%T)"
@@ -19,6 +19,6 @@ cd /tmp && export TMPDIR=/tmp
 for W in cfg4 cfg5; do
   echo "[other_cfgs] trace $W $(date +%T)"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace_$W" -o run -- \
-    python3 "$ROOT/bench.py" --workload $W --steps 5 --warmup 1 --no-cpu > "$OUT/bench_trace_$W.json" 2> "$OUT/bench_trace_$W.err"
+    python3 "$ROOT/bench.py" --full --workload $W --steps 5 --warmup 1 --no-cpu > "$OUT/bench_trace_$W.json" 2> "$OUT/bench_trace_$W.err"
 done
 echo "[other_cfgs] done $(date +%T)"

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/pmc_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-ARGS=("$@"); [ ${#ARGS[@]} -eq 0 ] && ARGS=(--steps 1 --warmup 1 --no-cpu)
+ARGS=("$@"); [ ${#ARGS[@]} -eq 0 ] && ARGS=(--full --steps 1 --warmup 1 --no-cpu)
 run() { name=$1; shift
   timeout -s KILL 180 rocprofv3 --pmc "$@" -T -f csv -d "$OUT/$name" -o run -- \
     python3 "$ROOT/bench.py" "${ARGS[@]}" > "$OUT/$name.json" 2> "$OUT/$name.err"
