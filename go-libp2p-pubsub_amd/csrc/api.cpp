@@ -179,8 +179,12 @@ static void read_switches(ps_engine* e) {
   if (const char* v = std::getenv("PSAMD_HOST_TIMING")) e->host_timing = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_FLOOD_PROFILE")) e->flood_profile = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_CHAIN_PROFILE")) e->chain_prof_path = v;
+  if (const char* v = std::getenv("PSAMD_DRAIN_TIMING")) e->drain.timing = std::atoi(v) != 0;
   const char* ab = std::getenv("PSAMD_AB");
   if (!ab || std::atoi(ab) == 0) return;
+  if (const char* v = std::getenv("PSAMD_DRAIN_SLAB_IDS"))  // (a slab holds at least one segment)
+    e->drain.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
+  if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.staged = std::strcmp(v, "direct") != 0;
   if (const char* v = std::getenv("PSAMD_TWIN")) e->twin_on = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_NARROW")) e->expand_opts = std::atoi(v) == 0 ? kExpandNoNarrow : 0u;
   if (const char* v = std::getenv("PSAMD_CHAIN_WORDS_LEAD"))
@@ -331,6 +335,12 @@ void ps_destroy(ps_engine* e) {
   if (e->rstream) (void)hipStreamSynchronize(e->rstream);
   if (e->qstream) (void)hipStreamSynchronize(e->qstream);
   if (e->tstream) (void)hipStreamSynchronize(e->tstream);
+  if (e->drain.copy_stream) {
+    (void)hipStreamSynchronize(e->drain.copy_stream);
+    (void)hipStreamDestroy(e->drain.copy_stream);
+  }
+  for (hipEvent_t ev : {e->drain.ev_emit[0], e->drain.ev_emit[1], e->drain.ev_copy[0], e->drain.ev_copy[1], e->drain.ev_t[0], e->drain.ev_t[1]})
+    if (ev) (void)hipEventDestroy(ev);
   for (auto ev : e->ev_k) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {e->ev_run0, e->ev_run1, e->ev_round, e->ev_xchg, e->ev_gate[0], e->ev_gate[1], e->ev_pre, e->ev_end,
                       e->ev_tend, e->ev_e2t})
@@ -689,6 +699,254 @@ int ps_read_peer_messages(ps_engine* e, uint32_t topic, uint32_t peer, uint32_t*
   *n_out = got.size();
   if (got.size() > cap) return e->fail(PS_E_RANGE, "output buffer too small");
   for (size_t k = 0; k < got.size(); ++k) msg_out[k] = got[k].second;
+  return PS_OK;
+}
+
+// ---- ps_drain: the batched drain (drain.hip) -----------------
+
+// The last window's drain tables, once per window.  A topic's window messages
+// by row bit: where (start round, publish order) ascends with the bit -- every
+// tree layout (plan_window_layout sorts the bits so) -- the id table is indexed
+// by bit and a mask marks the message bits; else (a mesh window with several
+// start rounds) the ids are stored in arrival order beside each one's bit.
+static int drain_tables(ps_engine* e) {
+  auto& D = e->drain;
+  if (D.seq == e->window_seq) return PS_OK;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  struct Ent {
+    uint64_t key;  // start round << 32 | message index: arrival order
+    uint32_t b, id;
+  };
+  std::vector<std::vector<Ent>> per(nt);
+  for (uint32_t i = 0; i < e->last_n; ++i) {
+    const uint32_t t = e->last_msgs[i].topic;
+    if (t >= nt || !e->last_topics[t].W || !e->last_cnt[t]) continue;
+    const uint32_t r = e->run_rank[i], lo = e->last_lo[t];
+    if (r < lo || r >= lo + e->last_cnt[t]) continue;
+    const uint32_t li = r - lo;
+    const uint32_t b = t < e->last_pos.size() && !e->last_pos[t].empty() ? e->last_pos[t][li] : li;
+    per[t].push_back({(static_cast<uint64_t>(e->last_msgs[i].start) << 32) | i, b, e->last_first + i});
+  }
+  std::vector<uint32_t> ids, order;
+  std::vector<uint64_t> mask;
+  std::vector<DrainGroup> groups;
+  D.topics.assign(nt, DrainTopic{});
+  for (uint32_t t = 0; t < nt; ++t) {
+    auto& P = per[t];
+    if (P.empty()) continue;
+    const TopicDev& d = e->last_topics[t];
+    DrainTopic& T = D.topics[t];
+    T.wbase = d.wbase;
+    T.nbase = d.nbase;
+    T.n_nodes = d.n_nodes;
+    T.W = d.W;
+    T.flags = d.flags & (kTopicMesh | kTopicGroups);
+    if (d.flags & kTopicGroups) {
+      T.group_lo = static_cast<uint32_t>(groups.size());
+      for (const StartGroup& g : e->last_groups[t]) groups.push_back({g.w0, g.wn});
+      T.group_n = static_cast<uint32_t>(groups.size()) - T.group_lo;
+    }
+    std::sort(P.begin(), P.end(), [](const Ent& x, const Ent& y) { return x.b < y.b; });
+    bool ordered = true;
+    for (size_t k = 1; k < P.size(); ++k) {
+      if (P[k].b == P[k - 1].b) return e->fail(PS_E_STATE, "two window messages share a row bit");
+      ordered &= P[k].key > P[k - 1].key;
+    }
+    if ((P.back().b >> 6) >= d.W) return e->fail(PS_E_STATE, "window message bit past the row");
+    T.tab0 = ids.size();
+    if (ordered) {
+      const uint32_t words = (P.back().b >> 6) + 1;
+      T.n_pos = words * 64;
+      T.aux0 = mask.size();
+      ids.resize(ids.size() + T.n_pos, kNone);
+      mask.resize(mask.size() + words, 0);
+      for (const Ent& x : P) {
+        ids[T.tab0 + x.b] = x.id;
+        mask[T.aux0 + (x.b >> 6)] |= 1ull << (x.b & 63);
+      }
+    } else {
+      std::sort(P.begin(), P.end(), [](const Ent& x, const Ent& y) { return x.key < y.key; });
+      T.flags |= kDrainGather;
+      T.n_pos = static_cast<uint32_t>(P.size());
+      T.aux0 = order.size();
+      for (const Ent& x : P) {
+        ids.push_back(x.id);
+        order.push_back(x.b);
+      }
+    }
+  }
+  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
+    hipError_t rc = buf.ensure(bytes);
+    if (rc == hipSuccess && bytes) rc = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, e->stream);
+    return rc;
+  };
+  HIP_TRY(up(D.d_topics, D.topics.data(), D.topics.size() * sizeof(DrainTopic)), "drain topics");
+  HIP_TRY(up(D.d_groups, groups.data(), groups.size() * sizeof(DrainGroup)), "drain groups");
+  HIP_TRY(up(D.d_ids, ids.data(), ids.size() * 4), "drain ids");
+  HIP_TRY(up(D.d_mask, mask.data(), mask.size() * 8), "drain masks");
+  HIP_TRY(up(D.d_order, order.data(), order.size() * 4), "drain order");
+  HIP_TRY(hipStreamSynchronize(e->stream), "sync");  // (the tables above leave scope)
+  D.seq = e->window_seq;
+  return PS_OK;
+}
+
+// topic -> peer -> node of the current node space (as ps_read_peer_messages builds it)
+static const std::vector<uint32_t>& drain_peer_map(ps_engine* e, uint32_t topic, const TopicDev& d) {
+  auto& pm = e->peer_node[topic];
+  if (e->peer_node_epoch.size() != e->topics.size()) e->peer_node_epoch.assign(e->topics.size(), ~0ull);
+  if (e->peer_node_epoch[topic] != e->graph_epoch) {
+    pm.assign(e->cfg.n_peers, kNone);
+    const uint32_t u0 = (d.flags & kTopicRootLocal) ? 1 : 0;
+    for (uint32_t k = u0; k < d.n_nodes; ++k) pm[e->node_peer[d.nbase + k]] = k;
+    e->peer_node_epoch[topic] = e->graph_epoch;
+  }
+  return pm;
+}
+
+static int drain_streams(ps_engine* e) {
+  auto& D = e->drain;
+  if (D.copy_stream) return PS_OK;
+  for (auto& ev : D.ev_emit) HIP_TRY(hipEventCreateWithFlags(&ev, kStreamEvent), "drain event");
+  for (auto& ev : D.ev_copy) HIP_TRY(hipEventCreateWithFlags(&ev, kStreamEvent), "drain event");
+  for (auto& ev : D.ev_t) HIP_TRY(hipEventCreate(&ev), "drain event");
+  HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking), "drain copy stream");
+  return PS_OK;
+}
+
+int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint64_t* off_out, uint32_t* msg_out,
+             size_t cap, uint64_t* total_out) {
+  if (!e || !off_out || !total_out || (n && (!topic || !peer)) || (cap && !msg_out)) return PS_E_INVAL;
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
+  if (const int rj = twin_join(e)) return rj;
+  for (size_t q = 0; q < n; ++q)
+    if (topic[q] >= e->topics.size() || peer[q] >= e->cfg.n_peers) return e->fail(PS_E_RANGE, "topic or peer out of range");
+  off_out[0] = 0;
+  *total_out = 0;
+  if (n == 0) return PS_OK;
+  if (n >= 0xFFFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  auto& D = e->drain;
+  int rc = ensure_mirrors(e);
+  if (!rc) rc = drain_tables(e);
+  if (!rc) rc = drain_streams(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+
+  // queries -> (topic, node, first segment); an empty answer has no segment
+  D.queries.resize(n);
+  uint64_t n_segs64 = 0;
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t t = topic[q];
+    const DrainTopic& T = D.topics[t];
+    DrainQuery& Q = D.queries[q];
+    Q = DrainQuery{t, 0, static_cast<uint32_t>(n_segs64), 0};
+    if (!T.n_pos) continue;  // idle in the window
+    const uint32_t u = drain_peer_map(e, t, e->last_topics[t])[peer[q]];
+    if (u == kNone) continue;  // the root, not subscribed, or another rank's
+    Q.node = u;
+    n_segs64 += ceil_div(T.n_pos, kDrainSegBits);
+    if (n_segs64 >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  }
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  D.off.assign(static_cast<size_t>(n_segs) + 1, 0);
+  float ms[4] = {0, 0, 0, 0};  // count, scan, emit, copy (PSAMD_DRAIN_TIMING)
+  auto t_begin = [&]() { return D.timing ? hipEventRecord(D.ev_t[0], s) : hipSuccess; };
+  auto t_end = [&](int k) -> hipError_t {
+    if (!D.timing) return hipSuccess;
+    hipError_t r = hipEventRecord(D.ev_t[1], s);
+    if (r == hipSuccess) r = hipEventSynchronize(D.ev_t[1]);
+    float t = 0;
+    if (r == hipSuccess) r = hipEventElapsedTime(&t, D.ev_t[0], D.ev_t[1]);
+    ms[k] += t;
+    return r;
+  };
+  DrainArgs a{};
+  if (n_segs) {
+    HIP_TRY(D.d_queries.ensure(n * sizeof(DrainQuery)), "alloc drain queries");
+    HIP_TRY(D.d_cnt.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain counts");
+    HIP_TRY(D.d_off.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain offsets");
+    size_t scan_bytes = 0;
+    HIP_TRY(drain_scan(nullptr, &scan_bytes, D.d_cnt.as<uint64_t>(), D.d_off.as<uint64_t>(), n_segs + 1, s),
+            "size drain scan");
+    HIP_TRY(D.d_scan.ensure(scan_bytes), "alloc drain scan");
+    HIP_TRY(hipMemcpyAsync(D.d_queries.p, D.queries.data(), n * sizeof(DrainQuery), hipMemcpyHostToDevice, s),
+            "upload drain queries");
+    a.seen = e->d_seen.as<uint64_t>();
+    a.gen = e->d_gen.as<uint8_t>();
+    a.gen_cur = e->gen_cur;
+    a.topics = D.d_topics.as<DrainTopic>();
+    a.groups = D.d_groups.as<DrainGroup>();
+    a.mask = D.d_mask.as<uint64_t>();
+    a.order = D.d_order.as<uint32_t>();
+    a.ids = D.d_ids.as<uint32_t>();
+    a.queries = D.d_queries.as<DrainQuery>();
+    a.n_queries = static_cast<uint32_t>(n);
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(launch_drain_count(a, n_segs, D.d_cnt.as<uint64_t>(), s), "k_drain_count");
+    HIP_TRY(t_end(0), "event");
+    HIP_TRY(t_begin(), "event");
+    size_t sb = D.d_scan.bytes;
+    HIP_TRY(drain_scan(D.d_scan.p, &sb, D.d_cnt.as<uint64_t>(), D.d_off.as<uint64_t>(), n_segs + 1, s), "drain scan");
+    HIP_TRY(t_end(1), "event");
+    HIP_TRY(hipMemcpyAsync(D.off.data(), D.d_off.p, (static_cast<size_t>(n_segs) + 1) * 8, hipMemcpyDeviceToHost, s),
+            "read drain offsets");
+    HIP_TRY(hipStreamSynchronize(s), "sync");
+  }
+  const uint64_t total = D.off[n_segs];
+  for (size_t q = 0; q < n; ++q) off_out[q] = D.off[D.queries[q].seg0];
+  off_out[n] = total;
+  *total_out = total;
+  if (total > cap) return e->fail(PS_E_RANGE, "output buffer too small");
+
+  // emit, slab by slab: the segments [lo, hi) whose ids fit one slab; slab k
+  // is copied out on the copy stream while slab k + 1 is emitted
+  const uint64_t slab = std::min<uint64_t>(D.slab_ids, std::max<uint64_t>(total, 1));
+  // both slabs, sized once (behind the copies of an earlier drain: all complete)
+  for (DevBuf& buf : D.d_slab) HIP_TRY(buf.ensure(slab * 4), "alloc drain slab");
+  struct Pending {
+    uint64_t base = 0, len = 0;
+  } pend;
+  uint32_t lo = 0, k = 0;  // k: slabs emitted; slab j lives in d_slab[j & 1]
+  // slab j's copy: behind its emit, on the copy stream (timing: in line)
+  auto copy_out = [&](uint32_t j) -> int {
+    hipStream_t cs = D.timing ? s : D.copy_stream;
+    if (!D.timing) HIP_TRY(hipStreamWaitEvent(cs, D.ev_emit[j & 1], 0), "wait");
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(hipMemcpyAsync(msg_out + pend.base, D.d_slab[j & 1].p, pend.len * 4, hipMemcpyDeviceToHost, cs),
+            "read drain slab");
+    HIP_TRY(t_end(3), "event");
+    HIP_TRY(hipEventRecord(D.ev_copy[j & 1], cs), "event");
+    return PS_OK;
+  };
+  while (lo < n_segs && D.off[lo] < total) {
+    const uint64_t base = D.off[lo];
+    const uint32_t hi =
+        static_cast<uint32_t>(std::upper_bound(D.off.begin() + lo, D.off.end(), base + slab) - D.off.begin()) - 1;
+    // (a segment holds at most kDrainSegBits <= slab ids, or all that is left: hi > lo)
+    if (hi <= lo) return e->fail(PS_E_STATE, "drain slab smaller than a segment");
+    const uint64_t len = D.off[hi] - base;
+    HIP_TRY(hipStreamWaitEvent(s, D.ev_copy[k & 1], 0), "wait");  // (slab k - 2 has left the buffer)
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(launch_drain_emit(a, lo, hi, D.d_off.as<uint64_t>(), base, D.d_slab[k & 1].as<uint32_t>(), len, D.staged, s),
+            "k_drain_emit");
+    HIP_TRY(t_end(2), "event");
+    HIP_TRY(hipEventRecord(D.ev_emit[k & 1], s), "event");
+    if (k)  // the slab before goes out while this one is emitted
+      if (const int rcc = copy_out(k - 1)) return rcc;
+    pend.base = base;
+    pend.len = len;
+    ++k;
+    lo = hi;
+  }
+  if (k)
+    if (const int rcc = copy_out(k - 1)) return rcc;
+  HIP_TRY(hipStreamSynchronize(D.copy_stream), "sync");
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  if (D.timing)
+    std::fprintf(stderr,
+                 "psamd drain: queries %zu segments %u ids %llu slabs %u emit %s count_ms %.4f scan_ms %.4f emit_ms %.4f "
+                 "copy_ms %.4f\n",
+                 n, n_segs, static_cast<unsigned long long>(total), k, D.staged ? "lds" : "direct", ms[0], ms[1], ms[2],
+                 ms[3]);
   return PS_OK;
 }
 

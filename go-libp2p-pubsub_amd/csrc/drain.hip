@@ -1,0 +1,166 @@
+// drain.hip -- the batched drain (ps_drain): the seen rows of
+// many (topic, peer) queries turned into message id lists on the device.
+//   k_drain_count  delivered positions per (query, segment)
+//   drain_scan     hipcub's exclusive sum over the segments
+//   k_drain_emit   one wave per segment: set positions -> ids, in order
+// A segment is kDrainSegBits positions of one query's row (kernels.hpp,
+// DrainTopic): lane l of its wave owns lane word l.
+#include <hipcub/hipcub.hpp>
+
+#include "devutil.hpp"
+
+namespace psamd {
+namespace {
+
+constexpr uint32_t kWave = 64;
+constexpr uint32_t kCountBlock = 256;
+constexpr uint64_t kNoWord = ~0ull;
+
+// word w of the row of node u: node-major, or the start group's block
+__device__ __forceinline__ uint64_t row_word_at(const DrainArgs& a, const DrainTopic& T, uint32_t u, uint32_t w) {
+  if (w >= T.W) return kNoWord;
+  if (!(T.flags & kTopicGroups)) return T.wbase + static_cast<uint64_t>(u) * T.W + w;
+  for (uint32_t g = 0; g < T.group_n; ++g) {
+    const DrainGroup G = a.groups[T.group_lo + g];
+    if (w < G.w0 + G.wn)
+      return w < G.w0 ? kNoWord
+                      : T.wbase + static_cast<uint64_t>(T.n_nodes) * G.w0 + static_cast<uint64_t>(u) * G.wn + (w - G.w0);
+  }
+  return kNoWord;
+}
+
+// the 64 positions from p0 of node u's row, bit i = position p0 + i delivered
+__device__ __forceinline__ uint64_t lane_word(const DrainArgs& a, const DrainTopic& T, uint32_t u, uint32_t p0) {
+  if (p0 >= T.n_pos) return 0;
+  if (!(T.flags & kDrainGather)) {
+    const uint64_t at = row_word_at(a, T, u, p0 >> 6);
+    return at == kNoWord ? 0ull : a.seen[at] & a.mask[T.aux0 + (p0 >> 6)];
+  }
+  const uint32_t n = min(64u, T.n_pos - p0);
+  uint64_t x = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t b = a.order[T.aux0 + p0 + i];
+    const uint64_t at = row_word_at(a, T, u, b >> 6);
+    if (at != kNoWord && (a.seen[at] >> (b & 63) & 1ull)) x |= 1ull << i;
+  }
+  return x;
+}
+
+// Segment s -> its query (the last one whose first segment is <= s) and its
+// index k within the query; false: the query's row holds nothing to read
+// (k past its positions, or a tree node the window did not reach).
+__device__ __forceinline__ bool locate(const DrainArgs& a, uint32_t s, DrainQuery* Q, DrainTopic* T, uint32_t* k) {
+  uint32_t lo = 0, hi = a.n_queries;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (a.queries[mid].seg0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return false;
+  *Q = a.queries[lo - 1];
+  *T = a.topics[Q->topic];
+  *k = s - Q->seg0;
+  if (static_cast<uint64_t>(*k) * kDrainSegBits >= T->n_pos || Q->node >= T->n_nodes) return false;
+  return (T->flags & kTopicMesh) || a.gen[T->nbase + Q->node] == static_cast<uint8_t>(a.gen_cur);
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src) {
+  const uint32_t lo = __shfl(static_cast<uint32_t>(v), src, 64);
+  const uint32_t hi = __shfl(static_cast<uint32_t>(v >> 32), src, 64);
+  return static_cast<uint64_t>(hi) << 32 | lo;
+}
+
+__global__ __launch_bounds__(kCountBlock) void k_drain_count(DrainArgs a, uint32_t n_segs, uint64_t* __restrict__ cnt) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kCountBlock / kWave) + threadIdx.x / kWave);
+  if (s > n_segs) return;
+  uint32_t c = 0;
+  if (s < n_segs) {
+    DrainQuery Q;
+    DrainTopic T;
+    uint32_t k;
+    if (locate(a, s, &Q, &T, &k)) c = __popcll(lane_word(a, T, Q.node, k * kDrainSegBits + lane * 64));
+  }
+  c = wave_sum_u32(c);
+  if (lane == 0) cnt[s] = c;
+}
+
+template <bool kStaged>
+__global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_lo, const uint64_t* __restrict__ off,
+                                                      uint64_t off0, uint32_t* __restrict__ out, uint64_t out_cap) {
+  __shared__ uint32_t stage[kStaged ? kDrainSegBits : 1];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t s = seg_lo + blockIdx.x;
+  DrainQuery Q;
+  DrainTopic T;
+  uint32_t k;
+  if (!locate(a, s, &Q, &T, &k)) return;  // (block-uniform)
+  const uint32_t p0 = k * kDrainSegBits + lane * 64;
+  uint64_t x = lane_word(a, T, Q.node, p0);
+  const uint32_t c = __popcll(x);
+  uint32_t incl = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(incl, d, 64);
+    if (lane >= static_cast<uint32_t>(d)) incl += t;
+  }
+  const uint32_t pre = incl - c;
+  const uint32_t total = __shfl(incl, 63, 64);
+  if (total == 0) return;
+  const uint64_t base = off[s] - off0;
+  const uint32_t* ids = a.ids + T.tab0;
+  if (kStaged) {
+    // lane word w at a time: lane l places position 64 w + l behind the set
+    // bits below it (consecutive LDS words), then whole-wave stores
+    for (uint32_t w = 0; w < kWave; ++w) {
+      const uint64_t xw = shfl_u64(x, static_cast<int>(w));
+      const uint32_t pw = __shfl(pre, static_cast<int>(w), 64);
+      if (xw == 0) continue;
+      if (xw >> lane & 1ull) stage[pw + __popcll(xw & ((1ull << lane) - 1))] = k * kDrainSegBits + w * 64 + lane;
+    }
+    __syncthreads();
+    for (uint32_t i = lane; i < total; i += kWave) {
+      const uint64_t o = base + i;
+      if (o < out_cap) out[o] = ids[stage[i]];
+    }
+  } else {
+    uint32_t p = pre;
+    while (x) {
+      const uint32_t b = __ffsll(static_cast<long long>(x)) - 1;
+      const uint64_t o = base + p++;
+      if (o < out_cap) out[o] = ids[p0 + b];
+      x &= x - 1;
+    }
+  }
+}
+
+}  // namespace
+
+hipError_t launch_drain_count(const DrainArgs& a, uint32_t n_segs, uint64_t* cnt, hipStream_t s) {
+  const uint32_t per = kCountBlock / kWave;
+  hipLaunchKernelGGL(k_drain_count, dim3((n_segs + 1 + per - 1) / per), dim3(kCountBlock), 0, s, a, n_segs, cnt);
+  return hipGetLastError();
+}
+
+hipError_t drain_scan(void* temp, size_t* temp_bytes, const uint64_t* cnt, uint64_t* off, uint32_t n, hipStream_t s) {
+  return hipcub::DeviceScan::ExclusiveSum(temp, *temp_bytes, cnt, off, n, s);
+}
+
+hipError_t launch_drain_emit(const DrainArgs& a, uint32_t seg_lo, uint32_t seg_hi, const uint64_t* off, uint64_t off0,
+                             uint32_t* out, uint64_t out_cap, bool staged, hipStream_t s) {
+  if (seg_hi <= seg_lo) return hipSuccess;
+  const dim3 grid(seg_hi - seg_lo);
+  if (staged)
+    hipLaunchKernelGGL(k_drain_emit<true>, grid, dim3(kWave), 0, s, a, seg_lo, off, off0, out, out_cap);
+  else
+    hipLaunchKernelGGL(k_drain_emit<false>, grid, dim3(kWave), 0, s, a, seg_lo, off, off0, out, out_cap);
+  return hipGetLastError();
+}
+
+}  // namespace psamd

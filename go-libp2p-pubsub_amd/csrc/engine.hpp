@@ -430,6 +430,24 @@ struct ps_engine {
   bool have_window = false;
   std::map<uint32_t, std::vector<uint32_t>> peer_node;  // topic -> peer -> node (ps_read_peer_messages)
   std::vector<uint64_t> peer_node_epoch;                 // graph_epoch each map was built for
+  uint64_t window_seq = 0;  // bumped whenever last_* change (a new last window)
+
+  // ps_drain: the last window's drain tables (per topic: bit ->
+  // message id, message mask or arrival order), built on the first drain
+  // after a window; count / offset / query staging; two output slabs
+  struct Drain {
+    uint64_t seq = ~0ull;  // window_seq the tables on the device were built for
+    std::vector<psamd::DrainTopic> topics;
+    psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order, d_queries, d_cnt, d_off, d_scan, d_slab[2];
+    std::vector<psamd::DrainQuery> queries;
+    std::vector<uint64_t> off;  // host copy of the segment offsets
+    hipStream_t copy_stream = nullptr;
+    hipEvent_t ev_emit[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};  // per slab
+    hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around one phase
+    uint64_t slab_ids = 64ull << 20;  // ids per slab (A/B: PSAMD_DRAIN_SLAB_IDS, at least one segment)
+    bool staged = true;               // LDS-staged emit (A/B: PSAMD_DRAIN_EMIT=direct)
+    bool timing = false;              // PSAMD_DRAIN_TIMING=1: phases run apart, times to stderr
+  } drain;
 
   // asynchronous runs (ps_run_async / ps_wait): the last window of a run may
   // leave its stats on the stream (pinned readback) so that the host plans

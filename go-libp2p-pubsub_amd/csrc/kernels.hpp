@@ -558,4 +558,54 @@ hipError_t launch_digest(const uint64_t* seen, const uint8_t* gen, uint32_t gen_
                          const TopicDev* topics, const GroupDev* groups, uint32_t n_nodes, uint64_t* out,
                          hipStream_t s);
 
+// ---- batched drain (drain.hip) -------------------------------
+// A query's row is cut into segments of kDrainSegBits positions: lane l of
+// the segment's wave owns the 64 positions of "lane word" 64 k + l.  For a
+// topic whose row bits ascend in arrival order a position is a virtual row
+// bit and the lane word is the row word under the topic's message mask; for
+// the others (kDrainGather: a mesh window with several start rounds) a
+// position is an arrival rank and the lane word is gathered bit by bit
+// through the topic's order table.  ids[tab0 + position] is the message id.
+constexpr uint32_t kDrainSegWords = 64;
+constexpr uint32_t kDrainSegBits = 64 * kDrainSegWords;
+constexpr uint32_t kDrainGather = 0x10000;  // DrainTopic.flags, next to kTopic*
+struct DrainTopic {
+  uint64_t wbase;   // first word of the topic's rows
+  uint64_t tab0;    // first entry of the topic's id table
+  uint64_t aux0;    // first mask word; kDrainGather: first entry of the order table
+  uint32_t nbase, n_nodes, W, flags;
+  uint32_t group_lo, group_n;  // kTopicGroups: the start groups (DrainGroup)
+  uint32_t n_pos;   // positions in use (a multiple of 64 unless kDrainGather)
+  uint32_t pad;
+};
+struct DrainGroup {
+  uint32_t w0, wn;
+};
+struct DrainQuery {
+  uint32_t topic;
+  uint32_t node;  // topic-relative
+  uint32_t seg0;  // the query's first segment (a query with an empty answer has none)
+  uint32_t pad;
+};
+struct DrainArgs {
+  const uint64_t* seen;
+  const uint8_t* gen;
+  uint32_t gen_cur;
+  const DrainTopic* topics;
+  const DrainGroup* groups;
+  const uint64_t* mask;
+  const uint32_t* order;
+  const uint32_t* ids;
+  const DrainQuery* queries;
+  uint32_t n_queries;
+};
+// cnt[s] = delivered positions of segment s, for s < n_segs; cnt[n_segs] = 0
+hipError_t launch_drain_count(const DrainArgs& a, uint32_t n_segs, uint64_t* cnt, hipStream_t s);
+// off[i] = cnt[0] + .. + cnt[i - 1] for i < n (temp == nullptr: sizes *temp_bytes)
+hipError_t drain_scan(void* temp, size_t* temp_bytes, const uint64_t* cnt, uint64_t* off, uint32_t n, hipStream_t s);
+// the ids of segments [seg_lo, seg_hi) to out[off[s] - off0 ..), below out_cap;
+// staged: through LDS with coalesced stores, else each lane stores its own
+hipError_t launch_drain_emit(const DrainArgs& a, uint32_t seg_lo, uint32_t seg_hi, const uint64_t* off, uint64_t off0,
+                             uint32_t* out, uint64_t out_cap, bool staged, hipStream_t s);
+
 }  // namespace psamd

@@ -120,22 +120,29 @@ Error Network::Flush() {
     return err(rc);
   }
   // processMessages (client.go:124-128): every open subscriber's channel gets
-  // what reached it, in arrival order
-  std::vector<uint32_t> ids(64);
+  // what reached it, in arrival order: one batched drain for all of them
+  std::vector<client*> open;
+  std::vector<uint32_t> qt, qp;
   for (auto& c : clients_) {
     if (!c->open_ || c->out_.closed_) continue;
-    size_t n = 0;
-    rc = ps_read_peer_messages(e_, c->topic_, c->peer_, ids.data(), ids.size(), &n);
-    if (rc == PS_E_RANGE && n > ids.size()) {
-      ids.resize(n);
-      rc = ps_read_peer_messages(e_, c->topic_, c->peer_, ids.data(), ids.size(), &n);
-    }
-    if (rc != PS_OK) return err(rc);
-    for (size_t k = 0; k < n; ++k) {
-      auto it = payload_.find(ids[k]);
-      if (it != payload_.end()) c->out_.q_.push_back(it->second);
-    }
+    open.push_back(c.get());
+    qt.push_back(c->topic_);
+    qp.push_back(c->peer_);
   }
+  std::vector<uint64_t> off(open.size() + 1);
+  std::vector<uint32_t> ids(64 * open.size());
+  uint64_t total = 0;
+  rc = ps_drain(e_, qt.data(), qp.data(), open.size(), off.data(), ids.data(), ids.size(), &total);
+  if (rc == PS_E_RANGE && total > ids.size()) {
+    ids.resize(total);
+    rc = ps_drain(e_, qt.data(), qp.data(), open.size(), off.data(), ids.data(), ids.size(), &total);
+  }
+  if (rc != PS_OK) return err(rc);
+  for (size_t q = 0; q < open.size(); ++q)
+    for (uint64_t k = off[q]; k < off[q + 1]; ++k) {
+      auto it = payload_.find(ids[k]);
+      if (it != payload_.end()) open[q]->out_.q_.push_back(it->second);
+    }
   payload_.clear();
   return Error{};
 }

@@ -1289,6 +1289,7 @@ int run_window(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<
     e->last_groups.swap(L.groups);
     e->have_window = true;
     e->last_slot = slot;
+    ++e->window_seq;
   };
   if (defer) {
     // asynchronous run: the counters follow the kernels on the stream into

@@ -152,6 +152,7 @@ PROTOTYPES = [
     ("ps_read_hops", C.c_int, [_P, _u32, _u8p]),
     ("ps_read_delivered", C.c_int, [_P, _u32, _u8p]),
     ("ps_read_peer_messages", C.c_int, [_P, _u32, _u32, _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("ps_drain", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u64p, _u32p, C.c_size_t, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -400,6 +401,26 @@ class Engine:
                 continue
             self._check(rc)
             return out[:n.value].copy()
+
+    def drain(self, topics, peers):
+        """client.Messages() of many subscribers at once (ps_drain): query q =
+        (topics[q], peers[q]); returns (off: uint64[n + 1], ids: uint32[total]),
+        query q's message ids, in arrival order, being ids[off[q]:off[q + 1]]."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        p = np.ascontiguousarray(peers, dtype=np.uint32)
+        if t.ndim != 1 or t.shape != p.shape:
+            raise ValueError("topics and peers must be 1-d arrays of one length")
+        n = t.size
+        off = np.empty(n + 1, dtype=np.uint64)
+        total = C.c_uint64()
+        tp, pp, op = _p(t, C.c_uint32), _p(p, C.c_uint32), _p(off, C.c_uint64)
+        rc = self._L.ps_drain(self._h, tp, pp, n, op, None, 0, C.byref(total))  # the sizing call
+        if rc != -7 or total.value == 0:
+            self._check(rc)
+            return off, np.empty(0, dtype=np.uint32)
+        ids = np.empty(total.value, dtype=np.uint32)
+        self._check(self._L.ps_drain(self._h, tp, pp, n, op, _p(ids, C.c_uint32), ids.size, C.byref(total)))
+        return off, ids
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -287,6 +287,17 @@ int ps_read_delivered(ps_engine* e, uint32_t msg, uint8_t* delivered_per_peer);
  *               PS_E_RANGE (with *n_out set) when cap is too small. */
 int ps_read_peer_messages(ps_engine* e, uint32_t topic, uint32_t peer, uint32_t* msg_out,
                           size_t cap, size_t* n_out);
+/* client.Messages() (client.go:26-28,124-128) for n subscribers at once:
+ * query q = (topic[q], peer[q]); its message ids, in the order
+ * ps_read_peer_messages gives them, are msg_out[off_out[q] .. off_out[q+1]).
+ * off_out has n + 1 entries; *total_out = off_out[n].  When total > cap,
+ * off_out and *total_out are still filled, msg_out is untouched and the call
+ * returns PS_E_RANGE (msg_out == NULL, cap == 0 is the sizing call).  The
+ * rows are turned into id lists on the GPU (one count, one scan, one emit per
+ * output slab); queries may repeat, in any order; PS_E_RANGE with nothing
+ * written for a topic or peer out of range. */
+int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint64_t* off_out,
+             uint32_t* msg_out, size_t cap, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a
