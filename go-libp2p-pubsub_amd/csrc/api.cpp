@@ -185,6 +185,7 @@ static void read_switches(ps_engine* e) {
   if (const char* v = std::getenv("PSAMD_DRAIN_SLAB_IDS"))  // (a slab holds at least one segment)
     e->drain.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
   if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.staged = std::strcmp(v, "direct") != 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) e->drain.mapped_out = std::strcmp(v, "mapped") == 0;
   if (const char* v = std::getenv("PSAMD_TWIN")) e->twin_on = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_NARROW")) e->expand_opts = std::atoi(v) == 0 ? kExpandNoNarrow : 0u;
   if (const char* v = std::getenv("PSAMD_CHAIN_WORDS_LEAD"))
@@ -341,6 +342,12 @@ void ps_destroy(ps_engine* e) {
   }
   for (hipEvent_t ev : {e->drain.ev_emit[0], e->drain.ev_emit[1], e->drain.ev_copy[0], e->drain.ev_copy[1], e->drain.ev_t[0], e->drain.ev_t[1]})
     if (ev) (void)hipEventDestroy(ev);
+  for (auto& sl : e->drain.slot) {
+    if (sl.ev_emit) (void)hipEventDestroy(sl.ev_emit);
+    if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
+    if (sl.h_in) (void)hipHostFree(sl.h_in);
+    if (sl.h_res) (void)hipHostFree(sl.h_res);
+  }
   for (auto ev : e->ev_k) (void)hipEventDestroy(ev);
   for (hipEvent_t ev : {e->ev_run0, e->ev_run1, e->ev_round, e->ev_xchg, e->ev_gate[0], e->ev_gate[1], e->ev_pre, e->ev_end,
                       e->ev_tend, e->ev_e2t})
@@ -786,6 +793,11 @@ static int drain_tables(ps_engine* e) {
   HIP_TRY(up(D.d_mask, mask.data(), mask.size() * 8), "drain masks");
   HIP_TRY(up(D.d_order, order.data(), order.size() * 4), "drain order");
   HIP_TRY(hipStreamSynchronize(e->stream), "sync");  // (the tables above leave scope)
+  D.p_topics = D.d_topics.as<DrainTopic>();
+  D.p_groups = D.d_groups.as<DrainGroup>();
+  D.p_ids = D.d_ids.as<uint32_t>();
+  D.p_mask = D.d_mask.as<uint64_t>();
+  D.p_order = D.d_order.as<uint32_t>();
   D.seq = e->window_seq;
   return PS_OK;
 }
@@ -825,11 +837,21 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
   if (n == 0) return PS_OK;
   if (n >= 0xFFFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
   auto& D = e->drain;
+  // (PSAMD_DRAIN_TIMING: the host phases of the call, the first after a window above all)
+  using hclock = std::chrono::steady_clock;
+  auto h_ms = [](hclock::time_point t0) { return std::chrono::duration<double, std::milli>(hclock::now() - t0).count(); };
+  double host_ms[3] = {0, 0, 0};  // node-space mirrors, table build + upload, queries (peer maps)
+  auto h0 = hclock::now();
   int rc = ensure_mirrors(e);
+  host_ms[0] = h_ms(h0);
+  h0 = hclock::now();
+  const bool tables_built = D.seq != e->window_seq;
   if (!rc) rc = drain_tables(e);
+  host_ms[1] = h_ms(h0);
   if (!rc) rc = drain_streams(e);
   if (rc) return rc;
   hipStream_t s = e->stream;
+  h0 = hclock::now();
 
   // queries -> (topic, node, first segment); an empty answer has no segment
   D.queries.resize(n);
@@ -847,6 +869,7 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
     if (n_segs64 >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many rows in one drain");
   }
   const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  host_ms[2] = h_ms(h0);
   D.off.assign(static_cast<size_t>(n_segs) + 1, 0);
   float ms[4] = {0, 0, 0, 0};  // count, scan, emit, copy (PSAMD_DRAIN_TIMING)
   auto t_begin = [&]() { return D.timing ? hipEventRecord(D.ev_t[0], s) : hipSuccess; };
@@ -873,11 +896,11 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
     a.seen = e->d_seen.as<uint64_t>();
     a.gen = e->d_gen.as<uint8_t>();
     a.gen_cur = e->gen_cur;
-    a.topics = D.d_topics.as<DrainTopic>();
-    a.groups = D.d_groups.as<DrainGroup>();
-    a.mask = D.d_mask.as<uint64_t>();
-    a.order = D.d_order.as<uint32_t>();
-    a.ids = D.d_ids.as<uint32_t>();
+    a.topics = D.p_topics;
+    a.groups = D.p_groups;
+    a.mask = D.p_mask;
+    a.order = D.p_order;
+    a.ids = D.p_ids;
     a.queries = D.d_queries.as<DrainQuery>();
     a.n_queries = static_cast<uint32_t>(n);
     HIP_TRY(t_begin(), "event");
@@ -895,7 +918,12 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
   for (size_t q = 0; q < n; ++q) off_out[q] = D.off[D.queries[q].seg0];
   off_out[n] = total;
   *total_out = total;
-  if (total > cap) return e->fail(PS_E_RANGE, "output buffer too small");
+  if (total > cap) {
+    if (D.timing)
+      std::fprintf(stderr, "psamd drain: queries %zu sizing host_mirrors_ms %.4f host_tables_ms %.4f (%s) host_queries_ms %.4f\n",
+                   n, host_ms[0], host_ms[1], tables_built ? "built" : "kept", host_ms[2]);
+    return e->fail(PS_E_RANGE, "output buffer too small");
+  }
 
   // emit, slab by slab: the segments [lo, hi) whose ids fit one slab; slab k
   // is copied out on the copy stream while slab k + 1 is emitted
@@ -944,9 +972,347 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
   if (D.timing)
     std::fprintf(stderr,
                  "psamd drain: queries %zu segments %u ids %llu slabs %u emit %s count_ms %.4f scan_ms %.4f emit_ms %.4f "
-                 "copy_ms %.4f\n",
+                 "copy_ms %.4f host_mirrors_ms %.4f host_tables_ms %.4f (%s) host_queries_ms %.4f\n",
                  n, n_segs, static_cast<unsigned long long>(total), k, D.staged ? "lds" : "direct", ms[0], ms[1], ms[2],
-                 ms[3]);
+                 ms[3], host_ms[0], host_ms[1], tables_built ? "built" : "kept", host_ms[2]);
+  return PS_OK;
+}
+
+// ---- ps_drain_begin / ps_drain_end -------------------------
+
+// ids one asynchronous drain may hold at most (its buffers are sized by an
+// upper bound, not by the total): larger drains go through ps_drain's slabs
+constexpr uint64_t kDrainAsyncMaxIds = 1ull << 30;
+
+static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// grow-only pinned memory (device-mapped); the old contents are dropped
+static hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need) {
+  if (need <= *cap) return hipSuccess;
+  if (*h) (void)hipHostFree(*h);
+  *h = nullptr;
+  *cap = 0;
+  void* p = nullptr;
+  hipError_t rc = hipHostMalloc(&p, std::max<size_t>(need + need / 2, 64 << 10), hipHostMallocMapped | hipHostMallocCoherent);
+  if (rc != hipSuccess) return rc;
+  *h = static_cast<uint8_t*>(p);
+  *cap = std::max<size_t>(need + need / 2, 64 << 10);
+  if (d) {
+    void* dp = nullptr;
+    rc = hipHostGetDevicePointer(&dp, p, 0);
+    *d = static_cast<uint8_t*>(dp);
+  }
+  return rc;
+}
+
+// The last window's tables for the asynchronous drain, once per window: the
+// host stages 12 B per window message (run index, row bit, start round) in
+// the slot's pinned memory and k_drain_tables builds the id table and the
+// mask from them behind the window, with no host wait.  A mesh topic of a
+// run with several start rounds keeps the host's arrival-order table
+// (kDrainGather, as drain_tables above), staged the same way.  `used`: the
+// bytes of S.h_in taken (the queries follow).
+static int drain_tables_async(ps_engine* e, ps_engine::Drain::Slot& S, size_t* used) {
+  auto& D = e->drain;
+  *used = 0;
+  if (D.seq == e->window_seq) return PS_OK;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  D.topics.assign(nt, DrainTopic{});
+  std::vector<DrainGroup> groups;
+  std::vector<uint32_t> built, gather;  // topics by build
+  uint64_t n_msgs = 0, n_pos = 0, n_gather = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const TopicDev& d = e->last_topics[t];
+    if (!d.W || !e->last_cnt[t]) continue;
+    DrainTopic& T = D.topics[t];
+    T.wbase = d.wbase;
+    T.nbase = d.nbase;
+    T.n_nodes = d.n_nodes;
+    T.W = d.W;
+    T.flags = d.flags & (kTopicMesh | kTopicGroups);
+    if (d.flags & kTopicGroups) {
+      T.group_lo = static_cast<uint32_t>(groups.size());
+      for (const StartGroup& g : e->last_groups[t]) groups.push_back({g.w0, g.wn});
+      T.group_n = static_cast<uint32_t>(groups.size()) - T.group_lo;
+    }
+    if ((d.flags & kTopicMesh) && !e->run_zero_start) {
+      T.flags |= kDrainGather;
+      gather.push_back(t);
+      n_gather += e->last_cnt[t];
+      continue;
+    }
+    // the positions in use end with the word of the highest bit (a bit past
+    // the row is the kernel's to report: the table never exceeds the row)
+    const auto& pos = t < e->last_pos.size() ? e->last_pos[t] : std::vector<uint32_t>();
+    uint32_t top = e->last_cnt[t] - 1;
+    if (!pos.empty()) top = *std::max_element(pos.begin(), pos.begin() + e->last_cnt[t]);
+    T.n_pos = (std::min<uint32_t>(top >> 6, d.W - 1) + 1) * 64;
+    T.tab0 = n_pos;
+    T.aux0 = n_pos >> 6;
+    n_pos += T.n_pos;
+    n_msgs += e->last_cnt[t];
+    built.push_back(t);
+  }
+  if (n_pos + n_gather >= (1ull << 31)) return e->fail(PS_E_RANGE, "drain tables too large: use ps_drain");
+  uint64_t g_ids = n_pos, g_ord = 0;
+  for (uint32_t t : gather) {
+    DrainTopic& T = D.topics[t];
+    T.n_pos = e->last_cnt[t];
+    T.tab0 = g_ids;
+    T.aux0 = g_ord;
+    g_ids += T.n_pos;
+    g_ord += T.n_pos;
+  }
+  // the block: topics | groups | built topics | their first messages | idx | bit | start | order | gather ids
+  const uint32_t nb = static_cast<uint32_t>(built.size());
+  const size_t o_topics = 0;
+  const size_t o_groups = align256(o_topics + nt * sizeof(DrainTopic));
+  const size_t o_btopic = align256(o_groups + groups.size() * sizeof(DrainGroup));
+  const size_t o_msg0 = align256(o_btopic + nb * 4);
+  const size_t o_idx = align256(o_msg0 + (nb + 1) * 4);
+  const size_t o_bit = align256(o_idx + n_msgs * 4);
+  const size_t o_start = align256(o_bit + n_msgs * 4);
+  const size_t o_order = align256(o_start + n_msgs * 4);
+  const size_t o_gids = align256(o_order + n_gather * 4);
+  const size_t block = align256(o_gids + n_gather * 4);
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + align256(S.n * sizeof(DrainQuery))), "alloc drain staging");
+  HIP_TRY(D.d_ablock.ensure(block), "alloc drain tables");
+  HIP_TRY(D.d_aids.ensure((n_pos + n_gather) * 4), "alloc drain ids");
+  HIP_TRY(D.d_amask.ensure((n_pos >> 6) * 8 + 8), "alloc drain masks");
+  HIP_TRY(D.d_akeys.ensure(n_pos * 8), "alloc drain keys");
+  uint8_t* h = S.h_in;
+  std::memcpy(h + o_topics, D.topics.data(), nt * sizeof(DrainTopic));
+  if (!groups.empty()) std::memcpy(h + o_groups, groups.data(), groups.size() * sizeof(DrainGroup));
+  uint32_t* h_btopic = reinterpret_cast<uint32_t*>(h + o_btopic);
+  uint32_t* h_msg0 = reinterpret_cast<uint32_t*>(h + o_msg0);
+  uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + o_idx);
+  uint32_t* h_bit = reinterpret_cast<uint32_t*>(h + o_bit);
+  uint32_t* h_start = reinterpret_cast<uint32_t*>(h + o_start);
+  uint32_t j = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t t = built[k], cnt = e->last_cnt[t];
+    h_btopic[k] = t;
+    h_msg0[k] = j;
+    // the window's slice of the topic-sorted run indices (rank lo .. lo + cnt)
+    const uint32_t* src = e->run_sorted.data() + e->run_topic_off[t] + e->last_lo[t];
+    const bool has_pos = t < e->last_pos.size() && !e->last_pos[t].empty();
+    for (uint32_t li = 0; li < cnt; ++li, ++j) {
+      const uint32_t i = src[li];
+      h_idx[j] = i;
+      h_bit[j] = has_pos ? e->last_pos[t][li] : li;
+      h_start[j] = e->last_msgs[i].start;
+    }
+  }
+  h_msg0[nb] = j;
+  uint32_t* h_order = reinterpret_cast<uint32_t*>(h + o_order);
+  uint32_t* h_gids = reinterpret_cast<uint32_t*>(h + o_gids);
+  for (uint32_t t : gather) {  // arrival order: (start round, run index) ascending
+    const uint32_t cnt = e->last_cnt[t];
+    const uint32_t* src = e->run_sorted.data() + e->run_topic_off[t] + e->last_lo[t];
+    const bool has_pos = t < e->last_pos.size() && !e->last_pos[t].empty();
+    std::vector<std::pair<uint64_t, uint32_t>> P(cnt);  // (key, bit)
+    for (uint32_t li = 0; li < cnt; ++li)
+      P[li] = {static_cast<uint64_t>(e->last_msgs[src[li]].start) << 32 | src[li], has_pos ? e->last_pos[t][li] : li};
+    std::sort(P.begin(), P.end());
+    const uint64_t o = D.topics[t].aux0;
+    for (uint32_t k = 0; k < cnt; ++k) {
+      if ((P[k].second >> 6) >= D.topics[t].W) return e->fail(PS_E_STATE, "window message bit past the row");
+      h_order[o + k] = P[k].second;
+      h_gids[o + k] = e->last_first + static_cast<uint32_t>(P[k].first);
+    }
+  }
+  hipStream_t s = e->stream;
+  uint8_t* db = D.d_ablock.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(db, h, block, hipMemcpyHostToDevice, s), "upload drain tables");
+  if (n_gather)
+    HIP_TRY(hipMemcpyAsync(D.d_aids.as<uint32_t>() + n_pos, db + o_gids, n_gather * 4, hipMemcpyDeviceToDevice, s),
+            "place drain ids");
+  D.d_err = reinterpret_cast<uint32_t*>(D.d_amask.as<uint64_t>() + (n_pos >> 6));
+  HIP_TRY(hipMemsetAsync(D.d_amask.p, 0, (n_pos >> 6) * 8 + 8, s), "clear drain masks");
+  if (n_pos) HIP_TRY(hipMemsetAsync(D.d_aids.p, 0xFF, n_pos * 4, s), "clear drain ids");
+  DrainBuild b{};
+  b.topics = reinterpret_cast<const DrainTopic*>(db + o_topics);
+  b.topic = reinterpret_cast<const uint32_t*>(db + o_btopic);
+  b.msg0 = reinterpret_cast<const uint32_t*>(db + o_msg0);
+  b.idx = reinterpret_cast<const uint32_t*>(db + o_idx);
+  b.bit = reinterpret_cast<const uint32_t*>(db + o_bit);
+  b.start = reinterpret_cast<const uint32_t*>(db + o_start);
+  b.n_built = nb;
+  b.n_msgs = static_cast<uint32_t>(n_msgs);
+  b.last_first = e->last_first;
+  b.n_pos = n_pos;
+  b.ids = D.d_aids.as<uint32_t>();
+  b.mask = D.d_amask.as<uint64_t>();
+  b.keys = D.d_akeys.as<uint64_t>();
+  b.err = D.d_err;
+  if (D.timing) HIP_TRY(hipEventRecord(D.ev_t[0], s), "event");
+  HIP_TRY(launch_drain_tables(b, s), "k_drain_tables");
+  if (D.timing) {  // (timing runs wait here: the build and its check, device time)
+    float t = 0;
+    HIP_TRY(hipEventRecord(D.ev_t[1], s), "event");
+    HIP_TRY(hipEventSynchronize(D.ev_t[1]), "event");
+    HIP_TRY(hipEventElapsedTime(&t, D.ev_t[0], D.ev_t[1]), "event");
+    std::fprintf(stderr, "psamd drain tables: topics %u messages %llu positions %llu gather %llu device_ms %.4f\n", nb,
+                 static_cast<unsigned long long>(n_msgs), static_cast<unsigned long long>(n_pos),
+                 static_cast<unsigned long long>(n_gather), t);
+  }
+  D.p_topics = b.topics;
+  D.p_groups = reinterpret_cast<const DrainGroup*>(db + o_groups);
+  D.p_ids = b.ids;
+  D.p_mask = b.mask;
+  D.p_order = reinterpret_cast<const uint32_t*>(db + o_order);
+  D.seq = e->window_seq;
+  *used = block;
+  return PS_OK;
+}
+
+int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n) {
+  if (!e || (n && (!topic || !peer))) return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_drain_begin on a multi-rank engine: use ps_drain");
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no run enqueued");
+  auto& D = e->drain;
+  if (D.slot_count == 2) return e->fail(PS_E_STATE, "two drains outstanding: ps_drain_end first");
+  for (size_t q = 0; q < n; ++q)
+    if (topic[q] >= e->topics.size() || peer[q] >= e->cfg.n_peers) return e->fail(PS_E_RANGE, "topic or peer out of range");
+  if (n >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  const auto t_host0 = std::chrono::steady_clock::now();
+  // behind the last launch of the window: `stream` follows a twin's tstream
+  if (const int rj = twin_join(e)) return rj;
+  int rc = ensure_mirrors(e);
+  if (!rc) rc = drain_streams(e);
+  if (rc) return rc;
+  auto& S = D.slot[(D.slot_head + D.slot_count) & 1];
+  if (!S.ev_emit) {
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_emit, kStreamEvent), "drain event");
+    // (the host reads the view after ev_done: it keeps the system-scope release)
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming), "drain event");
+  }
+  hipStream_t s = e->stream;
+  const uint64_t seq0 = D.seq;
+  S.n = n;
+  size_t used = 0;
+  if ((rc = drain_tables_async(e, S, &used))) {
+    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
+    return rc;
+  }
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + align256(n * sizeof(DrainQuery))), "alloc drain staging");
+
+  // queries -> (topic, node, first segment), as ps_drain; the output bound:
+  // every resolvable query may hold all of its topic's window messages
+  DrainQuery* hq = reinterpret_cast<DrainQuery*>(S.h_in + used);
+  uint64_t n_segs64 = 0, bound = 0;
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t t = topic[q];
+    const DrainTopic& T = D.topics[t];
+    hq[q] = DrainQuery{t, 0, static_cast<uint32_t>(n_segs64), 0};
+    if (!T.n_pos) continue;
+    const uint32_t u = drain_peer_map(e, t, e->last_topics[t])[peer[q]];
+    if (u == kNone) continue;
+    hq[q].node = u;
+    n_segs64 += ceil_div(T.n_pos, kDrainSegBits);
+    bound += e->last_cnt[t];
+    if (n_segs64 >= 0x7FFFFFFFull) break;
+  }
+  if (n_segs64 >= 0x7FFFFFFFull || bound > kDrainAsyncMaxIds) {
+    // no slot is taken: the table block staged in this slot's memory must
+    // have left it before the next ps_drain_begin writes there
+    if (used) HIP_TRY(hipStreamSynchronize(s), "sync");
+    return e->fail(PS_E_RANGE, n_segs64 >= 0x7FFFFFFFull ? "too many rows in one drain"
+                                                         : "drain may exceed 2^30 ids: use ps_drain");
+  }
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  S.hdr_bytes = align256((n + 2) * 8);
+  S.bound = bound;
+  const size_t res_bytes = S.hdr_bytes + bound * 4;
+  HIP_TRY(pinned_ensure(&S.h_res, &S.h_res_dev, &S.res_cap, res_bytes), "alloc drain view");
+  S.enqueued = false;
+  if (n_segs == 0) {  // nothing to read: the view is n + 1 zeros
+    std::memset(S.h_res, 0, (n + 2) * 8);
+    if (used) {  // (the table block staged in this slot: ps_drain_end waits for its upload)
+      HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+      S.enqueued = true;
+    }
+    ++D.slot_count;
+    return PS_OK;
+  }
+  HIP_TRY(S.d_queries.ensure(n * sizeof(DrainQuery)), "alloc drain queries");
+  HIP_TRY(S.d_cnt.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain counts");
+  HIP_TRY(S.d_off.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain offsets");
+  size_t scan_bytes = 0;
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, S.d_cnt.as<uint64_t>(), S.d_off.as<uint64_t>(), n_segs + 1, s),
+          "size drain scan");
+  HIP_TRY(S.d_scan.ensure(scan_bytes), "alloc drain scan");
+  if (!D.mapped_out) HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
+  HIP_TRY(hipMemcpyAsync(S.d_queries.p, hq, n * sizeof(DrainQuery), hipMemcpyHostToDevice, s), "upload drain queries");
+  DrainArgs a{};
+  a.seen = e->d_seen.as<uint64_t>();
+  a.gen = e->d_gen.as<uint8_t>();
+  a.gen_cur = e->gen_cur;
+  a.topics = D.p_topics;
+  a.groups = D.p_groups;
+  a.mask = D.p_mask;
+  a.order = D.p_order;
+  a.ids = D.p_ids;
+  a.queries = S.d_queries.as<DrainQuery>();
+  a.n_queries = static_cast<uint32_t>(n);
+  uint8_t* res = D.mapped_out ? S.h_res_dev : S.d_res.as<uint8_t>();
+  HIP_TRY(launch_drain_count(a, n_segs, S.d_cnt.as<uint64_t>(), s), "k_drain_count");
+  HIP_TRY(drain_scan(S.d_scan.p, &scan_bytes, S.d_cnt.as<uint64_t>(), S.d_off.as<uint64_t>(), n_segs + 1, s),
+          "drain scan");
+  // (the build's error word exists once a device build has run; the mask
+  // buffer's last word else)
+  if (!D.d_err) {
+    HIP_TRY(D.d_amask.ensure(8), "alloc drain masks");
+    D.d_err = D.d_amask.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(D.d_err, 0, 8, s), "clear drain error");
+  }
+  HIP_TRY(launch_drain_offsets(a.queries, a.n_queries, S.d_off.as<uint64_t>(), n_segs, D.d_err,
+                               reinterpret_cast<uint64_t*>(res), s),
+          "k_drain_offsets");
+  HIP_TRY(launch_drain_emit(a, 0, n_segs, S.d_off.as<uint64_t>(), 0, reinterpret_cast<uint32_t*>(res + S.hdr_bytes),
+                            bound, true, s),
+          "k_drain_emit");
+  // the emit is the last reader of the window's rows (run.cpp: drain_fence)
+  HIP_TRY(hipEventRecord(S.ev_emit, s), "event");
+  S.seen = e->d_seen.p;
+  S.emit_pending = true;
+  S.enqueued = true;
+  ++D.slot_count;
+  if (D.mapped_out) {
+    HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+  } else {
+    // the view leaves on the copy stream, beside whatever `stream` runs next
+    HIP_TRY(hipStreamWaitEvent(D.copy_stream, S.ev_emit, 0), "wait");
+    HIP_TRY(hipMemcpyAsync(S.h_res, S.d_res.p, res_bytes, hipMemcpyDeviceToHost, D.copy_stream), "read drain view");
+    HIP_TRY(hipEventRecord(S.ev_done, D.copy_stream), "event");
+  }
+  if (D.timing)
+    std::fprintf(stderr, "psamd drain_begin: queries %zu segments %u bound %llu tables %s out %s host_us %.1f\n", n, n_segs,
+                 static_cast<unsigned long long>(bound), used ? "built" : "kept", D.mapped_out ? "mapped" : "copy",
+                 std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_host0).count());
+  return PS_OK;
+}
+
+int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_out, uint64_t* total_out) {
+  if (!e || !off_out || !msg_out || !total_out) return PS_E_INVAL;
+  auto& D = e->drain;
+  if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
+  auto& S = D.slot[D.slot_head];
+  D.slot_head ^= 1;
+  --D.slot_count;
+  if (S.enqueued) {
+    HIP_TRY(hipEventSynchronize(S.ev_done), "wait for the drain");
+    S.emit_pending = false;
+    S.enqueued = false;
+  }
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(S.h_res);
+  *off_out = hdr;
+  *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.hdr_bytes);
+  *total_out = hdr[S.n];
+  if (const uint64_t err = hdr[S.n + 1])
+    return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
+                                                  : "drain tables: row bits do not ascend in arrival order");
+  if (hdr[S.n] > S.bound) return e->fail(PS_E_STATE, "drain total above its bound");
   return PS_OK;
 }
 

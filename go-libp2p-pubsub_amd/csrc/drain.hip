@@ -3,6 +3,10 @@
 //   k_drain_count  delivered positions per (query, segment)
 //   drain_scan     hipcub's exclusive sum over the segments
 //   k_drain_emit   one wave per segment: set positions -> ids, in order
+// and, for ps_drain_begin (§5.5b), which may not wait for the GPU:
+//   k_drain_tables        the window's bit -> id table and message mask
+//   k_drain_tables_check  arrival keys ascend with the row bit, per topic
+//   k_drain_offsets       per-query offsets, total and error word of a view
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -140,7 +144,96 @@ __global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_
   }
 }
 
+// ---- the window's drain tables built on the device (ps_drain_begin) ----------
+
+constexpr uint32_t kTabBlock = 256;
+
+// the built topic (index into b.topic) whose range of `first` holds x
+__device__ __forceinline__ uint32_t built_topic(const uint32_t* first, uint32_t n_built, uint32_t x) {
+  uint32_t lo = 0, hi = n_built;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= x) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;  // (first[0] = 0 <= x)
+}
+
+// One thread per window message: its id at its row bit, its mask bit set, its
+// arrival key beside the id for the check below.
+__global__ __launch_bounds__(kTabBlock) void k_drain_tables(DrainBuild b) {
+  const uint32_t j = blockIdx.x * kTabBlock + threadIdx.x;
+  if (j >= b.n_msgs) return;
+  const DrainTopic T = b.topics[b.topic[built_topic(b.msg0, b.n_built, j)]];
+  const uint32_t bit = b.bit[j], i = b.idx[j];
+  if (bit >= T.n_pos || (bit >> 6) >= T.W) {  // a bit past the row
+    *b.err = kDrainErrBit;
+    return;
+  }
+  const uint64_t m = 1ull << (bit & 63);
+  const uint64_t old = atomicOr(reinterpret_cast<unsigned long long*>(b.mask + T.aux0 + (bit >> 6)), m);
+  if (old & m) {  // two messages share the bit
+    *b.err = kDrainErrBit;
+    return;
+  }
+  b.ids[T.tab0 + bit] = b.last_first + i;
+  b.keys[T.tab0 + bit] = static_cast<uint64_t>(b.start[j]) << 32 | i;
+}
+
+// One thread per table position: a message bit's key must exceed the key of
+// the nearest lower message bit of its topic (the emit lists a row's set bits
+// in bit order, and that must be arrival order).
+__global__ __launch_bounds__(kTabBlock) void k_drain_tables_check(DrainBuild b) {
+  const uint64_t p = static_cast<uint64_t>(blockIdx.x) * kTabBlock + threadIdx.x;
+  if (p >= b.n_pos) return;
+  uint64_t w = p >> 6;
+  const uint64_t here = b.mask[w];
+  if (!(here >> (p & 63) & 1ull)) return;
+  // the topic's first mask word: the last built topic whose table starts at or below p
+  uint32_t lo = 0, hi = b.n_built;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (b.topics[b.topic[mid]].tab0 <= p) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint64_t w_first = b.topics[b.topic[lo - 1]].tab0 >> 6;
+  uint64_t below = here & ((1ull << (p & 63)) - 1);
+  while (!below && w > w_first) below = b.mask[--w];
+  if (!below) return;  // the topic's lowest message bit
+  const uint64_t q = w * 64 + (63 - __clzll(static_cast<long long>(below)));
+  if (b.keys[p] <= b.keys[q]) *b.err = kDrainErrOrder;
+}
+
+// The view's header: off[q] of every query from the segment offsets, the
+// total, and the table build's error word behind them.
+__global__ __launch_bounds__(kTabBlock) void k_drain_offsets(const DrainQuery* __restrict__ queries, uint32_t n,
+                                                             const uint64_t* __restrict__ seg_off, uint32_t n_segs,
+                                                             const uint32_t* __restrict__ err,
+                                                             uint64_t* __restrict__ hdr) {
+  const uint32_t q = blockIdx.x * kTabBlock + threadIdx.x;
+  if (q < n) hdr[q] = seg_off[queries[q].seg0];
+  else if (q == n) hdr[n] = seg_off[n_segs];
+  else if (q == n + 1) hdr[n + 1] = *err;
+}
+
 }  // namespace
+
+hipError_t launch_drain_tables(const DrainBuild& b, hipStream_t s) {
+  if (b.n_msgs == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_drain_tables, dim3((b.n_msgs + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, b);
+  hipError_t rc = hipGetLastError();
+  if (rc != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_drain_tables_check, dim3(static_cast<uint32_t>((b.n_pos + kTabBlock - 1) / kTabBlock)),
+                     dim3(kTabBlock), 0, s, b);
+  return hipGetLastError();
+}
+
+hipError_t launch_drain_offsets(const DrainQuery* queries, uint32_t n, const uint64_t* seg_off, uint32_t n_segs,
+                                const uint32_t* err, uint64_t* hdr, hipStream_t s) {
+  hipLaunchKernelGGL(k_drain_offsets, dim3((n + 2 + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, queries, n,
+                     seg_off, n_segs, err, hdr);
+  return hipGetLastError();
+}
 
 hipError_t launch_drain_count(const DrainArgs& a, uint32_t n_segs, uint64_t* cnt, hipStream_t s) {
   const uint32_t per = kCountBlock / kWave;

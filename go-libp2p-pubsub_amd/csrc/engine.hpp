@@ -447,6 +447,43 @@ struct ps_engine {
     uint64_t slab_ids = 64ull << 20;  // ids per slab (A/B: PSAMD_DRAIN_SLAB_IDS, at least one segment)
     bool staged = true;               // LDS-staged emit (A/B: PSAMD_DRAIN_EMIT=direct)
     bool timing = false;              // PSAMD_DRAIN_TIMING=1: phases run apart, times to stderr
+    // the tables the device holds for `seq`, wherever they were built (the
+    // synchronous build above, or ps_drain_begin's blocks below); every use
+    // is ordered on `stream`
+    const psamd::DrainTopic* p_topics = nullptr;
+    const psamd::DrainGroup* p_groups = nullptr;
+    const uint32_t* p_ids = nullptr;
+    const uint64_t* p_mask = nullptr;
+    const uint32_t* p_order = nullptr;
+
+    // ps_drain_begin / ps_drain_end.  The window's tables:
+    // one uploaded block (topics, groups, the build's message arrays, a
+    // gather topic's order), the id table (device-built positions, then the
+    // gather topics' ids), the mask words with the error word behind them,
+    // the check's keys.
+    psamd::DevBuf d_ablock, d_aids, d_amask, d_akeys;
+    uint32_t* d_err = nullptr;  // the last device build's error word (in d_amask)
+    // Two drains may be outstanding, in slots that alternate.  A slot owns
+    // its pinned input staging (queries and, when it builds them, the
+    // window's table block), its count / offset / scan / result buffers and
+    // its pinned view: (n + 2) u64 header words (off[0..n], the error word),
+    // then from hdr_bytes the ids.
+    struct Slot {
+      bool enqueued = false;      // work is on the GPU (else the view was written by the host)
+      bool emit_pending = false;  // ev_emit is recorded and ps_drain_end has not seen it complete
+      const void* seen = nullptr;  // the row set its emit reads
+      uint8_t* h_in = nullptr;
+      size_t in_cap = 0;
+      uint8_t* h_res = nullptr;
+      uint8_t* h_res_dev = nullptr;  // h_res, device-mapped
+      size_t res_cap = 0;
+      psamd::DevBuf d_queries, d_cnt, d_off, d_scan, d_res;
+      hipEvent_t ev_emit = nullptr, ev_done = nullptr;
+      size_t n = 0, hdr_bytes = 0;
+      uint64_t bound = 0;
+    } slot[2];
+    uint32_t slot_head = 0, slot_count = 0;
+    bool mapped_out = false;  // emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)
   } drain;
 
   // asynchronous runs (ps_run_async / ps_wait): the last window of a run may
@@ -578,6 +615,10 @@ int upload_graph(ps_engine* e);
 // run.cpp: the engine stream waits for tstream's last twin window (a no-op
 // when none is pending); every change of shared device state goes after it
 int twin_join(ps_engine* e);
+// run.cpp: stream s, about to start a window into the current row set (d_seen
+// & co.), waits for every pending ps_drain_begin emit that reads that set (a
+// no-op when none is pending, or for `stream`, which the drains run on)
+int drain_fence(ps_engine* e, hipStream_t s);
 
 // plan.cpp (host only: no device calls)
 int plan_window_layout(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win,

@@ -608,4 +608,32 @@ hipError_t drain_scan(void* temp, size_t* temp_bytes, const uint64_t* cnt, uint6
 hipError_t launch_drain_emit(const DrainArgs& a, uint32_t seg_lo, uint32_t seg_hi, const uint64_t* off, uint64_t off0,
                              uint32_t* out, uint64_t out_cap, bool staged, hipStream_t s);
 
+// The mask-layout tables of a window built on the device (ps_drain_begin):
+// window message j of the n_built topics that take this build (topic[k]'s
+// messages are j in [msg0[k], msg0[k + 1]); their tables lie back to back
+// from position 0, so a topic's first mask word is tab0 / 64) has run index
+// idx[j], row bit bit[j] and start round start[j].  ids and mask are cleared
+// (kNone / 0) on the stream before the build; err is cleared with them.
+constexpr uint32_t kDrainErrOrder = 1;  // a topic's arrival keys do not ascend with the row bit
+constexpr uint32_t kDrainErrBit = 2;    // a bit past the row, or two messages on one bit
+struct DrainBuild {
+  const DrainTopic* topics;
+  const uint32_t* topic;  // [n_built]
+  const uint32_t* msg0;   // [n_built + 1]
+  const uint32_t* idx;
+  const uint32_t* bit;
+  const uint32_t* start;
+  uint32_t n_built, n_msgs, last_first;
+  uint64_t n_pos;  // table positions of the built topics together
+  uint32_t* ids;
+  uint64_t* mask;
+  uint64_t* keys;  // start round << 32 | run index, by position (the check's scratch)
+  uint32_t* err;
+};
+// k_drain_tables, then k_drain_tables_check
+hipError_t launch_drain_tables(const DrainBuild& b, hipStream_t s);
+// hdr[q] = seg_off[queries[q].seg0] for q < n, hdr[n] = seg_off[n_segs], hdr[n + 1] = *err
+hipError_t launch_drain_offsets(const DrainQuery* queries, uint32_t n, const uint64_t* seg_off, uint32_t n_segs,
+                                const uint32_t* err, uint64_t* hdr, hipStream_t s);
+
 }  // namespace psamd

@@ -177,6 +177,13 @@ int twin_join(ps_engine* e) {
   return PS_OK;
 }
 
+int drain_fence(ps_engine* e, hipStream_t s) {
+  if (s == e->stream) return PS_OK;  // (the drains are enqueued on it: ordered already)
+  for (auto& S : e->drain.slot)
+    if (S.emit_pending && S.seen == e->d_seen.p) HIP_TRY(hipStreamWaitEvent(s, S.ev_emit, 0), "wait for a pending drain");
+  return PS_OK;
+}
+
 namespace {
 
 int stage_uploads(ps_engine* e, const Upload* ups, size_t n, hipStream_t s, StageCopy* fold = nullptr,
@@ -728,6 +735,12 @@ int run_window(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<
     s = e->pstream;
     ++e->overlapped;
   }
+  // s starts the window (`stream`, a twin's tstream, an overlapped window's
+  // pstream): off `stream`, a pending ps_drain_begin emit that reads the row
+  // set this window is about to write goes first.  A twin or an
+  // alternating-set window writes the set its predecessor's drain does not
+  // read, and waits for none of it.
+  if ((rc = drain_fence(e, s))) return rc;
   // the window's first kernel also copies the staged uploads, applies the
   // round-0 seeds of tree roots and clears the pull partial slots (level
   // mode without meshes; the eager seen clear below would erase the seeds)

@@ -153,6 +153,8 @@ PROTOTYPES = [
     ("ps_read_delivered", C.c_int, [_P, _u32, _u8p]),
     ("ps_read_peer_messages", C.c_int, [_P, _u32, _u32, _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ps_drain", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u64p, _u32p, C.c_size_t, _u64p]),
+    ("ps_drain_begin", C.c_int, [_P, _u32p, _u32p, C.c_size_t]),
+    ("ps_drain_end", C.c_int, [_P, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -238,6 +240,7 @@ class Engine:
             raise EngineError(rc, "ps_create failed (is a GPU visible?)")
         self._h = h
         self._L = L
+        self._drain_n = []  # query counts of the drains begun and not ended
         if plan:
             self.set_plan(**plan)
 
@@ -421,6 +424,30 @@ class Engine:
         ids = np.empty(total.value, dtype=np.uint32)
         self._check(self._L.ps_drain(self._h, tp, pp, n, op, _p(ids, C.c_uint32), ids.size, C.byref(total)))
         return off, ids
+
+    def drain_begin(self, topics, peers):
+        """Enqueues drain(topics, peers) of the last window of the last run
+        enqueued (ps_drain_begin) and returns without waiting for it; at most
+        two may be outstanding.  drain_end() completes the oldest."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        p = np.ascontiguousarray(peers, dtype=np.uint32)
+        if t.ndim != 1 or t.shape != p.shape:
+            raise ValueError("topics and peers must be 1-d arrays of one length")
+        self._check(self._L.ps_drain_begin(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size))
+        self._drain_n.append(t.size)
+
+    def drain_end(self, copy: bool = True):
+        """(off, ids) of the oldest drain_begin, as drain() returns them
+        (ps_drain_end).  copy=False: views of the engine's pinned memory,
+        valid until the next drain_begin."""
+        op, mp, total = _u64p(), _u32p(), C.c_uint64()
+        rc = self._L.ps_drain_end(self._h, C.byref(op), C.byref(mp), C.byref(total))
+        if rc != -8 and self._drain_n:  # (PS_E_NOTREADY: no slot was completed)
+            n = self._drain_n.pop(0)
+        self._check(rc)
+        off = np.ctypeslib.as_array(op, shape=(n + 1,))
+        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        return (off.copy(), ids.copy()) if copy else (off, ids)
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -298,6 +298,31 @@ int ps_read_peer_messages(ps_engine* e, uint32_t topic, uint32_t peer, uint32_t*
  * written for a topic or peer out of range. */
 int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint64_t* off_out,
              uint32_t* msg_out, size_t cap, uint64_t* total_out);
+/* ps_drain in two halves, for pipelined batches (as ps_run_async / ps_wait).
+ * ps_drain_begin answers the same queries as ps_drain for the last window of
+ * the last run *enqueued* (ps_run, or ps_run_async whether or not ps_wait has
+ * returned for it), and only enqueues: it returns while that run may still
+ * be executing.  ps_drain_end completes the oldest drain begun and lends the
+ * caller its result: query q's ids are (*msg_out)[(*off_out)[q] ..
+ * (*off_out)[q+1]), *off_out has n + 1 entries, *total_out = (*off_out)[n],
+ * list for list what ps_drain returns for that window.  Both pointers name
+ * pinned memory the engine owns, valid until the next ps_drain_begin or
+ * ps_destroy.
+ *   At most two drains are outstanding (two slots that alternate): a third
+ * ps_drain_begin returns PS_E_STATE; ps_drain_end with none outstanding and
+ * ps_drain_begin before any run return PS_E_NOTREADY; a topic or peer out of
+ * range returns PS_E_RANGE with nothing enqueued and no slot taken; n == 0 is
+ * a valid drain (off = {0}).  The result buffers are sized by an upper bound
+ * (the window's message count of each resolvable query's topic, summed); a
+ * bound above 2^30 ids returns PS_E_RANGE: use ps_drain, which emits in
+ * slabs.  A multi-rank engine returns PS_E_STATE.  A run split into several
+ * windows drains its last one, as ps_drain does.  ps_drain_end returns
+ * PS_E_STATE when the device-side check of the window's tables failed.  When
+ * the ps_wait of the run a drain belongs to fails (a k_flood timeout), the
+ * view's content is unspecified.  Every other call stays valid, and
+ * stream-ordered as before, while drains are outstanding. */
+int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n);
+int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

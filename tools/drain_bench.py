@@ -11,6 +11,20 @@ ps_read_peer_messages, on a workload of psengine/workloads.py after one step.
       scaled to --queries: the unchanged one-subscriber path
 
 Prints one JSON line and, with --out DIR, writes DIR/drain_bench.json.
+
+--pipelined: the drain in two halves (ps_drain_begin / ps_drain_end) inside the
+pipelined step loop, for 256, 1024 and 4096 pairs (--pipelined-queries), wall
+ms/step over --steps timed steps after --warmup:
+  (i)   publish, ps_run_async, ps_wait of the previous: no drain (bench.py's loop)
+  (ii)  ps_run then ps_drain, every step: the serial sink
+  (iii) publish, ps_run_async, ps_drain_begin, ps_wait and ps_drain_end of the
+        previous; the view copied out of device memory (copy) and emitted
+        straight into mapped pinned memory (mapped)
+with the host time inside ps_drain_begin, ps_overlapped_windows(), the link
+time of the view's bytes (the copy phase of a timed ps_drain in the same
+process), the host phases of the first synchronous drain after a window and
+the device time of k_drain_tables and its check.  Writes
+DIR/drain_async_bench.json.
 """
 from __future__ import annotations
 
@@ -101,6 +115,171 @@ def timed_phases(wl, qt, qp, emit, reps):
         return total, best, ids[:total].copy(), off.copy()
 
 
+def norm(ids):
+    """Message ids relative to the step's first (every step publishes the same batch under new ids)."""
+    return ids - ids.min() if ids.size else ids
+
+
+def fresh_engine(wl, env):
+    for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT", "PSAMD_DRAIN_ASYNC_OUT"):
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    eng = PE.Engine(wl.n_peers, len(wl.topics), seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    for k in env:
+        os.environ.pop(k, None)
+    return eng
+
+
+def loop_plain(eng, wl, n):
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        eng.run_async()
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+    eng.wait()
+
+
+def loop_serial(eng, wl, n, qt, qp, off, ids):
+    for _ in range(n):
+        eng.publish(wl.msg_topics)
+        eng.run()
+        rc, _ = raw_drain(eng, qt, qp, off, ids)
+        assert rc == 0, rc
+
+
+def loop_async(eng, wl, n, qt, qp, begin_s):
+    """Returns the last view (a copy).  begin_s: host seconds inside ps_drain_begin, appended per step."""
+    L, h = eng._L, eng._h
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    tp, pp = qt.ctypes.data_as(u32p), qp.ctypes.data_as(u32p)
+    op, mp, total = u64p(), u32p(), C.c_uint64()
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        eng.run_async()
+        t0 = time.perf_counter()
+        rc = L.ps_drain_begin(h, tp, pp, qt.size)
+        begin_s.append(time.perf_counter() - t0)
+        assert rc == 0, rc
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            rc = L.ps_drain_end(h, C.byref(op), C.byref(mp), C.byref(total))
+            assert rc == 0, rc
+    eng.wait()
+    rc = L.ps_drain_end(h, C.byref(op), C.byref(mp), C.byref(total))
+    assert rc == 0, rc
+    off = np.ctypeslib.as_array(op, shape=(qt.size + 1,)).copy()
+    ids = np.ctypeslib.as_array(mp, shape=(max(total.value, 1),))[:total.value].copy()
+    return off, ids
+
+
+def pipelined_main(a, wl):
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "steps": a.steps,
+           "warmup": a.warmup, "rows": []}
+    counts = [int(x) for x in a.pipelined_queries.split(",")]
+    queries = {n: pick_queries(wl, n, a.seed) for n in counts}
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        fn()
+        return 1e3 * (time.perf_counter() - t0) / a.steps
+
+    # the timing engine: link time of each view's bytes, the first-call host
+    # split and the device table build (every phase synchronised: not a wall figure)
+    link, first_call, tables_dev, want = {}, {}, {}, {}
+    eng = fresh_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for n in counts:
+            qt, qp = queries[n]
+            eng.publish(wl.msg_topics)
+            eng.run()
+            off = np.empty(n + 1, dtype=np.uint64)
+            with StderrCapture() as cap:
+                t0 = time.perf_counter()
+                rc, total = raw_drain(eng, qt, qp, off, None)
+                wall = 1e3 * (time.perf_counter() - t0)
+            if "engine_first_drain_sizing_call" not in res:  # (node-space mirrors and peer maps built here)
+                m = re.search(r"psamd drain: .*", cap.text)
+                cold = {k: float(v) for k, v in re.findall(r"(host_\w+_ms) ([0-9.]+)", m.group(0))} if m else {}
+                cold.update(wall_ms=wall, queries=n)
+                res["engine_first_drain_sizing_call"] = cold
+            ids = np.empty(max(total, 1), dtype=np.uint32)
+            eng.publish(wl.msg_topics)
+            eng.run()
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call after the window builds its tables)
+                with StderrCapture() as cap:
+                    t0 = time.perf_counter()
+                    rc, _ = raw_drain(eng, qt, qp, off, ids)
+                    wall = 1e3 * (time.perf_counter() - t0)
+                assert rc == 0, rc
+                m = re.search(r"psamd drain: .*", cap.text)
+                rows.append({k: float(v) for k, v in re.findall(r"(\w+_ms) ([0-9.]+)", m.group(0))})
+                rows[-1]["wall_ms"] = wall
+            first_call[n] = rows[0]
+            link[n] = min(r["copy_ms"] for r in rows[1:])
+            want[n] = (off.copy(), ids[:total].copy())
+            eng.publish(wl.msg_topics)
+            eng.run()
+            with StderrCapture() as cap:
+                eng.drain_begin(qt, qp)
+                eng.drain_end()
+            m = re.search(r"psamd drain tables: .*device_ms ([0-9.]+)", cap.text)
+            tables_dev[n] = {"device_ms": float(m.group(1)), "line": m.group(0)}
+    res["first_sync_drain_after_a_window"] = {str(n): first_call[n] for n in counts}
+    res["k_drain_tables_plus_check"] = {str(n): tables_dev[n] for n in counts}
+
+    eng = fresh_engine(wl, {})
+    with eng:
+        loop_plain(eng, wl, a.warmup)
+        o0 = eng.overlapped_windows()
+        res["plain_ms_per_step"] = timed(lambda: loop_plain(eng, wl, a.steps))
+        res["plain_overlapped_windows"] = eng.overlapped_windows() - o0
+        serial = {}
+        for n in counts:
+            qt, qp = queries[n]
+            off = np.empty(n + 1, dtype=np.uint64)
+            ids = np.empty(max(want[n][1].size, 1), dtype=np.uint32)
+            loop_serial(eng, wl, a.warmup, qt, qp, off, ids)
+            serial[n] = timed(lambda: loop_serial(eng, wl, a.steps, qt, qp, off, ids))
+            assert np.array_equal(off, want[n][0]) and np.array_equal(norm(ids[:want[n][1].size]), norm(want[n][1]))
+    asyn = {}
+    for variant in ("copy", "mapped"):
+        eng = fresh_engine(wl, {"PSAMD_AB": "1", "PSAMD_DRAIN_ASYNC_OUT": variant})
+        with eng:
+            for n in counts:
+                qt, qp = queries[n]
+                loop_async(eng, wl, a.warmup, qt, qp, [])
+                o0 = eng.overlapped_windows()
+                begin_s = []
+                t0 = time.perf_counter()
+                off, ids = loop_async(eng, wl, a.steps, qt, qp, begin_s)
+                ms = 1e3 * (time.perf_counter() - t0) / a.steps
+                assert np.array_equal(off, want[n][0]) and np.array_equal(norm(ids), norm(want[n][1]))
+                asyn[(variant, n)] = {"ms_per_step": ms, "begin_host_us_median": 1e6 * float(np.median(begin_s)),
+                                      "begin_host_us_max": 1e6 * float(np.max(begin_s)),
+                                      "overlapped_windows": eng.overlapped_windows() - o0}
+    for n in counts:
+        best = min(("copy", "mapped"), key=lambda v: asyn[(v, n)]["ms_per_step"])
+        floor = max(res["plain_ms_per_step"], link[n])
+        res["rows"].append({
+            "queries": n, "ids": int(want[n][1].size), "id_bytes": 4 * int(want[n][1].size),
+            "link_ms": link[n], "serial_ms_per_step": serial[n],
+            "async_copy": asyn[("copy", n)], "async_mapped": asyn[("mapped", n)], "faster": best,
+            "floor_ms": floor, "floor_is": "plain step" if res["plain_ms_per_step"] >= link[n] else "link time",
+            "async_over_floor": asyn[(best, n)]["ms_per_step"] / floor,
+            "serial_over_async": serial[n] / asyn[(best, n)]["ms_per_step"]})
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "drain_async_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WL.CONFIGS))
@@ -110,8 +289,14 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pipelined", action="store_true", help="the drain inside the pipelined step loop (see above)")
+    ap.add_argument("--pipelined-queries", default="256,1024,4096")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.pipelined:
+        return pipelined_main(a, wl)
     qt, qp = pick_queries(wl, a.queries, a.seed)
     res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "queries": a.queries}
 
