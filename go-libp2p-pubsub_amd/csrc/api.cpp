@@ -463,7 +463,20 @@ int ps_topic_set_tree(ps_engine* e, uint32_t topic, uint32_t root, const uint32_
   for (uint32_t c = 0; c < e->cfg.n_peers; ++c)
     if (parent[c] != PS_NONE && parent[c] >= e->cfg.n_peers) return e->fail(PS_E_INVAL, "parent id out of range");
   TopicHost& T = e->topics[topic];
+  // a tree set again over a built one keeps the last build's level sizes:
+  // the GPU rebuild sizes its launches from them, as it does for a join
+  // topic after churn (graph.cpp; a level that outgrew them is a counted
+  // retry).  Everything else of the record starts afresh.
+  TopicHost keep;
+  if (T.exists && T.kind == Kind::Parent) {
+    keep.depth = T.depth;
+    keep.top_levels = T.top_levels;
+    keep.level_off.swap(T.level_off);
+  }
   T = TopicHost{};
+  T.depth = keep.depth;
+  T.top_levels = keep.top_levels;
+  T.level_off.swap(keep.level_off);
   T.exists = true;
   T.kind = Kind::Parent;
   T.root = root;
@@ -1487,6 +1500,8 @@ int ps_plan_create(uint32_t n_peers, uint32_t n_topics, const uint32_t* roots, c
     return rc;
   }
   build_flags(e);
+  ++e->build_rep.host_builds;
+  e->build_rep.last_kind = 2;
   e->graph_dirty = e->flags_dirty = false;
   ++e->graph_epoch;
   ++e->flags_epoch;
@@ -1659,6 +1674,66 @@ int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size
     }
     default:
       return e->fail(PS_E_INVAL, "unknown plan table");
+  }
+  *n_out = v.size();
+  if (v.size() > cap) return PS_E_RANGE;
+  std::copy(v.begin(), v.end(), out);
+  return PS_OK;
+}
+
+int ps_graph_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out) {
+  if (!e || !n_out || (cap && !out)) return PS_E_INVAL;
+  if (!e->host_only) {
+    if (e->infl_count) return e->fail(PS_E_STATE, "asynchronous runs pending: ps_wait first");
+    if (e->drain.slot_count) return e->fail(PS_E_STATE, "a drain is outstanding: ps_drain_end first");
+    // the node space as the next ps_run would find it
+    int rc = upload_graph(e);
+    if (rc) return rc;
+    if (e->gpu_graph && what <= PS_GRAPH_COL) {
+      rc = ensure_mirrors(e);
+      if (rc) return rc;
+    }
+  }
+  std::vector<uint64_t> v;
+  const size_t nn = e->n_nodes;
+  switch (what) {
+    case PS_GRAPH_NODE_PEER:
+      v.assign(e->node_peer.begin(), e->node_peer.begin() + nn);
+      break;
+    case PS_GRAPH_NODE_PARENT:
+      v.assign(e->node_parent.begin(), e->node_parent.begin() + nn);
+      break;
+    case PS_GRAPH_NODE_TOPIC:
+      v.assign(e->node_topic.begin(), e->node_topic.begin() + nn);
+      break;
+    case PS_GRAPH_NODE_FLAGS:
+      v.assign(e->node_flags.begin(), e->node_flags.begin() + nn);
+      break;
+    case PS_GRAPH_ROW_PTR:
+      v.assign(e->row_ptr.begin(), e->row_ptr.begin() + nn + 1);
+      break;
+    case PS_GRAPH_COL:
+      v.assign(e->col.begin(), e->col.begin() + e->row_ptr[nn]);
+      break;
+    case PS_GRAPH_TOPIC: {
+      if (index >= e->topics.size()) return e->fail(PS_E_RANGE, "topic");
+      const TopicHost& T = e->topics[index];
+      const bool any = T.exists && T.n_nodes;
+      v = {T.exists ? 1u : 0u, T.nbase, any ? T.n_nodes : 0u, any ? T.depth : 0u, any ? T.max_deg : 0u, T.top_levels};
+      if (any) {
+        v.insert(v.end(), T.level_off.begin(), T.level_off.end());
+        v.insert(v.end(), T.level_internal.begin(), T.level_internal.end());
+      }
+      break;
+    }
+    case PS_GRAPH_BUILD: {
+      const auto& r = e->build_rep;
+      v = {r.gpu_builds, r.host_builds, r.fb_stall, r.fb_attempts, r.fb_capacity, r.fb_depth,
+           r.redo_grid, r.redo_order, r.redo_depth, r.last_kind, r.last_attempts};
+      break;
+    }
+    default:
+      return e->fail(PS_E_INVAL, "unknown graph table");
   }
   *n_out = v.size();
   if (v.size() > cap) return PS_E_RANGE;

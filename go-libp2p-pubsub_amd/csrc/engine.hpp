@@ -284,6 +284,16 @@ struct ps_engine {
   bool gpu_graph = false;     // the current node space was built on the GPU
   bool mirrors_valid = true;  // host copies of node_peer / flags / CSR are current
   std::vector<uint32_t> pairs_host, gstat_host, roots_host;
+  // which build produced the node spaces since creation (PS_GRAPH_BUILD,
+  // include/psengine_plan.h): plain host counters, bumped by gpu_build_graph
+  // and upload_graph (the probe: its one host build)
+  struct BuildReport {
+    uint64_t gpu_builds = 0, host_builds = 0;
+    uint64_t fb_stall = 0, fb_attempts = 0, fb_capacity = 0, fb_depth = 0;  // fall-backs to the host build
+    uint64_t redo_grid = 0, redo_order = 0, redo_depth = 0;                // GPU attempts repeated
+    uint32_t last_kind = 0;      // 0 none yet, 1 GPU, 2 host
+    uint32_t last_attempts = 0;  // GPU attempts of the last build (a host build after a fall-back keeps them)
+  } build_rep;
   bool live_dev_valid = false;  // d_live holds `live` (uploaded again only after ps_set_live)
   bool flags_built = false;     // the last GPU build wrote the node flags (no flags pass needed)
   uint32_t* pairs_pinned = nullptr;  // pinned staging of the parent deltas

@@ -514,7 +514,10 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
     if (e->topics[t].exists) act.push_back(t);
   const uint32_t na = static_cast<uint32_t>(act.size());
   const uint64_t cap = static_cast<uint64_t>(na) * n + 16;
+  auto& rep = e->build_rep;
+  rep.last_attempts = 0;
   if (cap >= 0xFFFFFFF0ull) {  // (every peer of every topic as a node: the host build sizes exactly)
+    ++rep.fb_capacity;
     *fallback = true;
     return PS_OK;
   }
@@ -577,6 +580,7 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
   const auto tb2 = clk::now();
   for (int attempt = 0;; ++attempt) {
     if (attempt >= 8) {
+      ++rep.fb_attempts;
       *fallback = true;
       return PS_OK;
     }
@@ -679,11 +683,14 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
     HIP_TRY(hipMemcpyAsync(blk.data(), gstat, blk_words * 4, hipMemcpyDeviceToHost, s), "read build block");
     HIP_TRY(hipStreamSynchronize(s), "sync");
     const uint32_t ev = gs[o_err];
+    rep.last_attempts = static_cast<uint32_t>(attempt) + 1;
     if (ev & kBuildErrStall) {
+      ++rep.fb_stall;
       *fallback = true;  // a stalled look-back: build on the host
       return PS_OK;
     }
     bool redo = false;
+    bool deeper = false;
     if (ev & kBuildErrGrid) {
       full_grids = true;
       redo = true;
@@ -696,16 +703,21 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
       const uint32_t done = gs[static_cast<size_t>(t) * kGstWords + kGstDone];
       if (lh[512 * t + done + 1] != lh[512 * t + done] || done < d_to[t]) {
         if (d_to[t] >= kBuildMaxDepth - 1 && lh[512 * t + done + 1] != lh[512 * t + done]) {
+          ++rep.fb_depth;
           *fallback = true;  // deeper than the level tables
           return PS_OK;
         }
         if (!(ev & (kBuildErrGrid | kBuildErrOrder)) && done >= d_to[t]) {
           d_to[t] = std::min<uint32_t>(kBuildMaxDepth - 1, 2 * d_to[t] + 8);
-          redo = true;
+          redo = deeper = true;
         }
       }
     }
     if (!redo) break;
+    // (a redo's reasons, counted once the attempt is known not to fall back)
+    if (ev & kBuildErrGrid) ++rep.redo_grid;
+    if (ev & kBuildErrOrder) ++rep.redo_order;
+    if (deeper) ++rep.redo_depth;
   }
   for (auto& q : e->early_q) q.ready = q.launched;
   const auto tb3 = clk::now();
@@ -760,6 +772,8 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
   e->gpu_graph = true;
   e->mirrors_valid = false;
   e->flags_built = true;  // (node flags from the current live mask: the flags pass can skip them)
+  ++rep.gpu_builds;
+  rep.last_kind = 1;
   return PS_OK;
 }
 
@@ -771,6 +785,7 @@ int upload_graph(ps_engine* e) {
   if (!e->graph_dirty && !e->flags_dirty) return PS_OK;
   if (e->graph_dirty) {
     bool built = false;
+    e->build_rep.last_attempts = 0;
     if (can_gpu_build(e)) {
       bool fallback = false;
       int rc = gpu_build_graph(e, &fallback);
@@ -780,6 +795,8 @@ int upload_graph(ps_engine* e) {
     if (!built) {
       int rc = build_graph(e);
       if (rc) return rc;
+      ++e->build_rep.host_builds;
+      e->build_rep.last_kind = 2;
       e->gpu_graph = false;
       e->mirrors_valid = true;
       const size_t nn = e->n_nodes;

@@ -170,6 +170,46 @@ PROTOTYPES = [
     ("ps_partition_owner", C.c_int, [_u32, _u32, _u32p, _u32, C.POINTER(DistConfig), _i32p]),
 ]
 
+# ps_graph_get tables (include/psengine_plan.h, bound by psengine.plan): test
+# support, not the drop-in boundary
+G_NODE_PEER, G_NODE_PARENT, G_NODE_TOPIC, G_NODE_FLAGS, G_ROW_PTR, G_COL, G_TOPIC, G_BUILD = range(8)
+NODE_LIVE, NODE_INTERNAL, NODE_SPLIT = 1, 2, 4
+BUILD_FIELDS = ("gpu_builds", "host_builds", "fallback_stall", "fallback_attempts", "fallback_capacity",
+                "fallback_depth", "redo_grid", "redo_order", "redo_depth", "last_kind", "last_attempts")
+BUILD_KINDS = {0: None, 1: "gpu", 2: "host"}
+
+
+def graph_get(L, h, what: int, index: int = 0) -> np.ndarray:
+    """ps_graph_get(what, index) of engine handle h as a uint64 array."""
+    n = C.c_size_t()
+    rc = L.ps_graph_get(h, what, index, None, 0, C.byref(n))
+    if rc not in (PS_OK, -7):
+        raise EngineError(rc, (L.ps_last_error(h) or b"ps_graph_get").decode())
+    out = np.zeros(max(1, n.value), dtype=np.uint64)
+    rc = L.ps_graph_get(h, what, index, _p(out, C.c_uint64), out.shape[0], C.byref(n))
+    if rc != PS_OK:
+        raise EngineError(rc, (L.ps_last_error(h) or b"ps_graph_get").decode())
+    return out[:n.value]
+
+
+def graph_topic(v) -> dict:
+    """PS_GRAPH_TOPIC's values by name."""
+    d = {k: int(x) for k, x in zip(("exists", "nbase", "n_nodes", "depth", "max_deg", "top_levels"), v)}
+    depth = d["depth"]
+    d["level_off"] = v[6:6 + depth + 2].astype(np.int64)
+    d["level_internal"] = v[6 + depth + 2:6 + 2 * depth + 3].astype(np.int64)
+    return d
+
+
+def build_report(v) -> dict:
+    """PS_GRAPH_BUILD's values by name; last_kind as "gpu" / "host" / None;
+    "fallbacks" and "redos" are the sums over their reasons."""
+    d = {k: int(x) for k, x in zip(BUILD_FIELDS, v)}
+    d["last_kind"] = BUILD_KINDS[d["last_kind"]]
+    d["fallbacks"] = sum(d[k] for k in BUILD_FIELDS if k.startswith("fallback_"))
+    d["redos"] = sum(d[k] for k in BUILD_FIELDS if k.startswith("redo_"))
+    return d
+
 _lib = None
 
 
@@ -453,6 +493,22 @@ class Engine:
         d = C.c_uint64()
         self._check(self._L.ps_seen_digest(self._h, C.byref(d)))
         return d.value
+
+    # the node space (tests): ps_graph_get
+    def graph(self, what: int, index: int = 0) -> np.ndarray:
+        """One table of the node space, brought up to date as the next run
+        would (ps_graph_get; G_* above)."""
+        from . import plan
+
+        return graph_get(plan.lib(), self._h, what, index)
+
+    def graph_topic(self, topic: int) -> dict:
+        return graph_topic(self.graph(G_TOPIC, topic))
+
+    def build_report(self) -> dict:
+        """Which build produced the node spaces so far: counters since
+        creation and the last build's kind and GPU attempts."""
+        return build_report(self.graph(G_BUILD))
 
     def overlapped_windows(self) -> int:
         """Pipelined windows whose prefix ran beside the previous window."""

@@ -7,7 +7,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import DistConfig, EngineError, PART_PEER, PlanOpts, _P, _p, _u32arr, load
+from . import (DistConfig, EngineError, G_BUILD, G_TOPIC, PART_PEER, PlanOpts, _P, _p, _u32arr, build_report,
+               graph_get, graph_topic, load)
 
 INFO, NODES, PARENT, GHOST_REF, TOPIC, LAYOUT, ROUND_KIND, PULL, PAIR, XCHG, SEGS, SHIP, PACK, CHAIN = range(14)
 CHAIN_FIELDS = ("node_begin", "node_end", "topic", "W", "row0", "w0", "S", "levels", "r0", "group")
@@ -22,6 +23,8 @@ PROTOTYPES = [
     ("ps_plan_window", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_size_t, C.c_uint32]),
     ("ps_plan_get", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_size_t,
                               C.POINTER(C.c_size_t)]),
+    ("ps_graph_get", C.c_int, [_P, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_size_t,
+                               C.POINTER(C.c_size_t)]),
 ]
 _bound = False
 
@@ -103,6 +106,16 @@ class Plan:
         if rc != 0:
             raise EngineError(rc, f"ps_plan_get({what}, {index})")
         return out[:n.value]
+
+    def graph(self, what: int, index: int = 0) -> np.ndarray:
+        """One table of the probe's node space (ps_graph_get; psengine.G_*)."""
+        return graph_get(lib(), self._h, what, index)
+
+    def graph_topic(self, topic: int) -> dict:
+        return graph_topic(self.graph(G_TOPIC, topic))
+
+    def build_report(self) -> dict:
+        return build_report(self.graph(G_BUILD))
 
     def info(self) -> dict:
         v = self.get(INFO)

@@ -52,6 +52,29 @@ int ps_plan_window(ps_engine* e, const uint32_t* topic_of_msg, const uint32_t* s
                                  node_end, topic, W, row0, w0, S, levels, r0, group, first[0..6] */
 int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out);
 
+/* ps_graph_get(what, index): the node space itself and which
+ * build produced it, on a real engine or on the probe; values and *n_out as
+ * ps_plan_get.  A real engine first brings its node space up to date exactly
+ * as ps_run would (the rebuild after topology changes, the flags after
+ * ps_set_live) and reads a GPU-built one back; it changes no later run.  If
+ * the topology changed since the last run (a run's own repairs and prunes
+ * count), that rebuild retires the last window's readbacks, as the next
+ * ps_run or ps_topic_depth would: read hops and digests first.
+ * PS_E_STATE while an asynchronous run or a drain is outstanding. */
+#define PS_GRAPH_NODE_PEER 0    /* per node: peer */
+#define PS_GRAPH_NODE_PARENT 1  /* per node: parent node (PS_NONE: root, or a parent on another rank) */
+#define PS_GRAPH_NODE_TOPIC 2   /* per node: topic */
+#define PS_GRAPH_NODE_FLAGS 3   /* per node: 1 live, 2 internal, 4 split */
+#define PS_GRAPH_ROW_PTR 4      /* nodes + 1 entries: a node's children are col[row_ptr[u] .. row_ptr[u + 1]) */
+#define PS_GRAPH_COL 5          /* per edge: child node */
+#define PS_GRAPH_TOPIC 6        /* index = topic: exists, nbase, n_nodes, depth, max_deg, top_levels, then (a
+                                   topic with nodes) level_off[0..depth+1], level_internal[0..depth] */
+#define PS_GRAPH_BUILD 7        /* since creation: GPU builds, host builds, fall-backs to the host build by
+                                   reason (stall, attempts, capacity, depth), repeated GPU attempts by reason
+                                   (grid, order, depth growth); then the last build: kind (0 none, 1 GPU,
+                                   2 host), GPU attempts */
+int ps_graph_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,20 @@ def make_engine(n, gpu_build, n_topics=1, **kw):
     return PE.Engine(n, n_topics, plan={"gpu_build": int(gpu_build)}, **kw)
 
 
+def assert_builds(eng, gpu_build, before=0, at_least=1):
+    """The engine's build report (ps_graph_get): a GPU-build engine built at
+    least `at_least` node spaces on the GPU since `before` and never fell
+    back to the host build; a host-build engine never used the GPU build.
+    Returns the count of its kind."""
+    rep = eng.build_report()
+    if gpu_build:
+        assert rep["gpu_builds"] >= before + at_least, (before, rep)
+        assert rep["fallbacks"] == 0 and rep["host_builds"] == 0 and rep["last_kind"] == "gpu", rep
+        return rep["gpu_builds"]
+    assert rep["gpu_builds"] == 0 and rep["last_kind"] == "host", rep
+    return rep["host_builds"]
+
+
 @pytest.mark.parametrize("gpu_build", [True, False])
 def test_cfg5_scaled_batches_match_oracle(gpu_build):
     """cfg5 shape at 20k peers: 90 % members, per batch 1 % leaves + 1 % joins,
@@ -35,6 +49,7 @@ def test_cfg5_scaled_batches_match_oracle(gpu_build):
     ot = O.Tree(wl.n_peers, 0, 2, 5, PE.Engine.topic_seed(seed, 0))
     WL.build_engine_topics(eng, wl)
     ot.join_all(wl.topics[0].join_order)
+    built = 0
     for b, (leave, join) in enumerate(plan):
         for p in leave:
             assert ot.leave(int(p)) in (0, -3)  # an orphaned peer cannot Part
@@ -52,6 +67,7 @@ def test_cfg5_scaled_batches_match_oracle(gpu_build):
             assert np.array_equal(eng.hops(first + m), exp), (b, m)
         assert run.deliveries == wl.n_msgs * int((exp != 0xFF).sum())
         assert np.array_equal(eng.parents(0), ot.parents()), b
+        built = assert_builds(eng, gpu_build, built)  # every batch's node space: a GPU build, no fall-back
     eng.close()
 
 
@@ -85,6 +101,7 @@ def test_cfg5_pipelined_churn_matches_oracle():
         assert np.array_equal(eng.parents(0), ot.parents()), b
     got.append(eng.wait().deliveries)
     assert got == want
+    assert_builds(eng, True, at_least=len(plan))  # one GPU build per batch at least, no fall-back
     eng.close()
 
 
@@ -99,6 +116,7 @@ def test_gpu_and_host_builds_agree_under_drops():
         e.topic_create(0, 0, 2, 5)
         e.join(0, np.arange(1, n, 2))
     members = set(range(1, n, 2))
+    built = [0, 0]
     for step in range(25):
         op = rng.random()
         if op < 0.3:
@@ -131,6 +149,10 @@ def test_gpu_and_host_builds_agree_under_drops():
             assert np.array_equal(engs[0].hops(firsts[0] + m), engs[1].hops(firsts[1] + m)), (step, m)
         assert engs[0].seen_digest() == engs[1].seen_digest(), step
         assert engs[0].depth(0) == engs[1].depth(0), step
+        # a step that changed the tree (or the first) rebuilt the node space: on the GPU, no fall-back
+        # (after the readbacks: the report brings the node space up to date, as depth() above does)
+        built = [assert_builds(e, g, built[i], at_least=1 if op < 0.6 or step == 0 else 0)
+                 for i, (e, g) in enumerate(zip(engs, (True, False)))]
     for e in engs:
         e.close()
 
@@ -149,6 +171,7 @@ def test_gpu_build_multi_topic_and_live_mask():
         st = e.run()
         out.append((st.deliveries, st.as_dict()["deliveries_per_round"], e.seen_digest(),
                     [e.depth(t) for t in range(len(wl.topics))]))
+        assert_builds(e, g)
         e.close()
     assert out[0] == out[1]
 
@@ -193,6 +216,8 @@ def test_gpu_build_prune_queries_shared_peers():
             assert np.array_equal(res[0], res[1]), (step, t)
             members[t] |= {int(p) for p, s in zip(join, res[0]) if s == 0}
             assert np.array_equal(engs[0].parents(t), engs[1].parents(t)), (step, t)
+    assert_builds(engs[0], True, at_least=8)  # a rebuild per step at least, each on the GPU
+    assert_builds(engs[1], False)
     for e in engs:
         e.close()
 
@@ -231,4 +256,5 @@ def test_cfg5_full_size_batches_match_oracle():
                 bad = np.nonzero(got != exp)[0][:8]
                 raise AssertionError(f"batch {b} msg {m}: peers {bad} got {got[bad]} want {exp[bad]}")
         assert np.array_equal(eng.parents(0), ot.parents()), b
+    assert_builds(eng, True, at_least=batches)
     eng.close()

@@ -6,6 +6,7 @@ exact count."""
 import numpy as np
 import pytest
 
+import graph_check as GC
 import oracle as O
 import psengine as PE
 
@@ -138,7 +139,9 @@ def test_deep_chain_beyond_255_hops(staggered, n):
     """Chains 700 and 5000 deep: more rounds than a hop byte holds and than
     the 4096 preallocated round rows.  Deliveries are exact; hops read back
     saturated at 254, as the restatement reports them; the host build takes
-    over from the GPU rebuild (depth > 254)."""
+    over from the GPU rebuild, which builds depths up to 253 and falls back
+    from depth 254 on (tests/test_gpu_build.py test_depth_boundary): the fall-
+    back is counted in the build report."""
     parent = np.full(n, O.NONE, dtype=np.uint32)
     parent[1:] = np.arange(n - 1)
     live = np.ones(n, dtype=np.uint8)
@@ -155,6 +158,9 @@ def test_deep_chain_beyond_255_hops(staggered, n):
         for m in (0, 1, k - 1):
             assert np.array_equal(e.hops(first + m), hops[0]), m
         assert e.depth(0) == (n - 1, n)
+        rep = e.build_report()
+        assert (rep["fallback_depth"], rep["last_kind"], rep["gpu_builds"], rep["host_builds"]) == (1, "host", 0, 1), rep
+        assert (rep["fallback_stall"], rep["fallback_attempts"], rep["fallback_capacity"]) == (0, 0, 0), rep
 
 
 def test_wide_join_beyond_65535_children():
@@ -173,6 +179,11 @@ def test_wide_join_beyond_65535_children():
         t.join_all(range(1, n))
         assert np.array_equal(par, t.parents())
         assert (par[1:w + 1] == 0).all()
+        # a GPU build (no fall-back) whose one child list is longer than the
+        # 4096 the build sorts: the right children under the root, in any order
+        rep = e.build_report()
+        assert (rep["last_kind"], rep["gpu_builds"], rep["host_builds"], rep["fallbacks"]) == ("gpu", 1, 0, 0), rep
+        GC.validate(GC.read(e), GC.reference(n, [(0, par)], np.ones(n, dtype=np.uint8)), "peer_upto_4096")
         first = e.publish(np.zeros(3))
         st = e.run()
         assert st.deliveries == 3 * (n - 1)
