@@ -186,6 +186,7 @@ static void read_switches(ps_engine* e) {
     e->drain.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
   if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.staged = std::strcmp(v, "direct") != 0;
   if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) e->drain.mapped_out = std::strcmp(v, "mapped") == 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) e->drain.share = std::strcmp(v, "private") != 0;
   if (const char* v = std::getenv("PSAMD_TWIN")) e->twin_on = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_NARROW")) e->expand_opts = std::atoi(v) == 0 ? kExpandNoNarrow : 0u;
   if (const char* v = std::getenv("PSAMD_CHAIN_WORDS_LEAD"))
@@ -988,6 +989,222 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
                  "copy_ms %.4f host_mirrors_ms %.4f host_tables_ms %.4f (%s) host_queries_ms %.4f\n",
                  n, n_segs, static_cast<unsigned long long>(total), k, D.staged ? "lds" : "direct", ms[0], ms[1], ms[2],
                  ms[3], host_ms[0], host_ms[1], tables_built ? "built" : "kept", host_ms[2]);
+  return PS_OK;
+}
+
+// ---- ps_drain_shared ---------------------------------------
+
+// ps_drain's answer with equal lists stored once.  k_drain_classify compares
+// every queried row of a mask-layout topic with the topic's message mask:
+// no message bit -> PS_NONE, every message bit -> the topic's shared list
+// (emitted from the mask itself), anything else -> a list of its own through
+// the count / scan / emit passes ps_drain uses.  The queries of arrival-order
+// (kDrainGather) topics have no mask to compare with: each takes a private
+// list.  Device -> host: 4 B x n verdicts, 8 B x (n_lists + 2) offsets, 4 B x
+// total ids.
+int ps_drain_shared(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint32_t* list_out,
+                    uint64_t* list_off_out, size_t list_cap, uint32_t* msg_out, size_t cap, uint32_t* n_lists_out,
+                    uint64_t* total_out) {
+  if (!e || !list_off_out || !n_lists_out || !total_out || (n && (!topic || !peer || !list_out)) || (cap && !msg_out))
+    return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_drain_shared on a multi-rank engine: use ps_drain");
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
+  if (const int rj = twin_join(e)) return rj;
+  for (size_t q = 0; q < n; ++q)
+    if (topic[q] >= e->topics.size() || peer[q] >= e->cfg.n_peers) return e->fail(PS_E_RANGE, "topic or peer out of range");
+  *n_lists_out = 0;
+  *total_out = 0;
+  if (n == 0) {
+    list_off_out[0] = 0;
+    return PS_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  auto& D = e->drain;
+  using hclock = std::chrono::steady_clock;
+  auto h_ms = [](hclock::time_point t0) { return std::chrono::duration<double, std::milli>(hclock::now() - t0).count(); };
+  double host_ms[2] = {0, 0};  // mirrors + tables + bins, list numbering
+  auto h0 = hclock::now();
+  int rc = ensure_mirrors(e);
+  if (!rc) rc = drain_tables(e);
+  if (!rc) rc = drain_streams(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  float ms[5] = {0, 0, 0, 0, 0};  // classify, count, scan, emit, copy (PSAMD_DRAIN_TIMING)
+  auto t_begin = [&]() { return D.timing ? hipEventRecord(D.ev_t[0], s) : hipSuccess; };
+  auto t_end = [&](int k) -> hipError_t {
+    if (!D.timing) return hipSuccess;
+    hipError_t r = hipEventRecord(D.ev_t[1], s);
+    if (r == hipSuccess) r = hipEventSynchronize(D.ev_t[1]);
+    float t = 0;
+    if (r == hipSuccess) r = hipEventElapsedTime(&t, D.ev_t[0], D.ev_t[1]);
+    ms[k] += t;
+    return r;
+  };
+
+  // queries -> nodes; those of mask-layout topics, sorted by topic (a
+  // counting sort: a topic's rows have one width), go to the classify pass
+  const uint32_t nt = static_cast<uint32_t>(D.topics.size());
+  constexpr uint32_t kOnHost = 0x80000000u;  // verdict decided here: | kDrainRow*
+  D.queries.resize(n);
+  D.verdict.assign(n, kOnHost);
+  std::vector<uint32_t> per_topic(nt + 1, 0);
+  std::vector<const uint32_t*> peer_map(nt, nullptr);  // (looked up once per topic, not per query)
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t t = topic[q];
+    const DrainTopic& T = D.topics[t];
+    DrainQuery& Q = D.queries[q];
+    Q = DrainQuery{t, 0, 0, 0};
+    if (!T.n_pos) continue;  // idle in the window
+    if (!peer_map[t]) peer_map[t] = drain_peer_map(e, t, e->last_topics[t]).data();
+    const uint32_t u = peer_map[t][peer[q]];
+    if (u == kNone) continue;  // the root, or not subscribed
+    Q.node = u;
+    if (T.flags & kDrainGather) {
+      D.verdict[q] = kOnHost | kDrainRowAny | kDrainRowMissing;
+    } else {
+      D.verdict[q] = 0;
+      ++per_topic[t + 1];
+    }
+  }
+  std::vector<DrainClassBin> bins;
+  uint64_t n_waves64 = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t n_q = per_topic[t + 1];
+    per_topic[t + 1] += per_topic[t];
+    if (!n_q) continue;
+    DrainClassBin B{};
+    B.topic = t;
+    B.q0 = per_topic[t];
+    B.n_q = n_q;
+    B.wave0 = static_cast<uint32_t>(n_waves64);
+    B.words = D.topics[t].n_pos / 64;
+    uint64_t steps = 0;  // of 64 lanes; a wave runs kDrainClassPer of them
+    if (B.words <= 64) {
+      while ((1u << B.lanes_log2) < B.words) ++B.lanes_log2;
+      steps = ((static_cast<uint64_t>(n_q) << B.lanes_log2) + 63) / 64;
+    } else {
+      B.waves = ceil_div(B.words, 64u);
+      steps = static_cast<uint64_t>(n_q) * B.waves;
+    }
+    n_waves64 += (steps + kDrainClassPer - 1) / kDrainClassPer;
+    if (n_waves64 * kDrainClassPer >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many rows in one drain");
+    bins.push_back(B);
+  }
+  const uint32_t n_waves = static_cast<uint32_t>(n_waves64);
+  const uint32_t n_class = per_topic[nt];
+  D.cqueries.resize(n_class);
+  for (size_t q = 0; q < n; ++q)
+    if (D.verdict[q] == 0) D.cqueries[per_topic[D.queries[q].topic]++] = DrainClassQuery{D.queries[q].node, static_cast<uint32_t>(q)};
+  host_ms[0] = h_ms(h0);
+
+  DrainArgs a{};
+  a.seen = e->d_seen.as<uint64_t>();
+  a.gen = e->d_gen.as<uint8_t>();
+  a.gen_cur = e->gen_cur;
+  a.topics = D.p_topics;
+  a.groups = D.p_groups;
+  a.mask = D.p_mask;
+  a.order = D.p_order;
+  a.ids = D.p_ids;
+  if (n_class) {
+    std::vector<uint32_t> got(n);
+    HIP_TRY(D.d_cbins.ensure(bins.size() * sizeof(DrainClassBin)), "alloc drain bins");
+    HIP_TRY(D.d_cqueries.ensure(static_cast<size_t>(n_class) * sizeof(DrainClassQuery)), "alloc drain queries");
+    HIP_TRY(D.d_verdict.ensure(n * 4), "alloc drain verdicts");
+    HIP_TRY(hipMemcpyAsync(D.d_cbins.p, bins.data(), bins.size() * sizeof(DrainClassBin), hipMemcpyHostToDevice, s),
+            "upload drain bins");
+    HIP_TRY(hipMemcpyAsync(D.d_cqueries.p, D.cqueries.data(), static_cast<size_t>(n_class) * sizeof(DrainClassQuery),
+                           hipMemcpyHostToDevice, s),
+            "upload drain queries");
+    HIP_TRY(hipMemsetAsync(D.d_verdict.p, 0, n * 4, s), "clear drain verdicts");
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(launch_drain_classify(a, D.d_cbins.as<DrainClassBin>(), static_cast<uint32_t>(bins.size()),
+                                  D.d_cqueries.as<DrainClassQuery>(), n_waves, D.d_verdict.as<uint32_t>(), s),
+            "k_drain_classify");
+    HIP_TRY(t_end(0), "event");
+    HIP_TRY(hipMemcpyAsync(got.data(), D.d_verdict.p, n * 4, hipMemcpyDeviceToHost, s), "read drain verdicts");
+    HIP_TRY(hipStreamSynchronize(s), "sync");  // (bins leaves scope; the verdicts number the lists)
+    for (size_t q = 0; q < n; ++q)
+      if (D.verdict[q] == 0) D.verdict[q] = got[q];
+  }
+
+  // lists, numbered by first use: one per topic with a full query, one per other query
+  h0 = hclock::now();
+  std::vector<uint32_t> topic_list(nt, PS_NONE);
+  std::vector<DrainQuery> lists;
+  uint64_t n_segs64 = 0;
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t v = D.verdict[q], t = topic[q];
+    if (!(v & kDrainRowAny)) {
+      list_out[q] = PS_NONE;
+      continue;
+    }
+    const bool full = !(v & kDrainRowMissing) && D.share;
+    if (full && topic_list[t] != PS_NONE) {
+      list_out[q] = topic_list[t];
+      continue;
+    }
+    list_out[q] = static_cast<uint32_t>(lists.size());
+    if (full) topic_list[t] = list_out[q];
+    lists.push_back(DrainQuery{t, full ? kDrainMaskRow : D.queries[q].node, static_cast<uint32_t>(n_segs64), 0});
+    n_segs64 += ceil_div(D.topics[t].n_pos, kDrainSegBits);
+    if (n_segs64 >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  }
+  const uint32_t n_lists = static_cast<uint32_t>(lists.size());
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  host_ms[1] = h_ms(h0);
+  *n_lists_out = n_lists;
+  D.hdr.assign(static_cast<size_t>(n_lists) + 2, 0);
+  if (n_lists) {
+    HIP_TRY(D.d_queries.ensure(static_cast<size_t>(n_lists) * sizeof(DrainQuery)), "alloc drain queries");
+    HIP_TRY(D.d_cnt.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain counts");
+    HIP_TRY(D.d_off.ensure((static_cast<size_t>(n_segs) + 1) * 8), "alloc drain offsets");
+    // (k_drain_offsets copies an error word behind the total: none here, a zero behind the header)
+    HIP_TRY(D.d_hdr.ensure((D.hdr.size() + 1) * 8), "alloc drain header");
+    uint32_t* const d_zero = reinterpret_cast<uint32_t*>(D.d_hdr.as<uint64_t>() + D.hdr.size());
+    HIP_TRY(hipMemsetAsync(d_zero, 0, 8, s), "clear drain error");
+    size_t scan_bytes = 0;
+    HIP_TRY(drain_scan(nullptr, &scan_bytes, D.d_cnt.as<uint64_t>(), D.d_off.as<uint64_t>(), n_segs + 1, s),
+            "size drain scan");
+    HIP_TRY(D.d_scan.ensure(scan_bytes), "alloc drain scan");
+    HIP_TRY(hipMemcpyAsync(D.d_queries.p, lists.data(), static_cast<size_t>(n_lists) * sizeof(DrainQuery),
+                           hipMemcpyHostToDevice, s),
+            "upload drain queries");
+    a.queries = D.d_queries.as<DrainQuery>();
+    a.n_queries = n_lists;
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(launch_drain_count(a, n_segs, D.d_cnt.as<uint64_t>(), s), "k_drain_count");
+    HIP_TRY(t_end(1), "event");
+    HIP_TRY(t_begin(), "event");
+    size_t sb = D.d_scan.bytes;
+    HIP_TRY(drain_scan(D.d_scan.p, &sb, D.d_cnt.as<uint64_t>(), D.d_off.as<uint64_t>(), n_segs + 1, s), "drain scan");
+    HIP_TRY(launch_drain_offsets(a.queries, n_lists, D.d_off.as<uint64_t>(), n_segs, d_zero, D.d_hdr.as<uint64_t>(), s),
+            "k_drain_offsets");
+    HIP_TRY(t_end(2), "event");
+    HIP_TRY(hipMemcpyAsync(D.hdr.data(), D.d_hdr.p, D.hdr.size() * 8, hipMemcpyDeviceToHost, s), "read drain offsets");
+    HIP_TRY(hipStreamSynchronize(s), "sync");  // (lists leaves scope; the total sizes the output)
+  }
+  const uint64_t total = D.hdr[n_lists];
+  *total_out = total;
+  if (list_cap >= n_lists) std::memcpy(list_off_out, D.hdr.data(), (static_cast<size_t>(n_lists) + 1) * 8);
+  if (list_cap < n_lists || total > cap) return e->fail(PS_E_RANGE, "output buffer too small");
+  if (total) {
+    HIP_TRY(D.d_lists.ensure(total * 4), "alloc drain lists");
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(launch_drain_emit(a, 0, n_segs, D.d_off.as<uint64_t>(), 0, D.d_lists.as<uint32_t>(), total, D.staged, s),
+            "k_drain_emit");
+    HIP_TRY(t_end(3), "event");
+    HIP_TRY(t_begin(), "event");
+    HIP_TRY(hipMemcpyAsync(msg_out, D.d_lists.p, total * 4, hipMemcpyDeviceToHost, s), "read drain lists");
+    HIP_TRY(t_end(4), "event");
+    HIP_TRY(hipStreamSynchronize(s), "sync");
+  }
+  if (D.timing)
+    std::fprintf(stderr,
+                 "psamd drain_shared: queries %zu classified %u waves %u lists %u segments %u ids %llu classify_ms %.4f "
+                 "count_ms %.4f scan_ms %.4f emit_ms %.4f copy_ms %.4f host_queries_ms %.4f host_lists_ms %.4f\n",
+                 n, n_class, n_waves, n_lists, n_segs, static_cast<unsigned long long>(total), ms[0], ms[1], ms[2], ms[3],
+                 ms[4], host_ms[0], host_ms[1]);
   return PS_OK;
 }
 

@@ -7,6 +7,8 @@
 //   k_drain_tables        the window's bit -> id table and message mask
 //   k_drain_tables_check  arrival keys ascend with the row bit, per topic
 //   k_drain_offsets       per-query offsets, total and error word of a view
+// and, for ps_drain_shared (§5.5c):
+//   k_drain_classify      per query: which of its topic's message bits the row holds
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -36,6 +38,7 @@ __device__ __forceinline__ uint64_t row_word_at(const DrainArgs& a, const DrainT
 // the 64 positions from p0 of node u's row, bit i = position p0 + i delivered
 __device__ __forceinline__ uint64_t lane_word(const DrainArgs& a, const DrainTopic& T, uint32_t u, uint32_t p0) {
   if (p0 >= T.n_pos) return 0;
+  if (u == kDrainMaskRow) return a.mask[T.aux0 + (p0 >> 6)];  // (a shared list: every message bit)
   if (!(T.flags & kDrainGather)) {
     const uint64_t at = row_word_at(a, T, u, p0 >> 6);
     return at == kNoWord ? 0ull : a.seen[at] & a.mask[T.aux0 + (p0 >> 6)];
@@ -64,7 +67,9 @@ __device__ __forceinline__ bool locate(const DrainArgs& a, uint32_t s, DrainQuer
   *Q = a.queries[lo - 1];
   *T = a.topics[Q->topic];
   *k = s - Q->seg0;
-  if (static_cast<uint64_t>(*k) * kDrainSegBits >= T->n_pos || Q->node >= T->n_nodes) return false;
+  if (static_cast<uint64_t>(*k) * kDrainSegBits >= T->n_pos) return false;
+  if (Q->node == kDrainMaskRow) return true;
+  if (Q->node >= T->n_nodes) return false;
   return (T->flags & kTopicMesh) || a.gen[T->nbase + Q->node] == static_cast<uint8_t>(a.gen_cur);
 }
 
@@ -140,6 +145,70 @@ __global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_
       const uint64_t o = base + p++;
       if (o < out_cap) out[o] = ids[p0 + b];
       x &= x - 1;
+    }
+  }
+}
+
+// ---- the shared drain's classify pass (ps_drain_shared) ----------------------
+
+constexpr uint32_t kClassBlock = 256;
+
+// One lane per (query, mask word): the row word under the mask against the
+// mask word, reduced over the query's lanes with two ballots.  A row of up to
+// 64 words lies in one aligned group of 1 << lanes_log2 lanes and its first
+// lane stores the verdict; a wider row spans `waves` steps, each of which ORs
+// its part into the (cleared) verdict word.  A wave takes kDrainClassPer steps
+// of one bin: the bin search and the topic are paid once, and the steps'
+// loads are issued together before the first is used.
+__global__ __launch_bounds__(kClassBlock) void k_drain_classify(DrainArgs a, const DrainClassBin* __restrict__ bins,
+                                                                uint32_t n_bins,
+                                                                const DrainClassQuery* __restrict__ queries,
+                                                                uint32_t n_waves, uint32_t* __restrict__ verdict) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * (kClassBlock / kWave) + threadIdx.x / kWave);
+  if (w >= n_waves) return;
+  uint32_t lo = 0, hi = n_bins;  // the last bin whose first wave is <= w (bins[0].wave0 = 0)
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (bins[mid].wave0 <= w) lo = mid + 1;
+    else hi = mid;
+  }
+  const DrainClassBin B = bins[lo - 1];
+  const DrainTopic T = a.topics[B.topic];
+  const bool wide = B.waves != 0;
+  const bool mesh = T.flags & kTopicMesh;
+  const uint32_t step0 = (w - B.wave0) * kDrainClassPer;
+  uint32_t slot[kDrainClassPer];
+  uint64_t x[kDrainClassPer], m[kDrainClassPer];
+  bool head[kDrainClassPer];  // the lane that reports the step's (group's) verdict
+#pragma unroll
+  for (uint32_t i = 0; i < kDrainClassPer; ++i) {
+    const uint32_t s = step0 + i;
+    const uint32_t qi = wide ? s / B.waves : (s << (6 - B.lanes_log2)) + (lane >> B.lanes_log2);
+    const uint32_t word = wide ? (s % B.waves) * kWave + lane : lane & ((1u << B.lanes_log2) - 1);
+    head[i] = qi < B.n_q && (wide ? lane == 0 : word == 0);
+    // (indices clamped into range, so that every load below is unconditional)
+    const DrainClassQuery Q = queries[B.q0 + min(qi, B.n_q - 1)];
+    slot[i] = Q.slot;
+    const uint32_t wc = min(word, B.words - 1);
+    const bool in = Q.node < T.n_nodes;
+    const uint32_t u = in ? Q.node : 0;
+    const uint64_t at = row_word_at(a, T, u, wc);
+    const bool fresh = mesh || a.gen[T.nbase + u] == static_cast<uint8_t>(a.gen_cur);
+    const bool live = qi < B.n_q && word < B.words;
+    m[i] = live ? a.mask[T.aux0 + wc] : 0ull;
+    x[i] = (at != kNoWord ? a.seen[at] : 0ull) & (live && in && fresh ? m[i] : 0ull);
+  }
+#pragma unroll
+  for (uint32_t i = 0; i < kDrainClassPer; ++i) {
+    const uint64_t bm = __ballot(x[i] != m[i]), ba = __ballot(x[i] != 0);
+    if (wide) {
+      const uint32_t v = (bm ? kDrainRowMissing : 0u) | (ba ? kDrainRowAny : 0u);
+      if (head[i] && v) atomicOr(verdict + slot[i], v);
+    } else {
+      const uint32_t g = 1u << B.lanes_log2;
+      const uint64_t gm = (g == kWave ? ~0ull : (1ull << g) - 1) << (lane & ~(g - 1));
+      if (head[i]) verdict[slot[i]] = ((bm & gm) ? kDrainRowMissing : 0u) | ((ba & gm) ? kDrainRowAny : 0u);
     }
   }
 }
@@ -232,6 +301,15 @@ hipError_t launch_drain_offsets(const DrainQuery* queries, uint32_t n, const uin
                                 const uint32_t* err, uint64_t* hdr, hipStream_t s) {
   hipLaunchKernelGGL(k_drain_offsets, dim3((n + 2 + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, queries, n,
                      seg_off, n_segs, err, hdr);
+  return hipGetLastError();
+}
+
+hipError_t launch_drain_classify(const DrainArgs& a, const DrainClassBin* bins, uint32_t n_bins,
+                                 const DrainClassQuery* queries, uint32_t n_waves, uint32_t* verdict, hipStream_t s) {
+  if (n_waves == 0) return hipSuccess;
+  const uint32_t per = kClassBlock / kWave;
+  hipLaunchKernelGGL(k_drain_classify, dim3((n_waves + per - 1) / per), dim3(kClassBlock), 0, s, a, bins, n_bins, queries,
+                     n_waves, verdict);
   return hipGetLastError();
 }
 

@@ -494,6 +494,14 @@ struct ps_engine {
     } slot[2];
     uint32_t slot_head = 0, slot_count = 0;
     bool mapped_out = false;  // emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)
+
+    // ps_drain_shared: the classify pass's bins, sorted
+    // queries and verdicts; the list queries' offsets header and ids
+    psamd::DevBuf d_cbins, d_cqueries, d_verdict, d_hdr, d_lists;
+    std::vector<psamd::DrainClassQuery> cqueries;
+    std::vector<uint32_t> verdict;
+    std::vector<uint64_t> hdr;
+    bool share = true;  // full rows share their topic's list (A/B: PSAMD_DRAIN_SHARED=private)
   } drain;
 
   // asynchronous runs (ps_run_async / ps_wait): the last window of a run may

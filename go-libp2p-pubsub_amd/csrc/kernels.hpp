@@ -583,10 +583,11 @@ struct DrainGroup {
 };
 struct DrainQuery {
   uint32_t topic;
-  uint32_t node;  // topic-relative
+  uint32_t node;  // topic-relative; kDrainMaskRow: the topic's message mask itself (ps_drain_shared)
   uint32_t seg0;  // the query's first segment (a query with an empty answer has none)
   uint32_t pad;
 };
+constexpr uint32_t kDrainMaskRow = 0xFFFFFFFFu;  // DrainQuery.node (mask-layout topics only)
 struct DrainArgs {
   const uint64_t* seen;
   const uint8_t* gen;
@@ -635,5 +636,28 @@ hipError_t launch_drain_tables(const DrainBuild& b, hipStream_t s);
 // hdr[q] = seg_off[queries[q].seg0] for q < n, hdr[n] = seg_off[n_segs], hdr[n + 1] = *err
 hipError_t launch_drain_offsets(const DrainQuery* queries, uint32_t n, const uint64_t* seg_off, uint32_t n_segs,
                                 const uint32_t* err, uint64_t* hdr, hipStream_t s);
+
+// ---- the shared drain's classify pass (ps_drain_shared) ----
+// The queries of mask-layout topics, sorted by topic: bin b holds the n_q
+// queries from q0 of one topic, whose row is `words` mask words wide.  Rows of
+// up to 64 words take 1 << lanes_log2 lanes each (the power of two at or above
+// `words`), 64 >> lanes_log2 queries to a step of 64 lanes; wider rows take
+// `waves` whole steps each.  A wave runs kDrainClassPer consecutive steps of
+// one bin (the bin's step count rounds up to that); its first wave is wave0.
+constexpr uint32_t kDrainClassPer = 4;  // (8: 58 VGPRs, 7 waves per SIMD, 12 % slower on cfg3)
+struct DrainClassBin {
+  uint32_t topic, q0, n_q, wave0;
+  uint32_t words, lanes_log2, waves, pad;
+};
+struct DrainClassQuery {
+  uint32_t node;  // topic-relative
+  uint32_t slot;  // the caller's query index: where the verdict goes
+};
+// verdict[slot] (cleared before the launch) of every query: which of the
+// topic's message bits its row holds
+constexpr uint32_t kDrainRowMissing = 1;  // a message bit the row does not hold: not full
+constexpr uint32_t kDrainRowAny = 2;      // a message bit the row holds: not empty
+hipError_t launch_drain_classify(const DrainArgs& a, const DrainClassBin* bins, uint32_t n_bins,
+                                 const DrainClassQuery* queries, uint32_t n_waves, uint32_t* verdict, hipStream_t s);
 
 }  // namespace psamd

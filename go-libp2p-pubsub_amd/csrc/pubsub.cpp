@@ -120,7 +120,8 @@ Error Network::Flush() {
     return err(rc);
   }
   // processMessages (client.go:124-128): every open subscriber's channel gets
-  // what reached it, in arrival order: one batched drain for all of them
+  // what reached it, in arrival order: one shared drain for all of them (the
+  // channels of one topic reference one id list)
   std::vector<client*> open;
   std::vector<uint32_t> qt, qp;
   for (auto& c : clients_) {
@@ -129,20 +130,27 @@ Error Network::Flush() {
     qt.push_back(c->topic_);
     qp.push_back(c->peer_);
   }
-  std::vector<uint64_t> off(open.size() + 1);
-  std::vector<uint32_t> ids(64 * open.size());
+  std::vector<uint32_t> list(open.size());
+  std::vector<uint64_t> off(max_topics_ + 1);
+  std::vector<uint32_t> ids(64 * max_topics_);
+  uint32_t n_lists = 0;
   uint64_t total = 0;
-  rc = ps_drain(e_, qt.data(), qp.data(), open.size(), off.data(), ids.data(), ids.size(), &total);
-  if (rc == PS_E_RANGE && total > ids.size()) {
+  rc = ps_drain_shared(e_, qt.data(), qp.data(), open.size(), list.data(), off.data(), off.size() - 1, ids.data(),
+                       ids.size(), &n_lists, &total);
+  if (rc == PS_E_RANGE && (total > ids.size() || n_lists + 1 > off.size())) {
     ids.resize(total);
-    rc = ps_drain(e_, qt.data(), qp.data(), open.size(), off.data(), ids.data(), ids.size(), &total);
+    off.resize(static_cast<size_t>(n_lists) + 1);
+    rc = ps_drain_shared(e_, qt.data(), qp.data(), open.size(), list.data(), off.data(), off.size() - 1, ids.data(),
+                         ids.size(), &n_lists, &total);
   }
   if (rc != PS_OK) return err(rc);
-  for (size_t q = 0; q < open.size(); ++q)
-    for (uint64_t k = off[q]; k < off[q + 1]; ++k) {
+  for (size_t q = 0; q < open.size(); ++q) {
+    if (list[q] == PS_NONE) continue;
+    for (uint64_t k = off[list[q]]; k < off[list[q] + 1]; ++k) {
       auto it = payload_.find(ids[k]);
       if (it != payload_.end()) open[q]->out_.q_.push_back(it->second);
     }
+  }
   payload_.clear();
   return Error{};
 }

@@ -153,6 +153,8 @@ PROTOTYPES = [
     ("ps_read_delivered", C.c_int, [_P, _u32, _u8p]),
     ("ps_read_peer_messages", C.c_int, [_P, _u32, _u32, _u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ps_drain", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u64p, _u32p, C.c_size_t, _u64p]),
+    ("ps_drain_shared", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u32p, _u64p, C.c_size_t, _u32p, C.c_size_t, _u32p,
+                                  _u64p]),
     ("ps_drain_begin", C.c_int, [_P, _u32p, _u32p, C.c_size_t]),
     ("ps_drain_end", C.c_int, [_P, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
@@ -464,6 +466,32 @@ class Engine:
         ids = np.empty(total.value, dtype=np.uint32)
         self._check(self._L.ps_drain(self._h, tp, pp, n, op, _p(ids, C.c_uint32), ids.size, C.byref(total)))
         return off, ids
+
+    def drain_shared(self, topics, peers):
+        """drain(topics, peers) with equal lists stored once (ps_drain_shared):
+        returns (list_of_query: uint32[n], list_off: uint64[n_lists + 1],
+        ids: uint32[total]); query q's ids are list l = list_of_query[q],
+        ids[list_off[l]:list_off[l + 1]], or nothing when l == NONE."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        p = np.ascontiguousarray(peers, dtype=np.uint32)
+        if t.ndim != 1 or t.shape != p.shape:
+            raise ValueError("topics and peers must be 1-d arrays of one length")
+        n = t.size
+        lists = np.empty(n, dtype=np.uint32)
+        off = np.zeros(1, dtype=np.uint64)
+        n_lists, total = C.c_uint32(), C.c_uint64()
+        tp, pp, lp = _p(t, C.c_uint32), _p(p, C.c_uint32), _p(lists, C.c_uint32)
+        rc = self._L.ps_drain_shared(self._h, tp, pp, n, lp, _p(off, C.c_uint64), 0, None, 0, C.byref(n_lists),
+                                     C.byref(total))  # the sizing call
+        if rc != -7 or n_lists.value == 0:
+            self._check(rc)
+            return lists, off, np.empty(0, dtype=np.uint32)
+        off = np.empty(n_lists.value + 1, dtype=np.uint64)
+        ids = np.empty(total.value, dtype=np.uint32)
+        self._check(self._L.ps_drain_shared(self._h, tp, pp, n, lp, _p(off, C.c_uint64), n_lists.value,
+                                            _p(ids, C.c_uint32) if ids.size else None, ids.size, C.byref(n_lists),
+                                            C.byref(total)))
+        return lists, off, ids
 
     def drain_begin(self, topics, peers):
         """Enqueues drain(topics, peers) of the last window of the last run

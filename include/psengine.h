@@ -323,6 +323,27 @@ int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
  * stream-ordered as before, while drains are outstanding. */
 int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n);
 int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_out, uint64_t* total_out);
+/* ps_drain with equal lists stored once.  Within one window every reached
+ * subscriber of a topic receives the same messages in the same order, so the
+ * answer is a few lists and one list number per query: query q's ids are list
+ * l = list_out[q], msg_out[list_off_out[l] .. list_off_out[l+1]), or nothing
+ * when list_out[q] == PS_NONE; expanded, that is ps_drain's answer for q, id
+ * for id.  The engine does not assume the equality: it compares every queried
+ * row with the topic's window messages on the GPU.  A row that holds all of
+ * them takes the topic's shared list (emitted once), a row that holds none
+ * takes PS_NONE, any other row takes a list of its own; so do the rows of a
+ * mesh topic whose window has several start rounds.  Lists are numbered in
+ * the order of the first query that uses them.
+ *   list_out has n entries and is always filled; list_off_out has
+ * list_cap + 1; *n_lists_out and *total_out (= list_off_out[n_lists]) are
+ * always set.  When list_cap < n_lists or cap < total the call returns
+ * PS_E_RANGE with msg_out untouched, and list_off_out filled only if list_cap
+ * suffices (msg_out == NULL, cap == 0 is the sizing call).  PS_E_RANGE with
+ * nothing written for a topic or peer out of range; PS_E_NOTREADY before any
+ * run; PS_E_STATE on a multi-rank engine (use ps_drain). */
+int ps_drain_shared(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint32_t* list_out,
+                    uint64_t* list_off_out, size_t list_cap, uint32_t* msg_out, size_t cap,
+                    uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

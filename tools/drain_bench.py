@@ -25,6 +25,14 @@ time of the view's bytes (the copy phase of a timed ps_drain in the same
 process), the host phases of the first synchronous drain after a window and
 the device time of k_drain_tables and its check.  Writes
 DIR/drain_async_bench.json.
+
+--shared: ps_drain_shared (equal lists stored once) against ps_drain on the
+same pairs of one window, for the counts of --pipelined-queries: the classify /
+count / scan / emit / copy phases, the wall clock of the untimed calls, ids and
+bytes moved to the host and the ratio of the two calls; then --large-queries
+pairs through ps_drain_shared alone (ps_drain is skipped there because of its
+output size), with classify's algorithmic bytes over its device time against
+the HBM spec.  Writes DIR/drain_shared_bench.json.
 """
 from __future__ import annotations
 
@@ -280,6 +288,133 @@ def pipelined_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+HBM_SPEC_BYTES_PER_S = 8e12
+
+
+def raw_shared(eng, qt, qp, lists, off, ids):
+    n_lists, total = C.c_uint32(), C.c_uint64()
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    rc = eng._L.ps_drain_shared(eng._h, qt.ctypes.data_as(u32p), qp.ctypes.data_as(u32p), qt.size,
+                                lists.ctypes.data_as(u32p), off.ctypes.data_as(u64p), off.size - 1,
+                                ids.ctypes.data_as(u32p) if ids is not None else None, 0 if ids is None else ids.size,
+                                C.byref(n_lists), C.byref(total))
+    return rc, n_lists.value, total.value
+
+
+def phase_line(text, tag):
+    m = re.search(rf"psamd {tag}: .*", text)
+    assert m, text
+    row = {k: float(v) for k, v in re.findall(r"(\w+_ms) ([0-9.]+)", m.group(0))}
+    for k in ("classified", "waves", "lists", "segments", "ids"):
+        mm = re.search(rf"\b{k} (\d+)", m.group(0))
+        if mm:
+            row[k] = int(mm.group(1))
+    return row
+
+
+def shared_sizes(eng, qt, qp):
+    lists = np.empty(qt.size, dtype=np.uint32)
+    rc, n_lists, total = raw_shared(eng, qt, qp, lists, np.empty(1, dtype=np.uint64), None)
+    assert rc in (0, -7), rc
+    return lists, np.empty(n_lists + 1, dtype=np.uint64), np.empty(max(total, 1), dtype=np.uint32), n_lists, total
+
+
+def same_answer(lists, loff, lids, off, ids):
+    """The shared result expanded is ps_drain's, query by query."""
+    for q in range(lists.size):
+        want = ids[int(off[q]):int(off[q + 1])]
+        got = lids[int(loff[lists[q]]):int(loff[lists[q] + 1])] if lists[q] != PE.NONE else lids[:0]
+        if not np.array_equal(got, want):
+            return False
+    return True
+
+
+def shared_main(a, wl):
+    """ps_drain_shared against ps_drain on the same queries of one window, in
+    one process: the phases (PSAMD_DRAIN_TIMING=1: run apart, each
+    synchronised), the wall clock of the untimed calls, the bytes that cross
+    the link; and one batch ps_drain is not asked to serve."""
+    counts = [int(x) for x in a.pipelined_queries.split(",")]
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "rows": []}
+    queries = {n: pick_queries(wl, n, a.seed) for n in counts + [a.large_queries]}
+    words = {}  # row words under the message mask, per topic: ceil(window messages / 64)
+    for t in range(len(wl.topics)):
+        words[t] = -(-int(np.sum(wl.msg_topics == t)) // 64)
+    phases, sizes = {}, {}
+    eng, _ = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for n in counts + [a.large_queries]:
+            qt, qp = queries[n]
+            lists, loff, lids, n_lists, total = shared_sizes(eng, qt, qp)
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call allocates; the very first builds the window's tables)
+                with StderrCapture() as cap:
+                    rc, _, _ = raw_shared(eng, qt, qp, lists, loff, lids)
+                assert rc == 0, rc
+                rows.append(phase_line(cap.text, "drain_shared"))
+            sh = min(rows[1:], key=lambda r: r["classify_ms"])
+            sizes[n] = (n_lists, total)
+            row = {"queries": n, "shared_phases": sh, "n_lists": n_lists, "shared_ids": total,
+                   "shared_bytes_to_host": 4 * n + 8 * (n_lists + 2) + 4 * total,
+                   "shared_bound_bytes": 8 * n + 8 * (n_lists + 1) + 4 * total}
+            # classify's algorithmic bytes: every classified row's words, the sorted query (8 B), the
+            # generation byte, the verdict (4 B); each queried topic's mask words once
+            alg = int(sum(8 * words[int(t)] for t in qt)) + 13 * n + 8 * sum(words[int(t)] for t in set(qt.tolist()))
+            row["classify_algorithmic_bytes"] = alg
+            row["classify_vs_hbm_spec"] = alg / (sh["classify_ms"] / 1e3) / HBM_SPEC_BYTES_PER_S if sh["classify_ms"] else None
+            if n == a.large_queries:
+                row["ps_drain"] = "skipped: its output would be %.1f GB of ids" % (
+                    4e-9 * sum(64.0 * words[int(t)] for t in qt))
+            else:
+                off = np.empty(n + 1, dtype=np.uint64)
+                rc, dtotal = raw_drain(eng, qt, qp, off, None)
+                assert rc in (0, -7), rc
+                ids = np.empty(max(dtotal, 1), dtype=np.uint32)
+                rows = []
+                for _ in range(a.reps + 1):
+                    with StderrCapture() as cap:
+                        rc, _ = raw_drain(eng, qt, qp, off, ids)
+                    assert rc == 0, rc
+                    rows.append(phase_line(cap.text, "drain"))
+                row["drain_phases"] = min(rows[1:], key=lambda r: r["count_ms"] + r["emit_ms"] + r["copy_ms"])
+                row.update(drain_ids=dtotal, drain_bytes_to_host=8 * (row["drain_phases"]["segments"] + 1) + 4 * dtotal)
+                assert same_answer(lists, loff, lids, off, ids)
+            phases[n] = row
+    eng, _ = stepped_engine(wl, {})
+    with eng:
+        for n in counts + [a.large_queries]:
+            qt, qp = queries[n]
+            row = phases[n]
+            lists = np.empty(n, dtype=np.uint32)
+            loff = np.empty(sizes[n][0] + 1, dtype=np.uint64)
+            lids = np.empty(max(sizes[n][1], 1), dtype=np.uint32)
+            walls = []
+            for _ in range(a.reps + 1):
+                t0 = time.perf_counter()
+                rc, _, _ = raw_shared(eng, qt, qp, lists, loff, lids)
+                walls.append(time.perf_counter() - t0)
+                assert rc == 0, rc
+            row["shared_wall_ms"] = 1e3 * min(walls[1:])
+            if n != a.large_queries:
+                off = np.empty(n + 1, dtype=np.uint64)
+                ids = np.empty(max(row["drain_ids"], 1), dtype=np.uint32)
+                walls = []
+                for _ in range(a.reps + 1):
+                    t0 = time.perf_counter()
+                    rc, _ = raw_drain(eng, qt, qp, off, ids)
+                    walls.append(time.perf_counter() - t0)
+                    assert rc == 0, rc
+                row["drain_wall_ms"] = 1e3 * min(walls[1:])
+                row["drain_over_shared_wall"] = row["drain_wall_ms"] / row["shared_wall_ms"]
+                row["bytes_ratio"] = row["drain_bytes_to_host"] / row["shared_bytes_to_host"]
+            res["rows"].append(row)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "drain_shared_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WL.CONFIGS))
@@ -293,10 +428,14 @@ def main():
     ap.add_argument("--pipelined-queries", default="256,1024,4096")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--shared", action="store_true", help="ps_drain_shared against ps_drain (see above)")
+    ap.add_argument("--large-queries", type=int, default=262144)
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
     if a.pipelined:
         return pipelined_main(a, wl)
+    if a.shared:
+        return shared_main(a, wl)
     qt, qp = pick_queries(wl, a.queries, a.seed)
     res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "queries": a.queries}
 
