@@ -1,0 +1,833 @@
+// drain.cpp -- the host side of the batched drain (kernels: drain.hip;
+// DESIGN.md §5.5): ps_drain, ps_drain_shared, ps_drain_begin / ps_drain_end.
+//
+// What the three paths rely on, between them and with run.cpp:
+//  - D.seq / D.p_*: one set of device tables per window, built by whichever
+//    path runs first (drain_tables on the host, drain_tables_async on the
+//    device) and reused by the others.  A device build given up half way sets
+//    D.seq to ~0 unless the tables were already this window's; a host build
+//    that fails leaves D.seq at its older value.
+//  - The device build stages its block in the slot's pinned h_in, the queries
+//    behind it.  A ps_drain_begin that fails after staging without taking the
+//    slot synchronises the stream first; a slot with no segment records
+//    ev_done only when it staged tables.
+//  - D.d_err lives behind the mask words of the device build; it is created
+//    (8 bytes, cleared) on first use when only host builds have run.
+//    ps_drain_shared passes a zero word behind its header instead.
+//  - ps_drain's slabs: ev_copy[k & 1] is waited on before slab k is emitted,
+//    slab k - 1 is copied while slab k is emitted; under timing the copy runs
+//    in line on `stream`.
+//  - Slot::seen / emit_pending / ev_emit are read by drain_fence (run.cpp).
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "engine.hpp"
+
+using namespace psamd;
+
+namespace {
+
+using Drain = ps_engine::Drain;
+using hclock = std::chrono::steady_clock;
+
+double ms_since(hclock::time_point t0) { return std::chrono::duration<double, std::milli>(hclock::now() - t0).count(); }
+
+// segments (or classify steps) one call may hold: the kernels index them in 32 bits
+constexpr uint64_t kDrainRowLimit = 0x7FFFFFFFull;
+// ids one asynchronous drain may hold at most (its buffers are sized by an
+// upper bound, not by the total): larger drains go through ps_drain's slabs
+constexpr uint64_t kDrainAsyncMaxIds = 1ull << 30;
+
+size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// PSAMD_DRAIN_TIMING: one phase on stream s between the two timing events,
+// waited for at its end.  Off: nothing is recorded and nothing waits.
+struct PhaseTimer {
+  const hipEvent_t* ev;
+  hipStream_t s;
+  bool on;
+  hipError_t begin() const { return on ? hipEventRecord(ev[0], s) : hipSuccess; }
+  hipError_t end(float& ms) const {
+    if (!on) return hipSuccess;
+    hipError_t r = hipEventRecord(ev[1], s);
+    if (r == hipSuccess) r = hipEventSynchronize(ev[1]);
+    float t = 0;
+    if (r == hipSuccess) r = hipEventElapsedTime(&t, ev[0], ev[1]);
+    ms += t;
+    return r;
+  }
+};
+
+// grow-only pinned memory (device-mapped); the old contents are dropped
+hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need) {
+  if (need <= *cap) return hipSuccess;
+  if (*h) (void)hipHostFree(*h);
+  *h = nullptr;
+  *cap = 0;
+  void* p = nullptr;
+  hipError_t rc = hipHostMalloc(&p, std::max<size_t>(need + need / 2, 64 << 10), hipHostMallocMapped | hipHostMallocCoherent);
+  if (rc != hipSuccess) return rc;
+  *h = static_cast<uint8_t*>(p);
+  *cap = std::max<size_t>(need + need / 2, 64 << 10);
+  if (d) {
+    void* dp = nullptr;
+    rc = hipHostGetDevicePointer(&dp, p, 0);
+    *d = static_cast<uint8_t*>(dp);
+  }
+  return rc;
+}
+
+// What every entry point needs after its own state checks: the node-space
+// mirrors (the peer maps read them), the drain's stream and events
+int drain_ready(ps_engine* e) {
+  if (const int rc = ensure_mirrors(e)) return rc;
+  auto& D = e->drain;
+  if (D.copy_stream) return PS_OK;
+  for (auto& ev : D.ev_emit) HIP_TRY(hipEventCreateWithFlags(&ev, kStreamEvent), "drain event");
+  for (auto& ev : D.ev_copy) HIP_TRY(hipEventCreateWithFlags(&ev, kStreamEvent), "drain event");
+  for (auto& ev : D.ev_t) HIP_TRY(hipEventCreate(&ev), "drain event");
+  HIP_TRY(hipStreamCreateWithFlags(&D.copy_stream, hipStreamNonBlocking), "drain copy stream");
+  return PS_OK;
+}
+
+int drain_check_queries(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n) {
+  for (size_t q = 0; q < n; ++q)
+    if (topic[q] >= e->topics.size() || peer[q] >= e->cfg.n_peers) return e->fail(PS_E_RANGE, "topic or peer out of range");
+  return PS_OK;
+}
+
+// the layout of topic t's rows in the last window; its start groups go to `groups`
+DrainTopic drain_topic_header(const ps_engine* e, uint32_t t, std::vector<DrainGroup>& groups) {
+  const TopicDev& d = e->last_topics[t];
+  DrainTopic T{};
+  T.wbase = d.wbase;
+  T.nbase = d.nbase;
+  T.n_nodes = d.n_nodes;
+  T.W = d.W;
+  T.flags = d.flags & (kTopicMesh | kTopicGroups);
+  if (d.flags & kTopicGroups) {
+    T.group_lo = static_cast<uint32_t>(groups.size());
+    for (const StartGroup& g : e->last_groups[t]) groups.push_back({g.w0, g.wn});
+    T.group_n = static_cast<uint32_t>(groups.size()) - T.group_lo;
+  }
+  return T;
+}
+
+// The last window's drain tables, once per window, built on the host.  A
+// topic's window messages by row bit: where (start round, publish order)
+// ascends with the bit -- every tree layout (plan_window_layout sorts the bits
+// so) -- the id table is indexed by bit and a mask marks the message bits;
+// else (a mesh window with several start rounds) the ids are stored in
+// arrival order beside each one's bit.
+int drain_tables(ps_engine* e) {
+  auto& D = e->drain;
+  if (D.seq == e->window_seq) return PS_OK;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  struct Ent {
+    uint64_t key;  // start round << 32 | message index: arrival order
+    uint32_t b, id;
+  };
+  std::vector<Ent> P;
+  std::vector<uint32_t> ids, order;
+  std::vector<uint64_t> mask;
+  std::vector<DrainGroup> groups;
+  D.topics.assign(nt, DrainTopic{});
+  for (uint32_t t = 0; t < nt; ++t) {
+    const TopicDev& d = e->last_topics[t];
+    if (!d.W || !e->last_cnt[t]) continue;
+    const WinSlice w = window_slice(e, t);
+    const uint32_t* bits = window_bits(e, t);
+    P.clear();
+    for (uint32_t li = 0; li < w.n; ++li) {
+      const uint32_t i = w.idx[li];
+      P.push_back({(static_cast<uint64_t>(e->last_msgs[i].start) << 32) | i, window_bit(bits, li), e->last_first + i});
+    }
+    DrainTopic& T = D.topics[t] = drain_topic_header(e, t, groups);
+    std::sort(P.begin(), P.end(), [](const Ent& x, const Ent& y) { return x.b < y.b; });
+    bool ordered = true;
+    for (size_t k = 1; k < P.size(); ++k) {
+      if (P[k].b == P[k - 1].b) return e->fail(PS_E_STATE, "two window messages share a row bit");
+      ordered &= P[k].key > P[k - 1].key;
+    }
+    if ((P.back().b >> 6) >= d.W) return e->fail(PS_E_STATE, "window message bit past the row");
+    T.tab0 = ids.size();
+    if (ordered) {
+      const uint32_t words = (P.back().b >> 6) + 1;
+      T.n_pos = words * 64;
+      T.aux0 = mask.size();
+      ids.resize(ids.size() + T.n_pos, kNone);
+      mask.resize(mask.size() + words, 0);
+      for (const Ent& x : P) {
+        ids[T.tab0 + x.b] = x.id;
+        mask[T.aux0 + (x.b >> 6)] |= 1ull << (x.b & 63);
+      }
+    } else {
+      std::sort(P.begin(), P.end(), [](const Ent& x, const Ent& y) { return x.key < y.key; });
+      T.flags |= kDrainGather;
+      T.n_pos = static_cast<uint32_t>(P.size());
+      T.aux0 = order.size();
+      for (const Ent& x : P) {
+        ids.push_back(x.id);
+        order.push_back(x.b);
+      }
+    }
+  }
+  auto up = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
+    hipError_t rc = buf.ensure(bytes);
+    if (rc == hipSuccess && bytes) rc = hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, e->stream);
+    return rc;
+  };
+  HIP_TRY(up(D.d_topics, D.topics.data(), D.topics.size() * sizeof(DrainTopic)), "drain topics");
+  HIP_TRY(up(D.d_groups, groups.data(), groups.size() * sizeof(DrainGroup)), "drain groups");
+  HIP_TRY(up(D.d_ids, ids.data(), ids.size() * 4), "drain ids");
+  HIP_TRY(up(D.d_mask, mask.data(), mask.size() * 8), "drain masks");
+  HIP_TRY(up(D.d_order, order.data(), order.size() * 4), "drain order");
+  HIP_TRY(hipStreamSynchronize(e->stream), "sync");  // (the tables above leave scope)
+  D.p_topics = D.d_topics.as<DrainTopic>();
+  D.p_groups = D.d_groups.as<DrainGroup>();
+  D.p_ids = D.d_ids.as<uint32_t>();
+  D.p_mask = D.d_mask.as<uint64_t>();
+  D.p_order = D.d_order.as<uint32_t>();
+  D.seq = e->window_seq;
+  return PS_OK;
+}
+
+// The last window's tables for the asynchronous drain, once per window: the
+// host stages 12 B per window message (run index, row bit, start round) in
+// the slot's pinned memory and k_drain_tables builds the id table and the
+// mask from them behind the window, with no host wait.  A mesh topic of a
+// run with several start rounds keeps the host's arrival-order table
+// (kDrainGather, as drain_tables above), staged the same way.  `used`: the
+// bytes of S.h_in taken (the queries follow).
+int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t* used) {
+  auto& D = e->drain;
+  *used = 0;
+  if (D.seq == e->window_seq) return PS_OK;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  D.topics.assign(nt, DrainTopic{});
+  std::vector<DrainGroup> groups;
+  std::vector<uint32_t> built, gather;  // topics by build
+  uint64_t n_msgs = 0, n_pos = 0, n_gather = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const TopicDev& d = e->last_topics[t];
+    const uint32_t cnt = e->last_cnt[t];
+    if (!d.W || !cnt) continue;
+    DrainTopic& T = D.topics[t] = drain_topic_header(e, t, groups);
+    if ((d.flags & kTopicMesh) && !e->run_zero_start) {
+      T.flags |= kDrainGather;
+      gather.push_back(t);
+      n_gather += cnt;
+      continue;
+    }
+    // the positions in use end with the word of the highest bit (a bit past
+    // the row is the kernel's to report: the table never exceeds the row)
+    const uint32_t* bits = window_bits(e, t);
+    const uint32_t top = bits ? *std::max_element(bits, bits + cnt) : cnt - 1;
+    T.n_pos = (std::min<uint32_t>(top >> 6, d.W - 1) + 1) * 64;
+    T.tab0 = n_pos;
+    T.aux0 = n_pos >> 6;
+    n_pos += T.n_pos;
+    n_msgs += cnt;
+    built.push_back(t);
+  }
+  if (n_pos + n_gather >= (1ull << 31)) return e->fail(PS_E_RANGE, "drain tables too large: use ps_drain");
+  uint64_t g_ids = n_pos, g_ord = 0;
+  for (uint32_t t : gather) {
+    DrainTopic& T = D.topics[t];
+    T.n_pos = e->last_cnt[t];
+    T.tab0 = g_ids;
+    T.aux0 = g_ord;
+    g_ids += T.n_pos;
+    g_ord += T.n_pos;
+  }
+  // the block: topics | groups | built topics | their first messages | idx | bit | start | order | gather ids
+  const uint32_t nb = static_cast<uint32_t>(built.size());
+  const size_t o_topics = 0;
+  const size_t o_groups = align256(o_topics + nt * sizeof(DrainTopic));
+  const size_t o_btopic = align256(o_groups + groups.size() * sizeof(DrainGroup));
+  const size_t o_msg0 = align256(o_btopic + nb * 4);
+  const size_t o_idx = align256(o_msg0 + (nb + 1) * 4);
+  const size_t o_bit = align256(o_idx + n_msgs * 4);
+  const size_t o_start = align256(o_bit + n_msgs * 4);
+  const size_t o_order = align256(o_start + n_msgs * 4);
+  const size_t o_gids = align256(o_order + n_gather * 4);
+  const size_t block = align256(o_gids + n_gather * 4);
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + align256(S.n * sizeof(DrainQuery))), "alloc drain staging");
+  HIP_TRY(D.d_ablock.ensure(block), "alloc drain tables");
+  HIP_TRY(D.d_aids.ensure((n_pos + n_gather) * 4), "alloc drain ids");
+  HIP_TRY(D.d_amask.ensure((n_pos >> 6) * 8 + 8), "alloc drain masks");
+  HIP_TRY(D.d_akeys.ensure(n_pos * 8), "alloc drain keys");
+  uint8_t* h = S.h_in;
+  std::memcpy(h + o_topics, D.topics.data(), nt * sizeof(DrainTopic));
+  if (!groups.empty()) std::memcpy(h + o_groups, groups.data(), groups.size() * sizeof(DrainGroup));
+  uint32_t* h_btopic = reinterpret_cast<uint32_t*>(h + o_btopic);
+  uint32_t* h_msg0 = reinterpret_cast<uint32_t*>(h + o_msg0);
+  uint32_t* h_idx = reinterpret_cast<uint32_t*>(h + o_idx);
+  uint32_t* h_bit = reinterpret_cast<uint32_t*>(h + o_bit);
+  uint32_t* h_start = reinterpret_cast<uint32_t*>(h + o_start);
+  uint32_t j = 0;
+  for (uint32_t k = 0; k < nb; ++k) {
+    const uint32_t t = built[k];
+    h_btopic[k] = t;
+    h_msg0[k] = j;
+    const WinSlice w = window_slice(e, t);
+    const uint32_t* bits = window_bits(e, t);
+    for (uint32_t li = 0; li < w.n; ++li, ++j) {
+      const uint32_t i = w.idx[li];
+      h_idx[j] = i;
+      h_bit[j] = window_bit(bits, li);
+      h_start[j] = e->last_msgs[i].start;
+    }
+  }
+  h_msg0[nb] = j;
+  uint32_t* h_order = reinterpret_cast<uint32_t*>(h + o_order);
+  uint32_t* h_gids = reinterpret_cast<uint32_t*>(h + o_gids);
+  std::vector<std::pair<uint64_t, uint32_t>> P;  // (key, bit)
+  for (uint32_t t : gather) {  // arrival order: (start round, run index) ascending
+    const WinSlice w = window_slice(e, t);
+    const uint32_t* bits = window_bits(e, t);
+    P.resize(w.n);
+    for (uint32_t li = 0; li < w.n; ++li)
+      P[li] = {static_cast<uint64_t>(e->last_msgs[w.idx[li]].start) << 32 | w.idx[li], window_bit(bits, li)};
+    std::sort(P.begin(), P.end());
+    const uint64_t o = D.topics[t].aux0;
+    for (uint32_t k = 0; k < w.n; ++k) {
+      if ((P[k].second >> 6) >= D.topics[t].W) return e->fail(PS_E_STATE, "window message bit past the row");
+      h_order[o + k] = P[k].second;
+      h_gids[o + k] = e->last_first + static_cast<uint32_t>(P[k].first);
+    }
+  }
+  hipStream_t s = e->stream;
+  uint8_t* db = D.d_ablock.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(db, h, block, hipMemcpyHostToDevice, s), "upload drain tables");
+  if (n_gather)
+    HIP_TRY(hipMemcpyAsync(D.d_aids.as<uint32_t>() + n_pos, db + o_gids, n_gather * 4, hipMemcpyDeviceToDevice, s),
+            "place drain ids");
+  D.d_err = reinterpret_cast<uint32_t*>(D.d_amask.as<uint64_t>() + (n_pos >> 6));
+  HIP_TRY(hipMemsetAsync(D.d_amask.p, 0, (n_pos >> 6) * 8 + 8, s), "clear drain masks");
+  if (n_pos) HIP_TRY(hipMemsetAsync(D.d_aids.p, 0xFF, n_pos * 4, s), "clear drain ids");
+  DrainBuild b{};
+  b.topics = reinterpret_cast<const DrainTopic*>(db + o_topics);
+  b.topic = reinterpret_cast<const uint32_t*>(db + o_btopic);
+  b.msg0 = reinterpret_cast<const uint32_t*>(db + o_msg0);
+  b.idx = reinterpret_cast<const uint32_t*>(db + o_idx);
+  b.bit = reinterpret_cast<const uint32_t*>(db + o_bit);
+  b.start = reinterpret_cast<const uint32_t*>(db + o_start);
+  b.n_built = nb;
+  b.n_msgs = static_cast<uint32_t>(n_msgs);
+  b.last_first = e->last_first;
+  b.n_pos = n_pos;
+  b.ids = D.d_aids.as<uint32_t>();
+  b.mask = D.d_amask.as<uint64_t>();
+  b.keys = D.d_akeys.as<uint64_t>();
+  b.err = D.d_err;
+  const PhaseTimer tm{D.ev_t, s, D.timing};  // (timing runs wait here: the build and its check, device time)
+  float build_ms = 0;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_tables(b, s), "k_drain_tables");
+  HIP_TRY(tm.end(build_ms), "event");
+  if (D.timing)
+    std::fprintf(stderr, "psamd drain tables: topics %u messages %llu positions %llu gather %llu device_ms %.4f\n", nb,
+                 static_cast<unsigned long long>(n_msgs), static_cast<unsigned long long>(n_pos),
+                 static_cast<unsigned long long>(n_gather), build_ms);
+  D.p_topics = b.topics;
+  D.p_groups = reinterpret_cast<const DrainGroup*>(db + o_groups);
+  D.p_ids = b.ids;
+  D.p_mask = b.mask;
+  D.p_order = reinterpret_cast<const uint32_t*>(db + o_order);
+  D.seq = e->window_seq;
+  *used = block;
+  return PS_OK;
+}
+
+// The node query (t, peer) reads, kNone where its answer is empty: a topic
+// idle in the window, the root, a peer not subscribed or another rank's.
+// `map`: topic t's peer map once looked up (a caller may keep it per topic).
+uint32_t drain_node(ps_engine* e, uint32_t t, uint32_t peer, const uint32_t*& map) {
+  if (!e->drain.topics[t].n_pos) return kNone;
+  if (!map) map = peer_node_map(e, t, e->last_topics[t]).data();
+  return map[peer];
+}
+
+// queries -> (topic, node, first segment) in `out`; an empty answer has no
+// segment.  Returns the segments; it stops at kDrainRowLimit or above (the
+// caller's error).  `bound`, if asked for: the ids at most (every resolved
+// query may hold all of its topic's window messages).
+uint64_t drain_resolve(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, DrainQuery* out,
+                       uint64_t* bound) {
+  const auto& D = e->drain;
+  uint64_t n_segs = 0, ids = 0;
+  for (size_t q = 0; q < n && n_segs < kDrainRowLimit; ++q) {
+    const uint32_t t = topic[q];
+    const uint32_t* map = nullptr;
+    out[q] = DrainQuery{t, 0, static_cast<uint32_t>(n_segs), 0};
+    const uint32_t u = drain_node(e, t, peer[q], map);
+    if (u == kNone) continue;
+    out[q].node = u;
+    n_segs += ceil_div(D.topics[t].n_pos, kDrainSegBits);
+    ids += e->last_cnt[t];
+  }
+  if (bound) *bound = ids;
+  return n_segs;
+}
+
+DrainArgs drain_args(const ps_engine* e) {  // (all but the queries)
+  const auto& D = e->drain;
+  DrainArgs a{};
+  a.seen = e->d_seen.as<uint64_t>();
+  a.gen = e->d_gen.as<uint8_t>();
+  a.gen_cur = e->gen_cur;
+  a.topics = D.p_topics;
+  a.groups = D.p_groups;
+  a.mask = D.p_mask;
+  a.order = D.p_order;
+  a.ids = D.p_ids;
+  return a;
+}
+
+// The queries to the device (a.queries from here on), every segment's ids
+// counted and the counts scanned into B.d_off (n_segs + 1 offsets), on stream
+// s; the buffers only grow.  The count is one timed phase; the scan's is left
+// open, for the caller to end behind whatever it adds to it.
+int drain_count_scan(ps_engine* e, DrainArgs& a, uint32_t n_segs, Drain::Scratch& B, const DrainQuery* queries,
+                     size_t n_queries, hipStream_t s, const PhaseTimer& tm, float& count_ms) {
+  const size_t n_off = static_cast<size_t>(n_segs) + 1;
+  HIP_TRY(B.d_queries.ensure(n_queries * sizeof(DrainQuery)), "alloc drain queries");
+  HIP_TRY(B.d_cnt.ensure(n_off * 8), "alloc drain counts");
+  HIP_TRY(B.d_off.ensure(n_off * 8), "alloc drain offsets");
+  size_t scan_bytes = 0;
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), n_segs + 1, s),
+          "size drain scan");
+  HIP_TRY(B.d_scan.ensure(scan_bytes), "alloc drain scan");
+  HIP_TRY(hipMemcpyAsync(B.d_queries.p, queries, n_queries * sizeof(DrainQuery), hipMemcpyHostToDevice, s),
+          "upload drain queries");
+  a.queries = B.d_queries.as<DrainQuery>();
+  a.n_queries = static_cast<uint32_t>(n_queries);
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_count(a, n_segs, B.d_cnt.as<uint64_t>(), s), "k_drain_count");
+  HIP_TRY(tm.end(count_ms), "event");
+  HIP_TRY(tm.begin(), "event");
+  scan_bytes = B.d_scan.bytes;
+  HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), n_segs + 1, s), "drain scan");
+  return PS_OK;
+}
+
+}  // namespace
+
+void psamd::drain_destroy(ps_engine* e) {
+  auto& D = e->drain;
+  if (D.copy_stream) {
+    (void)hipStreamSynchronize(D.copy_stream);
+    (void)hipStreamDestroy(D.copy_stream);
+  }
+  for (hipEvent_t ev : {D.ev_emit[0], D.ev_emit[1], D.ev_copy[0], D.ev_copy[1], D.ev_t[0], D.ev_t[1], D.slot[0].ev_emit,
+                        D.slot[0].ev_done, D.slot[1].ev_emit, D.slot[1].ev_done})
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto& sl : D.slot)
+    for (uint8_t* h : {sl.h_in, sl.h_res})
+      if (h) (void)hipHostFree(h);
+}
+
+extern "C" {
+
+// ---- ps_drain -----------------------------------------------
+
+int ps_drain(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint64_t* off_out, uint32_t* msg_out,
+             size_t cap, uint64_t* total_out) {
+  if (!e || !off_out || !total_out || (n && (!topic || !peer)) || (cap && !msg_out)) return PS_E_INVAL;
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
+  if (const int rj = twin_join(e)) return rj;
+  if (const int rq = drain_check_queries(e, topic, peer, n)) return rq;
+  off_out[0] = 0;
+  *total_out = 0;
+  if (n == 0) return PS_OK;
+  if (n >= 0xFFFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  auto& D = e->drain;
+  // (PSAMD_DRAIN_TIMING: the host phases of the call, the first after a window above all)
+  double host_ms[3] = {0, 0, 0};  // node-space mirrors, table build + upload, queries (peer maps)
+  auto h0 = hclock::now();
+  int rc = drain_ready(e);
+  host_ms[0] = ms_since(h0);
+  h0 = hclock::now();
+  const bool tables_built = D.seq != e->window_seq;
+  if (!rc) rc = drain_tables(e);
+  host_ms[1] = ms_since(h0);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  h0 = hclock::now();
+  D.queries.resize(n);
+  const uint64_t n_segs64 = drain_resolve(e, topic, peer, n, D.queries.data(), nullptr);
+  if (n_segs64 >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  host_ms[2] = ms_since(h0);
+  D.off.assign(static_cast<size_t>(n_segs) + 1, 0);
+  float ms[4] = {0, 0, 0, 0};  // count, scan, emit, copy (PSAMD_DRAIN_TIMING)
+  const PhaseTimer tm{D.ev_t, s, D.timing};
+  DrainArgs a = drain_args(e);
+  auto& B = D.scratch;
+  if (n_segs) {
+    if ((rc = drain_count_scan(e, a, n_segs, B, D.queries.data(), n, s, tm, ms[0]))) return rc;
+    HIP_TRY(tm.end(ms[1]), "event");
+    HIP_TRY(hipMemcpyAsync(D.off.data(), B.d_off.p, (static_cast<size_t>(n_segs) + 1) * 8, hipMemcpyDeviceToHost, s),
+            "read drain offsets");
+    HIP_TRY(hipStreamSynchronize(s), "sync");
+  }
+  const uint64_t total = D.off[n_segs];
+  for (size_t q = 0; q < n; ++q) off_out[q] = D.off[D.queries[q].seg0];
+  off_out[n] = total;
+  *total_out = total;
+  if (total > cap) {
+    if (D.timing)
+      std::fprintf(stderr, "psamd drain: queries %zu sizing host_mirrors_ms %.4f host_tables_ms %.4f (%s) host_queries_ms %.4f\n",
+                   n, host_ms[0], host_ms[1], tables_built ? "built" : "kept", host_ms[2]);
+    return e->fail(PS_E_RANGE, "output buffer too small");
+  }
+
+  // emit, slab by slab: the segments [lo, hi) whose ids fit one slab; slab k
+  // is copied out on the copy stream while slab k + 1 is emitted
+  const uint64_t slab = std::min<uint64_t>(D.slab_ids, std::max<uint64_t>(total, 1));
+  // both slabs, sized once (behind the copies of an earlier drain: all complete)
+  for (DevBuf& buf : D.d_slab) HIP_TRY(buf.ensure(slab * 4), "alloc drain slab");
+  uint64_t pend_base = 0, pend_len = 0;  // the slab emitted last, not yet copied
+  uint32_t lo = 0, k = 0;  // k: slabs emitted; slab j lives in d_slab[j & 1]
+  // slab j's copy: behind its emit, on the copy stream (timing: in line)
+  auto copy_out = [&](uint32_t j) -> int {
+    hipStream_t cs = D.timing ? s : D.copy_stream;
+    if (!D.timing) HIP_TRY(hipStreamWaitEvent(cs, D.ev_emit[j & 1], 0), "wait");
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(hipMemcpyAsync(msg_out + pend_base, D.d_slab[j & 1].p, pend_len * 4, hipMemcpyDeviceToHost, cs),
+            "read drain slab");
+    HIP_TRY(tm.end(ms[3]), "event");
+    HIP_TRY(hipEventRecord(D.ev_copy[j & 1], cs), "event");
+    return PS_OK;
+  };
+  while (lo < n_segs && D.off[lo] < total) {
+    const uint64_t base = D.off[lo];
+    const uint32_t hi =
+        static_cast<uint32_t>(std::upper_bound(D.off.begin() + lo, D.off.end(), base + slab) - D.off.begin()) - 1;
+    // (a segment holds at most kDrainSegBits <= slab ids, or all that is left: hi > lo)
+    if (hi <= lo) return e->fail(PS_E_STATE, "drain slab smaller than a segment");
+    const uint64_t len = D.off[hi] - base;
+    HIP_TRY(hipStreamWaitEvent(s, D.ev_copy[k & 1], 0), "wait");  // (slab k - 2 has left the buffer)
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(launch_drain_emit(a, lo, hi, B.d_off.as<uint64_t>(), base, D.d_slab[k & 1].as<uint32_t>(), len, D.staged, s),
+            "k_drain_emit");
+    HIP_TRY(tm.end(ms[2]), "event");
+    HIP_TRY(hipEventRecord(D.ev_emit[k & 1], s), "event");
+    if (k)  // the slab before goes out while this one is emitted
+      if (const int rcc = copy_out(k - 1)) return rcc;
+    pend_base = base;
+    pend_len = len;
+    ++k;
+    lo = hi;
+  }
+  if (k)
+    if (const int rcc = copy_out(k - 1)) return rcc;
+  HIP_TRY(hipStreamSynchronize(D.copy_stream), "sync");
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  if (D.timing)
+    std::fprintf(stderr,
+                 "psamd drain: queries %zu segments %u ids %llu slabs %u emit %s count_ms %.4f scan_ms %.4f emit_ms %.4f "
+                 "copy_ms %.4f host_mirrors_ms %.4f host_tables_ms %.4f (%s) host_queries_ms %.4f\n",
+                 n, n_segs, static_cast<unsigned long long>(total), k, D.staged ? "lds" : "direct", ms[0], ms[1], ms[2],
+                 ms[3], host_ms[0], host_ms[1], tables_built ? "built" : "kept", host_ms[2]);
+  return PS_OK;
+}
+
+// ---- ps_drain_shared ---------------------------------------
+
+// ps_drain's answer with equal lists stored once.  k_drain_classify compares
+// every queried row of a mask-layout topic with the topic's message mask:
+// no message bit -> PS_NONE, every message bit -> the topic's shared list
+// (emitted from the mask itself), anything else -> a list of its own through
+// the count / scan / emit passes ps_drain uses.  The queries of arrival-order
+// (kDrainGather) topics have no mask to compare with: each takes a private
+// list.  Device -> host: 4 B x n verdicts, 8 B x (n_lists + 2) offsets, 4 B x
+// total ids.
+int ps_drain_shared(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint32_t* list_out,
+                    uint64_t* list_off_out, size_t list_cap, uint32_t* msg_out, size_t cap, uint32_t* n_lists_out,
+                    uint64_t* total_out) {
+  if (!e || !list_off_out || !n_lists_out || !total_out || (n && (!topic || !peer || !list_out)) || (cap && !msg_out))
+    return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_drain_shared on a multi-rank engine: use ps_drain");
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
+  if (const int rj = twin_join(e)) return rj;
+  if (const int rq = drain_check_queries(e, topic, peer, n)) return rq;
+  *n_lists_out = 0;
+  *total_out = 0;
+  if (n == 0) {
+    list_off_out[0] = 0;
+    return PS_OK;
+  }
+  if (n >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  auto& D = e->drain;
+  double host_ms[2] = {0, 0};  // mirrors + tables + bins, list numbering
+  auto h0 = hclock::now();
+  int rc = drain_ready(e);
+  if (!rc) rc = drain_tables(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  float ms[5] = {0, 0, 0, 0, 0};  // classify, count, scan, emit, copy (PSAMD_DRAIN_TIMING)
+  const PhaseTimer tm{D.ev_t, s, D.timing};
+
+  // queries -> nodes; those of mask-layout topics, sorted by topic (a
+  // counting sort: a topic's rows have one width), go to the classify pass
+  const uint32_t nt = static_cast<uint32_t>(D.topics.size());
+  constexpr uint32_t kOnHost = 0x80000000u;  // verdict decided here: | kDrainRow*
+  D.queries.resize(n);
+  D.verdict.assign(n, kOnHost);
+  std::vector<uint32_t> per_topic(nt + 1, 0);
+  std::vector<const uint32_t*> peer_map(nt, nullptr);  // (looked up once per topic, not per query)
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t t = topic[q];
+    DrainQuery& Q = D.queries[q];
+    Q = DrainQuery{t, 0, 0, 0};
+    const uint32_t u = drain_node(e, t, peer[q], peer_map[t]);
+    if (u == kNone) continue;
+    Q.node = u;
+    if (D.topics[t].flags & kDrainGather) {
+      D.verdict[q] = kOnHost | kDrainRowAny | kDrainRowMissing;
+    } else {
+      D.verdict[q] = 0;
+      ++per_topic[t + 1];
+    }
+  }
+  std::vector<DrainClassBin> bins;
+  uint64_t n_waves64 = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t n_q = per_topic[t + 1];
+    per_topic[t + 1] += per_topic[t];
+    if (!n_q) continue;
+    DrainClassBin B{};
+    B.topic = t;
+    B.q0 = per_topic[t];
+    B.n_q = n_q;
+    B.wave0 = static_cast<uint32_t>(n_waves64);
+    B.words = D.topics[t].n_pos / 64;
+    uint64_t steps = 0;  // of 64 lanes; a wave runs kDrainClassPer of them
+    if (B.words <= 64) {
+      while ((1u << B.lanes_log2) < B.words) ++B.lanes_log2;
+      steps = ((static_cast<uint64_t>(n_q) << B.lanes_log2) + 63) / 64;
+    } else {
+      B.waves = ceil_div(B.words, 64u);
+      steps = static_cast<uint64_t>(n_q) * B.waves;
+    }
+    n_waves64 += (steps + kDrainClassPer - 1) / kDrainClassPer;
+    if (n_waves64 * kDrainClassPer >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+    bins.push_back(B);
+  }
+  const uint32_t n_waves = static_cast<uint32_t>(n_waves64);
+  const uint32_t n_class = per_topic[nt];
+  D.cqueries.resize(n_class);
+  for (size_t q = 0; q < n; ++q)
+    if (D.verdict[q] == 0) D.cqueries[per_topic[D.queries[q].topic]++] = DrainClassQuery{D.queries[q].node, static_cast<uint32_t>(q)};
+  host_ms[0] = ms_since(h0);
+
+  DrainArgs a = drain_args(e);
+  if (n_class) {
+    std::vector<uint32_t> got(n);
+    HIP_TRY(D.d_cbins.ensure(bins.size() * sizeof(DrainClassBin)), "alloc drain bins");
+    HIP_TRY(D.d_cqueries.ensure(static_cast<size_t>(n_class) * sizeof(DrainClassQuery)), "alloc drain queries");
+    HIP_TRY(D.d_verdict.ensure(n * 4), "alloc drain verdicts");
+    HIP_TRY(hipMemcpyAsync(D.d_cbins.p, bins.data(), bins.size() * sizeof(DrainClassBin), hipMemcpyHostToDevice, s),
+            "upload drain bins");
+    HIP_TRY(hipMemcpyAsync(D.d_cqueries.p, D.cqueries.data(), static_cast<size_t>(n_class) * sizeof(DrainClassQuery),
+                           hipMemcpyHostToDevice, s),
+            "upload drain queries");
+    HIP_TRY(hipMemsetAsync(D.d_verdict.p, 0, n * 4, s), "clear drain verdicts");
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(launch_drain_classify(a, D.d_cbins.as<DrainClassBin>(), static_cast<uint32_t>(bins.size()),
+                                  D.d_cqueries.as<DrainClassQuery>(), n_waves, D.d_verdict.as<uint32_t>(), s),
+            "k_drain_classify");
+    HIP_TRY(tm.end(ms[0]), "event");
+    HIP_TRY(hipMemcpyAsync(got.data(), D.d_verdict.p, n * 4, hipMemcpyDeviceToHost, s), "read drain verdicts");
+    HIP_TRY(hipStreamSynchronize(s), "sync");  // (bins leaves scope; the verdicts number the lists)
+    for (size_t q = 0; q < n; ++q)
+      if (D.verdict[q] == 0) D.verdict[q] = got[q];
+  }
+
+  // lists, numbered by first use: one per topic with a full query, one per other query
+  h0 = hclock::now();
+  std::vector<uint32_t> topic_list(nt, PS_NONE);
+  std::vector<DrainQuery> lists;
+  uint64_t n_segs64 = 0;
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t v = D.verdict[q], t = topic[q];
+    if (!(v & kDrainRowAny)) {
+      list_out[q] = PS_NONE;
+      continue;
+    }
+    const bool full = !(v & kDrainRowMissing) && D.share;
+    if (full && topic_list[t] != PS_NONE) {
+      list_out[q] = topic_list[t];
+      continue;
+    }
+    list_out[q] = static_cast<uint32_t>(lists.size());
+    if (full) topic_list[t] = list_out[q];
+    lists.push_back(DrainQuery{t, full ? kDrainMaskRow : D.queries[q].node, static_cast<uint32_t>(n_segs64), 0});
+    n_segs64 += ceil_div(D.topics[t].n_pos, kDrainSegBits);
+    if (n_segs64 >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  }
+  const uint32_t n_lists = static_cast<uint32_t>(lists.size());
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  host_ms[1] = ms_since(h0);
+  *n_lists_out = n_lists;
+  D.hdr.assign(static_cast<size_t>(n_lists) + 2, 0);
+  auto& B = D.scratch;
+  if (n_lists) {
+    // (k_drain_offsets copies an error word behind the total: none here, a zero behind the header)
+    HIP_TRY(D.d_hdr.ensure((D.hdr.size() + 1) * 8), "alloc drain header");
+    uint32_t* const d_zero = reinterpret_cast<uint32_t*>(D.d_hdr.as<uint64_t>() + D.hdr.size());
+    HIP_TRY(hipMemsetAsync(d_zero, 0, 8, s), "clear drain error");
+    if ((rc = drain_count_scan(e, a, n_segs, B, lists.data(), n_lists, s, tm, ms[1]))) return rc;
+    HIP_TRY(launch_drain_offsets(a.queries, n_lists, B.d_off.as<uint64_t>(), n_segs, d_zero, D.d_hdr.as<uint64_t>(), s),
+            "k_drain_offsets");
+    HIP_TRY(tm.end(ms[2]), "event");
+    HIP_TRY(hipMemcpyAsync(D.hdr.data(), D.d_hdr.p, D.hdr.size() * 8, hipMemcpyDeviceToHost, s), "read drain offsets");
+    HIP_TRY(hipStreamSynchronize(s), "sync");  // (lists leaves scope; the total sizes the output)
+  }
+  const uint64_t total = D.hdr[n_lists];
+  *total_out = total;
+  if (list_cap >= n_lists) std::memcpy(list_off_out, D.hdr.data(), (static_cast<size_t>(n_lists) + 1) * 8);
+  if (list_cap < n_lists || total > cap) return e->fail(PS_E_RANGE, "output buffer too small");
+  if (total) {
+    HIP_TRY(D.d_lists.ensure(total * 4), "alloc drain lists");
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(launch_drain_emit(a, 0, n_segs, B.d_off.as<uint64_t>(), 0, D.d_lists.as<uint32_t>(), total, D.staged, s),
+            "k_drain_emit");
+    HIP_TRY(tm.end(ms[3]), "event");
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(hipMemcpyAsync(msg_out, D.d_lists.p, total * 4, hipMemcpyDeviceToHost, s), "read drain lists");
+    HIP_TRY(tm.end(ms[4]), "event");
+    HIP_TRY(hipStreamSynchronize(s), "sync");
+  }
+  if (D.timing)
+    std::fprintf(stderr,
+                 "psamd drain_shared: queries %zu classified %u waves %u lists %u segments %u ids %llu classify_ms %.4f "
+                 "count_ms %.4f scan_ms %.4f emit_ms %.4f copy_ms %.4f host_queries_ms %.4f host_lists_ms %.4f\n",
+                 n, n_class, n_waves, n_lists, n_segs, static_cast<unsigned long long>(total), ms[0], ms[1], ms[2], ms[3],
+                 ms[4], host_ms[0], host_ms[1]);
+  return PS_OK;
+}
+
+// ---- ps_drain_begin / ps_drain_end -------------------------
+
+int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n) {
+  if (!e || (n && (!topic || !peer))) return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_drain_begin on a multi-rank engine: use ps_drain");
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no run enqueued");
+  auto& D = e->drain;
+  if (D.slot_count == 2) return e->fail(PS_E_STATE, "two drains outstanding: ps_drain_end first");
+  if (const int rq = drain_check_queries(e, topic, peer, n)) return rq;
+  if (n >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries");
+  const auto t_host0 = hclock::now();
+  // behind the last launch of the window: `stream` follows a twin's tstream
+  if (const int rj = twin_join(e)) return rj;
+  int rc = drain_ready(e);
+  if (rc) return rc;
+  auto& S = D.slot[(D.slot_head + D.slot_count) & 1];
+  if (!S.ev_emit) {
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_emit, kStreamEvent), "drain event");
+    // (the host reads the view after ev_done: it keeps the system-scope release)
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming), "drain event");
+  }
+  hipStream_t s = e->stream;
+  const uint64_t seq0 = D.seq;
+  S.n = n;
+  size_t used = 0;
+  if ((rc = drain_tables_async(e, S, &used))) {
+    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
+    return rc;
+  }
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + align256(n * sizeof(DrainQuery))), "alloc drain staging");
+
+  // the queries, resolved straight into the slot's staging behind the tables
+  DrainQuery* hq = reinterpret_cast<DrainQuery*>(S.h_in + used);
+  uint64_t bound = 0;
+  const uint64_t n_segs64 = drain_resolve(e, topic, peer, n, hq, &bound);
+  if (n_segs64 >= kDrainRowLimit || bound > kDrainAsyncMaxIds) {
+    // no slot is taken: the table block staged in this slot's memory must
+    // have left it before the next ps_drain_begin writes there
+    if (used) HIP_TRY(hipStreamSynchronize(s), "sync");
+    return e->fail(PS_E_RANGE, n_segs64 >= kDrainRowLimit ? "too many rows in one drain"
+                                                          : "drain may exceed 2^30 ids: use ps_drain");
+  }
+  const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
+  S.hdr_bytes = align256((n + 2) * 8);
+  S.bound = bound;
+  const size_t res_bytes = S.hdr_bytes + bound * 4;
+  HIP_TRY(pinned_ensure(&S.h_res, &S.h_res_dev, &S.res_cap, res_bytes), "alloc drain view");
+  S.enqueued = false;
+  if (n_segs == 0) {  // nothing to read: the view is n + 1 zeros
+    std::memset(S.h_res, 0, (n + 2) * 8);
+    if (used) {  // (the table block staged in this slot: ps_drain_end waits for its upload)
+      HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+      S.enqueued = true;
+    }
+    ++D.slot_count;
+    return PS_OK;
+  }
+  if (!D.mapped_out) HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
+  DrainArgs a = drain_args(e);
+  const PhaseTimer untimed{D.ev_t, s, false};  // (nothing here may wait for the stream)
+  float none = 0;
+  if ((rc = drain_count_scan(e, a, n_segs, S.scratch, hq, n, s, untimed, none))) return rc;
+  uint8_t* res = D.mapped_out ? S.h_res_dev : S.d_res.as<uint8_t>();
+  // (the build's error word exists once a device build has run; the mask
+  // buffer's last word else)
+  if (!D.d_err) {
+    HIP_TRY(D.d_amask.ensure(8), "alloc drain masks");
+    D.d_err = D.d_amask.as<uint32_t>();
+    HIP_TRY(hipMemsetAsync(D.d_err, 0, 8, s), "clear drain error");
+  }
+  const uint64_t* seg_off = S.scratch.d_off.as<uint64_t>();
+  HIP_TRY(launch_drain_offsets(a.queries, a.n_queries, seg_off, n_segs, D.d_err, reinterpret_cast<uint64_t*>(res), s),
+          "k_drain_offsets");
+  HIP_TRY(launch_drain_emit(a, 0, n_segs, seg_off, 0, reinterpret_cast<uint32_t*>(res + S.hdr_bytes), bound, true, s),
+          "k_drain_emit");
+  // the emit is the last reader of the window's rows (run.cpp: drain_fence)
+  HIP_TRY(hipEventRecord(S.ev_emit, s), "event");
+  S.seen = e->d_seen.p;
+  S.emit_pending = true;
+  S.enqueued = true;
+  ++D.slot_count;
+  if (D.mapped_out) {
+    HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+  } else {
+    // the view leaves on the copy stream, beside whatever `stream` runs next
+    HIP_TRY(hipStreamWaitEvent(D.copy_stream, S.ev_emit, 0), "wait");
+    HIP_TRY(hipMemcpyAsync(S.h_res, S.d_res.p, res_bytes, hipMemcpyDeviceToHost, D.copy_stream), "read drain view");
+    HIP_TRY(hipEventRecord(S.ev_done, D.copy_stream), "event");
+  }
+  if (D.timing)
+    std::fprintf(stderr, "psamd drain_begin: queries %zu segments %u bound %llu tables %s out %s host_us %.1f\n", n, n_segs,
+                 static_cast<unsigned long long>(bound), used ? "built" : "kept", D.mapped_out ? "mapped" : "copy",
+                 1e3 * ms_since(t_host0));
+  return PS_OK;
+}
+
+int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_out, uint64_t* total_out) {
+  if (!e || !off_out || !msg_out || !total_out) return PS_E_INVAL;
+  auto& D = e->drain;
+  if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
+  auto& S = D.slot[D.slot_head];
+  D.slot_head ^= 1;
+  --D.slot_count;
+  if (S.enqueued) {
+    HIP_TRY(hipEventSynchronize(S.ev_done), "wait for the drain");
+    S.emit_pending = false;
+    S.enqueued = false;
+  }
+  const uint64_t* hdr = reinterpret_cast<const uint64_t*>(S.h_res);
+  *off_out = hdr;
+  *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.hdr_bytes);
+  *total_out = hdr[S.n];
+  if (const uint64_t err = hdr[S.n + 1])
+    return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
+                                                  : "drain tables: row bits do not ascend in arrival order");
+  if (hdr[S.n] > S.bound) return e->fail(PS_E_STATE, "drain total above its bound");
+  return PS_OK;
+}
+
+}  // extern "C"

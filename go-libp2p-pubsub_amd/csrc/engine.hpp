@@ -6,7 +6,9 @@
 //              pairs, k_flood tasks, the ghost exchange) -- pure host code,
 //              tested on the CPU through include/psengine_plan.h
 //   run.cpp    plan uploads and the round loop on the GPU (ps_run*)
-//   api.cpp    the remaining C ABI (topics, membership, reads, multi-GPU)
+//   drain.cpp  the batched drain of the last window (ps_drain*), host side
+//   api.cpp    the remaining C ABI (lifecycle, topics, membership, reads,
+//              multi-GPU)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -438,7 +440,7 @@ struct ps_engine {
   std::vector<std::vector<psamd::StartGroup>> last_groups;  // topic -> the last window's start groups
   std::vector<psamd::TopicDev> last_topics;
   bool have_window = false;
-  std::map<uint32_t, std::vector<uint32_t>> peer_node;  // topic -> peer -> node (ps_read_peer_messages)
+  std::map<uint32_t, std::vector<uint32_t>> peer_node;  // topic -> peer -> node (peer_node_map)
   std::vector<uint64_t> peer_node_epoch;                 // graph_epoch each map was built for
   uint64_t window_seq = 0;  // bumped whenever last_* change (a new last window)
 
@@ -446,9 +448,15 @@ struct ps_engine {
   // message id, message mask or arrival order), built on the first drain
   // after a window; count / offset / query staging; two output slabs
   struct Drain {
+    // one call's queries on the device, the ids per segment, their offsets
+    // (the scan of the counts) and the scan's temporary storage
+    struct Scratch {
+      psamd::DevBuf d_queries, d_cnt, d_off, d_scan;
+    };
     uint64_t seq = ~0ull;  // window_seq the tables on the device were built for
     std::vector<psamd::DrainTopic> topics;
-    psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order, d_queries, d_cnt, d_off, d_scan, d_slab[2];
+    psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order, d_slab[2];
+    Scratch scratch;  // of ps_drain and ps_drain_shared (synchronous: one call at a time)
     std::vector<psamd::DrainQuery> queries;
     std::vector<uint64_t> off;  // host copy of the segment offsets
     hipStream_t copy_stream = nullptr;
@@ -487,7 +495,8 @@ struct ps_engine {
       uint8_t* h_res = nullptr;
       uint8_t* h_res_dev = nullptr;  // h_res, device-mapped
       size_t res_cap = 0;
-      psamd::DevBuf d_queries, d_cnt, d_off, d_scan, d_res;
+      Scratch scratch;
+      psamd::DevBuf d_res;
       hipEvent_t ev_emit = nullptr, ev_done = nullptr;
       size_t n = 0, hdr_bytes = 0;
       uint64_t bound = 0;
@@ -637,6 +646,38 @@ int twin_join(ps_engine* e);
 // & co.), waits for every pending ps_drain_begin emit that reads that set (a
 // no-op when none is pending, or for `stream`, which the drains run on)
 int drain_fence(ps_engine* e, hipStream_t s);
+// drain.cpp: frees the drain's stream, events and pinned memory (ps_destroy)
+void drain_destroy(ps_engine* e);
+
+// The last window's messages of topic t, in window-slot order (slot li = the
+// topic's rank last_lo + li): their run indices, a slice of run_sorted
+inline WinSlice window_slice(const ps_engine* e, uint32_t t) {
+  WinSlice w;
+  w.idx = e->run_sorted.data() + e->run_topic_off[t] + e->last_lo[t];
+  w.n = e->last_cnt[t];
+  return w;
+}
+// ... and their row bits by window slot (last_pos), looked up once per topic:
+// null where bit li is slot li itself
+inline const uint32_t* window_bits(const ps_engine* e, uint32_t t) {
+  return t < e->last_pos.size() && !e->last_pos[t].empty() ? e->last_pos[t].data() : nullptr;
+}
+inline uint32_t window_bit(const uint32_t* bits, uint32_t li) { return bits ? bits[li] : li; }
+// topic -> peer -> node of the current node space (kNone: the root on the rank
+// that owns it, a peer not subscribed or another rank's), built once per node
+// space; d = the topic's entry of last_topics.  (Inline: the drains look it
+// up once per query.)
+inline const std::vector<uint32_t>& peer_node_map(ps_engine* e, uint32_t topic, const TopicDev& d) {
+  auto& pm = e->peer_node[topic];
+  if (e->peer_node_epoch.size() != e->topics.size()) e->peer_node_epoch.assign(e->topics.size(), ~0ull);
+  if (e->peer_node_epoch[topic] != e->graph_epoch) {
+    pm.assign(e->cfg.n_peers, kNone);
+    const uint32_t u0 = (d.flags & kTopicRootLocal) ? 1 : 0;
+    for (uint32_t k = u0; k < d.n_nodes; ++k) pm[e->node_peer[d.nbase + k]] = k;
+    e->peer_node_epoch[topic] = e->graph_epoch;
+  }
+  return pm;
+}
 
 // plan.cpp (host only: no device calls)
 int plan_window_layout(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win,

@@ -12,8 +12,8 @@ LIB = os.path.join(LIBDIR, "libpsengine.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "pull.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp", "tree.cpp",
-           "dist.cpp", "codec.cpp", "pubsub.cpp"]
+SOURCES = ["kernels.hip", "pull.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp", "drain.cpp",
+           "tree.cpp", "dist.cpp", "codec.cpp", "pubsub.cpp"]
 HEADERS = ["kernels.hpp", "devutil.hpp", "gbuild.hpp", "tree.hpp", "dist.hpp", "engine.hpp"]
 
 

@@ -14,7 +14,7 @@ import pytest
 
 import oracle as O
 import psengine as PE
-from test_gpu_drain_batch import drain_lists, oracle_lists, random_mesh2, random_tree, tree_hops
+from test_gpu_drain_batch import drain_lists, oracle_lists, random_mesh2, random_tree, split, tree_hops
 
 pytestmark = pytest.mark.gpu
 
@@ -143,6 +143,54 @@ def test_mesh(paced):
         assert sum(len(g) for g in got) > n_msgs  # (somebody was reached)
         if not paced:  # a static live mask: whoever is reached holds every message
             assert res[1].size - 1 == 1 and res[2].size == n_msgs
+
+
+def test_on_device_built_tables_and_back():
+    """The three drains share one set of tables per window, built by whichever
+    runs first.  Window A: drain_begin builds them on the device (a tree topic
+    of 65 messages: two mask words, one bit in the second; a paced mesh topic:
+    the arrival-order table), and drain_shared and drain read those.  Window
+    B, the same batch again: drain_shared builds them on the host and
+    drain_begin reads those."""
+    rng = np.random.default_rng(131)
+    n, roots = 300, (3, 8)
+    parent = random_tree(rng, n, roots[0])
+    rp, cl = random_mesh2(rng, n, roots[1])
+    live = (rng.random(n) > 0.1).astype(np.uint8)
+    live[list(roots)] = 1
+    topics = np.concatenate([np.zeros(65), np.ones(40)]).astype(np.uint32)
+    starts = np.concatenate([np.zeros(65), rng.integers(0, 5, size=40)]).astype(np.uint32)
+    qt = np.repeat([0, 1], n).astype(np.uint32)
+    qp = np.tile(np.arange(n), 2).astype(np.uint32)
+    with PE.Engine(n, 2) as eng:
+        eng.set_tree(0, roots[0], parent)
+        eng.set_children(1, roots[1], rp, cl)
+        eng.set_live(live)
+
+        def window(shared_first):
+            first = eng.publish(topics, starts)
+            eng.run()
+            got = {}
+            for which in ("shared", "async") if shared_first else ("async", "shared"):
+                if which == "shared":
+                    got[which] = expand(*shared(eng, qt, qp))
+                else:
+                    eng.drain_begin(qt, qp)
+                    got[which] = split(*eng.drain_end())
+            want = drain_lists(eng, qt, qp)
+            assert got["shared"] == want
+            assert got["async"] == want
+            return first, want
+
+        first_a, a = window(shared_first=False)
+        hop = tree_hops(parent, roots[0], live)
+        assert a[:n] == oracle_lists(qt[:n], qp[:n], topics, starts, first_a, hop, roots[0])
+        # (both topics reached somebody: ten tree subscribers or more, more than one mesh subscriber)
+        assert sum(1 for x in a[:n] if len(x) == 65) >= 10 and sum(len(x) for x in a[n:]) > 40
+        first_b, b = window(shared_first=True)
+        assert first_b == first_a + topics.size
+        assert b[:n] == [[m + first_b - first_a for m in x] for x in a[:n]]
+        assert [len(x) for x in b[n:]] == [len(x) for x in a[n:]]
 
 
 def one_topic(n_msgs, seed):
