@@ -1,7 +1,8 @@
 // drain.cpp -- the host side of the batched drain (kernels: drain.hip;
-// DESIGN.md §5.5): ps_drain, ps_drain_shared, ps_drain_begin / ps_drain_end.
+// DESIGN.md §5.5): ps_drain, ps_drain_shared, ps_drain_begin / ps_drain_end,
+// ps_drain_shared_begin / ps_drain_shared_end.
 //
-// What the three paths rely on, between them and with run.cpp:
+// What the four paths rely on, between them and with run.cpp:
 //  - D.seq / D.p_*: one set of device tables per window, built by whichever
 //    path runs first (drain_tables on the host, drain_tables_async on the
 //    device) and reused by the others.  A device build given up half way sets
@@ -18,6 +19,18 @@
 //    slab k - 1 is copied while slab k is emitted; under timing the copy runs
 //    in line on `stream`.
 //  - Slot::seen / emit_pending / ev_emit are read by drain_fence (run.cpp).
+//  - The two slots serve both asynchronous forms, oldest first; Slot::shared
+//    says which end call completes a slot, and the other one leaves it alone.
+//  - ps_drain_shared_begin stages its input (queries, initial verdicts, sorted
+//    queries, bins) behind the table block in the slot's h_in, as ps_drain_begin
+//    stages its queries, and follows the same rule when it fails after staging.
+//    Both forms of ps_drain_shared sort their queries with drain_shared_sort,
+//    which leaves D.verdict and D.cqueries; neither is a copy's source in the
+//    asynchronous form (the slot's pinned staging is).
+//  - ps_drain_shared_begin sizes every buffer and grid from its caps; the
+//    counts live in the slot's DrainCtl on the device and reach the host only
+//    in the view's header.  Its ev_emit stands behind classify, count and emit
+//    alike (all on `stream`), and is recorded even when no list has a segment.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -199,8 +212,8 @@ int drain_tables(ps_engine* e) {
 // mask from them behind the window, with no host wait.  A mesh topic of a
 // run with several start rounds keeps the host's arrival-order table
 // (kDrainGather, as drain_tables above), staged the same way.  `used`: the
-// bytes of S.h_in taken (the queries follow).
-int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t* used) {
+// bytes of S.h_in taken; the caller stages `tail` bytes of its own behind them.
+int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used) {
   auto& D = e->drain;
   *used = 0;
   if (D.seq == e->window_seq) return PS_OK;
@@ -253,7 +266,7 @@ int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t* used) {
   const size_t o_order = align256(o_start + n_msgs * 4);
   const size_t o_gids = align256(o_order + n_gather * 4);
   const size_t block = align256(o_gids + n_gather * 4);
-  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + align256(S.n * sizeof(DrainQuery))), "alloc drain staging");
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + tail), "alloc drain staging");
   HIP_TRY(D.d_ablock.ensure(block), "alloc drain tables");
   HIP_TRY(D.d_aids.ensure((n_pos + n_gather) * 4), "alloc drain ids");
   HIP_TRY(D.d_amask.ensure((n_pos >> 6) * 8 + 8), "alloc drain masks");
@@ -410,6 +423,139 @@ int drain_count_scan(ps_engine* e, DrainArgs& a, uint32_t n_segs, Drain::Scratch
   HIP_TRY(tm.begin(), "event");
   scan_bytes = B.d_scan.bytes;
   HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), n_segs + 1, s), "drain scan");
+  return PS_OK;
+}
+
+// ps_drain_shared's queries sorted for the classify pass (both forms of the
+// call).  queries[q] = (topic, node) of every query; D.verdict[q] = 0 for a
+// query the classify pass decides (a row of a mask-layout topic), else
+// kOnHost | the verdict: nothing for a query without a row, any | missing --
+// a private list -- for a row of an arrival-order (kDrainGather) topic.  The
+// classified queries, sorted by topic (a counting sort: a topic's rows have
+// one width), go to D.cqueries, one bin per topic.  The sort is stable: a
+// topic's queries keep their order (k_drain_first relies on it).
+constexpr uint32_t kOnHost = 0x80000000u;
+struct SharedSort {
+  std::vector<DrainClassBin> bins;
+  uint32_t n_class = 0, n_waves = 0;
+  uint32_t n_rows = 0, n_gather = 0;  // queries with a row; those of kDrainGather topics
+  uint64_t row_ids = 0, gather_ids = 0, bin_ids = 0;  // window messages: per such query; per bin
+  uint32_t max_segs = 0;  // segments of the widest topic with a row queried
+};
+int drain_shared_sort(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, DrainQuery* queries,
+                      SharedSort* R) {
+  auto& D = e->drain;
+  const uint32_t nt = static_cast<uint32_t>(D.topics.size());
+  D.verdict.assign(n, kOnHost);
+  std::vector<uint32_t> per_topic(nt + 1, 0);
+  std::vector<const uint32_t*> peer_map(nt, nullptr);  // (looked up once per topic, not per query)
+  for (size_t q = 0; q < n; ++q) {
+    const uint32_t t = topic[q];
+    DrainQuery& Q = queries[q];
+    Q = DrainQuery{t, 0, 0, 0};
+    const uint32_t u = drain_node(e, t, peer[q], peer_map[t]);
+    if (u == kNone) continue;
+    Q.node = u;
+    ++R->n_rows;
+    R->row_ids += e->last_cnt[t];
+    R->max_segs = std::max(R->max_segs, ceil_div(D.topics[t].n_pos, kDrainSegBits));
+    if (D.topics[t].flags & kDrainGather) {
+      D.verdict[q] = kOnHost | kDrainRowAny | kDrainRowMissing;
+      ++R->n_gather;
+      R->gather_ids += e->last_cnt[t];
+    } else {
+      D.verdict[q] = 0;
+      ++per_topic[t + 1];
+    }
+  }
+  uint64_t n_waves64 = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t n_q = per_topic[t + 1];
+    per_topic[t + 1] += per_topic[t];
+    if (!n_q) continue;
+    DrainClassBin B{};
+    B.topic = t;
+    B.q0 = per_topic[t];
+    B.n_q = n_q;
+    B.wave0 = static_cast<uint32_t>(n_waves64);
+    B.words = D.topics[t].n_pos / 64;
+    uint64_t steps = 0;  // of 64 lanes; a wave runs kDrainClassPer of them
+    if (B.words <= 64) {
+      while ((1u << B.lanes_log2) < B.words) ++B.lanes_log2;
+      steps = ((static_cast<uint64_t>(n_q) << B.lanes_log2) + 63) / 64;
+    } else {
+      B.waves = ceil_div(B.words, 64u);
+      steps = static_cast<uint64_t>(n_q) * B.waves;
+    }
+    n_waves64 += (steps + kDrainClassPer - 1) / kDrainClassPer;
+    if (n_waves64 * kDrainClassPer >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+    R->bins.push_back(B);
+    R->bin_ids += e->last_cnt[t];
+  }
+  R->n_waves = static_cast<uint32_t>(n_waves64);
+  R->n_class = per_topic[nt];
+  D.cqueries.resize(R->n_class);
+  for (size_t q = 0; q < n; ++q)
+    if (D.verdict[q] == 0) D.cqueries[per_topic[queries[q].topic]++] = DrainClassQuery{queries[q].node, static_cast<uint32_t>(q)};
+  return PS_OK;
+}
+
+// The slot the next asynchronous drain takes, its events made
+int drain_next_slot(ps_engine* e, Drain::Slot** out) {
+  auto& D = e->drain;
+  auto& S = D.slot[(D.slot_head + D.slot_count) & 1];
+  if (!S.ev_emit) {
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_emit, kStreamEvent), "drain event");
+    // (the host reads the view after ev_done: it keeps the system-scope release)
+    HIP_TRY(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming), "drain event");
+  }
+  *out = &S;
+  return PS_OK;
+}
+
+// The device table build's error word: it exists once a device build has
+// run; the mask buffer's last word else
+int drain_err_word(ps_engine* e, hipStream_t s) {
+  auto& D = e->drain;
+  if (D.d_err) return PS_OK;
+  HIP_TRY(D.d_amask.ensure(8), "alloc drain masks");
+  D.d_err = D.d_amask.as<uint32_t>();
+  HIP_TRY(hipMemsetAsync(D.d_err, 0, 8, s), "clear drain error");
+  return PS_OK;
+}
+
+// An asynchronous drain's last steps, behind its last kernel on `stream`:
+// that kernel is the last reader of the window's rows (run.cpp: drain_fence);
+// the slot is taken; the view leaves on the copy stream, beside whatever
+// `stream` runs next (to_host), or was written in place (mapped memory).
+int drain_slot_enqueued(ps_engine* e, Drain::Slot& S, size_t res_bytes, bool to_host) {
+  auto& D = e->drain;
+  hipStream_t s = e->stream;
+  HIP_TRY(hipEventRecord(S.ev_emit, s), "event");
+  S.seen = e->d_seen.p;
+  S.emit_pending = true;
+  S.enqueued = true;
+  ++D.slot_count;
+  if (!to_host) {
+    HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+  } else {
+    HIP_TRY(hipStreamWaitEvent(D.copy_stream, S.ev_emit, 0), "wait");
+    HIP_TRY(hipMemcpyAsync(S.h_res, S.d_res.p, res_bytes, hipMemcpyDeviceToHost, D.copy_stream), "read drain view");
+    HIP_TRY(hipEventRecord(S.ev_done, D.copy_stream), "event");
+  }
+  return PS_OK;
+}
+
+// The oldest slot leaves the queue; its view is complete on return
+int drain_slot_complete(ps_engine* e, Drain::Slot& S) {
+  auto& D = e->drain;
+  D.slot_head ^= 1;
+  --D.slot_count;
+  if (S.enqueued) {
+    HIP_TRY(hipEventSynchronize(S.ev_done), "wait for the drain");
+    S.emit_pending = false;
+    S.enqueued = false;
+  }
   return PS_OK;
 }
 
@@ -571,57 +717,12 @@ int ps_drain_shared(ps_engine* e, const uint32_t* topic, const uint32_t* peer, s
   float ms[5] = {0, 0, 0, 0, 0};  // classify, count, scan, emit, copy (PSAMD_DRAIN_TIMING)
   const PhaseTimer tm{D.ev_t, s, D.timing};
 
-  // queries -> nodes; those of mask-layout topics, sorted by topic (a
-  // counting sort: a topic's rows have one width), go to the classify pass
   const uint32_t nt = static_cast<uint32_t>(D.topics.size());
-  constexpr uint32_t kOnHost = 0x80000000u;  // verdict decided here: | kDrainRow*
   D.queries.resize(n);
-  D.verdict.assign(n, kOnHost);
-  std::vector<uint32_t> per_topic(nt + 1, 0);
-  std::vector<const uint32_t*> peer_map(nt, nullptr);  // (looked up once per topic, not per query)
-  for (size_t q = 0; q < n; ++q) {
-    const uint32_t t = topic[q];
-    DrainQuery& Q = D.queries[q];
-    Q = DrainQuery{t, 0, 0, 0};
-    const uint32_t u = drain_node(e, t, peer[q], peer_map[t]);
-    if (u == kNone) continue;
-    Q.node = u;
-    if (D.topics[t].flags & kDrainGather) {
-      D.verdict[q] = kOnHost | kDrainRowAny | kDrainRowMissing;
-    } else {
-      D.verdict[q] = 0;
-      ++per_topic[t + 1];
-    }
-  }
-  std::vector<DrainClassBin> bins;
-  uint64_t n_waves64 = 0;
-  for (uint32_t t = 0; t < nt; ++t) {
-    const uint32_t n_q = per_topic[t + 1];
-    per_topic[t + 1] += per_topic[t];
-    if (!n_q) continue;
-    DrainClassBin B{};
-    B.topic = t;
-    B.q0 = per_topic[t];
-    B.n_q = n_q;
-    B.wave0 = static_cast<uint32_t>(n_waves64);
-    B.words = D.topics[t].n_pos / 64;
-    uint64_t steps = 0;  // of 64 lanes; a wave runs kDrainClassPer of them
-    if (B.words <= 64) {
-      while ((1u << B.lanes_log2) < B.words) ++B.lanes_log2;
-      steps = ((static_cast<uint64_t>(n_q) << B.lanes_log2) + 63) / 64;
-    } else {
-      B.waves = ceil_div(B.words, 64u);
-      steps = static_cast<uint64_t>(n_q) * B.waves;
-    }
-    n_waves64 += (steps + kDrainClassPer - 1) / kDrainClassPer;
-    if (n_waves64 * kDrainClassPer >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-    bins.push_back(B);
-  }
-  const uint32_t n_waves = static_cast<uint32_t>(n_waves64);
-  const uint32_t n_class = per_topic[nt];
-  D.cqueries.resize(n_class);
-  for (size_t q = 0; q < n; ++q)
-    if (D.verdict[q] == 0) D.cqueries[per_topic[D.queries[q].topic]++] = DrainClassQuery{D.queries[q].node, static_cast<uint32_t>(q)};
+  SharedSort R;
+  if ((rc = drain_shared_sort(e, topic, peer, n, D.queries.data(), &R))) return rc;
+  const std::vector<DrainClassBin>& bins = R.bins;
+  const uint32_t n_waves = R.n_waves, n_class = R.n_class;
   host_ms[0] = ms_since(h0);
 
   DrainArgs a = drain_args(e);
@@ -726,21 +827,20 @@ int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, si
   if (const int rj = twin_join(e)) return rj;
   int rc = drain_ready(e);
   if (rc) return rc;
-  auto& S = D.slot[(D.slot_head + D.slot_count) & 1];
-  if (!S.ev_emit) {
-    HIP_TRY(hipEventCreateWithFlags(&S.ev_emit, kStreamEvent), "drain event");
-    // (the host reads the view after ev_done: it keeps the system-scope release)
-    HIP_TRY(hipEventCreateWithFlags(&S.ev_done, hipEventDisableTiming), "drain event");
-  }
+  Drain::Slot* slot = nullptr;
+  if ((rc = drain_next_slot(e, &slot))) return rc;
+  auto& S = *slot;
   hipStream_t s = e->stream;
   const uint64_t seq0 = D.seq;
   S.n = n;
+  S.shared = false;
   size_t used = 0;
-  if ((rc = drain_tables_async(e, S, &used))) {
+  const size_t tail = align256(n * sizeof(DrainQuery));
+  if ((rc = drain_tables_async(e, S, tail, &used))) {
     D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
     return rc;
   }
-  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + align256(n * sizeof(DrainQuery))), "alloc drain staging");
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + tail), "alloc drain staging");
 
   // the queries, resolved straight into the slot's staging behind the tables
   DrainQuery* hq = reinterpret_cast<DrainQuery*>(S.h_in + used);
@@ -774,32 +874,13 @@ int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, si
   float none = 0;
   if ((rc = drain_count_scan(e, a, n_segs, S.scratch, hq, n, s, untimed, none))) return rc;
   uint8_t* res = D.mapped_out ? S.h_res_dev : S.d_res.as<uint8_t>();
-  // (the build's error word exists once a device build has run; the mask
-  // buffer's last word else)
-  if (!D.d_err) {
-    HIP_TRY(D.d_amask.ensure(8), "alloc drain masks");
-    D.d_err = D.d_amask.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(D.d_err, 0, 8, s), "clear drain error");
-  }
+  if ((rc = drain_err_word(e, s))) return rc;
   const uint64_t* seg_off = S.scratch.d_off.as<uint64_t>();
   HIP_TRY(launch_drain_offsets(a.queries, a.n_queries, seg_off, n_segs, D.d_err, reinterpret_cast<uint64_t*>(res), s),
           "k_drain_offsets");
   HIP_TRY(launch_drain_emit(a, 0, n_segs, seg_off, 0, reinterpret_cast<uint32_t*>(res + S.hdr_bytes), bound, true, s),
           "k_drain_emit");
-  // the emit is the last reader of the window's rows (run.cpp: drain_fence)
-  HIP_TRY(hipEventRecord(S.ev_emit, s), "event");
-  S.seen = e->d_seen.p;
-  S.emit_pending = true;
-  S.enqueued = true;
-  ++D.slot_count;
-  if (D.mapped_out) {
-    HIP_TRY(hipEventRecord(S.ev_done, s), "event");
-  } else {
-    // the view leaves on the copy stream, beside whatever `stream` runs next
-    HIP_TRY(hipStreamWaitEvent(D.copy_stream, S.ev_emit, 0), "wait");
-    HIP_TRY(hipMemcpyAsync(S.h_res, S.d_res.p, res_bytes, hipMemcpyDeviceToHost, D.copy_stream), "read drain view");
-    HIP_TRY(hipEventRecord(S.ev_done, D.copy_stream), "event");
-  }
+  if ((rc = drain_slot_enqueued(e, S, res_bytes, !D.mapped_out))) return rc;
   if (D.timing)
     std::fprintf(stderr, "psamd drain_begin: queries %zu segments %u bound %llu tables %s out %s host_us %.1f\n", n, n_segs,
                  static_cast<unsigned long long>(bound), used ? "built" : "kept", D.mapped_out ? "mapped" : "copy",
@@ -812,13 +893,8 @@ int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_ou
   auto& D = e->drain;
   if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
   auto& S = D.slot[D.slot_head];
-  D.slot_head ^= 1;
-  --D.slot_count;
-  if (S.enqueued) {
-    HIP_TRY(hipEventSynchronize(S.ev_done), "wait for the drain");
-    S.emit_pending = false;
-    S.enqueued = false;
-  }
+  if (S.shared) return e->fail(PS_E_STATE, "the oldest drain is a shared one: ps_drain_shared_end");
+  if (const int rc = drain_slot_complete(e, S)) return rc;
   const uint64_t* hdr = reinterpret_cast<const uint64_t*>(S.h_res);
   *off_out = hdr;
   *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.hdr_bytes);
@@ -827,6 +903,203 @@ int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_ou
     return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
                                                   : "drain tables: row bits do not ascend in arrival order");
   if (hdr[S.n] > S.bound) return e->fail(PS_E_STATE, "drain total above its bound");
+  return PS_OK;
+}
+
+// ---- ps_drain_shared_begin / ps_drain_shared_end -----------
+
+// ps_drain_shared's answer enqueued behind the last run, with no host wait:
+// tables (device build), classify, the list assignment (what the host loop of
+// ps_drain_shared does between its waits: k_drain_first / _keys / scan /
+// _lists), then count / scan / offsets / emit over the lists with the counts
+// read from the slot's control block, all on `stream`; the view (header,
+// list_off, list_of_query, ids) leaves in one copy on the copy stream.  The
+// host knows only the caps: every buffer and grid is sized by them.
+int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, size_t list_cap,
+                          size_t id_cap) {
+  if (!e || (n && (!topic || !peer))) return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_drain_shared_begin on a multi-rank engine: use ps_drain");
+  if (!e->have_window) return e->fail(PS_E_NOTREADY, "no run enqueued");
+  auto& D = e->drain;
+  if (D.slot_count == 2) return e->fail(PS_E_STATE, "two drains outstanding: end one first");
+  if (const int rq = drain_check_queries(e, topic, peer, n)) return rq;
+  if (n >= 0x7FFFFFFFull || list_cap >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries or lists");
+  const auto t_host0 = hclock::now();
+  if (const int rj = twin_join(e)) return rj;
+  int rc = drain_ready(e);
+  if (rc) return rc;
+  Drain::Slot* slot = nullptr;
+  if ((rc = drain_next_slot(e, &slot))) return rc;
+  auto& S = *slot;
+  hipStream_t s = e->stream;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+
+  // staged behind the tables: queries | initial verdicts | sorted queries | bins
+  const size_t o_v = align256(n * sizeof(DrainQuery));
+  const size_t o_cq = o_v + align256(n * 4);
+  const size_t o_bins = o_cq + align256(n * sizeof(DrainClassQuery));
+  const size_t tail = o_bins + align256(nt * sizeof(DrainClassBin));
+  const uint64_t seq0 = D.seq;
+  size_t used = 0;
+  if ((rc = drain_tables_async(e, S, tail, &used))) {
+    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
+    return rc;
+  }
+  // From here to the slot's taking, a failure leaves no slot taken: the table
+  // block staged in this slot's memory must have left it before the next
+  // begin writes there
+  auto give_up = [&](int code, const char* what) -> int {
+    if (used) HIP_TRY(hipStreamSynchronize(s), "sync");
+    return e->fail(code, what);
+  };
+  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + tail), "alloc drain staging");
+  uint8_t* const h = S.h_in + used;
+  DrainQuery* const hq = reinterpret_cast<DrainQuery*>(h);
+  SharedSort R;
+  if (drain_shared_sort(e, topic, peer, n, hq, &R)) return give_up(PS_E_RANGE, "too many rows in one drain");
+
+  // the caps: the engine's (the size of the answer while full rows share) or the caller's
+  if (list_cap == 0 && id_cap == 0) {
+    list_cap = D.share ? R.bins.size() + R.n_gather : R.n_rows;
+    id_cap = D.share ? R.bin_ids + R.gather_ids : R.row_ids;
+  }
+  if (id_cap > kDrainAsyncMaxIds) return give_up(PS_E_RANGE, "drain may exceed 2^30 ids: use ps_drain_shared");
+  const uint64_t seg_bound64 = static_cast<uint64_t>(list_cap) * R.max_segs;
+  // (the numbering scan keeps the segments in the low half of its key)
+  if (seg_bound64 >= kDrainRowLimit || static_cast<uint64_t>(n) * R.max_segs >= kDrainRowLimit)
+    return give_up(PS_E_RANGE, "too many rows in one drain");
+  const uint32_t seg_bound = static_cast<uint32_t>(seg_bound64);
+
+  S.n = n;
+  S.shared = true;
+  S.list_cap = list_cap;
+  S.id_cap = id_cap;
+  S.o_off = align256(sizeof(DrainSharedHdr));
+  S.o_lq = S.o_off + align256((list_cap + 1) * 8);
+  S.o_ids = S.o_lq + align256(n * 4);
+  const size_t res_bytes = S.o_ids + id_cap * 4;
+  HIP_TRY(pinned_ensure(&S.h_res, &S.h_res_dev, &S.res_cap, res_bytes), "alloc drain view");
+  S.enqueued = false;
+  if (R.n_rows == 0) {  // no row to read: no list, written here
+    std::memset(S.h_res, 0, S.o_off + 8);
+    std::memset(S.h_res + S.o_lq, 0xFF, n * 4);
+    if (used) {  // (the table block staged in this slot: the end waits for its upload)
+      HIP_TRY(hipEventRecord(S.ev_done, s), "event");
+      S.enqueued = true;
+    }
+    ++D.slot_count;
+    return PS_OK;
+  }
+
+  // device buffers, sized by n and the caps; they only grow
+  auto& B = S.scratch;
+  const size_t o_first = align256(sizeof(DrainCtl));
+  HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
+  HIP_TRY(S.d_in.ensure(tail), "alloc drain input");
+  HIP_TRY(S.d_key.ensure(2 * n * 8), "alloc drain keys");
+  HIP_TRY(S.d_aux.ensure(o_first + nt * 4), "alloc drain control");
+  HIP_TRY(B.d_queries.ensure(list_cap * sizeof(DrainQuery)), "alloc drain lists");
+  HIP_TRY(B.d_cnt.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain counts");
+  HIP_TRY(B.d_off.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain offsets");
+  size_t scan_bytes = 0, scan_keys = 0;  // one temporary for both scans
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s),
+          "size drain scan");
+  HIP_TRY(drain_scan(nullptr, &scan_keys, S.d_key.as<uint64_t>(), S.d_key.as<uint64_t>() + n, static_cast<uint32_t>(n), s),
+          "size drain scan");
+  HIP_TRY(B.d_scan.ensure(std::max(scan_bytes, scan_keys)), "alloc drain scan");
+
+  // the input: the initial verdicts (0 where the classify pass decides), the
+  // sorted queries and the bins beside the queries, in one upload
+  uint32_t* const hv = reinterpret_cast<uint32_t*>(h + o_v);
+  for (size_t q = 0; q < n; ++q) hv[q] = D.verdict[q] & ~kOnHost;
+  if (R.n_class) std::memcpy(h + o_cq, D.cqueries.data(), static_cast<size_t>(R.n_class) * sizeof(DrainClassQuery));
+  if (!R.bins.empty()) std::memcpy(h + o_bins, R.bins.data(), R.bins.size() * sizeof(DrainClassBin));
+  uint8_t* const din = S.d_in.as<uint8_t>();
+  HIP_TRY(hipMemcpyAsync(din, h, tail, hipMemcpyHostToDevice, s), "upload drain queries");
+  uint8_t* const aux = S.d_aux.as<uint8_t>();
+  DrainCtl* const ctl = reinterpret_cast<DrainCtl*>(aux);
+  HIP_TRY(hipMemsetAsync(aux + o_first, 0xFF, nt * 4, s), "preset drain firsts");
+  if ((rc = drain_err_word(e, s))) return rc;
+
+  // (PSAMD_DRAIN_TIMING: the phases run apart and are waited for; else nothing here waits)
+  float ms[5] = {0, 0, 0, 0, 0};  // classify, assign, count, scan + offsets, emit
+  const PhaseTimer tm{D.ev_t, s, D.timing};
+  DrainArgs a = drain_args(e);
+  uint32_t* const verdict = reinterpret_cast<uint32_t*>(din + o_v);
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_classify(a, reinterpret_cast<const DrainClassBin*>(din + o_bins), static_cast<uint32_t>(R.bins.size()),
+                                reinterpret_cast<const DrainClassQuery*>(din + o_cq), R.n_waves, verdict, s),
+          "k_drain_classify");
+  HIP_TRY(tm.end(ms[0]), "event");
+  uint8_t* const res = S.d_res.as<uint8_t>();
+  DrainAssign g{};
+  g.topics = D.p_topics;
+  g.queries = reinterpret_cast<const DrainQuery*>(din);
+  g.verdict = verdict;
+  g.sorted = reinterpret_cast<const DrainClassQuery*>(din + o_cq);
+  g.n_sorted = R.n_class;
+  g.n = static_cast<uint32_t>(n);
+  g.share = D.share;
+  g.first = reinterpret_cast<uint32_t*>(aux + o_first);
+  g.key = S.d_key.as<uint64_t>();
+  g.key_off = g.key + n;
+  g.scan_temp = B.d_scan.p;
+  g.scan_bytes = B.d_scan.bytes;
+  g.lists = B.d_queries.as<DrainQuery>();
+  g.list_cap = static_cast<uint32_t>(list_cap);
+  g.seg_bound = seg_bound;
+  g.list_of_query = reinterpret_cast<uint32_t*>(res + S.o_lq);
+  g.ctl = ctl;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_assign(g, s), "drain list assignment");
+  HIP_TRY(tm.end(ms[1]), "event");
+  a.queries = g.lists;
+  a.n_queries = 0;  // (the kernels read it from the control block)
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, B.d_cnt.as<uint64_t>(), s), "k_drain_count_dev");
+  HIP_TRY(tm.end(ms[2]), "event");
+  HIP_TRY(tm.begin(), "event");
+  scan_bytes = B.d_scan.bytes;
+  HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s), "drain scan");
+  HIP_TRY(launch_drain_offsets_dev(g.lists, ctl, g.list_cap, B.d_off.as<uint64_t>(), id_cap, D.d_err,
+                                   reinterpret_cast<DrainSharedHdr*>(res), reinterpret_cast<uint64_t*>(res + S.o_off), s),
+          "k_drain_offsets_dev");
+  HIP_TRY(tm.end(ms[3]), "event");
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_emit_dev(a, ctl, seg_bound, B.d_off.as<uint64_t>(), reinterpret_cast<uint32_t*>(res + S.o_ids), id_cap, s),
+          "k_drain_emit_dev");
+  HIP_TRY(tm.end(ms[4]), "event");
+  // classify reads every queried row, count and emit the private ones: the
+  // event behind the emit covers them all, with or without a segment
+  if ((rc = drain_slot_enqueued(e, S, res_bytes, true))) return rc;
+  if (D.timing)
+    std::fprintf(stderr,
+                 "psamd drain_shared_begin: queries %zu classified %u waves %u list_cap %zu id_cap %zu seg_bound %u tables %s "
+                 "classify_ms %.4f assign_ms %.4f count_ms %.4f scan_ms %.4f emit_ms %.4f view_bytes %zu host_us %.1f\n",
+                 n, R.n_class, R.n_waves, list_cap, id_cap, seg_bound, used ? "built" : "kept", ms[0], ms[1], ms[2], ms[3],
+                 ms[4], res_bytes, 1e3 * ms_since(t_host0));
+  return PS_OK;
+}
+
+int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t** list_off_out, const uint32_t** msg_out,
+                        uint32_t* n_lists_out, uint64_t* total_out) {
+  if (!e || !list_out || !list_off_out || !msg_out || !n_lists_out || !total_out) return PS_E_INVAL;
+  auto& D = e->drain;
+  if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
+  auto& S = D.slot[D.slot_head];
+  if (!S.shared) return e->fail(PS_E_STATE, "the oldest drain is not a shared one: ps_drain_end");
+  if (const int rc = drain_slot_complete(e, S)) return rc;
+  const DrainSharedHdr* hdr = reinterpret_cast<const DrainSharedHdr*>(S.h_res);
+  *list_out = reinterpret_cast<const uint32_t*>(S.h_res + S.o_lq);
+  *list_off_out = reinterpret_cast<const uint64_t*>(S.h_res + S.o_off);
+  *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.o_ids);
+  *n_lists_out = hdr->n_lists;
+  *total_out = hdr->total;
+  if (hdr->err)
+    return e->fail(PS_E_STATE, hdr->err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
+                                                       : "drain tables: row bits do not ascend in arrival order");
+  if (hdr->over)
+    return e->fail(PS_E_RANGE, hdr->over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
   return PS_OK;
 }
 

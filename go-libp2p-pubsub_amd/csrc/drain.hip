@@ -9,6 +9,12 @@
 //   k_drain_offsets       per-query offsets, total and error word of a view
 // and, for ps_drain_shared (§5.5c):
 //   k_drain_classify      per query: which of its topic's message bits the row holds
+// and, for ps_drain_shared_begin (§5.5d), which may not wait either:
+//   k_drain_first / _keys / _lists  the lists numbered by first use and their
+//                         segments laid out, around one scan (the host loop
+//                         of ps_drain_shared on the device)
+//   k_drain_count_dev / _offsets_dev / _emit_dev  count, offsets and emit over
+//                         those lists, the counts read from a control block
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -100,12 +106,12 @@ __global__ __launch_bounds__(kCountBlock) void k_drain_count(DrainArgs a, uint32
   if (lane == 0) cnt[s] = c;
 }
 
+// One wave: the ids of segment s to out[off[s] - off0 ..), below out_cap
 template <bool kStaged>
-__global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_lo, const uint64_t* __restrict__ off,
-                                                      uint64_t off0, uint32_t* __restrict__ out, uint64_t out_cap) {
-  __shared__ uint32_t stage[kStaged ? kDrainSegBits : 1];
+__device__ __forceinline__ void emit_segment(const DrainArgs& a, uint32_t s, const uint64_t* __restrict__ off,
+                                             uint64_t off0, uint32_t* __restrict__ out, uint64_t out_cap,
+                                             uint32_t* stage) {
   const uint32_t lane = threadIdx.x;
-  const uint32_t s = seg_lo + blockIdx.x;
   DrainQuery Q;
   DrainTopic T;
   uint32_t k;
@@ -147,6 +153,13 @@ __global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_
       x &= x - 1;
     }
   }
+}
+
+template <bool kStaged>
+__global__ __launch_bounds__(kWave) void k_drain_emit(DrainArgs a, uint32_t seg_lo, const uint64_t* __restrict__ off,
+                                                      uint64_t off0, uint32_t* __restrict__ out, uint64_t out_cap) {
+  __shared__ uint32_t stage[kStaged ? kDrainSegBits : 1];
+  emit_segment<kStaged>(a, seg_lo + blockIdx.x, off, off0, out, out_cap, stage);
 }
 
 // ---- the shared drain's classify pass (ps_drain_shared) ----------------------
@@ -285,7 +298,183 @@ __global__ __launch_bounds__(kTabBlock) void k_drain_offsets(const DrainQuery* _
   else if (q == n + 1) hdr[n + 1] = *err;
 }
 
+// ---- list assignment on the device (ps_drain_shared_begin) -------------------
+// One thread per query, three passes around one scan: what the host loop of
+// ps_drain_shared does between its two waits.
+
+struct AssignRole {
+  bool any, full, creates;
+  uint32_t segs;  // segments of the list the query creates (0: creates none)
+};
+
+__device__ __forceinline__ bool assign_full(const DrainAssign& g, uint32_t q) {
+  const uint32_t v = g.verdict[q];
+  return (v & kDrainRowAny) && !(v & kDrainRowMissing) && g.share;
+}
+
+// (from k_drain_keys on: first[] is complete)
+__device__ __forceinline__ AssignRole assign_role(const DrainAssign& g, uint32_t q, uint32_t t) {
+  AssignRole r;
+  r.any = g.verdict[q] & kDrainRowAny;
+  r.full = assign_full(g, q);
+  r.creates = r.any && (!r.full || g.first[t] == q);
+  r.segs = r.creates ? (g.topics[t].n_pos + kDrainSegBits - 1) / kDrainSegBits : 0;
+  return r;
+}
+
+// first[t] = the least full query of topic t: a 32-bit atomicMin, the minimum
+// whatever the order.  One thread per *sorted* query (the classify pass's
+// input: topic by topic, a topic's queries in ascending query order; the
+// others are never full), so that the lowest full lane of a topic within a
+// wave holds the wave's minimum for it and speaks for the lanes above:
+// atomics on one word run one after the other, and a topic may have thousands
+// of full queries.  (One atomic per full query: 0.81 ms for the assignment at
+// 262,144 cfg3 pairs; skipping those above the word's current value, read
+// past the L1: 0.51 ms, the whole grid being resident at once.)
+__global__ __launch_bounds__(kTabBlock) void k_drain_first(DrainAssign g) {
+  const uint32_t i = blockIdx.x * kTabBlock + threadIdx.x;
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  uint32_t q = 0, t = 0xFFFFFFFFu;
+  bool full = false;
+  if (i < g.n_sorted) {
+    q = g.sorted[i].slot;
+    t = g.queries[q].topic;
+    full = assign_full(g, q);
+  }
+  const uint64_t below = __ballot(full) & ((1ull << lane) - 1);
+  const uint32_t t_below = __shfl(t, below ? 63 - __clzll(static_cast<long long>(below)) : 0, 64);
+  if (!full || (below && t_below == t)) return;  // (a topic's lanes are consecutive: the nearest full lane below decides)
+  uint32_t* const w = g.first + t;
+  if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > q) atomicMin(w, q);
+}
+
+__global__ __launch_bounds__(kTabBlock) void k_drain_keys(DrainAssign g) {
+  const uint32_t q = blockIdx.x * kTabBlock + threadIdx.x;
+  if (q >= g.n) return;
+  const AssignRole r = assign_role(g, q, g.queries[q].topic);
+  g.key[q] = static_cast<uint64_t>(r.creates) << 32 | r.segs;
+}
+
+// key_off[q] = lists << 32 | segments created by the queries before q: a
+// creating query's list number and first segment.  Nothing is stored past
+// list_cap; the last query leaves the counts in the control block.
+__global__ __launch_bounds__(kTabBlock) void k_drain_lists(DrainAssign g) {
+  const uint32_t q = blockIdx.x * kTabBlock + threadIdx.x;
+  if (q >= g.n) return;
+  const DrainQuery Q = g.queries[q];
+  const AssignRole r = assign_role(g, q, Q.topic);
+  const uint64_t at = g.key_off[q];
+  const uint32_t l = static_cast<uint32_t>(at >> 32), seg0 = static_cast<uint32_t>(at);
+  uint32_t mine = 0xFFFFFFFFu;  // (PS_NONE)
+  if (r.creates) {
+    mine = l;
+    if (l < g.list_cap) g.lists[l] = DrainQuery{Q.topic, r.full ? kDrainMaskRow : Q.node, seg0, 0};
+  } else if (r.full) {
+    mine = static_cast<uint32_t>(g.key_off[g.first[Q.topic]] >> 32);
+  }
+  g.list_of_query[q] = mine;
+  if (q == g.n - 1) {
+    DrainCtl c{};
+    c.n_lists = l + (r.creates ? 1u : 0u);
+    c.n_segs = seg0 + r.segs;
+    const bool over = c.n_lists > g.list_cap || c.n_segs > g.seg_bound;  // (the second: never, by the bound's making)
+    c.use_lists = over ? 0u : c.n_lists;
+    c.use_segs = over ? 0u : c.n_segs;
+    c.over = over ? kDrainOverLists : 0u;
+    *g.ctl = c;
+  }
+}
+
+// k_drain_count over the lists: the counts from the control block, zeros up to the bound
+__global__ __launch_bounds__(kCountBlock) void k_drain_count_dev(DrainArgs a, const DrainCtl* __restrict__ ctl,
+                                                                 uint32_t seg_bound, uint64_t* __restrict__ cnt) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kCountBlock / kWave) + threadIdx.x / kWave);
+  if (s > seg_bound) return;
+  a.n_queries = ctl->use_lists;
+  uint32_t c = 0;
+  if (s < ctl->use_segs) {
+    DrainQuery Q;
+    DrainTopic T;
+    uint32_t k;
+    if (locate(a, s, &Q, &T, &k)) c = __popcll(lane_word(a, T, Q.node, k * kDrainSegBits + lane * 64));
+  }
+  c = wave_sum_u32(c);
+  if (lane == 0) cnt[s] = c;
+}
+
+// The view's header and list_off[0 .. list_cap]: a list's offset from its
+// first segment's, the total from n_lists on.  The thread of the total also
+// decides whether the ids fit (the emit behind reads ctl->over).
+__global__ __launch_bounds__(kTabBlock) void k_drain_offsets_dev(const DrainQuery* __restrict__ lists, DrainCtl* ctl,
+                                                                 uint32_t list_cap,
+                                                                 const uint64_t* __restrict__ seg_off, uint64_t id_cap,
+                                                                 const uint32_t* __restrict__ err,
+                                                                 DrainSharedHdr* __restrict__ hdr,
+                                                                 uint64_t* __restrict__ list_off) {
+  const uint32_t l = blockIdx.x * kTabBlock + threadIdx.x;
+  if (l > list_cap) return;
+  const uint32_t n_lists = ctl->use_lists;
+  const uint64_t total = seg_off[ctl->use_segs];
+  list_off[l] = l < n_lists ? seg_off[lists[l].seg0] : total;
+  if (l == 0) {
+    const uint32_t over = ctl->over | (total > id_cap ? kDrainOverIds : 0u);
+    ctl->over = over;
+    hdr->total = total;
+    hdr->n_lists = ctl->n_lists;
+    hdr->over = over;
+    hdr->err = *err;
+    hdr->pad = 0;
+  }
+}
+
+__global__ __launch_bounds__(kWave) void k_drain_emit_dev(DrainArgs a, const DrainCtl* __restrict__ ctl,
+                                                          const uint64_t* __restrict__ off, uint32_t* __restrict__ out,
+                                                          uint64_t out_cap) {
+  __shared__ uint32_t stage[kDrainSegBits];
+  if (ctl->over || blockIdx.x >= ctl->use_segs) return;  // (block-uniform)
+  a.n_queries = ctl->use_lists;
+  emit_segment<true>(a, blockIdx.x, off, 0, out, out_cap, stage);
+}
+
 }  // namespace
+
+hipError_t launch_drain_assign(const DrainAssign& g, hipStream_t s) {
+  if (g.n == 0) return hipSuccess;
+  const dim3 grid((g.n + kTabBlock - 1) / kTabBlock), block(kTabBlock);
+  if (g.n_sorted) hipLaunchKernelGGL(k_drain_first, dim3((g.n_sorted + kTabBlock - 1) / kTabBlock), block, 0, s, g);
+  hipLaunchKernelGGL(k_drain_keys, grid, block, 0, s, g);
+  hipError_t rc = hipGetLastError();
+  if (rc != hipSuccess) return rc;
+  size_t bytes = g.scan_bytes;
+  rc = hipcub::DeviceScan::ExclusiveSum(g.scan_temp, bytes, g.key, g.key_off, g.n, s);
+  if (rc != hipSuccess) return rc;
+  hipLaunchKernelGGL(k_drain_lists, grid, block, 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_drain_count_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, uint64_t* cnt,
+                                  hipStream_t s) {
+  const uint32_t per = kCountBlock / kWave;
+  hipLaunchKernelGGL(k_drain_count_dev, dim3((seg_bound + 1 + per - 1) / per), dim3(kCountBlock), 0, s, a, ctl,
+                     seg_bound, cnt);
+  return hipGetLastError();
+}
+
+hipError_t launch_drain_offsets_dev(const DrainQuery* lists, DrainCtl* ctl, uint32_t list_cap, const uint64_t* seg_off,
+                                    uint64_t id_cap, const uint32_t* err, DrainSharedHdr* hdr, uint64_t* list_off,
+                                    hipStream_t s) {
+  hipLaunchKernelGGL(k_drain_offsets_dev, dim3((list_cap + 1 + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, lists,
+                     ctl, list_cap, seg_off, id_cap, err, hdr, list_off);
+  return hipGetLastError();
+}
+
+hipError_t launch_drain_emit_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, const uint64_t* off,
+                                 uint32_t* out, uint64_t id_cap, hipStream_t s) {
+  if (seg_bound == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_drain_emit_dev, dim3(seg_bound), dim3(kWave), 0, s, a, ctl, off, out, id_cap);
+  return hipGetLastError();
+}
 
 hipError_t launch_drain_tables(const DrainBuild& b, hipStream_t s) {
   if (b.n_msgs == 0) return hipSuccess;

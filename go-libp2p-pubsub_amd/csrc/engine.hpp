@@ -500,6 +500,15 @@ struct ps_engine {
       hipEvent_t ev_emit = nullptr, ev_done = nullptr;
       size_t n = 0, hdr_bytes = 0;
       uint64_t bound = 0;
+      // ps_drain_shared_begin takes the same slots.  Its
+      // input on the device (queries, verdicts, sorted queries, bins), the
+      // numbering scan's keys and their sums, the control block with the
+      // topics' first full queries behind it; its view: a DrainSharedHdr, then
+      // list_off[list_cap + 1], list_of_query[n] and ids[id_cap] at o_*
+      bool shared = false;
+      psamd::DevBuf d_in, d_key, d_aux;
+      size_t list_cap = 0, id_cap = 0;
+      size_t o_off = 0, o_lq = 0, o_ids = 0;
     } slot[2];
     uint32_t slot_head = 0, slot_count = 0;
     bool mapped_out = false;  // emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)

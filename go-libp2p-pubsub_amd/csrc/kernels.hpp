@@ -660,4 +660,59 @@ constexpr uint32_t kDrainRowAny = 2;      // a message bit the row holds: not em
 hipError_t launch_drain_classify(const DrainArgs& a, const DrainClassBin* bins, uint32_t n_bins,
                                  const DrainClassQuery* queries, uint32_t n_waves, uint32_t* verdict, hipStream_t s);
 
+// ---- the shared drain in two halves (ps_drain_shared_begin) --
+// What ps_drain_shared does on the host between its two waits, on the device:
+// the lists numbered by first use and their segments laid out from the
+// verdicts, then count / scan / offsets / emit over those lists with the
+// counts read from a control block -- the host knows only the caps.
+constexpr uint32_t kDrainOverLists = 1;  // DrainCtl.over: more lists than list_cap
+constexpr uint32_t kDrainOverIds = 2;    // ... more ids than id_cap
+struct DrainCtl {
+  uint32_t n_lists, n_segs;  // exact, whatever the caps
+  uint32_t use_lists, use_segs;  // what the passes behind run over: the above, or 0 past list_cap
+  uint32_t over;             // kDrainOver*
+  uint32_t pad[3];
+};
+// The view's first 256 bytes (the parts behind are 256-byte aligned)
+struct DrainSharedHdr {
+  uint64_t total;
+  uint32_t n_lists;
+  uint32_t over;  // kDrainOver*
+  uint32_t err;   // the table build's error word (kDrainErr*)
+  uint32_t pad;
+};
+struct DrainAssign {
+  const DrainTopic* topics;
+  const DrainQuery* queries;  // [n] topic and node of every query (seg0 unused)
+  const uint32_t* verdict;    // [n] kDrainRow* after the classify pass
+  const DrainClassQuery* sorted;  // [n_sorted] the classify pass's queries: by topic, ascending slot within one
+  uint32_t n_sorted;
+  uint32_t n;
+  uint32_t share;             // 0: a full row takes a private list (the PSAMD_DRAIN_SHARED seam)
+  uint32_t* first;            // [topics] least full query of the topic; preset to all ones
+  uint64_t* key;              // [n] creates << 32 | segments created; key_off: its exclusive scan
+  uint64_t* key_off;
+  void* scan_temp;
+  size_t scan_bytes;
+  DrainQuery* lists;          // [list_cap]
+  uint32_t list_cap;
+  uint32_t seg_bound;         // segments list_cap lists hold at most: what the passes behind are sized for
+  uint32_t* list_of_query;    // [n], in the view
+  DrainCtl* ctl;
+};
+// k_drain_first, k_drain_keys, the scan, k_drain_lists
+hipError_t launch_drain_assign(const DrainAssign& g, hipStream_t s);
+// As launch_drain_count / _offsets / _emit with a.queries = the lists and the
+// counts from ctl: cnt[s] for every s <= seg_bound (zero from ctl->use_segs
+// on); the header, list_off[0 .. list_cap] (the total from n_lists on) and
+// kDrainOverIds; the ids, below id_cap, of at most seg_bound segments and
+// none once ctl->over is set.
+hipError_t launch_drain_count_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, uint64_t* cnt,
+                                  hipStream_t s);
+hipError_t launch_drain_offsets_dev(const DrainQuery* lists, DrainCtl* ctl, uint32_t list_cap, const uint64_t* seg_off,
+                                    uint64_t id_cap, const uint32_t* err, DrainSharedHdr* hdr, uint64_t* list_off,
+                                    hipStream_t s);
+hipError_t launch_drain_emit_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, const uint64_t* off,
+                                 uint32_t* out, uint64_t id_cap, hipStream_t s);
+
 }  // namespace psamd

@@ -157,6 +157,8 @@ PROTOTYPES = [
                                   _u64p]),
     ("ps_drain_begin", C.c_int, [_P, _u32p, _u32p, C.c_size_t]),
     ("ps_drain_end", C.c_int, [_P, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
+    ("ps_drain_shared_begin", C.c_int, [_P, _u32p, _u32p, C.c_size_t, C.c_size_t, C.c_size_t]),
+    ("ps_drain_shared_end", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -282,7 +284,7 @@ class Engine:
             raise EngineError(rc, "ps_create failed (is a GPU visible?)")
         self._h = h
         self._L = L
-        self._drain_n = []  # query counts of the drains begun and not ended
+        self._drain_n = []  # (shared, query count) of the drains begun and not ended
         if plan:
             self.set_plan(**plan)
 
@@ -502,7 +504,7 @@ class Engine:
         if t.ndim != 1 or t.shape != p.shape:
             raise ValueError("topics and peers must be 1-d arrays of one length")
         self._check(self._L.ps_drain_begin(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size))
-        self._drain_n.append(t.size)
+        self._drain_n.append((False, t.size))
 
     def drain_end(self, copy: bool = True):
         """(off, ids) of the oldest drain_begin, as drain() returns them
@@ -510,12 +512,45 @@ class Engine:
         valid until the next drain_begin."""
         op, mp, total = _u64p(), _u32p(), C.c_uint64()
         rc = self._L.ps_drain_end(self._h, C.byref(op), C.byref(mp), C.byref(total))
-        if rc != -8 and self._drain_n:  # (PS_E_NOTREADY: no slot was completed)
-            n = self._drain_n.pop(0)
+        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is a shared one)
+        if rc != -8 and self._drain_n and not self._drain_n[0][0]:
+            n = self._drain_n.pop(0)[1]
         self._check(rc)
         off = np.ctypeslib.as_array(op, shape=(n + 1,))
         ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
         return (off.copy(), ids.copy()) if copy else (off, ids)
+
+    def drain_shared_begin(self, topics, peers, list_cap: int = 0, id_cap: int = 0):
+        """Enqueues drain_shared(topics, peers) of the last window of the last
+        run enqueued (ps_drain_shared_begin) and returns without waiting for
+        it; it shares drain_begin's two slots.  list_cap = id_cap = 0: the
+        engine's caps, the size of the answer.  drain_shared_end() completes
+        the oldest."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        p = np.ascontiguousarray(peers, dtype=np.uint32)
+        if t.ndim != 1 or t.shape != p.shape:
+            raise ValueError("topics and peers must be 1-d arrays of one length")
+        self._check(self._L.ps_drain_shared_begin(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size, list_cap,
+                                                  id_cap))
+        self._drain_n.append((True, t.size))
+
+    def drain_shared_end(self, copy: bool = True):
+        """(list_of_query, list_off, ids) of the oldest drain_shared_begin, as
+        drain_shared() returns them (ps_drain_shared_end).  copy=False: views
+        of the engine's pinned memory, valid until the next begin of either
+        kind."""
+        lp, op, mp = _u32p(), _u64p(), _u32p()
+        n_lists, total = C.c_uint32(), C.c_uint64()
+        rc = self._L.ps_drain_shared_end(self._h, C.byref(lp), C.byref(op), C.byref(mp), C.byref(n_lists),
+                                         C.byref(total))
+        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is not a shared one)
+        if rc != -8 and self._drain_n and self._drain_n[0][0]:
+            n = self._drain_n.pop(0)[1]
+        self._check(rc)
+        lists = np.ctypeslib.as_array(lp, shape=(n,)) if n else np.empty(0, dtype=np.uint32)
+        off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
+        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        return (lists.copy(), off.copy(), ids.copy()) if copy else (lists, off, ids)
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

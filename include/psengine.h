@@ -344,6 +344,38 @@ int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_ou
 int ps_drain_shared(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, uint32_t* list_out,
                     uint64_t* list_off_out, size_t list_cap, uint32_t* msg_out, size_t cap,
                     uint32_t* n_lists_out, uint64_t* total_out);
+/* ps_drain_shared in two halves, for pipelined batches: ps_drain_shared's
+ * answer for the window ps_drain_begin reads (the last window of the last run
+ * enqueued), enqueued behind that run with no wait in between -- the lists are
+ * numbered and laid out on the GPU.  ps_drain_shared_end completes the oldest
+ * drain begun and lends the caller its result: (*list_out)[0 .. n),
+ * (*list_off_out)[0 .. *n_lists_out] and (*msg_out)[0 .. *total_out) are entry
+ * for entry what ps_drain_shared returns for that window.  The pointers name
+ * pinned memory the engine owns, valid until the next ps_drain_begin or
+ * ps_drain_shared_begin, or ps_destroy.
+ *   The view is sized by caps, since the host cannot know the counts without
+ * waiting: at most list_cap lists and id_cap ids.  list_cap == 0 && id_cap ==
+ * 0 selects the engine's own: one list per distinct topic among the queries
+ * that resolve to a row (one per such query of a mesh topic whose window has
+ * several start rounds) and those topics' window message counts, summed --
+ * the size of the answer, which no healthy engine exceeds.  An id cap above
+ * 2^30 returns PS_E_RANGE: use ps_drain_shared.  When the answer exceeds a
+ * cap, no id is emitted and ps_drain_shared_end returns PS_E_RANGE;
+ * *list_out and *n_lists_out are exact then, *list_off_out and *total_out are
+ * exact if n_lists <= list_cap, and the ids are unspecified.
+ *   The two slots are ps_drain_begin's: at most two drains of either kind
+ * are outstanding, completed oldest first, each by the end call of its kind
+ * (the other returns PS_E_STATE and completes nothing).  A third begin
+ * returns PS_E_STATE; an end with none outstanding and a begin before any run
+ * return PS_E_NOTREADY; a topic or peer out of range returns PS_E_RANGE with
+ * nothing enqueued and no slot taken; n == 0 is a valid drain (no list,
+ * list_off = {0}); a multi-rank engine returns PS_E_STATE;
+ * ps_drain_shared_end returns PS_E_STATE when the device-side check of the
+ * window's tables failed. */
+int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, size_t list_cap,
+                          size_t id_cap);
+int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t** list_off_out,
+                        const uint32_t** msg_out, uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -33,6 +33,14 @@ bytes moved to the host and the ratio of the two calls; then --large-queries
 pairs through ps_drain_shared alone (ps_drain is skipped there because of its
 output size), with classify's algorithmic bytes over its device time against
 the HBM spec.  Writes DIR/drain_shared_bench.json.
+
+--pipelined --shared: the shared drain in two halves (ps_drain_shared_begin /
+ps_drain_shared_end) inside the pipelined step loop, in one process beside
+loop (i) and loop (iii) (copy) above: wall ms/step, the host time inside the
+begin call, ps_overlapped_windows() and the view's bytes; then, on a quiet
+engine with PSAMD_DRAIN_TIMING=1, the device time of its classify / list
+assignment / count / scan / emit passes for the counts of --pipelined-queries
+and --large-queries.  Writes DIR/drain_shared_async_bench.json.
 """
 from __future__ import annotations
 
@@ -288,6 +296,118 @@ def pipelined_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def loop_shared_async(eng, wl, n, qt, qp, begin_s):
+    """Loop (iii) with ps_drain_shared_begin / _end.  Returns the last view (copies)."""
+    L, h = eng._L, eng._h
+    u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    tp, pp = qt.ctypes.data_as(u32p), qp.ctypes.data_as(u32p)
+    lp, op, mp, n_lists, total = u32p(), u64p(), u32p(), C.c_uint32(), C.c_uint64()
+    end = lambda: L.ps_drain_shared_end(h, C.byref(lp), C.byref(op), C.byref(mp), C.byref(n_lists), C.byref(total))
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        eng.run_async()
+        t0 = time.perf_counter()
+        rc = L.ps_drain_shared_begin(h, tp, pp, qt.size, 0, 0)
+        begin_s.append(time.perf_counter() - t0)
+        assert rc == 0, rc
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            rc = end()
+            assert rc == 0, rc
+    eng.wait()
+    rc = end()
+    assert rc == 0, rc
+    lists = np.ctypeslib.as_array(lp, shape=(qt.size,)).copy()
+    off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,)).copy()
+    ids = np.ctypeslib.as_array(mp, shape=(max(total.value, 1),))[:total.value].copy()
+    return lists, off, ids
+
+
+def pipelined_shared_main(a, wl):
+    counts = [int(x) for x in a.pipelined_queries.split(",")]
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "steps": a.steps,
+           "warmup": a.warmup, "rows": [], "device_phases": []}
+    queries = {n: pick_queries(wl, n, a.seed) for n in counts + [a.large_queries]}
+
+    # the quiet timing engine: the synchronous call's answer (the reference of
+    # the loops below) and the device time of every pass of the new call
+    want = {}
+    eng, _ = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for n in counts + [a.large_queries]:
+            qt, qp = queries[n]
+            want[n] = eng.drain_shared(qt, qp)
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call allocates)
+                with StderrCapture() as cap:
+                    eng.drain_shared_begin(qt, qp)
+                    got = eng.drain_shared_end()
+                assert all(np.array_equal(x, y) for x, y in zip(got, want[n]))
+                row = phase_line(cap.text, "drain_shared_begin")
+                for k in ("list_cap", "id_cap", "seg_bound", "view_bytes"):
+                    row[k] = int(re.search(rf"\b{k} (\d+)", cap.text).group(1))
+                rows.append(row)
+            best = min(rows[1:], key=lambda r: r["classify_ms"] + r["assign_ms"])
+            with StderrCapture() as cap:
+                eng.drain_shared(qt, qp)
+            sync = [phase_line(x, "drain_shared") for x in cap.text.splitlines() if "psamd drain_shared:" in x][-1]
+            print(f"device phases, {n} pairs: done", file=sys.stderr, flush=True)
+            res["device_phases"].append({"queries": n, "begin": best, "synchronous": sync,
+                                         "assign_over_classify": best["assign_ms"] / best["classify_ms"]
+                                         if best["classify_ms"] else None})
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        fn()
+        return 1e3 * (time.perf_counter() - t0) / a.steps
+
+    eng = fresh_engine(wl, {})
+    with eng:
+        loop_plain(eng, wl, a.warmup)
+        o0 = eng.overlapped_windows()
+        res["plain_ms_per_step"] = timed(lambda: loop_plain(eng, wl, a.steps))
+        res["plain_overlapped_windows"] = eng.overlapped_windows() - o0
+    for n in counts:
+        qt, qp = queries[n]
+        row = {"queries": n, "n_lists": int(want[n][1].size - 1), "shared_ids": int(want[n][2].size)}
+        eng = fresh_engine(wl, {})
+        with eng:
+            loop_async(eng, wl, a.warmup, qt, qp, [])
+            o0 = eng.overlapped_windows()
+            begin_s = []
+            t0 = time.perf_counter()
+            off, ids = loop_async(eng, wl, a.steps, qt, qp, begin_s)
+            row["drain_begin"] = {"ms_per_step": 1e3 * (time.perf_counter() - t0) / a.steps,
+                                  "begin_host_us_median": 1e6 * float(np.median(begin_s)),
+                                  "overlapped_windows": eng.overlapped_windows() - o0,
+                                  "bytes_to_host": 8 * (n + 2) + 4 * int(ids.size)}
+        eng = fresh_engine(wl, {})
+        with eng:
+            loop_shared_async(eng, wl, a.warmup, qt, qp, [])
+            o0 = eng.overlapped_windows()
+            begin_s = []
+            t0 = time.perf_counter()
+            lists, loff, lids = loop_shared_async(eng, wl, a.steps, qt, qp, begin_s)
+            ms = 1e3 * (time.perf_counter() - t0) / a.steps
+            assert np.array_equal(lists, want[n][0]) and np.array_equal(loff, want[n][1])
+            assert np.array_equal(norm(lids), norm(want[n][2]))
+            assert same_answer(lists, loff, lids, off, ids)
+            row["drain_shared_begin"] = {"ms_per_step": ms, "begin_host_us_median": 1e6 * float(np.median(begin_s)),
+                                         "begin_host_us_max": 1e6 * float(np.max(begin_s)),
+                                         "overlapped_windows": eng.overlapped_windows() - o0}
+        print(f"pipelined loops, {n} pairs: done", file=sys.stderr, flush=True)
+        row["shared_over_plain"] = row["drain_shared_begin"]["ms_per_step"] / res["plain_ms_per_step"]
+        row["drain_begin_over_shared"] = row["drain_begin"]["ms_per_step"] / row["drain_shared_begin"]["ms_per_step"]
+        res["rows"].append(row)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "drain_shared_async_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 HBM_SPEC_BYTES_PER_S = 8e12
 
 
@@ -432,6 +552,8 @@ def main():
     ap.add_argument("--large-queries", type=int, default=262144)
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.pipelined and a.shared:
+        return pipelined_shared_main(a, wl)
     if a.pipelined:
         return pipelined_main(a, wl)
     if a.shared:

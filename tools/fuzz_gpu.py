@@ -314,13 +314,20 @@ def case_drain(rng, max_peers):
         first = e.publish(topics, starts)
         e.run()
         hops = np.stack([e.hops(first + m) for m in range(n_msgs)])  # [msg][peer]
-        for p in rng.choice(n, size=min(n, 12), replace=False):
+        peers = rng.choice(n, size=min(n, 12), replace=False)
+        for p in peers:
             for t in range(n_topics):
                 ids = [m for m in range(n_msgs) if topics[m] == t and hops[m, p] != 0xFF]
                 exp = [first + m for m in sorted(ids, key=lambda m: (int(starts[m]), m))]
                 got = e.peer_messages(t, int(p)).tolist()
                 if got != exp:
                     return f"peer {p} topic {t}: drain {got[:6]}... != {exp[:6]}..."
+        # the shared drain in two halves against the synchronous one, the same pairs
+        qt, qp = np.tile(np.arange(n_topics), peers.size), np.repeat(peers, n_topics)
+        e.drain_shared_begin(qt, qp)
+        got, want = e.drain_shared_end(), e.drain_shared(qt, qp)
+        if not all(np.array_equal(x, y) for x, y in zip(got, want)):
+            return f"drain_shared_begin/_end differs from drain_shared over {qt.size} pairs"
     return None
 
 
