@@ -843,6 +843,7 @@ int ps_plan_create(uint32_t n_peers, uint32_t n_topics, const uint32_t* roots, c
   auto* e = new (std::nothrow) ps_engine();
   if (!e) return PS_E_NOMEM;
   e->host_only = true;
+  e->flood_grid = 1;  // (no device to ask: the probe plans as a run with k_flood available)
   e->cfg.n_peers = n_peers;
   e->cfg.n_topics = n_topics;
   e->cfg.msg_window = kDefaultWindow;
@@ -916,18 +917,8 @@ int ps_plan_window(ps_engine* e, const uint32_t* topic_of_msg, const uint32_t* s
   WindowLayout& L = e->probe;
   rc = plan_window_layout(e, msgs, win, L);
   if (rc) return rc;
-  e->round_kind.clear();
-  if (!L.level) return PS_OK;
-  plan_pull_chunks(e, L);
-  bool gch = false;
-  rc = plan_ghost(e, L, &gch);
-  if (rc) return rc;
-  // the k_flood split a one-rank run would take (its rounds replay as pulls)
-  const uint32_t first = e->world == 1 && e->flood_on && !deep_window(e, L) ? plan_flood_rounds(e, L) : 0;
-  plan_pair_chunks(e, L, first);
-  if (e->world > 1) annotate_chunks(e, L);
-  e->round_kind = e->pair.kind;
-  return PS_OK;
+  // the schedule a run would take (k_flood's rounds replay as pulls)
+  return plan_window_schedule(e, msgs, win, L, e->probe_sched);
 }
 
 int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out) {
@@ -1040,6 +1031,20 @@ int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size
                            c.w0, c.S, c.levels, c.r0, c.group});
         for (uint32_t f = 0; f <= kChainLevels; ++f) v.push_back(c.first[f]);
       }
+      break;
+    }
+    case PS_PLAN_SCHEDULE: {
+      if (!L) return e->fail(PS_E_RANGE, "no window planned");
+      const WindowSchedule& S = e->probe_sched;
+      const size_t lv = L->level ? 1 : 0;  // (the level tables are the last level window's otherwise)
+      v = {S.flood_rounds, S.pre_P, S.n_slots, S.reach_rows, S.mode, S.total, lv * S.lgrid.size(),
+           lv * e->woff_host.size(), lv * e->desc_host.size(), S.seed_off.size()};
+      if (lv) {
+        v.insert(v.end(), S.lgrid.begin(), S.lgrid.end());
+        v.insert(v.end(), e->woff_host.begin(), e->woff_host.end());
+        v.insert(v.end(), e->desc_host.begin(), e->desc_host.end());
+      }
+      v.insert(v.end(), S.seed_off.begin(), S.seed_off.end());
       break;
     }
     default:

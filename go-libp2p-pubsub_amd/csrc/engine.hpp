@@ -2,10 +2,14 @@
 // its translation units:
 //   graph.cpp  the node space: per-topic BFS numbering (host, or rebuilt on
 //              the GPU by gbuild.hip), multi-GPU partition and ghost tables
-//   plan.cpp   one window's layout and its launch plans (pull chunks, round
-//              pairs, k_flood tasks, the ghost exchange) -- pure host code,
-//              tested on the CPU through include/psengine_plan.h
-//   run.cpp    plan uploads and the round loop on the GPU (ps_run*)
+//   plan.cpp   one window's layout, its launch plans (pull chunks, round
+//              pairs, k_flood tasks, the ghost exchange) and its schedule
+//              (WindowSchedule: seeds, launch grids, counter slots, the
+//              prefix) -- pure host code, tested on the CPU through
+//              include/psengine_plan.h
+//   run.cpp    one window as a list of stages over a WindowRun (plan uploads,
+//              streams and row sets, window start, level or compaction
+//              rounds, finish), and ps_run* / ps_wait around it
 //   drain.cpp  the batched drain of the last window (ps_drain*), host side
 //   api.cpp    the remaining C ABI (lifecycle, topics, membership, reads,
 //              multi-GPU)
@@ -192,6 +196,32 @@ struct WindowLayout {
   bool level = false;                      // level mode (else the compaction path)
 };
 
+// One window's schedule (plan_window_schedule): everything run.cpp needs to
+// enqueue the window that the host can work out without the device.  The
+// level plans themselves stay engine members (pull, pair, flood, ghost: cached
+// across windows), as do the reduce descriptors, slot offsets and round kinds
+// (desc_host, woff_host, round_kind: later code and Inflight read them).
+struct WindowSchedule {
+  std::vector<SeedDev> seeds;                  // root injections, grouped by round:
+  std::vector<uint32_t> seed_off;              // round r's are [seed_off[r], seed_off[r + 1])
+  std::vector<std::vector<uint8_t>> starts_of;  // topic -> start rounds present in the window
+  bool deep = false;                           // deep_window(): per-round launches from round 1
+  bool flood_ok = false;
+  uint32_t flood_rounds = 0;                   // rounds 1..flood_rounds: k_flood
+  bool changed = false, gch = false;           // level plans rebuilt (any; the ghost plan)
+  std::vector<uint32_t> lgrid;                 // per-round launches: blocks (L and G parts together), 0 on a
+                                               // multi-round launch's continuation rounds
+  uint32_t n_slots = 0;                        // level mode: partial counter slots of the window
+  uint32_t reach_rows = 0, reach_slot0 = 0;    // level-aligned: reach counter rows, their first pseudo-slot
+  std::vector<std::vector<uint64_t>> cap;      // compaction on N ranks: cap[r][from * world + to] items
+  uint64_t max_send = 0, max_recv = 0;         // ... and the largest round's region bytes
+  uint64_t total = 0;                          // level mode: the window's row bytes
+  bool alt_plan = false;                       // a deep window that may alternate row sets
+  uint32_t pre_P = 0;                          // deep windows: the prefix is rounds 1..pre_P
+  uint32_t mode = PS_MODE_COMPACT;
+  std::chrono::steady_clock::time_point t_seeds;  // host timing: the seeds are done, the planners start
+};
+
 // Level mode, one launch kind per round; the round's chunks are
 // [off[q], off[q+1]); on N ranks the chunks of nodes fed by a ghost parent
 // come last, from gsplit[q] (they wait for the round's exchange).
@@ -259,6 +289,7 @@ struct ps_engine {
   uint32_t n_cus = 256, expand_grid = 2048;
   bool host_only = false;        // a planner probe (psengine_plan.h): no device
   psamd::WindowLayout probe;     // the probe's last planned window
+  psamd::WindowSchedule probe_sched;  // ... and its schedule (PS_PLAN_SCHEDULE)
   bool host_timing = false;      // PSAMD_HOST_TIMING=1: host phase times to stderr
   bool sig_windows = true;        // pipelined one-rank windows end with a pinned flag, not an event (A/B: PSAMD_SIG_WINDOWS=0)
   // per-window uploads (topic table, seeds, descriptors) kept on the device:
@@ -699,6 +730,23 @@ void annotate_chunks(ps_engine* e, const WindowLayout& L);
 uint32_t plan_flood_rounds(const ps_engine* e, const WindowLayout& L);
 // A deep single-start window: chains from round 1, no k_flood.
 bool deep_window(const ps_engine* e, const WindowLayout& L);
+// The window's schedule: seeds, start rounds, the level planners above in
+// their order (or the compaction capacities), then plan_schedule_pairs.  The
+// planner probe and run.cpp both plan a window through it.  Fills
+// e->round_kind, desc_host and woff_host; writes every topic's round-0 seed
+// range into L.tab.  No HIP call -- but on N ranks with in-place rows the
+// ghost plan hands this rank's row-set address (d_seen.p) to the others, so
+// run.cpp allocates the window's row set before it plans the schedule.
+int plan_window_schedule(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win,
+                         WindowLayout& L, WindowSchedule& S);
+// Its pair part: the pair / chain plan and all that hangs on it (round kinds,
+// reduce descriptors, slots, launch grids, row bytes, the prefix).  run.cpp
+// calls it a second time when the uploaded chains overflow the level tables
+// (pair.key cleared: the plan is rebuilt without chains).
+void plan_schedule_pairs(ps_engine* e, const WindowLayout& L, WindowSchedule& S);
+// Compaction mode: round r's k_expand grid, from the frontier bound of the
+// start rounds present.
+uint32_t round_grid(const ps_engine* e, const WindowLayout& L, const WindowSchedule& S, uint32_t r);
 
 // run.cpp
 int run_body(ps_engine* e, ps_stats* st, bool may_defer);

@@ -944,4 +944,244 @@ void annotate_chunks(ps_engine* e, const WindowLayout& L) {
   ++PP.version;
 }
 
+namespace {
+
+// Root injections (owned roots only) as seed words grouped by round:
+// seeds[seed_off[r] .. seed_off[r + 1]) are round r's, and every topic's
+// round-0 range goes into its table entry (seed_lo, seed_n).
+void plan_seeds(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win, WindowLayout& L,
+                WindowSchedule& S) {
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  const uint32_t max_start = L.max_start;
+  auto& tab = L.tab;
+  std::vector<std::vector<uint64_t>> inj(nt);  // mask[t][round][word]
+  for (uint32_t t = 0; t < nt; ++t) {
+    const TopicDev& d = tab[t];
+    if (d.W == 0 || !(d.flags & kTopicRootLocal)) continue;
+    inj[t].assign(static_cast<size_t>(max_start + 1) * d.W, 0);
+    if (e->run_zero_start) {  // bits 0 .. n-1 of round 0
+      for (uint32_t w = 0; w < win[t].n / 64; ++w) inj[t][w] = ~0ull;
+      if (win[t].n % 64) inj[t][win[t].n / 64] = (1ull << (win[t].n % 64)) - 1;
+    } else {
+      for (uint32_t li = 0; li < win[t].n; ++li) {
+        const uint32_t b = L.pos[t].empty() ? li : L.pos[t][li];
+        // (level-aligned: every message is seeded before launch round 1)
+        const uint32_t r0 = L.aligned ? 0u : msgs[win[t].idx[li]].start;
+        inj[t][static_cast<size_t>(r0) * d.W + (b >> 6)] |= 1ull << (b & 63);
+      }
+    }
+  }
+  auto& seeds = S.seeds;
+  seeds.clear();
+  S.seed_off.assign(max_start + 2, 0);
+  for (uint32_t r = 0; r <= max_start; ++r) {
+    for (uint32_t t = 0; t < nt; ++t) {
+      TopicDev& d = tab[t];
+      if (r == 0) d.seed_lo = static_cast<uint32_t>(seeds.size());
+      if (inj[t].empty()) continue;
+      if (d.flags & kTopicGroups) {
+        // group-major: the root's block of the group starting this round is
+        // set whole (k_window_init zeroes block 0 only)
+        for (const StartGroup& g : L.groups[t])
+          if (g.start == r)
+            for (uint32_t w = g.w0; w < g.w0 + g.wn; ++w)
+              seeds.push_back(SeedDev{phys_word(d, L.groups[t], 0, w), inj[t][static_cast<size_t>(r) * d.W + w],
+                                      d.nbase, 1});
+      } else {
+        for (uint32_t w = 0; w < d.W; ++w) {
+          const uint64_t m = inj[t][static_cast<size_t>(r) * d.W + w];
+          if (m) seeds.push_back(SeedDev{d.wbase + w, m, d.nbase, 0});  // root = node 0
+        }
+      }
+      if (r == 0) d.seed_n = static_cast<uint32_t>(seeds.size()) - d.seed_lo;
+    }
+    S.seed_off[r + 1] = static_cast<uint32_t>(seeds.size());
+  }
+}
+
+// Compaction mode on N ranks: cross-rank capacities (items = node words) per
+// round, cap[r][from * world + to], and the largest round's region bytes.
+void plan_compact_caps(ps_engine* e, const WindowLayout& L, WindowSchedule& S) {
+  const int32_t world = e->world, me = e->rank;
+  const uint32_t planned0 = L.planned0;
+  auto& cap = S.cap;
+  cap.assign(planned0 + 1, std::vector<uint64_t>(static_cast<size_t>(world) * world, 0));
+  for (uint32_t t = 0; t < e->topics.size(); ++t) {
+    const TopicHost& T = e->topics[t];
+    if (S.starts_of[t].empty()) continue;
+    const uint64_t Wt = L.wglob[t];
+    for (const auto& c : T.cross)
+      for (uint32_t s0 = 0; s0 <= L.max_start; ++s0) {
+        const uint32_t r = c.level + 1 + s0;
+        if (S.starts_of[t][s0] && r <= planned0) cap[r][c.from * world + c.to] += c.count * Wt;
+      }
+  }
+  for (uint32_t r = 1; r <= planned0; ++r) {
+    uint64_t sb = 0, rb = 0;
+    for (int32_t q = 0; q < world; ++q) {
+      if (cap[r][me * world + q]) sb += kRegionHeader + cap[r][me * world + q] * sizeof(XItem);
+      if (cap[r][q * world + me]) rb += kRegionHeader + cap[r][q * world + me] * sizeof(XItem);
+    }
+    S.max_send = std::max(S.max_send, sb);
+    S.max_recv = std::max(S.max_recv, rb);
+  }
+}
+
+}  // namespace
+
+uint32_t round_grid(const ps_engine* e, const WindowLayout& L, const WindowSchedule& S, uint32_t r) {
+  if (L.any_mesh) return e->expand_grid;
+  uint64_t bound = 0;
+  for (uint32_t t = 0; t < e->topics.size(); ++t) {
+    if (L.tab[t].W == 0) continue;
+    const auto& li = e->topics[t].level_internal;
+    for (uint32_t s0 = 0; s0 <= L.max_start; ++s0) {
+      if (!S.starts_of[t][s0] || r < 1 + s0) continue;
+      const uint32_t d = r - 1 - s0;
+      if (d < li.size()) bound += li[d];
+    }
+  }
+  const uint64_t blocks = (bound + 3) / 4;  // ~1 entry per wave at least
+  return static_cast<uint32_t>(std::max<uint64_t>(1, std::min<uint64_t>(e->expand_grid, blocks)));
+}
+
+void plan_schedule_pairs(ps_engine* e, const WindowLayout& L, WindowSchedule& S) {
+  const uint32_t planned0 = L.planned0, flood_rounds = S.flood_rounds, reach_rows = S.reach_rows;
+  S.changed |= plan_pair_chunks(e, L, flood_rounds);
+  if (e->world > 1 && S.changed) annotate_chunks(e, L);
+  e->round_kind = e->pair.kind;
+  // desc[3q..]: round q's partial slots (first, end, stride) for the reduce
+  auto& desc = e->desc_host;
+  desc.assign(3 * (planned0 + 2 + reach_rows), 0);
+  uint32_t slot = 0;
+  if (flood_rounds) {
+    desc[0] = 0;  // row 0: k_flood's timeout word (slot 0)
+    desc[1] = 1;
+    desc[2] = 1;
+    for (uint32_t q = 1; q <= flood_rounds; ++q) {
+      desc[3 * q] = e->flood.slot0[q];
+      desc[3 * q + 1] = e->flood.slot0[q] + e->flood.nslot[q];
+      desc[3 * q + 2] = e->flood.nslot[q] ? 1 : 0;
+    }
+    slot = e->flood.slots;
+  }
+  // the launches of round q own the slots [woff[q], woff[q+1]): one per
+  // block (pull) or wave (pair), at most kPullSlots; the L and G parts of
+  // a round share them (counters are added)
+  auto& lgrid = S.lgrid;
+  lgrid.assign(planned0 + 1, 0);
+  auto& woff = e->woff_host;
+  woff.assign(planned0 + 2, 0);
+  woff[flood_rounds + 1] = slot;
+  const bool prefix = S.deep && flood_rounds == 0;  // (only these windows have one)
+  std::vector<std::pair<uint32_t, uint32_t>> ls;    // their launches: (first round, last round)
+  for (uint32_t q = flood_rounds + 1; q <= planned0; ++q) {
+    const uint8_t kq = e->round_kind[q];
+    const bool multi_round = kq == PS_K_PAIR || kq == PS_K_CHAIN;
+    const uint32_t len = multi_round ? e->pair.len[q] : 1u;
+    lgrid[q] = multi_round ? e->pair.hi[q] - e->pair.lo[q]  // (one one-wave workgroup per chunk)
+                           : ceil_div(e->pull.gsplit[q] - e->pull.off[q], kBlock / 64) +
+                                 ceil_div(e->pull.off[q + 1] - e->pull.gsplit[q], kBlock / 64);
+    for (uint32_t k = q; k < q + len; ++k) {  // a multi-round launch: one slot range per round
+      woff[k + 1] = woff[k] + std::min<uint32_t>(lgrid[q], multi_round ? kPairSlots : kPullSlots);
+      desc[3 * k] = woff[k];
+      desc[3 * k + 1] = woff[k + 1];
+      desc[3 * k + 2] = 1;
+    }
+    for (uint32_t k = 1; k < len; ++k) lgrid[q + k] = 0;
+    if (prefix && (multi_round || kq == PS_K_PULL)) ls.emplace_back(q, q + len - 1);
+    q += len - 1;
+  }
+  S.n_slots = woff[planned0 + 1];
+  // level-aligned: the reach counts (2 per (topic, level) segment, kNumCtr
+  // per slot) as pseudo-slots after the rounds', one reduce row each
+  S.reach_slot0 = S.n_slots;
+  for (uint32_t j = 0; j < reach_rows; ++j) {
+    desc[3 * (planned0 + 1 + j)] = S.n_slots + j;
+    desc[3 * (planned0 + 1 + j) + 1] = S.n_slots + j + 1;
+    desc[3 * (planned0 + 1 + j) + 2] = 1;
+  }
+  S.n_slots += reach_rows;
+
+  S.total = 0;
+  for (uint32_t q = 1; q <= planned0 && q < e->pull.bytes.size(); ++q) S.total += e->pull.bytes[q];
+  // deep windows of at least overlap_min_bytes alternate between the two row
+  // sets (engine.hpp, twin windows): a window's prefix then writes no row its
+  // predecessor's last launch still reads, so the prefix may hold every
+  // launch but the last (the gate: recorded before that launch)
+  S.alt_plan = e->twin_on && L.level && e->world == 1 && S.deep && flood_rounds == 0 &&
+               S.total >= e->overlap_min_bytes;
+  // the prefix (deep windows): leading launches of at most 1/64 of the
+  // window's row bytes, rounds 1..pre_P, followed by a launch starting at
+  // round pre_P + 1 (the gate) and at least one more
+  S.pre_P = 0;
+  if (prefix) {
+    uint64_t acc = 0;
+    for (size_t i = 0; i + 2 < ls.size(); ++i) {
+      uint64_t b = 0;
+      for (uint32_t q = ls[i].first; q <= ls[i].second && q < e->pull.bytes.size(); ++q) b += e->pull.bytes[q];
+      if (acc + b > S.total / 64 || ls[i + 1].first != ls[i].second + 1) break;
+      acc += b;
+      S.pre_P = ls[i].second;
+    }
+    // alternating row sets: every launch but the last is the prefix --
+    // nothing the predecessor's last launch reads is written by it
+    if (S.alt_plan && ls.size() >= 2) {
+      bool contiguous = true;
+      for (size_t i = 0; i + 1 < ls.size(); ++i) contiguous = contiguous && ls[i + 1].first == ls[i].second + 1;
+      if (contiguous) S.pre_P = ls[ls.size() - 2].second;
+    }
+  }
+}
+
+int plan_window_schedule(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win,
+                         WindowLayout& L, WindowSchedule& S) {
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+  S = WindowSchedule{};
+  plan_seeds(e, msgs, win, L, S);
+  S.t_seeds = std::chrono::steady_clock::now();
+  // Start rounds present per topic.  A node at BFS level d receives a
+  // message started at round s in round s + d and is expanded in round
+  // s + d + 1: that bounds each round's frontier (round_grid) and, for the
+  // multi-GPU compaction exchange, each round's cross-rank traffic exactly.
+  S.starts_of.resize(nt);
+  for (uint32_t t = 0; t < nt; ++t) {
+    if (win[t].n == 0 || !e->topics[t].exists) continue;
+    S.starts_of[t].assign(L.max_start + 1, 0);
+    if (e->run_zero_start)
+      S.starts_of[t][0] = 1;
+    else
+      for (uint32_t li = 0; li < win[t].n; ++li) S.starts_of[t][msgs[win[t].idx[li]].start] = 1;
+  }
+  // Level mode: one rank runs the leading rounds whose rows are small
+  // (latency bound) as ONE persistent k_flood launch, then k_pull_pair /
+  // k_pull launches (bandwidth bound); N ranks run k_pull_pair / k_pull with
+  // the ghost exchange between rounds.  PSAMD_FLOOD=0 selects per-round
+  // launches on one rank too.
+  // deep single-start windows: per-round launches from round 1 (their first
+  // few form the prefix that may overlap the previous window)
+  S.deep = deep_window(e, L);
+  S.flood_ok = !S.deep && L.level && e->world == 1 && e->flood_on && !e->flood_broken && e->flood_grid > 0 &&
+               e->n_nodes < 0x80000000u;  // k_flood marks node ids with bit 31
+  // level-aligned windows: counter rows of the reach counts after the rounds'
+  S.reach_rows =
+      L.aligned ? static_cast<uint32_t>(ceil_div(2ull * L.split.n_segs, static_cast<uint64_t>(kNumCtr))) : 0u;
+  if (L.level) {
+    S.changed = plan_pull_chunks(e, L);
+    if (S.flood_ok) {
+      S.flood_rounds = plan_flood_rounds(e, L);
+      if (S.flood_rounds) plan_flood_tasks(e, L, S.flood_rounds);
+    }
+    const int rc = plan_ghost(e, L, &S.gch);
+    if (rc) return rc;
+    S.changed |= S.gch;
+    plan_schedule_pairs(e, L, S);
+  } else {
+    e->round_kind.clear();  // (accumulate_window: every round k_expand)
+    if (e->world > 1) plan_compact_caps(e, L, S);
+  }
+  S.mode = S.flood_rounds ? PS_MODE_FLOOD : L.level ? PS_MODE_LEVEL_PULL : PS_MODE_COMPACT;
+  return PS_OK;
+}
+
 }  // namespace psamd

@@ -10,7 +10,8 @@ import numpy as np
 from . import (DistConfig, EngineError, G_BUILD, G_TOPIC, PART_PEER, PlanOpts, _P, _p, _u32arr, build_report,
                graph_get, graph_topic, load)
 
-INFO, NODES, PARENT, GHOST_REF, TOPIC, LAYOUT, ROUND_KIND, PULL, PAIR, XCHG, SEGS, SHIP, PACK, CHAIN = range(14)
+(INFO, NODES, PARENT, GHOST_REF, TOPIC, LAYOUT, ROUND_KIND, PULL, PAIR, XCHG, SEGS, SHIP, PACK, CHAIN,
+ SCHEDULE) = range(15)
 CHAIN_FIELDS = ("node_begin", "node_end", "topic", "W", "row0", "w0", "S", "levels", "r0", "group")
 CHAIN_LEVELS = 6  # kChainLevels
 CHUNK_FIELDS = ("node_begin", "node_end", "topic", "W", "row0", "e_lo", "e_hi", "gin", "gout", "group",
@@ -164,6 +165,19 @@ class Plan:
     def pack(self, q: int):
         v = self.get(PACK, q).reshape(-1, 6).astype(np.int64)
         return [dict(zip(("e0", "e1", "gseg", "W", "row", "unit0"), (int(x) for x in r))) for r in v]
+
+    def schedule(self) -> dict:
+        """The window's schedule (PS_PLAN_SCHEDULE): scalars, then lgrid and woff per round, the reduce
+        descriptors as (first, end, stride) rows and seed_off per start round."""
+        v = self.get(SCHEDULE).astype(np.int64)
+        keys = ("flood_rounds", "pre_P", "n_slots", "reach_rows", "mode", "row_bytes")
+        out = {k: int(x) for k, x in zip(keys, v)}
+        at = 10
+        for name, n in zip(("lgrid", "woff", "desc", "seed_off"), v[6:10]):
+            out[name] = v[at:at + n]
+            at += int(n)
+        out["desc"] = out["desc"].reshape(-1, 3)
+        return out
 
     def chain(self, q: int):
         """(rounds, [chunk dicts]) of the chain launch starting at round q (rounds 0: none)."""

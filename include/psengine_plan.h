@@ -50,6 +50,17 @@ int ps_plan_window(ps_engine* e, const uint32_t* topic_of_msg, const uint32_t* s
 #define PS_PLAN_PACK 12       /* index = round: per root segment e0, e1, gseg, W, row, unit0 */
 #define PS_PLAN_CHAIN 13      /* index = round: rounds of the launch, then per chunk 17 values: node_begin,
                                  node_end, topic, W, row0, w0, S, levels, r0, group, first[0..6] */
+#define PS_PLAN_SCHEDULE 14   /* the window's schedule, as a run enqueues it.  Ten header values: k_flood
+                                 rounds (rounds 1..that many), prefix P (deep windows: rounds 1..P may run
+                                 beside the previous window), partial counter slots, reach rows, PS_MODE_*,
+                                 the window's row bytes, then the lengths nl, nw, nd, ns of the four tables
+                                 that follow (nl = nw = nd = 0 outside level mode):
+                                 lgrid[nl]    per round 0..planned: workgroups of the launch starting there
+                                              (0: none, or a continuation round of a multi-round launch)
+                                 woff[nw]     per round 0..planned+1: the round's first counter slot
+                                 desc[nd]     (first slot, end slot, stride) per reduce row: rounds
+                                              0..planned+1, then one row per reach row
+                                 seed_off[ns] per start round 0..latest+1: seeds before that round */
 int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out);
 
 /* ps_graph_get(what, index): the node space itself and which

@@ -658,3 +658,160 @@ def test_chain_run_with_wide_parent_span_plan():
     c = ch[0]
     assert (c["node_begin"], c["node_end"]) == (l3, l3 + 4)
     assert parent[c["node_end"] - 1] - parent[c["node_begin"]] == l2_last - l2_first > 65535
+
+
+# --- the window schedule (PS_PLAN_SCHEDULE): what a run enqueues from the plans ---
+
+SLOTS = 256  # kPullSlots = kPairSlots
+
+
+def binary_tree(n=6000):
+    parent = np.full(n, NONE, dtype=np.uint32)
+    parent[1:] = (np.arange(1, n) - 1) // 2  # complete: 13 levels
+    return parent
+
+
+def launches_of(p):
+    """[(first round, last round)] of the window's per-round launches (after
+    k_flood's rounds), from the round kinds: a pair or chain launch covers
+    the continuation rounds (K_PAIR2 / K_CHAIN2) behind it."""
+    kinds = [int(k) for k in p.get(PL.ROUND_KIND)]
+    rounds = p.info()["rounds"]
+    out = []
+    q = p.schedule()["flood_rounds"] + 1
+    while q <= rounds:
+        last = q
+        while last + 1 <= rounds and kinds[last + 1] in (PE.K_PAIR2, PE.K_CHAIN2):
+            last += 1
+        if kinds[q] in (PE.K_PULL, PE.K_PAIR, PE.K_CHAIN):
+            out.append((q, last))
+        q = last + 1
+    return out
+
+
+def check_schedule(p):
+    """What run.cpp's comments promise of a level window's counter slots and
+    reduce descriptors (plan_schedule_pairs)."""
+    s = p.schedule()
+    rounds = p.info()["rounds"]
+    kinds = [int(k) for k in p.get(PL.ROUND_KIND)]
+    lgrid, woff, desc = s["lgrid"], s["woff"], s["desc"]
+    assert len(lgrid) == rounds + 1 and len(woff) == rounds + 2 and len(desc) == rounds + 2 + s["reach_rows"]
+    assert np.all(np.diff(woff) >= 0)
+    f = s["flood_rounds"]
+    assert s["mode"] == (PE.MODE_FLOOD if f else PE.MODE_LEVEL_PULL)
+    assert all(k == PE.K_FLOOD for k in kinds[1:f + 1])
+    for k in range(f + 1, rounds + 1):
+        assert tuple(desc[k]) == (woff[k], woff[k + 1], 1), (k, desc[k], woff[k:k + 2])
+    q = f + 1
+    while q <= rounds:  # launch by launch
+        last = q
+        while last + 1 <= rounds and kinds[last + 1] in (PE.K_PAIR2, PE.K_CHAIN2):
+            last += 1
+        multi = kinds[q] in (PE.K_PAIR, PE.K_CHAIN)
+        assert multi == (last > q), (q, last, kinds)
+        assert all(lgrid[k] == 0 for k in range(q + 1, last + 1)), (q, last, lgrid)
+        for k in range(q, last + 1):
+            assert woff[k + 1] - woff[k] == min(int(lgrid[q]), SLOTS), (q, k, lgrid[q], woff[k:k + 2])
+        q = last + 1
+    for j in range(s["reach_rows"]):  # one pseudo-slot per reach row, behind the rounds'
+        assert tuple(desc[rounds + 1 + j]) == (woff[rounds + 1] + j, woff[rounds + 1] + j + 1, 1)
+    assert s["n_slots"] == woff[rounds + 1] + s["reach_rows"]
+    so = s["seed_off"]
+    assert so[0] == 0 and np.all(np.diff(so) >= 0)
+    return s
+
+
+def deep_plan(monkeypatch, twin, **opts):
+    monkeypatch.setenv("PSAMD_AB", "1")
+    monkeypatch.setenv("PSAMD_TWIN", str(twin))
+    p = PL.Plan(binary_tree()[None, :], [0], plan={"overlap_min_bytes": 0, **opts})
+    p.window(np.zeros(3000, dtype=np.uint32))
+    return p
+
+
+def round_bytes(p):
+    """Row bytes each round of a one-rank single-start window writes: round q, level q."""
+    T, W = p.topic(0), p.layout(0)["W"]
+    return [0] + [int(n) * W * 8 for n in np.diff(T["level_off"])[1:]]
+
+
+def test_schedule_deep_window_prefix(monkeypatch):
+    """A deep window's prefix (run.cpp: rounds 1..pre_P may run beside the
+    previous window): whole launches, contiguous from round 1, at most 1/64
+    of the window's row bytes, with the gate launch and at least one more
+    behind it; no k_flood."""
+    p = deep_plan(monkeypatch, twin=0, overlap=1)
+    s = check_schedule(p)
+    ls = launches_of(p)
+    rb = round_bytes(p)
+    assert s["flood_rounds"] == 0 and s["mode"] == PE.MODE_LEVEL_PULL
+    assert s["row_bytes"] == sum(rb)
+    P = s["pre_P"]
+    assert P > 0 and P in [b for _, b in ls], (P, ls)
+    pre = [l for l in ls if l[1] <= P]
+    assert pre[0][0] == 1 and all(a[1] + 1 == b[0] for a, b in zip(pre, pre[1:])), pre
+    assert 64 * sum(rb[1:P + 1]) <= s["row_bytes"], (P, rb)
+    assert len(ls) - len(pre) >= 2, (ls, P)
+
+
+def test_schedule_deep_window_alternating_sets(monkeypatch):
+    """With twin windows on, a deep window over the byte floor alternates row
+    sets: its prefix is every launch but the last."""
+    p = deep_plan(monkeypatch, twin=1, overlap=1)
+    s = check_schedule(p)
+    ls = launches_of(p)
+    assert s["flood_rounds"] == 0 and len(ls) >= 2
+    assert s["pre_P"] == ls[-2][1] and ls[-1][0] == s["pre_P"] + 1, (s["pre_P"], ls)
+
+
+def test_schedule_deep_window_overlap_off(monkeypatch):
+    """Without the overlap nothing is deep: k_flood takes the leading rounds and there is no prefix."""
+    p = deep_plan(monkeypatch, twin=1, overlap=0)
+    s = check_schedule(p)
+    assert s["pre_P"] == 0 and s["flood_rounds"] > 0 and s["mode"] == PE.MODE_FLOOD
+
+
+@pytest.mark.parametrize("chain", [2, 4])
+def test_schedule_wide_rows(chain):
+    rng, trees, roots, live = build(1, PE.PART_PEER, n=1200, n_topics=1, seed=5, fan=3)
+    p = PL.Plan(np.stack(trees), roots, plan={"chain_max": chain, "chain_max_groups": chain, "flood": 0})
+    p.window(np.zeros(52000, dtype=np.uint32))
+    s = check_schedule(p)
+    assert s["flood_rounds"] == 0 and s["pre_P"] == 0 and list(s["seed_off"]) == [0, 52000 // 64 + 1]
+
+
+@pytest.mark.parametrize("staggered", [False, True])
+def test_schedule_two_rank_peer_partition(staggered):
+    rng, trees, roots, live = build(2, PE.PART_PEER, seed=17 + 3 * staggered, fan=4)
+    topics = rng.integers(0, len(trees), size=300)
+    starts = rng.integers(0, 4, size=300) if staggered else None
+    for r in range(2):
+        p = PL.Plan(np.stack(trees), roots, 2, r, PE.PART_PEER)
+        p.window(topics, starts)
+        s = check_schedule(p)
+        assert s["flood_rounds"] == 0 and s["pre_P"] == 0  # (k_flood and the prefix are one-rank plans)
+        # the seeds are the owned roots' words, by start round
+        assert len(s["seed_off"]) == (4 if staggered else 1) + 1
+
+
+@pytest.mark.parametrize("align", [0, 1])
+def test_schedule_seeds_paced(align):
+    """Seeds by start round (seed_off): a burst seeds in round 0 only; a paced
+    window (starts i % 8) seeds its start groups in rounds 0..7 -- or, level-
+    aligned, everything before launch round 1."""
+    parent = binary_tree()
+    msgs = np.zeros(3000, dtype=np.uint32)
+    burst = PL.Plan(parent[None, :], [0], plan={"overlap_min_bytes": 0})
+    burst.window(msgs)
+    sb = check_schedule(burst)
+    assert list(sb["seed_off"]) == [0, 47], sb["seed_off"]  # ceil(3000 / 64) non-zero words of the root row
+    p = PL.Plan(parent[None, :], [0], plan={"align_groups": align, "overlap_min_bytes": 0})
+    p.window(msgs, (np.arange(3000) % 8).astype(np.uint32))
+    s = check_schedule(p)
+    per_round = np.diff(s["seed_off"])
+    if align:  # (the planners see one start round: the only seed round is 0)
+        assert list(s["seed_off"]) == [0, 47] and s["reach_rows"] > 0, s
+    else:  # one group-major block of the root row per start round
+        assert len(per_round) == 8 and np.all(per_round > 0) and s["reach_rows"] == 0, s
+        assert per_round.sum() == sum(g[2] for g in p.layout(0)["groups"])  # every word of every block
