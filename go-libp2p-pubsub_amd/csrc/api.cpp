@@ -37,6 +37,7 @@ int dist_common(ps_engine* e, const ps_dist_config* dc) {
   if ((dc->flags & PS_DIST_F_COPY) && (dc->flags & PS_DIST_F_INPLACE))
     return e->fail(PS_E_INVAL, "PS_DIST_F_INPLACE reads rows in place: not with PS_DIST_F_COPY");
   if (!e->pending.empty()) return e->fail(PS_E_STATE, "messages pending");
+  if (e->drain.sink.on) return e->fail(PS_E_STATE, "a sink is set (one rank only): clear it with ps_sink_set first");
   // (every check above passed: the mode changes together with rank and world)
   e->inplace = dc->world > 1 && (dc->flags & PS_DIST_F_INPLACE) != 0;
   e->rank = dc->rank;

@@ -1,8 +1,9 @@
 // drain.cpp -- the host side of the batched drain (kernels: drain.hip;
 // DESIGN.md §5.5): ps_drain, ps_drain_shared, ps_drain_begin / ps_drain_end,
-// ps_drain_shared_begin / ps_drain_shared_end.
+// ps_drain_shared_begin / ps_drain_shared_end, and the sink (ps_sink_set /
+// ps_sink_take, §5.5e): the shared drain behind every window of a run.
 //
-// What the four paths rely on, between them and with run.cpp:
+// What the paths rely on, between them and with run.cpp:
 //  - D.seq / D.p_*: one set of device tables per window, built by whichever
 //    path runs first (drain_tables on the host, drain_tables_async on the
 //    device) and reused by the others.  A device build given up half way sets
@@ -31,6 +32,14 @@
 //    counts live in the slot's DrainCtl on the device and reach the host only
 //    in the view's header.  Its ev_emit stands behind classify, count and emit
 //    alike (all on `stream`), and is recorded even when no list has a segment.
+//  - The sink runs ps_drain_shared_begin's passes behind every window run.cpp
+//    remembers, on `stream`, with buffers of its own (Drain::Sink): it always
+//    builds that window's tables (D.seq), so a later drain of the last window
+//    reuses them.  Each window stages its input in a region of its result's
+//    pinned arena that no other window of the run uses.  The counts never
+//    reach the host between windows: k_sink_commit keeps them in two cursors
+//    that alternate by window.  Sink::fence names the last sink emit over each
+//    row set for drain_fence; a result's copy follows the last window's.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -89,6 +98,26 @@ hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need) {
     *d = static_cast<uint8_t*>(dp);
   }
   return rc;
+}
+
+// `bytes` of the sink result's pinned staging that no other window of its run
+// uses: several windows stage before any of their uploads has run.  A chunk
+// too small is left as it is (uploads may still read it) and a larger one
+// added; sink_open folds them into one once the run before is complete.
+hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out) {
+  bytes = align256(bytes);
+  if (R.arena.empty() || R.arena_used + bytes > R.arena.back().cap) {
+    size_t cap = std::max<size_t>(bytes, 64 << 10);
+    if (!R.arena.empty()) cap = std::max(cap, 2 * R.arena.back().cap);
+    void* p = nullptr;
+    const hipError_t rc = hipHostMalloc(&p, cap, hipHostMallocMapped | hipHostMallocCoherent);
+    if (rc != hipSuccess) return rc;
+    R.arena.push_back({static_cast<uint8_t*>(p), cap});
+    R.arena_used = 0;
+  }
+  *out = R.arena.back().h + R.arena_used;
+  R.arena_used += bytes;
+  return hipSuccess;
 }
 
 // What every entry point needs after its own state checks: the node-space
@@ -213,7 +242,10 @@ int drain_tables(ps_engine* e) {
 // run with several start rounds keeps the host's arrival-order table
 // (kDrainGather, as drain_tables above), staged the same way.  `used`: the
 // bytes of S.h_in taken; the caller stages `tail` bytes of its own behind them.
-int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used) {
+// `arena` (the sink): the block goes to a region of that result's staging
+// instead, returned in *staged.
+int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used, Drain::Sink::Res* arena = nullptr,
+                       uint8_t** staged = nullptr) {
   auto& D = e->drain;
   *used = 0;
   if (D.seq == e->window_seq) return PS_OK;
@@ -266,12 +298,18 @@ int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used) 
   const size_t o_order = align256(o_start + n_msgs * 4);
   const size_t o_gids = align256(o_order + n_gather * 4);
   const size_t block = align256(o_gids + n_gather * 4);
-  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + tail), "alloc drain staging");
+  uint8_t* h = nullptr;
+  if (arena) {
+    HIP_TRY(sink_stage(*arena, block + tail, &h), "alloc sink staging");
+    *staged = h;
+  } else {
+    HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + tail), "alloc drain staging");
+    h = S.h_in;
+  }
   HIP_TRY(D.d_ablock.ensure(block), "alloc drain tables");
   HIP_TRY(D.d_aids.ensure((n_pos + n_gather) * 4), "alloc drain ids");
   HIP_TRY(D.d_amask.ensure((n_pos >> 6) * 8 + 8), "alloc drain masks");
   HIP_TRY(D.d_akeys.ensure(n_pos * 8), "alloc drain keys");
-  uint8_t* h = S.h_in;
   std::memcpy(h + o_topics, D.topics.data(), nt * sizeof(DrainTopic));
   if (!groups.empty()) std::memcpy(h + o_groups, groups.data(), groups.size() * sizeof(DrainGroup));
   uint32_t* h_btopic = reinterpret_cast<uint32_t*>(h + o_btopic);
@@ -435,13 +473,7 @@ int drain_count_scan(ps_engine* e, DrainArgs& a, uint32_t n_segs, Drain::Scratch
 // one width), go to D.cqueries, one bin per topic.  The sort is stable: a
 // topic's queries keep their order (k_drain_first relies on it).
 constexpr uint32_t kOnHost = 0x80000000u;
-struct SharedSort {
-  std::vector<DrainClassBin> bins;
-  uint32_t n_class = 0, n_waves = 0;
-  uint32_t n_rows = 0, n_gather = 0;  // queries with a row; those of kDrainGather topics
-  uint64_t row_ids = 0, gather_ids = 0, bin_ids = 0;  // window messages: per such query; per bin
-  uint32_t max_segs = 0;  // segments of the widest topic with a row queried
-};
+using SharedSort = Drain::SharedSort;
 int drain_shared_sort(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, DrainQuery* queries,
                       SharedSort* R) {
   auto& D = e->drain;
@@ -559,7 +591,305 @@ int drain_slot_complete(ps_engine* e, Drain::Slot& S) {
   return PS_OK;
 }
 
+// A device buffer of the sink's result grown with its contents kept: the
+// windows before have written there, on s.  (Not the steady state: the next
+// run of the same shape finds the room.)
+int sink_grow(ps_engine* e, DevBuf& buf, size_t need, hipStream_t s) {
+  if (need <= buf.bytes) return PS_OK;
+  DevBuf nb;
+  HIP_TRY(nb.ensure(std::max(need, 2 * buf.bytes)), "alloc sink result");
+  if (buf.bytes) {
+    HIP_TRY(hipMemcpyAsync(nb.p, buf.p, buf.bytes, hipMemcpyDeviceToDevice, s), "move sink result");
+    HIP_TRY(hipStreamSynchronize(s), "sync");
+  }
+  buf.swap(nb);
+  return PS_OK;
+}
+
+constexpr size_t kSinkHdrBytes = 256;  // the cursors in front of list_off; the view's header
+static_assert(2 * sizeof(SinkCursor) <= kSinkHdrBytes, "both cursors lie in front of list_off");
+
 }  // namespace
+
+// ---- the sink's run hooks (run.cpp calls them) ---------------
+
+int psamd::sink_precheck(ps_engine* e) {
+  auto& D = e->drain;
+  auto& K = D.sink;
+  if (!K.on) return PS_OK;
+  if (K.count == 2) return e->fail(PS_E_STATE, "two sink results untaken: ps_sink_take first");
+  if (K.list_cap || K.id_cap) return PS_OK;
+  // the engine's id cap for this run at most: a topic's messages once, or once
+  // per query where every query takes a private list
+  std::vector<uint32_t> per_topic(e->topics.size(), 0);
+  uint32_t most = 0;
+  for (uint32_t t : K.topic) most = std::max(most, ++per_topic[t]);
+  const bool paced = e->pending_nonzero_start;
+  if (static_cast<uint64_t>(e->pending.size()) * ((!D.share || paced) ? most : 1u) <= kDrainAsyncMaxIds) return PS_OK;
+  uint64_t bound = 0;
+  for (const RunMsg& m : e->pending) {
+    const bool priv = !D.share || (paced && e->topics[m.topic].kind == Kind::Children);
+    bound += priv ? per_topic[m.topic] : (per_topic[m.topic] ? 1u : 0u);
+  }
+  if (bound > kDrainAsyncMaxIds) return e->fail(PS_E_RANGE, "the sink's result may exceed 2^30 ids: run smaller batches");
+  return PS_OK;
+}
+
+int psamd::sink_open(ps_engine* e) {
+  auto& K = e->drain.sink;
+  if (!K.on) return PS_OK;
+  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  auto& R = K.res[(K.head + K.count) & 1];
+  // (the slot's last run is complete: its result was taken or discarded)
+  if (R.arena.size() > 1) {
+    size_t cap = 0;
+    for (auto& c : R.arena) {
+      cap += c.cap;
+      (void)hipHostFree(c.h);
+    }
+    R.arena.clear();
+    uint8_t* h = nullptr;
+    R.arena_used = 0;
+    HIP_TRY(sink_stage(R, cap, &h), "alloc sink staging");
+  }
+  if (!R.ev_done) HIP_TRY(hipEventCreateWithFlags(&R.ev_done, hipEventDisableTiming), "sink event");
+  R.arena_used = 0;
+  R.windows = 0;
+  R.list_cap = K.list_cap;
+  R.id_cap = K.id_cap;
+  R.enqueued = false;
+  R.run = ++K.runs;
+  K.open = &R;
+  K.host_ms = 0;
+  return PS_OK;
+}
+
+void psamd::sink_abort(ps_engine* e) {
+  auto& K = e->drain.sink;
+  if (!K.open) return;
+  // the slot is given up: what its windows staged must have left the staging
+  (void)hipStreamSynchronize(e->stream);
+  K.runs_done = std::max(K.runs_done, K.open->run);
+  K.open = nullptr;
+}
+
+// ps_drain_shared_begin's work for the window just remembered, into the open
+// result: tables, classify, assign, count and scan as there, then k_sink_commit
+// and k_sink_emit at the run's cursor.  All on `stream`; nothing waits.
+int psamd::sink_window(ps_engine* e) {
+  auto& D = e->drain;
+  auto& K = D.sink;
+  if (!K.open) return PS_OK;
+  auto& R = *K.open;
+  const auto t_host0 = hclock::now();
+  const size_t n = K.topic.size();
+  const uint32_t w = R.windows;
+  if (const int rj = twin_join(e)) return rj;
+  int rc = drain_ready(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  const uint32_t nt = static_cast<uint32_t>(e->topics.size());
+
+  // staged behind the tables, in this window's own region: queries | initial verdicts | sorted queries | bins
+  const size_t o_v = align256(n * sizeof(DrainQuery));
+  const size_t o_cq = o_v + align256(n * 4);
+  const size_t o_bins = o_cq + align256(n * sizeof(DrainClassQuery));
+  const size_t tail = o_bins + align256(nt * sizeof(DrainClassBin));
+  const uint64_t seq0 = D.seq;
+  size_t used = 0;
+  uint8_t* h = nullptr;
+  const bool timing = D.timing;  // (a timed build waits for the stream: nothing of the sink may)
+  D.timing = false;
+  rc = drain_tables_async(e, D.slot[0], tail, &used, &R, &h);
+  D.timing = timing;
+  if (rc) {
+    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
+    return rc;
+  }
+  if (!used) HIP_TRY(sink_stage(R, tail, &h), "alloc sink staging");
+  h += used;
+
+  // the sorted queries: the last window's while the node space and every
+  // topic's window shape are the same
+  std::vector<uint64_t> key{e->graph_epoch, nt, n};
+  for (uint32_t t = 0; t < nt; ++t) {
+    key.push_back(static_cast<uint64_t>(D.topics[t].flags) << 32 | D.topics[t].n_pos);
+    key.push_back(e->last_cnt[t]);
+  }
+  if (key != K.sort_key) {
+    K.sort_key.clear();
+    K.sort_r = SharedSort{};
+    K.sort_tail.assign(tail, 0);
+    uint8_t* const c = K.sort_tail.data();
+    if (drain_shared_sort(e, K.topic.data(), K.peer.data(), n, reinterpret_cast<DrainQuery*>(c), &K.sort_r))
+      return e->fail(PS_E_RANGE, "too many rows in one sink window");
+    uint32_t* const hv = reinterpret_cast<uint32_t*>(c + o_v);
+    for (size_t q = 0; q < n; ++q) hv[q] = D.verdict[q] & ~kOnHost;
+    if (K.sort_r.n_class)
+      std::memcpy(c + o_cq, D.cqueries.data(), static_cast<size_t>(K.sort_r.n_class) * sizeof(DrainClassQuery));
+    if (!K.sort_r.bins.empty()) std::memcpy(c + o_bins, K.sort_r.bins.data(), K.sort_r.bins.size() * sizeof(DrainClassBin));
+    K.sort_key = key;
+  }
+  const SharedSort& S = K.sort_r;
+  std::memcpy(h, K.sort_tail.data(), tail);
+
+  // this window's caps, and the run's as far as this window
+  size_t win_lists = std::min<size_t>(K.list_cap, S.n_rows);
+  if (K.list_cap == 0 && K.id_cap == 0) {
+    win_lists = D.share ? S.bins.size() + S.n_gather : S.n_rows;
+    R.list_cap += win_lists;
+    R.id_cap += D.share ? S.bin_ids + S.gather_ids : S.row_ids;
+  }
+  if (R.id_cap > kDrainAsyncMaxIds) return e->fail(PS_E_RANGE, "the sink's result may exceed 2^30 ids");
+  const uint64_t seg_bound64 = static_cast<uint64_t>(win_lists) * S.max_segs;
+  if (seg_bound64 >= kDrainRowLimit || static_cast<uint64_t>(n) * S.max_segs >= kDrainRowLimit ||
+      R.list_cap >= 0x7FFFFFFFull || (static_cast<uint64_t>(w) + 1) * n >= (1ull << 32))
+    return e->fail(PS_E_RANGE, "too many rows in one sink window");
+  const uint32_t seg_bound = static_cast<uint32_t>(seg_bound64);
+
+  // the result on the device: it grows with the windows, contents kept
+  if ((rc = sink_grow(e, R.d_wl, (static_cast<size_t>(w) + 1) * n * 4, s)) ||
+      (rc = sink_grow(e, R.d_off, kSinkHdrBytes + (R.list_cap + 1) * 8, s)) || (rc = sink_grow(e, R.d_ids, R.id_cap * 4, s)))
+    return rc;
+  SinkCursor* const cur = R.d_off.as<SinkCursor>();
+  if (w == 0) HIP_TRY(hipMemsetAsync(cur, 0, kSinkHdrBytes, s), "clear sink cursor");
+
+  // the passes' buffers, sized by n and the window's caps; they only grow
+  auto& B = K.scratch;
+  const size_t o_first = align256(sizeof(DrainCtl));
+  HIP_TRY(K.d_in.ensure(tail), "alloc drain input");
+  HIP_TRY(K.d_key.ensure(2 * n * 8), "alloc drain keys");
+  HIP_TRY(K.d_aux.ensure(o_first + nt * 4), "alloc drain control");
+  HIP_TRY(K.d_lq.ensure(n * 4), "alloc sink lists");
+  HIP_TRY(B.d_queries.ensure(win_lists * sizeof(DrainQuery)), "alloc drain lists");
+  HIP_TRY(B.d_cnt.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain counts");
+  HIP_TRY(B.d_off.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain offsets");
+  size_t scan_bytes = 0, scan_keys = 0;
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s),
+          "size drain scan");
+  HIP_TRY(drain_scan(nullptr, &scan_keys, K.d_key.as<uint64_t>(), K.d_key.as<uint64_t>() + n, static_cast<uint32_t>(n), s),
+          "size drain scan");
+  HIP_TRY(B.d_scan.ensure(std::max(scan_bytes, scan_keys)), "alloc drain scan");
+  uint8_t* const aux = K.d_aux.as<uint8_t>();
+  DrainCtl* const ctl = reinterpret_cast<DrainCtl*>(aux);
+  if ((rc = drain_err_word(e, s))) return rc;
+
+  SinkCommit c{};
+  c.lists = B.d_queries.as<DrainQuery>();
+  c.ctl = ctl;
+  c.seg_off = B.d_off.as<uint64_t>();
+  c.win_lq = K.d_lq.as<uint32_t>();
+  c.err = D.d_err;
+  c.cur = cur;
+  c.list_off = reinterpret_cast<uint64_t*>(R.d_off.as<uint8_t>() + kSinkHdrBytes);
+  c.win_list = R.d_wl.as<uint32_t>();
+  c.w = w;
+  c.n = static_cast<uint32_t>(n);
+  c.win_list_cap = static_cast<uint32_t>(win_lists);
+  c.list_cap = static_cast<uint32_t>(R.list_cap);
+  c.id_cap = R.id_cap;
+  if (S.n_rows == 0) {  // no row to read: a row of PS_NONE, and the cursor moves on by one window
+    if (n) HIP_TRY(hipMemsetAsync(K.d_lq.p, 0xFF, n * 4, s), "clear sink lists");
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(DrainCtl), s), "clear drain control");
+    HIP_TRY(hipMemsetAsync(B.d_off.p, 0, 8, s), "clear drain offsets");
+    c.win_list_cap = 0;
+    HIP_TRY(launch_sink_commit(c, s), "k_sink_commit");
+  } else {
+    uint8_t* const din = K.d_in.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(din, h, tail, hipMemcpyHostToDevice, s), "upload drain queries");
+    HIP_TRY(hipMemsetAsync(aux + o_first, 0xFF, nt * 4, s), "preset drain firsts");
+    DrainArgs a = drain_args(e);
+    uint32_t* const verdict = reinterpret_cast<uint32_t*>(din + o_v);
+    HIP_TRY(launch_drain_classify(a, reinterpret_cast<const DrainClassBin*>(din + o_bins), static_cast<uint32_t>(S.bins.size()),
+                                  reinterpret_cast<const DrainClassQuery*>(din + o_cq), S.n_waves, verdict, s),
+            "k_drain_classify");
+    DrainAssign g{};
+    g.topics = D.p_topics;
+    g.queries = reinterpret_cast<const DrainQuery*>(din);
+    g.verdict = verdict;
+    g.sorted = reinterpret_cast<const DrainClassQuery*>(din + o_cq);
+    g.n_sorted = S.n_class;
+    g.n = static_cast<uint32_t>(n);
+    g.share = D.share;
+    g.first = reinterpret_cast<uint32_t*>(aux + o_first);
+    g.key = K.d_key.as<uint64_t>();
+    g.key_off = g.key + n;
+    g.scan_temp = B.d_scan.p;
+    g.scan_bytes = B.d_scan.bytes;
+    g.lists = B.d_queries.as<DrainQuery>();
+    g.list_cap = static_cast<uint32_t>(win_lists);
+    g.seg_bound = seg_bound;
+    g.list_of_query = K.d_lq.as<uint32_t>();
+    g.ctl = ctl;
+    HIP_TRY(launch_drain_assign(g, s), "drain list assignment");
+    a.queries = g.lists;
+    a.n_queries = 0;  // (the kernels read it from the control block)
+    HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, B.d_cnt.as<uint64_t>(), s), "k_drain_count_dev");
+    scan_bytes = B.d_scan.bytes;
+    HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s), "drain scan");
+    HIP_TRY(launch_sink_commit(c, s), "k_sink_commit");
+    HIP_TRY(launch_sink_emit(a, ctl, cur, w, seg_bound, B.d_off.as<uint64_t>(), R.d_ids.as<uint32_t>(), R.id_cap, s),
+            "k_sink_emit");
+  }
+
+  // the last reader of this window's rows on `stream` (run.cpp: drain_fence):
+  // the entry of this row set, else one whose row set is gone
+  Drain::Sink::Fence* F = nullptr;
+  for (auto& f : K.fence)
+    if (f.seen == e->d_seen.p) F = &f;
+  for (auto& f : K.fence)
+    if (!F && (!f.seen || f.seen != e->d_seen_b.p)) F = &f;
+  if (!F) return e->fail(PS_E_STATE, "sink: no fence entry for the row set");
+  if (!F->ev) HIP_TRY(hipEventCreateWithFlags(&F->ev, kStreamEvent), "sink event");
+  HIP_TRY(hipEventRecord(F->ev, s), "event");
+  F->seen = e->d_seen.p;
+  F->run = R.run;
+  K.last_ev = F->ev;
+  R.windows = w + 1;
+  K.host_ms += ms_since(t_host0);
+  return PS_OK;
+}
+
+// The run's result leaves behind its last window: the cursor that window
+// left (the header), win_list, list_off and the ids, on the copy stream.
+int psamd::sink_close(ps_engine* e) {
+  auto& D = e->drain;
+  auto& K = D.sink;
+  if (!K.open) return PS_OK;
+  auto& R = *K.open;
+  const auto t_host0 = hclock::now();
+  const size_t n = K.topic.size();
+  R.o_wl = kSinkHdrBytes;
+  R.o_off = R.o_wl + align256(static_cast<size_t>(R.windows) * n * 4);
+  R.o_ids = R.o_off + align256((R.list_cap + 1) * 8);
+  const size_t res_bytes = R.o_ids + R.id_cap * 4;
+  HIP_TRY(pinned_ensure(&R.h_res, nullptr, &R.res_cap, res_bytes), "alloc sink view");
+  if (R.windows == 0) {  // no window ran: an empty result, written here
+    std::memset(R.h_res, 0, kSinkHdrBytes);
+    std::memset(R.h_res + R.o_off, 0, 8);
+  } else {
+    hipStream_t cs = D.copy_stream;
+    const uint8_t* const d_off = R.d_off.as<uint8_t>();
+    HIP_TRY(hipStreamWaitEvent(cs, K.last_ev, 0), "wait");
+    HIP_TRY(hipMemcpyAsync(R.h_res, d_off + (R.windows & 1) * sizeof(SinkCursor), sizeof(SinkCursor), hipMemcpyDeviceToHost, cs),
+            "read sink header");
+    if (n)
+      HIP_TRY(hipMemcpyAsync(R.h_res + R.o_wl, R.d_wl.p, static_cast<size_t>(R.windows) * n * 4, hipMemcpyDeviceToHost, cs),
+              "read sink lists");
+    HIP_TRY(hipMemcpyAsync(R.h_res + R.o_off, d_off + kSinkHdrBytes, (R.list_cap + 1) * 8, hipMemcpyDeviceToHost, cs),
+            "read sink offsets");
+    if (R.id_cap)
+      HIP_TRY(hipMemcpyAsync(R.h_res + R.o_ids, R.d_ids.p, R.id_cap * 4, hipMemcpyDeviceToHost, cs), "read sink ids");
+    HIP_TRY(hipEventRecord(R.ev_done, cs), "event");
+    R.enqueued = true;
+  }
+  K.open = nullptr;
+  ++K.count;
+  if (D.timing)
+    std::fprintf(stderr, "psamd sink: queries %zu windows %u list_cap %zu id_cap %zu view_bytes %zu host_us %.1f\n", n,
+                 R.windows, R.list_cap, R.id_cap, res_bytes, 1e3 * (K.host_ms + ms_since(t_host0)));
+  return PS_OK;
+}
 
 void psamd::drain_destroy(ps_engine* e) {
   auto& D = e->drain;
@@ -567,6 +897,13 @@ void psamd::drain_destroy(ps_engine* e) {
     (void)hipStreamSynchronize(D.copy_stream);
     (void)hipStreamDestroy(D.copy_stream);
   }
+  for (auto& r : D.sink.res) {
+    for (auto& c : r.arena) (void)hipHostFree(c.h);
+    if (r.h_res) (void)hipHostFree(r.h_res);
+    if (r.ev_done) (void)hipEventDestroy(r.ev_done);
+  }
+  for (auto& f : D.sink.fence)
+    if (f.ev) (void)hipEventDestroy(f.ev);
   for (hipEvent_t ev : {D.ev_emit[0], D.ev_emit[1], D.ev_copy[0], D.ev_copy[1], D.ev_t[0], D.ev_t[1], D.slot[0].ev_emit,
                         D.slot[0].ev_done, D.slot[1].ev_emit, D.slot[1].ev_done})
     if (ev) (void)hipEventDestroy(ev);
@@ -1095,6 +1432,63 @@ int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t*
   *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.o_ids);
   *n_lists_out = hdr->n_lists;
   *total_out = hdr->total;
+  if (hdr->err)
+    return e->fail(PS_E_STATE, hdr->err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
+                                                       : "drain tables: row bits do not ascend in arrival order");
+  if (hdr->over)
+    return e->fail(PS_E_RANGE, hdr->over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
+  return PS_OK;
+}
+
+// ---- ps_sink_set / ps_sink_take ----------------------------
+
+int ps_sink_set(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, size_t list_cap, size_t id_cap) {
+  if (!e || (n && (!topic || !peer))) return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_sink_set on a multi-rank engine");
+  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
+  if (const int rq = drain_check_queries(e, topic, peer, n)) return rq;
+  if (n >= 0x7FFFFFFFull || list_cap >= 0x7FFFFFFFull) return e->fail(PS_E_RANGE, "too many queries or lists");
+  if (id_cap > kDrainAsyncMaxIds) return e->fail(PS_E_RANGE, "a sink result holds 2^30 ids at most");
+  auto& D = e->drain;
+  auto& K = D.sink;
+  // results not yet taken are discarded: whatever still fills them ends first
+  if (K.runs) {
+    HIP_TRY(hipStreamSynchronize(e->stream), "sync");
+    if (D.copy_stream) HIP_TRY(hipStreamSynchronize(D.copy_stream), "sync");
+  }
+  K.head = K.count = 0;
+  K.runs_done = K.runs;
+  for (auto& r : K.res) r.enqueued = false;
+  K.sort_key.clear();
+  K.topic.assign(topic, topic + n);
+  K.peer.assign(peer, peer + n);
+  K.list_cap = list_cap;
+  K.id_cap = id_cap;
+  K.on = n > 0;
+  return PS_OK;
+}
+
+int ps_sink_take(ps_engine* e, const uint32_t** win_list_out, const uint64_t** list_off_out, const uint32_t** msg_out,
+                 uint32_t* n_windows_out, uint32_t* n_lists_out, uint64_t* total_out) {
+  if (!e || !win_list_out || !list_off_out || !msg_out || !n_windows_out || !n_lists_out || !total_out) return PS_E_INVAL;
+  auto& K = e->drain.sink;
+  if (K.count == 0) return e->fail(PS_E_NOTREADY, "no sink result outstanding");
+  auto& R = K.res[K.head];
+  K.head ^= 1;
+  --K.count;
+  if (R.enqueued) {
+    HIP_TRY(hipEventSynchronize(R.ev_done), "wait for the sink result");
+    R.enqueued = false;
+  }
+  K.runs_done = std::max(K.runs_done, R.run);  // (its emits are complete: drain_fence waits for none of them)
+  const SinkCursor* hdr = reinterpret_cast<const SinkCursor*>(R.h_res);
+  *win_list_out = reinterpret_cast<const uint32_t*>(R.h_res + R.o_wl);
+  *list_off_out = reinterpret_cast<const uint64_t*>(R.h_res + R.o_off);
+  *msg_out = reinterpret_cast<const uint32_t*>(R.h_res + R.o_ids);
+  *n_windows_out = hdr->windows;
+  *n_lists_out = hdr->lists;
+  *total_out = hdr->ids;
+  if (hdr->windows != R.windows) return e->fail(PS_E_STATE, "sink: the result's window count is not the run's");
   if (hdr->err)
     return e->fail(PS_E_STATE, hdr->err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
                                                        : "drain tables: row bits do not ascend in arrival order");

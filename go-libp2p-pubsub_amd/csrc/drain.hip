@@ -15,6 +15,10 @@
 //                         of ps_drain_shared on the device)
 //   k_drain_count_dev / _offsets_dev / _emit_dev  count, offsets and emit over
 //                         those lists, the counts read from a control block
+// and, for the sink (ps_sink_set, §5.5e), every window of a run into one result:
+//   k_sink_commit         a window's list offsets and list numbers at the
+//                         run's cursor, and the cursor moved on
+//   k_sink_emit           k_drain_emit_dev at the cursor's id count
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -437,7 +441,65 @@ __global__ __launch_bounds__(kWave) void k_drain_emit_dev(DrainArgs a, const Dra
   emit_segment<true>(a, blockIdx.x, off, 0, out, out_cap, stage);
 }
 
+// ---- the sink: a window's lists into the run's result (ps_sink_set) ----------
+
+// Where k_drain_offsets_dev writes a view of its own, this writes the window's
+// part of the run's: list_off from the run's list and id counts so far, row w
+// of win_list with the window's list numbers rebased, and the next cursor.
+// Every thread reads cur[w & 1], which this launch does not write; thread 0
+// alone writes cur[(w + 1) & 1].  Nothing is stored past list_cap.
+__global__ __launch_bounds__(kTabBlock) void k_sink_commit(SinkCommit c) {
+  const uint32_t i = blockIdx.x * kTabBlock + threadIdx.x;
+  const SinkCursor C = c.cur[c.w & 1];
+  const DrainCtl ctl = *c.ctl;
+  const uint64_t total = c.seg_off[ctl.use_segs];
+  if (i <= ctl.use_lists && i <= c.win_list_cap) {
+    const uint64_t at = static_cast<uint64_t>(C.lists) + i;
+    if (at <= c.list_cap) c.list_off[at] = C.ids + (i < ctl.use_lists ? c.seg_off[c.lists[i].seg0] : total);
+  }
+  if (i < c.n) {
+    const uint32_t v = c.win_lq[i];
+    c.win_list[static_cast<uint64_t>(c.w) * c.n + i] = v == 0xFFFFFFFFu ? v : C.lists + v;  // (PS_NONE stays)
+  }
+  if (i == 0) {
+    SinkCursor N{};
+    N.ids = C.ids + total;
+    N.lists = C.lists + ctl.n_lists;
+    N.windows = C.windows + 1;
+    N.over = C.over | ctl.over | (static_cast<uint64_t>(C.lists) + ctl.n_lists > c.list_cap ? kDrainOverLists : 0u) |
+             (C.ids + total > c.id_cap ? kDrainOverIds : 0u);
+    N.err = C.err | *c.err;
+    c.cur[(c.w + 1) & 1] = N;
+  }
+}
+
+// k_drain_emit_dev at the run's id count before this window: any base, so the
+// wave's dword stores start at any multiple of four bytes
+__global__ __launch_bounds__(kWave) void k_sink_emit(DrainArgs a, const DrainCtl* __restrict__ ctl,
+                                                     const SinkCursor* __restrict__ cur, uint32_t w,
+                                                     const uint64_t* __restrict__ off, uint32_t* __restrict__ out,
+                                                     uint64_t id_cap) {
+  __shared__ uint32_t stage[kDrainSegBits];
+  if (cur[(w + 1) & 1].over || blockIdx.x >= ctl->use_segs) return;  // (block-uniform)
+  a.n_queries = ctl->use_lists;
+  const uint64_t base = cur[w & 1].ids;  // (no overflow: base + the window's ids <= id_cap)
+  emit_segment<true>(a, blockIdx.x, off, 0, out + base, id_cap - base, stage);
+}
+
 }  // namespace
+
+hipError_t launch_sink_commit(const SinkCommit& c, hipStream_t s) {
+  const uint32_t threads = c.win_list_cap + 1 > c.n ? c.win_list_cap + 1 : c.n;
+  hipLaunchKernelGGL(k_sink_commit, dim3((threads + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_sink_emit(const DrainArgs& a, const DrainCtl* ctl, const SinkCursor* cur, uint32_t w,
+                            uint32_t seg_bound, const uint64_t* off, uint32_t* out, uint64_t id_cap, hipStream_t s) {
+  if (seg_bound == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_sink_emit, dim3(seg_bound), dim3(kWave), 0, s, a, ctl, cur, w, off, out, id_cap);
+  return hipGetLastError();
+}
 
 hipError_t launch_drain_assign(const DrainAssign& g, hipStream_t s) {
   if (g.n == 0) return hipSuccess;

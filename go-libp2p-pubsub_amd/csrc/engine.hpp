@@ -551,6 +551,63 @@ struct ps_engine {
     std::vector<uint32_t> verdict;
     std::vector<uint64_t> hdr;
     bool share = true;  // full rows share their topic's list (A/B: PSAMD_DRAIN_SHARED=private)
+    // what drain_shared_sort (drain.cpp) leaves beside the sorted queries
+    struct SharedSort {
+      std::vector<psamd::DrainClassBin> bins;
+      uint32_t n_class = 0, n_waves = 0;
+      uint32_t n_rows = 0, n_gather = 0;  // queries with a row; those of kDrainGather topics
+      uint64_t row_ids = 0, gather_ids = 0, bin_ids = 0;  // window messages: per such query; per bin
+      uint32_t max_segs = 0;  // segments of the widest topic with a row queried
+    };
+
+    // ps_sink_set / ps_sink_take: standing queries drained
+    // behind every window of a run into one result per run.  Two results may
+    // be untaken, in slots that alternate; a slot owns its result on the
+    // device (win_list rows; the two cursors with list_off behind them; ids),
+    // its pinned view and the pinned staging of its run's windows.  The
+    // per-window passes share one set of device buffers: they all run on
+    // `stream`, one window after the other.
+    struct Sink {
+      bool on = false;
+      std::vector<uint32_t> topic, peer;
+      size_t list_cap = 0, id_cap = 0;  // the caller's (both zero: the engine's, summed over the windows)
+      struct Chunk {
+        uint8_t* h = nullptr;
+        size_t cap = 0;
+      };
+      struct Res {
+        psamd::DevBuf d_wl, d_off, d_ids;  // d_off: SinkCursor[2] in its first 256 bytes
+        std::vector<Chunk> arena;          // pinned staging: every window of the run takes its own region
+        size_t arena_used = 0;             // ... of the last chunk
+        uint8_t* h_res = nullptr;
+        size_t res_cap = 0;
+        hipEvent_t ev_done = nullptr;
+        bool enqueued = false;  // (else the host wrote the view: a run without a window)
+        uint32_t windows = 0;
+        size_t list_cap = 0, id_cap = 0;     // as far as the last window
+        size_t o_wl = 0, o_off = 0, o_ids = 0;  // the view: a SinkCursor, then these
+        uint64_t run = 0;                    // the run's number (drain_fence)
+      } res[2];
+      uint32_t head = 0, count = 0;  // untaken results, oldest first
+      Res* open = nullptr;           // the run being enqueued
+      uint64_t runs = 0, runs_done = 0;  // runs opened; the last whose result was seen complete
+      // the last sink emit per row set: a window about to write the set waits for it
+      struct Fence {
+        const void* seen = nullptr;
+        hipEvent_t ev = nullptr;
+        uint64_t run = 0;  // 0: nothing pending
+      } fence[2];
+      hipEvent_t last_ev = nullptr;  // the fence event behind the open run's last window
+      double host_ms = 0;            // PSAMD_DRAIN_TIMING: the open run's host time in the sink
+      // per-window passes (see Slot)
+      Scratch scratch;
+      psamd::DevBuf d_in, d_key, d_aux, d_lq;
+      // the sorted queries of the last window, kept while the node space and
+      // the topics' window shapes stay
+      std::vector<uint64_t> sort_key;
+      std::vector<uint8_t> sort_tail;
+      SharedSort sort_r;
+    } sink;
   } drain;
 
   // asynchronous runs (ps_run_async / ps_wait): the last window of a run may
@@ -688,6 +745,16 @@ int twin_join(ps_engine* e);
 int drain_fence(ps_engine* e, hipStream_t s);
 // drain.cpp: frees the drain's stream, events and pinned memory (ps_destroy)
 void drain_destroy(ps_engine* e);
+// drain.cpp, the sink (ps_sink_set; all no-ops while none is set).  A run
+// asks sink_precheck before it touches the pending messages (both results
+// untaken, or an answer that may pass 2^30 ids), opens a result, calls
+// sink_window behind every window it remembered and closes the result behind
+// the last one; sink_abort gives the open result's slot up (a run that failed).
+int sink_precheck(ps_engine* e);
+int sink_open(ps_engine* e);
+int sink_window(ps_engine* e);
+int sink_close(ps_engine* e);
+void sink_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

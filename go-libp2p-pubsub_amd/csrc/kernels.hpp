@@ -715,4 +715,39 @@ hipError_t launch_drain_offsets_dev(const DrainQuery* lists, DrainCtl* ctl, uint
 hipError_t launch_drain_emit_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, const uint64_t* off,
                                  uint32_t* out, uint64_t id_cap, hipStream_t s);
 
+// ---- the sink: every window of a run into one result (ps_sink_set) --
+// The run cursor: what the windows so far have added to the result.  Two of
+// them alternate: window w reads cur[w & 1] as its base -- the window header,
+// which nothing writes while the window's commit and emit run -- and its
+// commit leaves cur[(w + 1) & 1] for the next window.  The one the last window
+// left is the result's header.
+struct SinkCursor {
+  uint64_t ids;      // ids so far: exact while the lists fit
+  uint32_t lists;    // lists so far: exact, whatever the caps
+  uint32_t windows;  // windows so far
+  uint32_t over;     // kDrainOver*, sticky: no id is emitted from the first overflow on
+  uint32_t err;      // the windows' table error words (kDrainErr*)
+  uint32_t pad[2];
+};
+struct SinkCommit {
+  const DrainQuery* lists;      // the window's lists (k_drain_lists)
+  const DrainCtl* ctl;          // ... and their counts
+  const uint64_t* seg_off;      // the window's scanned segment counts
+  const uint32_t* win_lq;       // [n] the window's own list numbers (PS_NONE: none)
+  const uint32_t* err;          // the window's table error word
+  SinkCursor* cur;              // [2]
+  uint64_t* list_off;           // [list_cap + 1] the run's
+  uint32_t* win_list;           // [windows x n] the run's
+  uint32_t w, n;                // the window's number in the run; queries
+  uint32_t win_list_cap;        // lists this window's passes were sized for
+  uint32_t list_cap;            // the run's caps as far as this window
+  uint64_t id_cap;
+};
+// k_sink_commit: list_off[base + l], row w of win_list, the next cursor.
+hipError_t launch_sink_commit(const SinkCommit& c, hipStream_t s);
+// k_sink_emit: k_drain_emit_dev with the output base read from cur[w & 1] and
+// the verdict on the caps from cur[(w + 1) & 1]
+hipError_t launch_sink_emit(const DrainArgs& a, const DrainCtl* ctl, const SinkCursor* cur, uint32_t w,
+                            uint32_t seg_bound, const uint64_t* off, uint32_t* out, uint64_t id_cap, hipStream_t s);
+
 }  // namespace psamd

@@ -181,6 +181,10 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   if (s == e->stream) return PS_OK;  // (the drains are enqueued on it: ordered already)
   for (auto& S : e->drain.slot)
     if (S.emit_pending && S.seen == e->d_seen.p) HIP_TRY(hipStreamWaitEvent(s, S.ev_emit, 0), "wait for a pending drain");
+  // ... and the sink's: the last emit it enqueued over this row set, in this run or one not yet seen complete
+  const auto& K = e->drain.sink;
+  for (const auto& F : K.fence)
+    if (F.run > K.runs_done && F.seen == e->d_seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending sink drain");
   return PS_OK;
 }
 
@@ -1445,8 +1449,11 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
       win[t].n = lo < per[t].n ? std::min(cap, per[t].n - lo) : 0;
     }
     e->defer_last = e->defer_phase && k + 1 == n_win;
+    const uint64_t seq0 = e->window_seq;
     int rc = run_window(e, msgs, win, st);
     e->defer_last = false;
+    // (the window that was remembered: after a k_flood timeout, its re-run)
+    if (!rc && e->window_seq != seq0) rc = sink_window(e);
     if (rc) return rc;
   }
   return PS_OK;
@@ -1558,7 +1565,20 @@ bool split_aligned_window(ps_stats* st, const uint64_t* hs, uint32_t r, uint32_t
 
 // ps_run's body.  may_defer: the last window of the final phase may leave its
 // counters on the stream (ps_run_async); *stp is completed by ps_wait then.
+int run_windows(ps_engine* e, ps_stats* stp, bool may_defer);
+
+// The run with the sink's result around it (ps_sink_set; nothing while none
+// is set): refused before the pending messages are touched, opened, closed
+// behind the last window, given up when the run fails.
 int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
+  int rc = sink_precheck(e);
+  if (rc || (rc = sink_open(e))) return rc;
+  if (!(rc = run_windows(e, stp, may_defer))) rc = sink_close(e);
+  if (rc) sink_abort(e);
+  return rc;
+}
+
+int run_windows(ps_engine* e, ps_stats* stp, bool may_defer) {
   const auto t_host0 = std::chrono::steady_clock::now();
   e->t_run0 = t_host0;
   ps_stats& st = *stp;

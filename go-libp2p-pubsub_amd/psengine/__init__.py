@@ -159,6 +159,8 @@ PROTOTYPES = [
     ("ps_drain_end", C.c_int, [_P, C.POINTER(_u64p), C.POINTER(_u32p), _u64p]),
     ("ps_drain_shared_begin", C.c_int, [_P, _u32p, _u32p, C.c_size_t, C.c_size_t, C.c_size_t]),
     ("ps_drain_shared_end", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p, _u64p]),
+    ("ps_sink_set", C.c_int, [_P, _u32p, _u32p, C.c_size_t, C.c_size_t, C.c_size_t]),
+    ("ps_sink_take", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p, _u32p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -285,6 +287,7 @@ class Engine:
         self._h = h
         self._L = L
         self._drain_n = []  # (shared, query count) of the drains begun and not ended
+        self._sink_n = 0  # standing queries (sink_set)
         if plan:
             self.set_plan(**plan)
 
@@ -551,6 +554,32 @@ class Engine:
         off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
         ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
         return (lists.copy(), off.copy(), ids.copy()) if copy else (lists, off, ids)
+
+    def sink_set(self, topics, peers, list_cap: int = 0, id_cap: int = 0):
+        """Registers standing queries (ps_sink_set): from now on every window
+        of every run is drained for them, one result per run (sink_take).  No
+        query clears the sink; results not yet taken are discarded."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        p = np.ascontiguousarray(peers, dtype=np.uint32)
+        if t.ndim != 1 or t.shape != p.shape:
+            raise ValueError("topics and peers must be 1-d arrays of one length")
+        self._check(self._L.ps_sink_set(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size, list_cap, id_cap))
+        self._sink_n = t.size
+
+    def sink_take(self, copy: bool = True):
+        """(win_list[n_windows, n], list_off, ids) of the oldest run not yet
+        taken (ps_sink_take): query q's list in window w, or PS_NONE; list l
+        is ids[list_off[l]:list_off[l + 1]].  copy=False: views of the
+        engine's pinned memory, valid until the second run after its own."""
+        wp, op, mp = _u32p(), _u64p(), _u32p()
+        n_windows, n_lists, total = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._check(self._L.ps_sink_take(self._h, C.byref(wp), C.byref(op), C.byref(mp), C.byref(n_windows),
+                                         C.byref(n_lists), C.byref(total)))
+        n, nw = self._sink_n, n_windows.value
+        wl = np.ctypeslib.as_array(wp, shape=(nw, n)) if nw and n else np.empty((nw, n), dtype=np.uint32)
+        off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
+        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        return (wl.copy(), off.copy(), ids.copy()) if copy else (wl, off, ids)
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

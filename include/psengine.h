@@ -376,6 +376,46 @@ int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* p
                           size_t id_cap);
 int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t** list_off_out,
                         const uint32_t** msg_out, uint32_t* n_lists_out, uint64_t* total_out);
+/* The sink: standing queries the engine drains itself behind EVERY window of
+ * a run, into one answer per run (every read above answers for the last
+ * window of the last run only; a run has several windows when a topic exceeds
+ * msg_window or after ps_topic_drop).
+ *   ps_sink_set registers the n queries (topic[q], peer[q]) -- repeats and any
+ * order allowed, the arrays are copied; n == 0 clears the sink (the pointers
+ * may be NULL).  A topic or peer out of range returns PS_E_RANGE and the
+ * previous sink stays.  PS_E_STATE with a run in flight and on a multi-rank
+ * engine; ps_dist_init* on an engine whose sink is set returns PS_E_STATE.
+ * Setting or clearing discards results not yet taken.
+ *   While a sink is set, every window of every ps_run / ps_run_async enqueues
+ * behind itself the shared drain of ps_drain_shared_begin for the standing
+ * queries, resolved against the node space that window ran on, and the run's
+ * windows accumulate: win_list[w * n + q] is query q's list in window w or
+ * PS_NONE, the lists numbered run-wide in order of first use (window by
+ * window, within a window as ps_drain_shared numbers them); list l is
+ * msg[list_off[l] .. list_off[l + 1]), total = list_off[n_lists].  Window by
+ * window this is entry for entry ps_drain_shared's answer for that window,
+ * the list numbers shifted by the lists of the windows before, the ids dense.
+ * Query q's deliveries of the run are its lists concatenated in window
+ * order, which is arrival order.  Windows that run nothing do not count; a
+ * run without a window gives n_windows = 0.
+ *   Caps as ps_drain_shared_begin's, for the run: both zero selects the
+ * engine's own, summed over the run's windows (a run whose answer may pass
+ * 2^30 ids returns PS_E_RANGE from ps_run / ps_run_async, the messages left
+ * pending).  When the answer exceeds a cap no further id is emitted and
+ * ps_sink_take returns PS_E_RANGE; win_list, n_windows and n_lists are exact
+ * then, list_off and total are exact if n_lists <= list_cap.
+ *   ps_sink_take completes the oldest untaken run's result (one event wait)
+ * and lends it from pinned memory; PS_E_NOTREADY with none outstanding,
+ * PS_E_STATE when a window's device-side table check failed.  Two result
+ * slots alternate: a view stays valid until the second run enqueued after
+ * its own, the next ps_sink_set or ps_destroy; with both untaken, ps_run /
+ * ps_run_async return PS_E_STATE before touching the pending messages.  A
+ * run that fails gives up its slot; after a failed ps_wait that run's result
+ * is unspecified.  The slots are the sink's own: ps_drain_begin and
+ * ps_drain_shared_begin keep theirs. */
+int ps_sink_set(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, size_t list_cap, size_t id_cap);
+int ps_sink_take(ps_engine* e, const uint32_t** win_list_out, const uint64_t** list_off_out, const uint32_t** msg_out,
+                 uint32_t* n_windows_out, uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

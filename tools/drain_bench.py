@@ -41,6 +41,13 @@ begin call, ps_overlapped_windows() and the view's bytes; then, on a quiet
 engine with PSAMD_DRAIN_TIMING=1, the device time of its classify / list
 assignment / count / scan / emit passes for the counts of --pipelined-queries
 and --large-queries.  Writes DIR/drain_shared_async_bench.json.
+
+--sink: the sink (ps_sink_set / ps_sink_take) in the pipelined loop against
+the loop of --pipelined --shared, the two alternating in one process, --reps
+timings each: wall ms/step, the host time of ps_run_async (with the begin call
+in the other loop), ps_overlapped_windows(); one case with msg_window cut so
+that the largest topic takes three windows per step; the host time of the sink
+per run from PSAMD_DRAIN_TIMING's clock.  Writes DIR/sink_bench.json.
 """
 from __future__ import annotations
 
@@ -408,6 +415,138 @@ def pipelined_shared_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def loop_sink(eng, wl, n, run_s):
+    """publish; ps_run_async; ps_wait of the previous; ps_sink_take of the
+    previous (a sink is set).  Returns the last view (copies)."""
+    view = None
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        t0 = time.perf_counter()
+        eng.run_async()
+        run_s.append(time.perf_counter() - t0)
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            view = eng.sink_take(copy=False)
+    eng.wait()
+    view = eng.sink_take(copy=False)
+    return tuple(x.copy() for x in view)
+
+
+def loop_shared_async_timed(eng, wl, n, qt, qp, run_s):
+    """loop_shared_async with the host time of ps_run_async + ps_drain_shared_begin per step."""
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        t0 = time.perf_counter()
+        eng.run_async()
+        eng.drain_shared_begin(qt, qp)
+        run_s.append(time.perf_counter() - t0)
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            eng.drain_shared_end(copy=False)
+    eng.wait()
+    return eng.drain_shared_end()
+
+
+def sink_main(a, wl):
+    """--sink: the pipelined loop with a sink set (publish; ps_run_async;
+    ps_wait and ps_sink_take of the previous) against the loop of
+    --pipelined --shared (ps_drain_shared_begin / _end behind every run), both
+    in this process and alternating, --reps timings each; one multi-window
+    case (msg_window cut so that the largest topic takes three windows); the
+    host time of the sink per run from PSAMD_DRAIN_TIMING's host clock."""
+    counts = [int(x) for x in a.pipelined_queries.split(",")]
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "steps": a.steps,
+           "warmup": a.warmup, "reps": a.reps, "rows": []}
+    queries = {n: pick_queries(wl, n, a.seed) for n in counts}
+
+    def engine(env, msg_window=65536):
+        os.environ.update(env)
+        e = PE.Engine(wl.n_peers, len(wl.topics), seed=wl.seed, msg_window=msg_window)
+        WL.build_engine_topics(e, wl)
+        for k in env:
+            os.environ.pop(k, None)
+        return e
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        out = fn()
+        return 1e3 * (time.perf_counter() - t0) / a.steps, out
+
+    with engine({}) as plain:
+        loop_plain(plain, wl, a.warmup)
+        res["plain_ms_per_step"] = [timed(lambda: loop_plain(plain, wl, a.steps))[0] for _ in range(a.reps)]
+    for n in counts:
+        qt, qp = queries[n]
+        row = {"queries": n, "shared_begin_ms_per_step": [], "sink_ms_per_step": []}
+        with engine({}) as par, engine({}) as snk:
+            snk.sink_set(qt, qp)
+            loop_shared_async_timed(par, wl, a.warmup, qt, qp, [])
+            loop_sink(snk, wl, a.warmup, [])
+            o_par, o_snk = par.overlapped_windows(), snk.overlapped_windows()
+            host_par, host_snk = [], []
+            for _ in range(a.reps):
+                ms, want = timed(lambda: loop_shared_async_timed(par, wl, a.steps, qt, qp, host_par))
+                row["shared_begin_ms_per_step"].append(ms)
+                ms, got = timed(lambda: loop_sink(snk, wl, a.steps, host_snk))
+                row["sink_ms_per_step"].append(ms)
+                assert got[0].shape == (1, n) and np.array_equal(got[0][0], want[0]) and np.array_equal(got[1], want[1])
+                assert np.array_equal(norm(got[2]), norm(want[2]))
+            row["n_lists"] = int(want[1].size - 1)
+            row["ids"] = int(want[2].size)
+            row["shared_begin_overlapped_windows"] = par.overlapped_windows() - o_par
+            row["sink_overlapped_windows"] = snk.overlapped_windows() - o_snk
+            row["run_async_plus_begin_host_us_median"] = 1e6 * float(np.median(host_par))
+            row["run_async_with_sink_host_us_median"] = 1e6 * float(np.median(host_snk))
+        sp, ss = row["shared_begin_ms_per_step"], row["sink_ms_per_step"]
+        row["sink_median_over_shared_begin_median"] = float(np.median(ss) / np.median(sp))
+        row["sink_median_within_shared_begin_spread"] = bool(min(sp) <= np.median(ss) <= max(sp))
+        with engine({"PSAMD_DRAIN_TIMING": "1"}) as tim:
+            tim.sink_set(qt, qp)
+            with StderrCapture() as cap:
+                loop_sink(tim, wl, 8, [])
+                tim.publish(wl.msg_topics)
+                tim.run()
+                tim.drain_shared(qt, qp)
+            us = [float(x) for x in re.findall(r"psamd sink: .*host_us ([0-9.]+)", cap.text)]
+            row["sink_host_us_per_run_median"] = float(np.median(us[2:]))
+            row["view_bytes"] = int(re.findall(r"psamd sink: .*view_bytes (\d+)", cap.text)[-1])
+            m = re.findall(r"psamd drain_shared: .*copy_ms ([0-9.]+)", cap.text)
+            row["link_ms_of_the_ids"] = float(m[-1]) if m else None
+        print(f"sink loops, {n} pairs: done", file=sys.stderr, flush=True)
+        res["rows"].append(row)
+
+    # three windows per step: the largest topic's messages over three windows
+    most = int(np.bincount(wl.msg_topics).max())
+    cap3 = ((most + 2) // 3 + 63) // 64 * 64
+    qt, qp = queries[counts[-1]]
+    multi = {"queries": counts[-1], "msg_window": cap3, "largest_topic_msgs": most}
+    with engine({}, cap3) as plain, engine({}, cap3) as snk:
+        snk.sink_set(qt, qp)
+        loop_plain(plain, wl, a.warmup)
+        loop_sink(snk, wl, a.warmup, [])
+        o_plain, o_snk = plain.overlapped_windows(), snk.overlapped_windows()
+        multi["plain_ms_per_step"], multi["sink_ms_per_step"] = [], []
+        for _ in range(a.reps):
+            multi["plain_ms_per_step"].append(timed(lambda: loop_plain(plain, wl, a.steps))[0])
+            ms, got = timed(lambda: loop_sink(snk, wl, a.steps, []))
+            multi["sink_ms_per_step"].append(ms)
+        multi["windows_per_step"] = int(got[0].shape[0])
+        multi["n_lists"] = int(got[1].size - 1)
+        multi["ids"] = int(got[2].size)
+        multi["plain_overlapped_windows"] = plain.overlapped_windows() - o_plain
+        multi["sink_overlapped_windows"] = snk.overlapped_windows() - o_snk
+    res["three_windows"] = multi
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "sink_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 HBM_SPEC_BYTES_PER_S = 8e12
 
 
@@ -550,8 +689,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--shared", action="store_true", help="ps_drain_shared against ps_drain (see above)")
     ap.add_argument("--large-queries", type=int, default=262144)
+    ap.add_argument("--sink", action="store_true", help="the sink in the pipelined loop against ps_drain_shared_begin's")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.sink:
+        return sink_main(a, wl)
     if a.pipelined and a.shared:
         return pipelined_shared_main(a, wl)
     if a.pipelined:
