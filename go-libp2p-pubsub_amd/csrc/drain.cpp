@@ -6,40 +6,17 @@
 // What the paths rely on, between them and with run.cpp:
 //  - D.seq / D.p_*: one set of device tables per window, built by whichever
 //    path runs first (drain_tables on the host, drain_tables_async on the
-//    device) and reused by the others.  A device build given up half way sets
-//    D.seq to ~0 unless the tables were already this window's; a host build
-//    that fails leaves D.seq at its older value.
-//  - The device build stages its block in the slot's pinned h_in, the queries
-//    behind it.  A ps_drain_begin that fails after staging without taking the
-//    slot synchronises the stream first; a slot with no segment records
-//    ev_done only when it staged tables.
+//    device; the sink always builds its window's) and reused by the others.
 //  - D.d_err lives behind the mask words of the device build; it is created
 //    (8 bytes, cleared) on first use when only host builds have run.
 //    ps_drain_shared passes a zero word behind its header instead.
 //  - ps_drain's slabs: ev_copy[k & 1] is waited on before slab k is emitted,
 //    slab k - 1 is copied while slab k is emitted; under timing the copy runs
 //    in line on `stream`.
-//  - Slot::seen / emit_pending / ev_emit are read by drain_fence (run.cpp).
-//  - The two slots serve both asynchronous forms, oldest first; Slot::shared
-//    says which end call completes a slot, and the other one leaves it alone.
-//  - ps_drain_shared_begin stages its input (queries, initial verdicts, sorted
-//    queries, bins) behind the table block in the slot's h_in, as ps_drain_begin
-//    stages its queries, and follows the same rule when it fails after staging.
-//    Both forms of ps_drain_shared sort their queries with drain_shared_sort,
-//    which leaves D.verdict and D.cqueries; neither is a copy's source in the
-//    asynchronous form (the slot's pinned staging is).
-//  - ps_drain_shared_begin sizes every buffer and grid from its caps; the
-//    counts live in the slot's DrainCtl on the device and reach the host only
-//    in the view's header.  Its ev_emit stands behind classify, count and emit
-//    alike (all on `stream`), and is recorded even when no list has a segment.
-//  - The sink runs ps_drain_shared_begin's passes behind every window run.cpp
-//    remembers, on `stream`, with buffers of its own (Drain::Sink): it always
-//    builds that window's tables (D.seq), so a later drain of the last window
-//    reuses them.  Each window stages its input in a region of its result's
-//    pinned arena that no other window of the run uses.  The counts never
-//    reach the host between windows: k_sink_commit keeps them in two cursors
-//    that alternate by window.  Sink::fence names the last sink emit over each
-//    row set for drain_fence; a result's copy follows the last window's.
+//  - Slot::seen / emit_pending / ev_emit and Sink::fence (the last sink emit
+//    over each row set) are read by drain_fence (run.cpp).
+//  - ps_drain_shared_begin and the sink run one pass over their queries
+//    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -120,6 +97,19 @@ hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out) {
   return hipSuccess;
 }
 
+// Where one call stages its input: a slot's pinned h_in, all of it (one call
+// takes once), or a region of a sink result's arena
+struct Staging {
+  Drain::Slot* slot;
+  Drain::Sink::Res* arena;
+  hipError_t take(size_t bytes, uint8_t** out) const {
+    if (arena) return sink_stage(*arena, bytes, out);
+    const hipError_t rc = pinned_ensure(&slot->h_in, nullptr, &slot->in_cap, bytes);
+    *out = slot->h_in;
+    return rc;
+  }
+};
+
 // What every entry point needs after its own state checks: the node-space
 // mirrors (the peer maps read them), the drain's stream and events
 int drain_ready(ps_engine* e) {
@@ -161,7 +151,8 @@ DrainTopic drain_topic_header(const ps_engine* e, uint32_t t, std::vector<DrainG
 // ascends with the bit -- every tree layout (plan_window_layout sorts the bits
 // so) -- the id table is indexed by bit and a mask marks the message bits;
 // else (a mesh window with several start rounds) the ids are stored in
-// arrival order beside each one's bit.
+// arrival order beside each one's bit.  A build that fails leaves D.seq at
+// its older value.
 int drain_tables(ps_engine* e) {
   auto& D = e->drain;
   if (D.seq == e->window_seq) return PS_OK;
@@ -240,15 +231,20 @@ int drain_tables(ps_engine* e) {
 // the slot's pinned memory and k_drain_tables builds the id table and the
 // mask from them behind the window, with no host wait.  A mesh topic of a
 // run with several start rounds keeps the host's arrival-order table
-// (kDrainGather, as drain_tables above), staged the same way.  `used`: the
-// bytes of S.h_in taken; the caller stages `tail` bytes of its own behind them.
-// `arena` (the sink): the block goes to a region of that result's staging
-// instead, returned in *staged.
-int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used, Drain::Sink::Res* arena = nullptr,
-                       uint8_t** staged = nullptr) {
+// (kDrainGather, as drain_tables above), staged the same way.  *tail_out:
+// `tail` bytes of `st` for the caller's own input, behind the block (`used`
+// bytes of it) where one was built, all that is taken where the tables were
+// kept.  `timed` (PSAMD_DRAIN_TIMING): the build is waited for and reported.
+// A build given up half way is no table: D.seq names none until it is complete.
+int drain_tables_async(ps_engine* e, const Staging& st, size_t tail, bool timed, size_t* used, uint8_t** tail_out) {
   auto& D = e->drain;
+  const char* const what = st.arena ? "alloc sink staging" : "alloc drain staging";
   *used = 0;
-  if (D.seq == e->window_seq) return PS_OK;
+  if (D.seq == e->window_seq) {
+    HIP_TRY(st.take(tail, tail_out), what);
+    return PS_OK;
+  }
+  D.seq = ~0ull;
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
   D.topics.assign(nt, DrainTopic{});
   std::vector<DrainGroup> groups;
@@ -299,13 +295,8 @@ int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used, 
   const size_t o_gids = align256(o_order + n_gather * 4);
   const size_t block = align256(o_gids + n_gather * 4);
   uint8_t* h = nullptr;
-  if (arena) {
-    HIP_TRY(sink_stage(*arena, block + tail, &h), "alloc sink staging");
-    *staged = h;
-  } else {
-    HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, block + tail), "alloc drain staging");
-    h = S.h_in;
-  }
+  HIP_TRY(st.take(block + tail, &h), what);
+  *tail_out = h + block;
   HIP_TRY(D.d_ablock.ensure(block), "alloc drain tables");
   HIP_TRY(D.d_aids.ensure((n_pos + n_gather) * 4), "alloc drain ids");
   HIP_TRY(D.d_amask.ensure((n_pos >> 6) * 8 + 8), "alloc drain masks");
@@ -373,12 +364,12 @@ int drain_tables_async(ps_engine* e, Drain::Slot& S, size_t tail, size_t* used, 
   b.mask = D.d_amask.as<uint64_t>();
   b.keys = D.d_akeys.as<uint64_t>();
   b.err = D.d_err;
-  const PhaseTimer tm{D.ev_t, s, D.timing};  // (timing runs wait here: the build and its check, device time)
+  const PhaseTimer tm{D.ev_t, s, timed};  // (timing runs wait here: the build and its check, device time)
   float build_ms = 0;
   HIP_TRY(tm.begin(), "event");
   HIP_TRY(launch_drain_tables(b, s), "k_drain_tables");
   HIP_TRY(tm.end(build_ms), "event");
-  if (D.timing)
+  if (timed)
     std::fprintf(stderr, "psamd drain tables: topics %u messages %llu positions %llu gather %llu device_ms %.4f\n", nb,
                  static_cast<unsigned long long>(n_msgs), static_cast<unsigned long long>(n_pos),
                  static_cast<unsigned long long>(n_gather), build_ms);
@@ -556,6 +547,160 @@ int drain_err_word(ps_engine* e, hipStream_t s) {
   return PS_OK;
 }
 
+// ---- the shared-list pass: ps_drain_shared_begin's, and the sink's per window ----
+
+// Its input, one block and one upload: queries | initial verdicts | sorted queries | bins
+struct SharedLayout {
+  size_t n;
+  uint32_t nt;
+  size_t o_v, o_cq, o_bins, tail;
+  SharedLayout(size_t n_queries, uint32_t n_topics)
+      : n(n_queries),
+        nt(n_topics),
+        o_v(align256(n * sizeof(DrainQuery))),
+        o_cq(o_v + align256(n * 4)),
+        o_bins(o_cq + align256(n * sizeof(DrainClassQuery))),
+        tail(o_bins + align256(nt * sizeof(DrainClassBin))) {}
+};
+
+// The block filled at c (L.tail bytes): drain_shared_sort's queries, the
+// verdicts the passes start from (0 where the classify pass decides), the
+// sorted queries and the bins.  No std::vector is a copy's source afterwards.
+int shared_stage(ps_engine* e, const uint32_t* topic, const uint32_t* peer, const SharedLayout& L, uint8_t* c,
+                 SharedSort* R) {
+  auto& D = e->drain;
+  if (const int rc = drain_shared_sort(e, topic, peer, L.n, reinterpret_cast<DrainQuery*>(c), R)) return rc;
+  uint32_t* const hv = reinterpret_cast<uint32_t*>(c + L.o_v);
+  for (size_t q = 0; q < L.n; ++q) hv[q] = D.verdict[q] & ~kOnHost;
+  if (R->n_class) std::memcpy(c + L.o_cq, D.cqueries.data(), static_cast<size_t>(R->n_class) * sizeof(DrainClassQuery));
+  if (!R->bins.empty()) std::memcpy(c + L.o_bins, R->bins.data(), R->bins.size() * sizeof(DrainClassBin));
+  return PS_OK;
+}
+
+// One window's caps and segment bound.  `own`: the engine's caps (the size of
+// the answer while full rows share) replace the caller's.  False: more rows
+// than the kernels index (the numbering scan keeps the segments in the low
+// half of its key).
+bool shared_caps(const Drain& D, const SharedSort& R, size_t n, bool own, size_t* list_cap, size_t* id_cap,
+                 uint32_t* seg_bound) {
+  if (own) {
+    *list_cap = D.share ? R.bins.size() + R.n_gather : R.n_rows;
+    *id_cap = D.share ? R.bin_ids + R.gather_ids : R.row_ids;
+  }
+  const uint64_t bound = static_cast<uint64_t>(*list_cap) * R.max_segs;
+  *seg_bound = static_cast<uint32_t>(bound);
+  return bound < kDrainRowLimit && static_cast<uint64_t>(n) * R.max_segs < kDrainRowLimit;
+}
+
+// The pass on `stream`, nothing waited for (but a timed phase): the block at
+// h uploaded, k_drain_classify over its verdict words, the list assignment
+// into at most list_cap lists (list_of_query: n words), then count and scan
+// over the lists.  Every buffer and grid is sized by n and the caps -- the
+// counts stay in the control block on the device -- and B only grows.
+// ms: classify, assign, count; the scan's phase is left open, as
+// drain_count_scan leaves it.  *args: queries = the lists (the kernels read
+// their number from *ctl); B.scratch.d_off: seg_bound + 1 offsets.
+int shared_pass(ps_engine* e, Drain::ListBufs& B, const SharedLayout& L, const uint8_t* h, const SharedSort& R,
+                size_t list_cap, uint32_t seg_bound, uint32_t* list_of_query, const PhaseTimer& tm, float* ms,
+                DrainArgs* args, DrainCtl** ctl_out) {
+  auto& D = e->drain;
+  auto& C = B.scratch;
+  hipStream_t s = e->stream;
+  const size_t n = L.n, n_off = static_cast<size_t>(seg_bound) + 1;
+  const size_t o_first = align256(sizeof(DrainCtl));
+  HIP_TRY(B.d_in.ensure(L.tail), "alloc drain input");
+  HIP_TRY(B.d_key.ensure(2 * n * 8), "alloc drain keys");
+  HIP_TRY(B.d_aux.ensure(o_first + L.nt * 4), "alloc drain control");
+  HIP_TRY(C.d_queries.ensure(list_cap * sizeof(DrainQuery)), "alloc drain lists");
+  HIP_TRY(C.d_cnt.ensure(n_off * 8), "alloc drain counts");
+  HIP_TRY(C.d_off.ensure(n_off * 8), "alloc drain offsets");
+  uint64_t* const cnt = C.d_cnt.as<uint64_t>();
+  uint64_t* const off = C.d_off.as<uint64_t>();
+  uint64_t* const key = B.d_key.as<uint64_t>();
+  size_t scan_bytes = 0, scan_keys = 0;  // one temporary for both scans
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, cnt, off, seg_bound + 1, s), "size drain scan");
+  HIP_TRY(drain_scan(nullptr, &scan_keys, key, key + n, static_cast<uint32_t>(n), s), "size drain scan");
+  HIP_TRY(C.d_scan.ensure(std::max(scan_bytes, scan_keys)), "alloc drain scan");
+
+  uint8_t* const din = B.d_in.as<uint8_t>();
+  uint8_t* const aux = B.d_aux.as<uint8_t>();
+  DrainCtl* const ctl = reinterpret_cast<DrainCtl*>(aux);
+  HIP_TRY(hipMemcpyAsync(din, h, L.tail, hipMemcpyHostToDevice, s), "upload drain queries");
+  HIP_TRY(hipMemsetAsync(aux + o_first, 0xFF, L.nt * 4, s), "preset drain firsts");
+  if (const int rc = drain_err_word(e, s)) return rc;
+
+  DrainArgs a = drain_args(e);
+  uint32_t* const verdict = reinterpret_cast<uint32_t*>(din + L.o_v);
+  const DrainClassQuery* const sorted = reinterpret_cast<const DrainClassQuery*>(din + L.o_cq);
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_classify(a, reinterpret_cast<const DrainClassBin*>(din + L.o_bins), static_cast<uint32_t>(R.bins.size()),
+                                sorted, R.n_waves, verdict, s),
+          "k_drain_classify");
+  HIP_TRY(tm.end(ms[0]), "event");
+  DrainAssign g{};
+  g.topics = D.p_topics;
+  g.queries = reinterpret_cast<const DrainQuery*>(din);
+  g.verdict = verdict;
+  g.sorted = sorted;
+  g.n_sorted = R.n_class;
+  g.n = static_cast<uint32_t>(n);
+  g.share = D.share;
+  g.first = reinterpret_cast<uint32_t*>(aux + o_first);
+  g.key = key;
+  g.key_off = key + n;
+  g.scan_temp = C.d_scan.p;
+  g.scan_bytes = C.d_scan.bytes;
+  g.lists = C.d_queries.as<DrainQuery>();
+  g.list_cap = static_cast<uint32_t>(list_cap);
+  g.seg_bound = seg_bound;
+  g.list_of_query = list_of_query;
+  g.ctl = ctl;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_assign(g, s), "drain list assignment");
+  HIP_TRY(tm.end(ms[1]), "event");
+  a.queries = g.lists;
+  a.n_queries = 0;  // (the kernels read it from the control block)
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, cnt, s), "k_drain_count_dev");
+  HIP_TRY(tm.end(ms[2]), "event");
+  HIP_TRY(tm.begin(), "event");
+  scan_bytes = C.d_scan.bytes;
+  HIP_TRY(drain_scan(C.d_scan.p, &scan_bytes, cnt, off, seg_bound + 1, s), "drain scan");
+  *args = a;
+  *ctl_out = ctl;
+  return PS_OK;
+}
+
+// ---- what the two asynchronous forms share around their slots ------------------
+
+// A begin call fails between drain_tables_async and the taking of its slot:
+// a table block staged in the slot's memory (`staged`) must have left it
+// before the next begin writes there
+int drain_give_up(ps_engine* e, bool staged, int code, const char* what) {
+  if (staged) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
+  return e->fail(code, what);
+}
+
+// The slot is taken with a view the host wrote.  Nothing of it is on the GPU
+// but a table block it staged: the end call then waits for that upload.
+int drain_slot_host_view(ps_engine* e, Drain::Slot& S, bool staged) {
+  if (staged) {
+    HIP_TRY(hipEventRecord(S.ev_done, e->stream), "event");
+    S.enqueued = true;
+  }
+  ++e->drain.slot_count;
+  return PS_OK;
+}
+
+// What an end call returns for the error and overflow words of its view
+int drain_view_status(ps_engine* e, uint64_t err, uint32_t over) {
+  if (err)
+    return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
+                                                  : "drain tables: row bits do not ascend in arrival order");
+  if (over) return e->fail(PS_E_RANGE, over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
+  return PS_OK;
+}
+
 // An asynchronous drain's last steps, behind its last kernel on `stream`:
 // that kernel is the last reader of the window's rows (run.cpp: drain_fence);
 // the slot is taken; the view leaves on the copy stream, beside whatever
@@ -673,9 +818,11 @@ void psamd::sink_abort(ps_engine* e) {
   K.open = nullptr;
 }
 
-// ps_drain_shared_begin's work for the window just remembered, into the open
-// result: tables, classify, assign, count and scan as there, then k_sink_commit
-// and k_sink_emit at the run's cursor.  All on `stream`; nothing waits.
+// The window just remembered, drained into the open result: its tables (always
+// built here: a later drain of the last window reuses them), the shared-list
+// pass that ps_drain_shared_begin runs, then k_sink_commit and k_sink_emit at
+// the run's cursor -- the counts never reach the host between windows.  All
+// on `stream`; nothing waits.
 int psamd::sink_window(ps_engine* e) {
   auto& D = e->drain;
   auto& K = D.sink;
@@ -690,24 +837,12 @@ int psamd::sink_window(ps_engine* e) {
   hipStream_t s = e->stream;
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
 
-  // staged behind the tables, in this window's own region: queries | initial verdicts | sorted queries | bins
-  const size_t o_v = align256(n * sizeof(DrainQuery));
-  const size_t o_cq = o_v + align256(n * 4);
-  const size_t o_bins = o_cq + align256(n * sizeof(DrainClassQuery));
-  const size_t tail = o_bins + align256(nt * sizeof(DrainClassBin));
-  const uint64_t seq0 = D.seq;
+  // the tables and the window's input in a region of the arena that no other
+  // window of the run uses (a timed build waits for the stream: nothing of the sink may)
+  const SharedLayout L(n, nt);
   size_t used = 0;
   uint8_t* h = nullptr;
-  const bool timing = D.timing;  // (a timed build waits for the stream: nothing of the sink may)
-  D.timing = false;
-  rc = drain_tables_async(e, D.slot[0], tail, &used, &R, &h);
-  D.timing = timing;
-  if (rc) {
-    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
-    return rc;
-  }
-  if (!used) HIP_TRY(sink_stage(R, tail, &h), "alloc sink staging");
-  h += used;
+  if ((rc = drain_tables_async(e, Staging{nullptr, &R}, L.tail, false, &used, &h))) return rc;
 
   // the sorted queries: the last window's while the node space and every
   // topic's window shape are the same
@@ -719,33 +854,27 @@ int psamd::sink_window(ps_engine* e) {
   if (key != K.sort_key) {
     K.sort_key.clear();
     K.sort_r = SharedSort{};
-    K.sort_tail.assign(tail, 0);
-    uint8_t* const c = K.sort_tail.data();
-    if (drain_shared_sort(e, K.topic.data(), K.peer.data(), n, reinterpret_cast<DrainQuery*>(c), &K.sort_r))
+    K.sort_tail.assign(L.tail, 0);
+    if (shared_stage(e, K.topic.data(), K.peer.data(), L, K.sort_tail.data(), &K.sort_r))
       return e->fail(PS_E_RANGE, "too many rows in one sink window");
-    uint32_t* const hv = reinterpret_cast<uint32_t*>(c + o_v);
-    for (size_t q = 0; q < n; ++q) hv[q] = D.verdict[q] & ~kOnHost;
-    if (K.sort_r.n_class)
-      std::memcpy(c + o_cq, D.cqueries.data(), static_cast<size_t>(K.sort_r.n_class) * sizeof(DrainClassQuery));
-    if (!K.sort_r.bins.empty()) std::memcpy(c + o_bins, K.sort_r.bins.data(), K.sort_r.bins.size() * sizeof(DrainClassBin));
     K.sort_key = key;
   }
   const SharedSort& S = K.sort_r;
-  std::memcpy(h, K.sort_tail.data(), tail);
+  std::memcpy(h, K.sort_tail.data(), L.tail);
 
-  // this window's caps, and the run's as far as this window
-  size_t win_lists = std::min<size_t>(K.list_cap, S.n_rows);
-  if (K.list_cap == 0 && K.id_cap == 0) {
-    win_lists = D.share ? S.bins.size() + S.n_gather : S.n_rows;
+  // this window's caps (the caller's: the run's, for min(list_cap, rows)
+  // lists a window), and the run's as far as this window
+  const bool own = K.list_cap == 0 && K.id_cap == 0;
+  size_t win_lists = std::min<size_t>(K.list_cap, S.n_rows), win_ids = 0;
+  uint32_t seg_bound = 0;
+  const bool rows_fit = shared_caps(D, S, n, own, &win_lists, &win_ids, &seg_bound);
+  if (own) {
     R.list_cap += win_lists;
-    R.id_cap += D.share ? S.bin_ids + S.gather_ids : S.row_ids;
+    R.id_cap += win_ids;
   }
   if (R.id_cap > kDrainAsyncMaxIds) return e->fail(PS_E_RANGE, "the sink's result may exceed 2^30 ids");
-  const uint64_t seg_bound64 = static_cast<uint64_t>(win_lists) * S.max_segs;
-  if (seg_bound64 >= kDrainRowLimit || static_cast<uint64_t>(n) * S.max_segs >= kDrainRowLimit ||
-      R.list_cap >= 0x7FFFFFFFull || (static_cast<uint64_t>(w) + 1) * n >= (1ull << 32))
+  if (!rows_fit || R.list_cap >= 0x7FFFFFFFull || (static_cast<uint64_t>(w) + 1) * n >= (1ull << 32))
     return e->fail(PS_E_RANGE, "too many rows in one sink window");
-  const uint32_t seg_bound = static_cast<uint32_t>(seg_bound64);
 
   // the result on the device: it grows with the windows, contents kept
   if ((rc = sink_grow(e, R.d_wl, (static_cast<size_t>(w) + 1) * n * 4, s)) ||
@@ -754,30 +883,30 @@ int psamd::sink_window(ps_engine* e) {
   SinkCursor* const cur = R.d_off.as<SinkCursor>();
   if (w == 0) HIP_TRY(hipMemsetAsync(cur, 0, kSinkHdrBytes, s), "clear sink cursor");
 
-  // the passes' buffers, sized by n and the window's caps; they only grow
-  auto& B = K.scratch;
-  const size_t o_first = align256(sizeof(DrainCtl));
-  HIP_TRY(K.d_in.ensure(tail), "alloc drain input");
-  HIP_TRY(K.d_key.ensure(2 * n * 8), "alloc drain keys");
-  HIP_TRY(K.d_aux.ensure(o_first + nt * 4), "alloc drain control");
+  // The window's lists, counted and scanned.  No row to read: a row of PS_NONE,
+  // no list, and the cursor moves on by one window.
+  auto& B = K.lb;
   HIP_TRY(K.d_lq.ensure(n * 4), "alloc sink lists");
-  HIP_TRY(B.d_queries.ensure(win_lists * sizeof(DrainQuery)), "alloc drain lists");
-  HIP_TRY(B.d_cnt.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain counts");
-  HIP_TRY(B.d_off.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain offsets");
-  size_t scan_bytes = 0, scan_keys = 0;
-  HIP_TRY(drain_scan(nullptr, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s),
-          "size drain scan");
-  HIP_TRY(drain_scan(nullptr, &scan_keys, K.d_key.as<uint64_t>(), K.d_key.as<uint64_t>() + n, static_cast<uint32_t>(n), s),
-          "size drain scan");
-  HIP_TRY(B.d_scan.ensure(std::max(scan_bytes, scan_keys)), "alloc drain scan");
-  uint8_t* const aux = K.d_aux.as<uint8_t>();
-  DrainCtl* const ctl = reinterpret_cast<DrainCtl*>(aux);
-  if ((rc = drain_err_word(e, s))) return rc;
-
+  DrainArgs a{};
+  DrainCtl* ctl = nullptr;
+  if (S.n_rows == 0) {
+    HIP_TRY(B.d_aux.ensure(sizeof(DrainCtl)), "alloc drain control");
+    HIP_TRY(B.scratch.d_off.ensure(8), "alloc drain offsets");
+    ctl = B.d_aux.as<DrainCtl>();
+    if ((rc = drain_err_word(e, s))) return rc;
+    if (n) HIP_TRY(hipMemsetAsync(K.d_lq.p, 0xFF, n * 4, s), "clear sink lists");
+    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(DrainCtl), s), "clear drain control");
+    HIP_TRY(hipMemsetAsync(B.scratch.d_off.p, 0, 8, s), "clear drain offsets");
+  } else {
+    const PhaseTimer untimed{D.ev_t, s, false};
+    float none[3] = {0, 0, 0};
+    if ((rc = shared_pass(e, B, L, h, S, win_lists, seg_bound, K.d_lq.as<uint32_t>(), untimed, none, &a, &ctl))) return rc;
+  }
+  const uint64_t* const seg_off = B.scratch.d_off.as<uint64_t>();
   SinkCommit c{};
-  c.lists = B.d_queries.as<DrainQuery>();
+  c.lists = a.queries;  // (not read where the window has no list)
   c.ctl = ctl;
-  c.seg_off = B.d_off.as<uint64_t>();
+  c.seg_off = seg_off;
   c.win_lq = K.d_lq.as<uint32_t>();
   c.err = D.d_err;
   c.cur = cur;
@@ -785,52 +914,12 @@ int psamd::sink_window(ps_engine* e) {
   c.win_list = R.d_wl.as<uint32_t>();
   c.w = w;
   c.n = static_cast<uint32_t>(n);
-  c.win_list_cap = static_cast<uint32_t>(win_lists);
+  c.win_list_cap = S.n_rows ? static_cast<uint32_t>(win_lists) : 0;
   c.list_cap = static_cast<uint32_t>(R.list_cap);
   c.id_cap = R.id_cap;
-  if (S.n_rows == 0) {  // no row to read: a row of PS_NONE, and the cursor moves on by one window
-    if (n) HIP_TRY(hipMemsetAsync(K.d_lq.p, 0xFF, n * 4, s), "clear sink lists");
-    HIP_TRY(hipMemsetAsync(ctl, 0, sizeof(DrainCtl), s), "clear drain control");
-    HIP_TRY(hipMemsetAsync(B.d_off.p, 0, 8, s), "clear drain offsets");
-    c.win_list_cap = 0;
-    HIP_TRY(launch_sink_commit(c, s), "k_sink_commit");
-  } else {
-    uint8_t* const din = K.d_in.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(din, h, tail, hipMemcpyHostToDevice, s), "upload drain queries");
-    HIP_TRY(hipMemsetAsync(aux + o_first, 0xFF, nt * 4, s), "preset drain firsts");
-    DrainArgs a = drain_args(e);
-    uint32_t* const verdict = reinterpret_cast<uint32_t*>(din + o_v);
-    HIP_TRY(launch_drain_classify(a, reinterpret_cast<const DrainClassBin*>(din + o_bins), static_cast<uint32_t>(S.bins.size()),
-                                  reinterpret_cast<const DrainClassQuery*>(din + o_cq), S.n_waves, verdict, s),
-            "k_drain_classify");
-    DrainAssign g{};
-    g.topics = D.p_topics;
-    g.queries = reinterpret_cast<const DrainQuery*>(din);
-    g.verdict = verdict;
-    g.sorted = reinterpret_cast<const DrainClassQuery*>(din + o_cq);
-    g.n_sorted = S.n_class;
-    g.n = static_cast<uint32_t>(n);
-    g.share = D.share;
-    g.first = reinterpret_cast<uint32_t*>(aux + o_first);
-    g.key = K.d_key.as<uint64_t>();
-    g.key_off = g.key + n;
-    g.scan_temp = B.d_scan.p;
-    g.scan_bytes = B.d_scan.bytes;
-    g.lists = B.d_queries.as<DrainQuery>();
-    g.list_cap = static_cast<uint32_t>(win_lists);
-    g.seg_bound = seg_bound;
-    g.list_of_query = K.d_lq.as<uint32_t>();
-    g.ctl = ctl;
-    HIP_TRY(launch_drain_assign(g, s), "drain list assignment");
-    a.queries = g.lists;
-    a.n_queries = 0;  // (the kernels read it from the control block)
-    HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, B.d_cnt.as<uint64_t>(), s), "k_drain_count_dev");
-    scan_bytes = B.d_scan.bytes;
-    HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s), "drain scan");
-    HIP_TRY(launch_sink_commit(c, s), "k_sink_commit");
-    HIP_TRY(launch_sink_emit(a, ctl, cur, w, seg_bound, B.d_off.as<uint64_t>(), R.d_ids.as<uint32_t>(), R.id_cap, s),
-            "k_sink_emit");
-  }
+  HIP_TRY(launch_sink_commit(c, s), "k_sink_commit");
+  if (S.n_rows)
+    HIP_TRY(launch_sink_emit(a, ctl, cur, w, seg_bound, seg_off, R.d_ids.as<uint32_t>(), R.id_cap, s), "k_sink_emit");
 
   // the last reader of this window's rows on `stream` (run.cpp: drain_fence):
   // the entry of this row set, else one whose row set is gone
@@ -1168,28 +1257,19 @@ int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, si
   if ((rc = drain_next_slot(e, &slot))) return rc;
   auto& S = *slot;
   hipStream_t s = e->stream;
-  const uint64_t seq0 = D.seq;
   S.n = n;
   S.shared = false;
   size_t used = 0;
-  const size_t tail = align256(n * sizeof(DrainQuery));
-  if ((rc = drain_tables_async(e, S, tail, &used))) {
-    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
-    return rc;
-  }
-  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + tail), "alloc drain staging");
+  uint8_t* h = nullptr;
+  if ((rc = drain_tables_async(e, Staging{&S, nullptr}, align256(n * sizeof(DrainQuery)), D.timing, &used, &h))) return rc;
 
   // the queries, resolved straight into the slot's staging behind the tables
-  DrainQuery* hq = reinterpret_cast<DrainQuery*>(S.h_in + used);
+  DrainQuery* hq = reinterpret_cast<DrainQuery*>(h);
   uint64_t bound = 0;
   const uint64_t n_segs64 = drain_resolve(e, topic, peer, n, hq, &bound);
-  if (n_segs64 >= kDrainRowLimit || bound > kDrainAsyncMaxIds) {
-    // no slot is taken: the table block staged in this slot's memory must
-    // have left it before the next ps_drain_begin writes there
-    if (used) HIP_TRY(hipStreamSynchronize(s), "sync");
-    return e->fail(PS_E_RANGE, n_segs64 >= kDrainRowLimit ? "too many rows in one drain"
-                                                          : "drain may exceed 2^30 ids: use ps_drain");
-  }
+  if (n_segs64 >= kDrainRowLimit || bound > kDrainAsyncMaxIds)
+    return drain_give_up(e, used, PS_E_RANGE, n_segs64 >= kDrainRowLimit ? "too many rows in one drain"
+                                                                         : "drain may exceed 2^30 ids: use ps_drain");
   const uint32_t n_segs = static_cast<uint32_t>(n_segs64);
   S.hdr_bytes = align256((n + 2) * 8);
   S.bound = bound;
@@ -1198,21 +1278,16 @@ int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, si
   S.enqueued = false;
   if (n_segs == 0) {  // nothing to read: the view is n + 1 zeros
     std::memset(S.h_res, 0, (n + 2) * 8);
-    if (used) {  // (the table block staged in this slot: ps_drain_end waits for its upload)
-      HIP_TRY(hipEventRecord(S.ev_done, s), "event");
-      S.enqueued = true;
-    }
-    ++D.slot_count;
-    return PS_OK;
+    return drain_slot_host_view(e, S, used);
   }
   if (!D.mapped_out) HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
   DrainArgs a = drain_args(e);
   const PhaseTimer untimed{D.ev_t, s, false};  // (nothing here may wait for the stream)
   float none = 0;
-  if ((rc = drain_count_scan(e, a, n_segs, S.scratch, hq, n, s, untimed, none))) return rc;
+  if ((rc = drain_count_scan(e, a, n_segs, S.lb.scratch, hq, n, s, untimed, none))) return rc;
   uint8_t* res = D.mapped_out ? S.h_res_dev : S.d_res.as<uint8_t>();
   if ((rc = drain_err_word(e, s))) return rc;
-  const uint64_t* seg_off = S.scratch.d_off.as<uint64_t>();
+  const uint64_t* seg_off = S.lb.scratch.d_off.as<uint64_t>();
   HIP_TRY(launch_drain_offsets(a.queries, a.n_queries, seg_off, n_segs, D.d_err, reinterpret_cast<uint64_t*>(res), s),
           "k_drain_offsets");
   HIP_TRY(launch_drain_emit(a, 0, n_segs, seg_off, 0, reinterpret_cast<uint32_t*>(res + S.hdr_bytes), bound, true, s),
@@ -1236,9 +1311,7 @@ int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_ou
   *off_out = hdr;
   *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.hdr_bytes);
   *total_out = hdr[S.n];
-  if (const uint64_t err = hdr[S.n + 1])
-    return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
-                                                  : "drain tables: row bits do not ascend in arrival order");
+  if (const int rc = drain_view_status(e, hdr[S.n + 1], 0)) return rc;
   if (hdr[S.n] > S.bound) return e->fail(PS_E_STATE, "drain total above its bound");
   return PS_OK;
 }
@@ -1271,41 +1344,20 @@ int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* p
   hipStream_t s = e->stream;
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
 
-  // staged behind the tables: queries | initial verdicts | sorted queries | bins
-  const size_t o_v = align256(n * sizeof(DrainQuery));
-  const size_t o_cq = o_v + align256(n * 4);
-  const size_t o_bins = o_cq + align256(n * sizeof(DrainClassQuery));
-  const size_t tail = o_bins + align256(nt * sizeof(DrainClassBin));
-  const uint64_t seq0 = D.seq;
+  // staged in the slot's pinned input, behind the table block where one is
+  // built.  From here to the slot's taking a failure gives the slot up.
+  const SharedLayout L(n, nt);
   size_t used = 0;
-  if ((rc = drain_tables_async(e, S, tail, &used))) {
-    D.seq = seq0 == e->window_seq ? seq0 : ~0ull;  // (a build given up half way is no table)
-    return rc;
-  }
-  // From here to the slot's taking, a failure leaves no slot taken: the table
-  // block staged in this slot's memory must have left it before the next
-  // begin writes there
-  auto give_up = [&](int code, const char* what) -> int {
-    if (used) HIP_TRY(hipStreamSynchronize(s), "sync");
-    return e->fail(code, what);
-  };
-  HIP_TRY(pinned_ensure(&S.h_in, nullptr, &S.in_cap, used + tail), "alloc drain staging");
-  uint8_t* const h = S.h_in + used;
-  DrainQuery* const hq = reinterpret_cast<DrainQuery*>(h);
+  uint8_t* h = nullptr;
+  if ((rc = drain_tables_async(e, Staging{&S, nullptr}, L.tail, D.timing, &used, &h))) return rc;
   SharedSort R;
-  if (drain_shared_sort(e, topic, peer, n, hq, &R)) return give_up(PS_E_RANGE, "too many rows in one drain");
+  if (shared_stage(e, topic, peer, L, h, &R)) return drain_give_up(e, used, PS_E_RANGE, "too many rows in one drain");
 
-  // the caps: the engine's (the size of the answer while full rows share) or the caller's
-  if (list_cap == 0 && id_cap == 0) {
-    list_cap = D.share ? R.bins.size() + R.n_gather : R.n_rows;
-    id_cap = D.share ? R.bin_ids + R.gather_ids : R.row_ids;
-  }
-  if (id_cap > kDrainAsyncMaxIds) return give_up(PS_E_RANGE, "drain may exceed 2^30 ids: use ps_drain_shared");
-  const uint64_t seg_bound64 = static_cast<uint64_t>(list_cap) * R.max_segs;
-  // (the numbering scan keeps the segments in the low half of its key)
-  if (seg_bound64 >= kDrainRowLimit || static_cast<uint64_t>(n) * R.max_segs >= kDrainRowLimit)
-    return give_up(PS_E_RANGE, "too many rows in one drain");
-  const uint32_t seg_bound = static_cast<uint32_t>(seg_bound64);
+  // the caps: the engine's or the caller's
+  uint32_t seg_bound = 0;
+  const bool rows_fit = shared_caps(D, R, n, list_cap == 0 && id_cap == 0, &list_cap, &id_cap, &seg_bound);
+  if (id_cap > kDrainAsyncMaxIds) return drain_give_up(e, used, PS_E_RANGE, "drain may exceed 2^30 ids: use ps_drain_shared");
+  if (!rows_fit) return drain_give_up(e, used, PS_E_RANGE, "too many rows in one drain");
 
   S.n = n;
   S.shared = true;
@@ -1320,90 +1372,25 @@ int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* p
   if (R.n_rows == 0) {  // no row to read: no list, written here
     std::memset(S.h_res, 0, S.o_off + 8);
     std::memset(S.h_res + S.o_lq, 0xFF, n * 4);
-    if (used) {  // (the table block staged in this slot: the end waits for its upload)
-      HIP_TRY(hipEventRecord(S.ev_done, s), "event");
-      S.enqueued = true;
-    }
-    ++D.slot_count;
-    return PS_OK;
+    return drain_slot_host_view(e, S, used);
   }
-
-  // device buffers, sized by n and the caps; they only grow
-  auto& B = S.scratch;
-  const size_t o_first = align256(sizeof(DrainCtl));
-  HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
-  HIP_TRY(S.d_in.ensure(tail), "alloc drain input");
-  HIP_TRY(S.d_key.ensure(2 * n * 8), "alloc drain keys");
-  HIP_TRY(S.d_aux.ensure(o_first + nt * 4), "alloc drain control");
-  HIP_TRY(B.d_queries.ensure(list_cap * sizeof(DrainQuery)), "alloc drain lists");
-  HIP_TRY(B.d_cnt.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain counts");
-  HIP_TRY(B.d_off.ensure((static_cast<size_t>(seg_bound) + 1) * 8), "alloc drain offsets");
-  size_t scan_bytes = 0, scan_keys = 0;  // one temporary for both scans
-  HIP_TRY(drain_scan(nullptr, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s),
-          "size drain scan");
-  HIP_TRY(drain_scan(nullptr, &scan_keys, S.d_key.as<uint64_t>(), S.d_key.as<uint64_t>() + n, static_cast<uint32_t>(n), s),
-          "size drain scan");
-  HIP_TRY(B.d_scan.ensure(std::max(scan_bytes, scan_keys)), "alloc drain scan");
-
-  // the input: the initial verdicts (0 where the classify pass decides), the
-  // sorted queries and the bins beside the queries, in one upload
-  uint32_t* const hv = reinterpret_cast<uint32_t*>(h + o_v);
-  for (size_t q = 0; q < n; ++q) hv[q] = D.verdict[q] & ~kOnHost;
-  if (R.n_class) std::memcpy(h + o_cq, D.cqueries.data(), static_cast<size_t>(R.n_class) * sizeof(DrainClassQuery));
-  if (!R.bins.empty()) std::memcpy(h + o_bins, R.bins.data(), R.bins.size() * sizeof(DrainClassBin));
-  uint8_t* const din = S.d_in.as<uint8_t>();
-  HIP_TRY(hipMemcpyAsync(din, h, tail, hipMemcpyHostToDevice, s), "upload drain queries");
-  uint8_t* const aux = S.d_aux.as<uint8_t>();
-  DrainCtl* const ctl = reinterpret_cast<DrainCtl*>(aux);
-  HIP_TRY(hipMemsetAsync(aux + o_first, 0xFF, nt * 4, s), "preset drain firsts");
-  if ((rc = drain_err_word(e, s))) return rc;
 
   // (PSAMD_DRAIN_TIMING: the phases run apart and are waited for; else nothing here waits)
   float ms[5] = {0, 0, 0, 0, 0};  // classify, assign, count, scan + offsets, emit
   const PhaseTimer tm{D.ev_t, s, D.timing};
-  DrainArgs a = drain_args(e);
-  uint32_t* const verdict = reinterpret_cast<uint32_t*>(din + o_v);
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_drain_classify(a, reinterpret_cast<const DrainClassBin*>(din + o_bins), static_cast<uint32_t>(R.bins.size()),
-                                reinterpret_cast<const DrainClassQuery*>(din + o_cq), R.n_waves, verdict, s),
-          "k_drain_classify");
-  HIP_TRY(tm.end(ms[0]), "event");
+  HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
   uint8_t* const res = S.d_res.as<uint8_t>();
-  DrainAssign g{};
-  g.topics = D.p_topics;
-  g.queries = reinterpret_cast<const DrainQuery*>(din);
-  g.verdict = verdict;
-  g.sorted = reinterpret_cast<const DrainClassQuery*>(din + o_cq);
-  g.n_sorted = R.n_class;
-  g.n = static_cast<uint32_t>(n);
-  g.share = D.share;
-  g.first = reinterpret_cast<uint32_t*>(aux + o_first);
-  g.key = S.d_key.as<uint64_t>();
-  g.key_off = g.key + n;
-  g.scan_temp = B.d_scan.p;
-  g.scan_bytes = B.d_scan.bytes;
-  g.lists = B.d_queries.as<DrainQuery>();
-  g.list_cap = static_cast<uint32_t>(list_cap);
-  g.seg_bound = seg_bound;
-  g.list_of_query = reinterpret_cast<uint32_t*>(res + S.o_lq);
-  g.ctl = ctl;
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_drain_assign(g, s), "drain list assignment");
-  HIP_TRY(tm.end(ms[1]), "event");
-  a.queries = g.lists;
-  a.n_queries = 0;  // (the kernels read it from the control block)
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, B.d_cnt.as<uint64_t>(), s), "k_drain_count_dev");
-  HIP_TRY(tm.end(ms[2]), "event");
-  HIP_TRY(tm.begin(), "event");
-  scan_bytes = B.d_scan.bytes;
-  HIP_TRY(drain_scan(B.d_scan.p, &scan_bytes, B.d_cnt.as<uint64_t>(), B.d_off.as<uint64_t>(), seg_bound + 1, s), "drain scan");
-  HIP_TRY(launch_drain_offsets_dev(g.lists, ctl, g.list_cap, B.d_off.as<uint64_t>(), id_cap, D.d_err,
+  DrainArgs a{};
+  DrainCtl* ctl = nullptr;
+  if ((rc = shared_pass(e, S.lb, L, h, R, list_cap, seg_bound, reinterpret_cast<uint32_t*>(res + S.o_lq), tm, ms, &a, &ctl)))
+    return rc;
+  const uint64_t* const seg_off = S.lb.scratch.d_off.as<uint64_t>();
+  HIP_TRY(launch_drain_offsets_dev(a.queries, ctl, static_cast<uint32_t>(list_cap), seg_off, id_cap, D.d_err,
                                    reinterpret_cast<DrainSharedHdr*>(res), reinterpret_cast<uint64_t*>(res + S.o_off), s),
           "k_drain_offsets_dev");
   HIP_TRY(tm.end(ms[3]), "event");
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_drain_emit_dev(a, ctl, seg_bound, B.d_off.as<uint64_t>(), reinterpret_cast<uint32_t*>(res + S.o_ids), id_cap, s),
+  HIP_TRY(launch_drain_emit_dev(a, ctl, seg_bound, seg_off, reinterpret_cast<uint32_t*>(res + S.o_ids), id_cap, s),
           "k_drain_emit_dev");
   HIP_TRY(tm.end(ms[4]), "event");
   // classify reads every queried row, count and emit the private ones: the
@@ -1432,12 +1419,7 @@ int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t*
   *msg_out = reinterpret_cast<const uint32_t*>(S.h_res + S.o_ids);
   *n_lists_out = hdr->n_lists;
   *total_out = hdr->total;
-  if (hdr->err)
-    return e->fail(PS_E_STATE, hdr->err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
-                                                       : "drain tables: row bits do not ascend in arrival order");
-  if (hdr->over)
-    return e->fail(PS_E_RANGE, hdr->over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
-  return PS_OK;
+  return drain_view_status(e, hdr->err, hdr->over);
 }
 
 // ---- ps_sink_set / ps_sink_take ----------------------------
@@ -1489,12 +1471,7 @@ int ps_sink_take(ps_engine* e, const uint32_t** win_list_out, const uint64_t** l
   *n_lists_out = hdr->lists;
   *total_out = hdr->ids;
   if (hdr->windows != R.windows) return e->fail(PS_E_STATE, "sink: the result's window count is not the run's");
-  if (hdr->err)
-    return e->fail(PS_E_STATE, hdr->err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
-                                                       : "drain tables: row bits do not ascend in arrival order");
-  if (hdr->over)
-    return e->fail(PS_E_RANGE, hdr->over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
-  return PS_OK;
+  return drain_view_status(e, hdr->err, hdr->over);
 }
 
 }  // extern "C"

@@ -484,6 +484,14 @@ struct ps_engine {
     struct Scratch {
       psamd::DevBuf d_queries, d_cnt, d_off, d_scan;
     };
+    // the shared-list pass's device buffers (drain.cpp: shared_pass; DESIGN.md
+    // §5.5d): the lists and their counts, the input block (queries, verdicts,
+    // sorted queries, bins), the numbering scan's keys and their sums, the
+    // control block with the topics' first full queries behind it
+    struct ListBufs {
+      Scratch scratch;
+      psamd::DevBuf d_in, d_key, d_aux;
+    };
     uint64_t seq = ~0ull;  // window_seq the tables on the device were built for
     std::vector<psamd::DrainTopic> topics;
     psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order, d_slab[2];
@@ -526,18 +534,15 @@ struct ps_engine {
       uint8_t* h_res = nullptr;
       uint8_t* h_res_dev = nullptr;  // h_res, device-mapped
       size_t res_cap = 0;
-      Scratch scratch;
+      ListBufs lb;  // (ps_drain_begin uses its scratch alone)
       psamd::DevBuf d_res;
       hipEvent_t ev_emit = nullptr, ev_done = nullptr;
       size_t n = 0, hdr_bytes = 0;
       uint64_t bound = 0;
       // ps_drain_shared_begin takes the same slots.  Its
-      // input on the device (queries, verdicts, sorted queries, bins), the
-      // numbering scan's keys and their sums, the control block with the
-      // topics' first full queries behind it; its view: a DrainSharedHdr, then
-      // list_off[list_cap + 1], list_of_query[n] and ids[id_cap] at o_*
+      // view: a DrainSharedHdr, then list_off[list_cap + 1], list_of_query[n]
+      // and ids[id_cap] at o_*
       bool shared = false;
-      psamd::DevBuf d_in, d_key, d_aux;
       size_t list_cap = 0, id_cap = 0;
       size_t o_off = 0, o_lq = 0, o_ids = 0;
     } slot[2];
@@ -599,9 +604,9 @@ struct ps_engine {
       } fence[2];
       hipEvent_t last_ev = nullptr;  // the fence event behind the open run's last window
       double host_ms = 0;            // PSAMD_DRAIN_TIMING: the open run's host time in the sink
-      // per-window passes (see Slot)
-      Scratch scratch;
-      psamd::DevBuf d_in, d_key, d_aux, d_lq;
+      // per-window passes: the window's list_of_query beside their buffers
+      ListBufs lb;
+      psamd::DevBuf d_lq;
       // the sorted queries of the last window, kept while the node space and
       // the topics' window shapes stay
       std::vector<uint64_t> sort_key;

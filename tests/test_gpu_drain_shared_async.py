@@ -310,6 +310,31 @@ def test_caps_one_short_through_the_seam(monkeypatch):
         assert expand(*want) == drain_lists(eng, qt, qp)
 
 
+def test_refused_after_staging_takes_no_slot():
+    """An id_cap above 2^30 is refused after the window's table block was
+    staged in the slot: the call gives the slot up.  The next begin finds the
+    tables kept and writes its input where that block lay; both slots are
+    still free, and both views are the synchronous call's."""
+    rng = np.random.default_rng(17)
+    n, root, n_msgs = 40, 2, 50
+    parent = random_tree(rng, n, root)
+    with PE.Engine(n, 1) as eng:
+        eng.set_tree(0, root, parent)
+        first = eng.publish(np.zeros(n_msgs))
+        eng.run()  # (no drain yet: the window's tables are not built)
+        qp = np.arange(n)
+        qt = np.zeros(n, dtype=np.uint32)
+        assert raw_begin(eng, qt, qp, 1, (1 << 30) + 1) == E_RANGE
+        eng.drain_shared_begin(qt, qp)
+        eng.drain_shared_begin(qt, qp)
+        assert raw_begin(eng, qt, qp) == E_STATE  # both slots taken: the refused call took none
+        got = [eng.drain_shared_end(), eng.drain_shared_end()]
+        want = shared(eng, qt, qp)
+        assert want[1].tolist() == [0, n_msgs] and want[2].tolist() == list(range(first, first + n_msgs))
+        for g in got:
+            same(g, want)
+
+
 # ---- 6. pipelined ------------------------------------------------------------------------
 
 def pipelined(e, batches, qt, qp):
