@@ -711,14 +711,24 @@ int ps_seen_digest(ps_engine* e, uint64_t* digest_out) {
   if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
   if (const int rj = twin_join(e)) return rj;
   HIP_TRY(hipMemsetAsync(e->d_digest.p, 0, 8, e->stream), "clear digest");
+  // (PSAMD_DRAIN_TIMING, once a drain has made the events: k_digest's device
+  // time, the yardstick of the audience classify pass -- DESIGN.md §5.5f)
+  const bool timed = e->drain.timing && e->drain.ev_t[0];
+  if (timed) HIP_TRY(hipEventRecord(e->drain.ev_t[0], e->stream), "event");
   HIP_TRY(launch_digest(e->d_seen.as<uint64_t>(), e->d_gen.as<uint8_t>(), e->gen_cur, e->d_node_peer.as<uint32_t>(),
                         e->d_node_topic.as<uint16_t>(),
                         (e->last_slot ? e->d_topics1 : e->d_topics).as<TopicDev>(),
                         (e->last_slot ? e->d_groups1 : e->d_groups).as<GroupDev>(),
                         e->n_nodes, e->d_digest.as<uint64_t>(), e->stream),
           "digest");
+  if (timed) HIP_TRY(hipEventRecord(e->drain.ev_t[1], e->stream), "event");
   HIP_TRY(hipMemcpyAsync(digest_out, e->d_digest.p, 8, hipMemcpyDeviceToHost, e->stream), "read digest");
   HIP_TRY(hipStreamSynchronize(e->stream), "sync");
+  if (timed) {
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, e->drain.ev_t[0], e->drain.ev_t[1]), "event");
+    std::fprintf(stderr, "psamd digest: device_ms %.4f\n", ms);
+  }
   return PS_OK;
 }
 

@@ -19,6 +19,10 @@
 //   k_sink_commit         a window's list offsets and list numbers at the
 //                         run's cursor, and the cursor moved on
 //   k_sink_emit           k_drain_emit_dev at the cursor's id count
+// and, for ps_drain_topics (§5.5f), a topic's whole audience with no query list:
+//   k_audience_classify   one streaming pass over a topic's rows: a verdict
+//                         byte per node, the full and other nodes per strip
+//   k_audience_emit       the nodes that are not full, in node order
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -227,6 +231,163 @@ __global__ __launch_bounds__(kClassBlock) void k_drain_classify(DrainArgs a, con
       const uint64_t gm = (g == kWave ? ~0ull : (1ull << g) - 1) << (lane & ~(g - 1));
       if (head[i]) verdict[slot[i]] = ((bm & gm) ? kDrainRowMissing : 0u) | ((ba & gm) ? kDrainRowAny : 0u);
     }
+  }
+}
+
+// ---- a topic's audience (ps_drain_topics) -------------------------------------
+
+constexpr uint32_t kAudBlock = 256;
+constexpr uint32_t kAudPer = 4;  // row loads a lane has in flight (twice that for rows wider than a wave)
+static_assert(kAudStripBytes / ((kWave + 1) * 8) <= kWave, "a strip of rows wider than a wave: a bit per node");
+
+// a node that is not on its topic's shared list
+__device__ __forceinline__ bool aud_exception(uint32_t v, uint32_t share) { return !share || v != kDrainRowAny; }
+
+// One wave per strip, front to back.  Rows of up to 64 mask words: an aligned
+// group of lanes per row as in k_drain_classify, 64 >> lanes_log2 rows to a
+// load and kAudPer loads in flight; the lane's mask word is read once for the
+// strip.  Wider rows: 64 words to a load, two nodes at a time with kAudPer
+// loads each in flight.  The generation bytes are read first: a stale row is
+// not loaded.
+// Group-major rows are addressed word by word through row_word_at, so a node's
+// blocks are all walked here and its verdict is written once.
+__global__ __launch_bounds__(kAudBlock) void k_audience_classify(DrainArgs a, AudArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s > g.n_strips) return;
+  if (s == g.n_strips) {  // (the scan's last input)
+    if (lane == 0) g.n_exc[s] = 0;
+    return;
+  }
+  const AudStrip S = g.strips[s];
+  const DrainTopic T = a.topics[S.topic];
+  const bool mesh = T.flags & kTopicMesh;
+  const uint8_t cur = static_cast<uint8_t>(a.gen_cur);
+  const uint8_t* __restrict__ gen = a.gen + T.nbase;
+  uint8_t* __restrict__ out = g.verdict + S.v0;
+  const uint32_t words = T.n_pos / 64;
+  uint32_t n_exc = 0, n_full = 0;  // (wave-uniform)
+  if (T.flags & kDrainGather) {
+    for (uint32_t i = lane; i < S.n; i += kWave) out[i] = kDrainRowAny | kDrainRowMissing;
+    n_exc = S.n;
+  } else if (words <= kWave) {
+    uint32_t l2 = 0;
+    while ((1u << l2) < words) ++l2;
+    const uint32_t gl = 1u << l2, per = kWave >> l2;
+    const uint32_t word = lane & (gl - 1), sub = lane >> l2;
+    const bool has_word = word < words;
+    const uint64_t m = has_word ? a.mask[T.aux0 + word] : 0ull;
+    const uint64_t gm = (gl == kWave ? ~0ull : (1ull << gl) - 1) << (lane & ~(gl - 1));
+    for (uint32_t i0 = 0; i0 < S.n; i0 += per * kAudPer) {
+      bool read[kAudPer];
+      uint64_t x[kAudPer];
+#pragma unroll
+      for (uint32_t k = 0; k < kAudPer; ++k) {
+        const uint32_t i = i0 + k * per + sub;
+        read[k] = has_word && i < S.n && (mesh || gen[S.u0 + min(i, S.n - 1)] == cur);
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kAudPer; ++k) {
+        x[k] = 0;
+        if (read[k]) {
+          const uint64_t at = row_word_at(a, T, S.u0 + i0 + k * per + sub, word);
+          if (at != kNoWord) x[k] = a.seen[at] & m;
+        }
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kAudPer; ++k) {
+        const uint32_t i = i0 + k * per + sub;
+        const bool in = i < S.n;
+        const uint64_t bm = __ballot(in && x[k] != m), ba = __ballot(x[k] != 0);
+        const uint32_t v = ((bm & gm) ? kDrainRowMissing : 0u) | ((ba & gm) ? kDrainRowAny : 0u);
+        const bool head = in && word == 0;
+        if (head) out[i] = static_cast<uint8_t>(v);
+        const uint32_t heads = __popcll(__ballot(head));
+        const uint32_t exc = __popcll(__ballot(head && aud_exception(v, g.share)));
+        n_exc += exc;
+        n_full += heads - exc;
+      }
+    }
+  } else {
+    // At most 31 nodes (kAudStripBytes of rows 65 words wide or more): a bit
+    // per node in wave-uniform words.  The generation bytes are read once,
+    // lane i node i's; the mask words of a step of 64 * kAudPer words are
+    // read once for all nodes; the fresh nodes go two at a time, so that
+    // 2 * kAudPer row loads are in flight and no load waits for a verdict.
+    const uint32_t n = min(S.n, kWave);
+    const uint64_t fresh = __ballot(lane < n && (mesh || gen[S.u0 + min(lane, n - 1)] == cur));
+    uint64_t any_bits = 0, miss_bits = 0;
+    for (uint32_t w0 = 0; w0 < words; w0 += kWave * kAudPer) {
+      uint64_t m[kAudPer];
+#pragma unroll
+      for (uint32_t k = 0; k < kAudPer; ++k) {
+        const uint32_t w = w0 + k * kWave + lane;
+        m[k] = w < words ? a.mask[T.aux0 + w] : 0ull;
+      }
+      uint64_t todo = fresh;
+      while (todo) {
+        const uint32_t i0 = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint32_t i1 = todo ? __builtin_ctzll(todo) : i0;  // (an odd node out is read twice)
+        todo &= todo - 1;
+        uint64_t x0[kAudPer], x1[kAudPer];
+#pragma unroll
+        for (uint32_t k = 0; k < kAudPer; ++k) {
+          const uint32_t w = w0 + k * kWave + lane;
+          x0[k] = 0;
+          x1[k] = 0;
+          if (w < words) {
+            const uint64_t at0 = row_word_at(a, T, S.u0 + i0, w), at1 = row_word_at(a, T, S.u0 + i1, w);
+            if (at0 != kNoWord) x0[k] = a.seen[at0] & m[k];
+            if (at1 != kNoWord) x1[k] = a.seen[at1] & m[k];
+          }
+        }
+        bool miss0 = false, any0 = false, miss1 = false, any1 = false;
+#pragma unroll
+        for (uint32_t k = 0; k < kAudPer; ++k) {
+          miss0 |= x0[k] != m[k];
+          any0 |= x0[k] != 0;
+          miss1 |= x1[k] != m[k];
+          any1 |= x1[k] != 0;
+        }
+        miss_bits |= (__ballot(miss0) ? 1ull << i0 : 0ull) | (__ballot(miss1) ? 1ull << i1 : 0ull);
+        any_bits |= (__ballot(any0) ? 1ull << i0 : 0ull) | (__ballot(any1) ? 1ull << i1 : 0ull);
+      }
+    }
+    uint32_t v = kDrainRowMissing;  // (a stale row: none)
+    if (fresh >> lane & 1ull) v = ((miss_bits >> lane & 1ull) ? kDrainRowMissing : 0u) | ((any_bits >> lane & 1ull) ? kDrainRowAny : 0u);
+    if (lane < n) out[lane] = static_cast<uint8_t>(v);
+    n_exc = __popcll(__ballot(lane < n && aud_exception(v, g.share)));
+    n_full = n - n_exc;
+  }
+  if (lane == 0) {
+    g.n_exc[s] = n_exc;
+    g.n_full[s] = n_full;
+  }
+}
+
+// One wave per strip: the nodes that are not full, in node order (ballot and
+// lane prefix), from the strip's offset on
+__global__ __launch_bounds__(kAudBlock) void k_audience_emit(AudArgs g, AudEmit o) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  if (g.n_exc[s] == 0) return;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  uint64_t at = o.off[s];
+  for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+    const uint32_t i = i0 + lane;
+    const uint32_t v = i < S.n ? vin[i] : 0u;
+    const bool exc = i < S.n && aud_exception(v, g.share);
+    const uint64_t b = __ballot(exc);
+    const uint64_t to = at + __popcll(b & ((1ull << lane) - 1));
+    if (exc && to < o.cap) {
+      o.peer[to] = o.node_peer[S.nbase + S.u0 + i];
+      o.node[to] = S.u0 + i;
+      o.verdict[to] = static_cast<uint8_t>(v);
+    }
+    at += __popcll(b);
   }
 }
 
@@ -561,6 +722,19 @@ hipError_t launch_drain_classify(const DrainArgs& a, const DrainClassBin* bins, 
   const uint32_t per = kClassBlock / kWave;
   hipLaunchKernelGGL(k_drain_classify, dim3((n_waves + per - 1) / per), dim3(kClassBlock), 0, s, a, bins, n_bins, queries,
                      n_waves, verdict);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_classify(const DrainArgs& a, const AudArgs& g, hipStream_t s) {
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_classify, dim3((g.n_strips + 1 + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_emit(const AudArgs& g, const AudEmit& o, hipStream_t s) {
+  if (g.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_emit, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g, o);
   return hipGetLastError();
 }
 

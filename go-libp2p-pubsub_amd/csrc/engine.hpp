@@ -565,6 +565,19 @@ struct ps_engine {
       uint32_t max_segs = 0;  // segments of the widest topic with a row queried
     };
 
+    // ps_drain_topics: the strips, verdict bytes and strip
+    // counts on the device, the exception records behind them, and the
+    // answer the call lends (host memory; the ids pinned) until the next call
+    struct Audience {
+      psamd::DevBuf d_strips, d_verdict, d_exc, d_full, d_rec;
+      std::vector<psamd::AudStrip> strips;
+      std::vector<uint32_t> strip_full, topic_list, exc_peer, exc_list, exc_node;
+      std::vector<uint8_t> exc_verdict;
+      std::vector<uint64_t> strip_off, n_nodes, n_full, exc_off, list_off;
+      uint8_t* h_ids = nullptr;
+      size_t ids_cap = 0;
+    } aud;
+
     // ps_sink_set / ps_sink_take: standing queries drained
     // behind every window of a run into one result per run.  Two results may
     // be untaken, in slots that alternate; a slot owns its result on the

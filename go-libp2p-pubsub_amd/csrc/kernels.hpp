@@ -715,6 +715,49 @@ hipError_t launch_drain_offsets_dev(const DrainQuery* lists, DrainCtl* ctl, uint
 hipError_t launch_drain_emit_dev(const DrainArgs& a, const DrainCtl* ctl, uint32_t seg_bound, const uint64_t* off,
                                  uint32_t* out, uint64_t id_cap, hipStream_t s);
 
+// ---- a topic's audience (ps_drain_topics) -------------------
+// The non-root nodes of the requested topics that have window messages, cut
+// into strips: runs of consecutive nodes of one topic, kAudStripBytes of rows
+// at most (a row counted at the lanes it takes: the power of two at or above
+// its mask words up to 64 words, the words themselves above) and at least one
+// node.  Strips lie in request order, a topic's in node order; verdict byte
+// v0 + i belongs to node u0 + i.  Nothing here comes from a subscriber list:
+// the host builds the strips from the topics' node ranges alone.
+constexpr uint32_t kAudStripBytes = 16384;
+struct AudStrip {
+  uint32_t topic;
+  uint32_t u0, n;   // topic-relative first node, nodes
+  uint32_t nbase;   // the topic's first node (node_peer, gen)
+  uint64_t v0;      // the strip's first verdict byte
+};
+struct AudArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  uint32_t share;     // 0: a full row is an exception too (the PSAMD_DRAIN_SHARED seam)
+  uint8_t* verdict;   // one kDrainRow* byte per node; kDrainRowAny alone: the row is full
+  uint64_t* n_exc;    // [n_strips + 1] per strip: the nodes that are not full; 0 behind the last
+  uint32_t* n_full;   // [n_strips] ... and the full ones
+};
+// k_audience_classify: one wave streams one strip's rows under the topic's
+// message mask (a tree node of another generation is "none", its row not
+// read; every node of a kDrainGather topic is any | missing, as
+// ps_drain_shared treats its rows) and leaves the verdict bytes and the
+// strip's two counts.
+hipError_t launch_audience_classify(const DrainArgs& a, const AudArgs& g, hipStream_t s);
+// k_audience_emit: one wave per strip reads the verdict bytes alone and
+// writes the nodes that are not full, in node order, from record off[strip]
+// on (the exclusive sum of n_exc), below cap: the node's peer, its
+// topic-relative number and its verdict.
+struct AudEmit {
+  const uint32_t* node_peer;
+  const uint64_t* off;
+  uint32_t* peer;
+  uint32_t* node;
+  uint8_t* verdict;
+  uint64_t cap;
+};
+hipError_t launch_audience_emit(const AudArgs& g, const AudEmit& o, hipStream_t s);
+
 // ---- the sink: every window of a run into one result (ps_sink_set) --
 // The run cursor: what the windows so far have added to the result.  Two of
 // them alternate: window w reads cur[w & 1] as its base -- the window header,

@@ -161,6 +161,9 @@ PROTOTYPES = [
     ("ps_drain_shared_end", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p, _u64p]),
     ("ps_sink_set", C.c_int, [_P, _u32p, _u32p, C.c_size_t, C.c_size_t, C.c_size_t]),
     ("ps_sink_take", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p, _u32p, _u64p]),
+    ("ps_drain_topics", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p),
+                                  C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p),
+                                  C.POINTER(_u32p), _u32p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -580,6 +583,35 @@ class Engine:
         off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
         ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
         return (wl.copy(), off.copy(), ids.copy()) if copy else (wl, off, ids)
+
+    def drain_topics(self, topics) -> dict:
+        """Each named topic's whole audience in the last window, with no query
+        per subscriber (ps_drain_topics): a dict of numpy copies --
+        topic_list[n], n_nodes[n], n_full[n], exc_off[n + 1], exc_peer[E],
+        exc_list[E], list_off[n_lists + 1], ids[total].  Entry i's shared list
+        is topic_list[i] (or NONE), held by n_full[i] of its n_nodes[i]
+        non-root nodes; the others are exc_peer / exc_list[exc_off[i]:
+        exc_off[i + 1]], in node order; list l is ids[list_off[l]:
+        list_off[l + 1]]."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        n = t.size
+        tl, ep, el, mp = _u32p(), _u32p(), _u32p(), _u32p()
+        nn, nf, eo, lo = _u64p(), _u64p(), _u64p(), _u64p()
+        n_lists, total = C.c_uint32(), C.c_uint64()
+        self._check(self._L.ps_drain_topics(self._h, _p(t, C.c_uint32), n, C.byref(tl), C.byref(nn), C.byref(nf),
+                                            C.byref(eo), C.byref(ep), C.byref(el), C.byref(lo), C.byref(mp),
+                                            C.byref(n_lists), C.byref(total)))
+
+        def arr(p, k, dt):
+            return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.empty(0, dtype=dt)
+
+        exc_off = arr(eo, n + 1, np.uint64)
+        n_exc = int(exc_off[n])
+        return {"topic_list": arr(tl, n, np.uint32), "n_nodes": arr(nn, n, np.uint64), "n_full": arr(nf, n, np.uint64),
+                "exc_off": exc_off, "exc_peer": arr(ep, n_exc, np.uint32), "exc_list": arr(el, n_exc, np.uint32),
+                "list_off": arr(lo, n_lists.value + 1, np.uint64), "ids": arr(mp, total.value, np.uint32)}
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -416,6 +416,46 @@ int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t*
 int ps_sink_set(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, size_t list_cap, size_t id_cap);
 int ps_sink_take(ps_engine* e, const uint32_t** win_list_out, const uint64_t** list_off_out, const uint32_t** msg_out,
                  uint32_t* n_windows_out, uint32_t* n_lists_out, uint64_t* total_out);
+/* A topic's whole audience, with no query per subscriber: who received what in
+ * the last window of the last run, for the n distinct topics named.  Within a
+ * window every reached subscriber of a topic holds the same list (the engine
+ * checks this on the GPU, as ps_drain_shared does), so the answer per topic is
+ * one list, the number of nodes that hold it, and the few that do not.
+ *   Let Q be the peers of every non-root node of topic[i] in the node space
+ * the window ran on, in ascending node (breadth-first) order, and A be
+ * ps_drain_shared's answer for the queries (topic[i], Q).  Then n_nodes[i] =
+ * |Q|; topic_list[i] is the list every message of the topic in the window, in
+ * arrival order, or PS_NONE when no row holds it (an idle topic, a topic no
+ * node of which was reached, a mesh topic whose window has several start
+ * rounds); n_full[i] counts the queries of Q that A gives that list; the
+ * others are the exceptions exc_off[i] .. exc_off[i+1], in Q's order:
+ * exc_peer is the peer, exc_list is PS_NONE where A gives PS_NONE and else a
+ * private list with the ids A gives.  A topic with no message in the window
+ * has n_full = 0 and no exception (nothing was sent, nobody missed anything);
+ * every other topic has n_full[i] + exc_off[i+1] - exc_off[i] == n_nodes[i].
+ * Lists are numbered in request order, a topic's shared list (if any) before
+ * the private lists of its exceptions in their order; list l is
+ * msg[list_off[l] .. list_off[l+1]), total = list_off[n_lists].
+ *   Subscribed peers that are not in the node space -- unattached peers and
+ * orphans, for which ps_topic_get_parents gives PS_NONE -- are not part of the
+ * answer, as in every other read.
+ *   The call blocks and needs no sizing call: the arrays are lent from host
+ * memory the engine owns, valid until the next ps_drain_topics or ps_destroy.
+ * PS_E_INVAL for a NULL output, n > 0 without topic, or a topic named twice;
+ * PS_E_RANGE with nothing written for a topic out of range, and when the
+ * lists exceed what one drain call holds; PS_E_NOTREADY before any run;
+ * PS_E_STATE on a multi-rank engine.  n == 0 is valid: exc_off = {0},
+ * list_off = {0}. */
+int ps_drain_topics(ps_engine* e, const uint32_t* topic, size_t n,
+                    const uint32_t** topic_list_out,  /* [n]                 */
+                    const uint64_t** n_nodes_out,     /* [n]                 */
+                    const uint64_t** n_full_out,      /* [n]                 */
+                    const uint64_t** exc_off_out,     /* [n + 1]             */
+                    const uint32_t** exc_peer_out,    /* [exc_off[n]]        */
+                    const uint32_t** exc_list_out,    /* [exc_off[n]]        */
+                    const uint64_t** list_off_out,    /* [n_lists + 1]       */
+                    const uint32_t** msg_out,         /* [total]             */
+                    uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -48,6 +48,15 @@ timings each: wall ms/step, the host time of ps_run_async (with the begin call
 in the other loop), ps_overlapped_windows(); one case with msg_window cut so
 that the largest topic takes three windows per step; the host time of the sink
 per run from PSAMD_DRAIN_TIMING's clock.  Writes DIR/sink_bench.json.
+
+--topics: ps_drain_topics (each topic's audience as one list plus exceptions)
+over every topic of one window, --reps timings: its wall clock and its classify
+/ scan / emit / lists / copy phases, the row bytes the classify pass covers
+over its device time against the HBM spec; against (a) ps_drain_shared over
+every subscription in the node space as explicit queries -- both wall clocks,
+the host share of each, and that the expanded answers agree -- and (b) the
+device time of k_digest (ps_seen_digest), which reads the same rows once under
+the same generation test.  Writes DIR/drain_topics_bench.json.
 """
 from __future__ import annotations
 
@@ -550,6 +559,105 @@ def sink_main(a, wl):
 HBM_SPEC_BYTES_PER_S = 8e12
 
 
+def all_subscriptions(eng, n_topics):
+    """(topic, peer) of every non-root node, topic by topic in node order; the first query of each topic."""
+    node_peer = eng.graph(PE.G_NODE_PEER)
+    parts, first = [], [0]
+    for t in range(n_topics):
+        g = eng.graph_topic(t)
+        lo, hi = g["nbase"] + 1, g["nbase"] + g["n_nodes"]
+        parts.append(node_peer[lo:max(lo, hi)].astype(np.uint32) if g["exists"] else np.empty(0, dtype=np.uint32))
+        first.append(first[-1] + parts[-1].size)
+    qt = np.repeat(np.arange(n_topics, dtype=np.uint32), np.diff(first))
+    return qt, np.concatenate(parts), first
+
+
+def topics_agree(r, first, n_peers, qp, lists, loff, lids):
+    """ps_drain_topics' answer r expanded per subscription equals ps_drain_shared's (lists, loff, lids)."""
+    ours = np.empty(qp.size, dtype=np.uint32)
+    at = np.zeros(n_peers, dtype=np.int64)
+    for i in range(len(first) - 1):
+        q = qp[first[i]:first[i + 1]]
+        ours[first[i]:first[i + 1]] = r["topic_list"][i]
+        at[q] = np.arange(first[i], first[i + 1])
+        e0, e1 = int(r["exc_off"][i]), int(r["exc_off"][i + 1])
+        ours[at[r["exc_peer"][e0:e1]]] = r["exc_list"][e0:e1]
+    if not np.array_equal(ours == PE.NONE, lists == PE.NONE):
+        return False
+    keep = ours != PE.NONE
+    pairs = np.unique(np.stack([ours[keep], lists[keep]]), axis=1)
+    return all(np.array_equal(r["ids"][int(r["list_off"][a]):int(r["list_off"][a + 1])], lids[int(loff[b]):int(loff[b + 1])])
+               for a, b in pairs.T)
+
+
+def topics_main(a, wl):
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps}
+    eng, _ = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        qt, qp, first = all_subscriptions(eng, nt)
+        res["subscriptions_in_the_node_space"] = int(qt.size)
+        rows = []
+        for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+            with StderrCapture() as cap:
+                r = eng.drain_topics(topics)
+            row = phase_line(cap.text, "drain_topics")
+            for k in ("strips", "nodes", "row_bytes", "exceptions"):
+                row[k] = int(re.search(rf"\b{k} (\d+)", cap.text).group(1))
+            rows.append(row)
+        res["topics_phases"] = rows[1:]
+        lists, loff, lids, n_lists, total = shared_sizes(eng, qt, qp)
+        rows = []
+        for _ in range(a.reps + 1):
+            with StderrCapture() as cap:
+                rc, _, _ = raw_shared(eng, qt, qp, lists, loff, lids)
+            assert rc == 0, rc
+            rows.append(phase_line(cap.text, "drain_shared"))
+        res["shared_phases"] = rows[1:]
+        res["answers_agree"] = bool(topics_agree(r, first, wl.n_peers, qp, lists, loff, lids[:total]))
+        assert res["answers_agree"]
+        res.update(n_full=int(r["n_full"].sum()), exceptions=int(r["exc_peer"].size), lists=int(r["list_off"].size - 1),
+                   ids=int(r["ids"].size), shared_lists=n_lists, shared_ids=total)
+        digest = []
+        for _ in range(a.reps + 1):
+            with StderrCapture() as cap:
+                eng.seen_digest()
+            digest.append(float(re.search(r"psamd digest: device_ms ([0-9.]+)", cap.text).group(1)))
+        res["k_digest_device_ms"] = digest[1:]
+    eng, _ = stepped_engine(wl, {})
+    with eng:
+        walls = {"topics": [], "shared": [], "digest": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            eng.drain_topics(topics)
+            walls["topics"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            rc, _, _ = raw_shared(eng, qt, qp, lists, loff, lids)
+            walls["shared"].append(1e3 * (time.perf_counter() - t0))
+            assert rc == 0, rc
+            t0 = time.perf_counter()
+            eng.seen_digest()
+            walls["digest"].append(1e3 * (time.perf_counter() - t0))
+    res["topics_wall_ms"], res["shared_wall_ms"], res["digest_wall_ms"] = (walls[k][1:] for k in ("topics", "shared", "digest"))
+    tp, sp = res["topics_phases"], res["shared_phases"]
+    res["topics_host_ms"] = [p["host_strips_ms"] + p["host_lists_ms"] for p in tp]
+    res["shared_host_ms"] = [p["host_queries_ms"] + p["host_lists_ms"] for p in sp]
+    res["shared_over_topics_wall"] = float(np.median(res["shared_wall_ms"]) / np.median(res["topics_wall_ms"]))
+    cls, dig = [p["classify_ms"] for p in tp], res["k_digest_device_ms"]
+    res["classify_ms"] = cls
+    res["classify_over_digest"] = float(np.median(cls) / np.median(dig))
+    res["digest_spread_ms"] = max(dig) - min(dig)
+    res["classify_within_digest_plus_spread"] = bool(np.median(cls) <= np.median(dig) + max(max(dig) - min(dig), max(cls) - min(cls)))
+    res["classify_vs_hbm_spec"] = tp[0]["row_bytes"] / (float(np.median(cls)) / 1e3) / HBM_SPEC_BYTES_PER_S
+    res["digest_vs_hbm_spec"] = tp[0]["row_bytes"] / (float(np.median(dig)) / 1e3) / HBM_SPEC_BYTES_PER_S
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "drain_topics_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -690,8 +798,11 @@ def main():
     ap.add_argument("--shared", action="store_true", help="ps_drain_shared against ps_drain (see above)")
     ap.add_argument("--large-queries", type=int, default=262144)
     ap.add_argument("--sink", action="store_true", help="the sink in the pipelined loop against ps_drain_shared_begin's")
+    ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.topics:
+        return topics_main(a, wl)
     if a.sink:
         return sink_main(a, wl)
     if a.pipelined and a.shared:
