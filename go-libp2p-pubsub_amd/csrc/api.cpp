@@ -2,7 +2,7 @@
 // space (graph.cpp), the planners (plan.cpp) and the round loop (run.cpp):
 // lifecycle, topics and membership, publishes, result readbacks, multi-GPU
 // set-up; and the host-only planner probe (include/psengine_plan.h).  The
-// batched drain (ps_drain*) is drain.cpp's.
+// batched drain (ps_drain*, ps_sink_*) is the drain_*.cpp files'.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -181,14 +181,14 @@ static void read_switches(ps_engine* e) {
   if (const char* v = std::getenv("PSAMD_HOST_TIMING")) e->host_timing = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_FLOOD_PROFILE")) e->flood_profile = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_CHAIN_PROFILE")) e->chain_prof_path = v;
-  if (const char* v = std::getenv("PSAMD_DRAIN_TIMING")) e->drain.timing = std::atoi(v) != 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_TIMING")) e->drain.env.timing = std::atoi(v) != 0;
   const char* ab = std::getenv("PSAMD_AB");
   if (!ab || std::atoi(ab) == 0) return;
   if (const char* v = std::getenv("PSAMD_DRAIN_SLAB_IDS"))  // (a slab holds at least one segment)
-    e->drain.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
-  if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.staged = std::strcmp(v, "direct") != 0;
-  if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) e->drain.mapped_out = std::strcmp(v, "mapped") == 0;
-  if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) e->drain.share = std::strcmp(v, "private") != 0;
+    e->drain.env.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
+  if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.env.staged = std::strcmp(v, "direct") != 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) e->drain.env.mapped_out = std::strcmp(v, "mapped") == 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) e->drain.env.share = std::strcmp(v, "private") != 0;
   if (const char* v = std::getenv("PSAMD_TWIN")) e->twin_on = std::atoi(v) != 0;
   if (const char* v = std::getenv("PSAMD_NARROW")) e->expand_opts = std::atoi(v) == 0 ? kExpandNoNarrow : 0u;
   if (const char* v = std::getenv("PSAMD_CHAIN_WORDS_LEAD"))
@@ -713,7 +713,7 @@ int ps_seen_digest(ps_engine* e, uint64_t* digest_out) {
   HIP_TRY(hipMemsetAsync(e->d_digest.p, 0, 8, e->stream), "clear digest");
   // (PSAMD_DRAIN_TIMING, once a drain has made the events: k_digest's device
   // time, the yardstick of the audience classify pass -- DESIGN.md §5.5f)
-  const bool timed = e->drain.timing && e->drain.ev_t[0];
+  const bool timed = e->drain.env.timing && e->drain.ev_t[0];
   if (timed) HIP_TRY(hipEventRecord(e->drain.ev_t[0], e->stream), "event");
   HIP_TRY(launch_digest(e->d_seen.as<uint64_t>(), e->d_gen.as<uint8_t>(), e->gen_cur, e->d_node_peer.as<uint32_t>(),
                         e->d_node_topic.as<uint16_t>(),

@@ -1,0 +1,166 @@
+// drain_impl.hpp -- what the host files of the batched drain share (kernels:
+// drain.hip).  One file per call family:
+//   drain_tables.cpp  per window, not per call: the entry checks, both table
+//                     builds, query resolution, count + scan, pinned staging
+//   drain.cpp         ps_drain, ps_drain_begin / ps_drain_end, the slots
+//   drain_shared.cpp  ps_drain_shared, ps_drain_shared_begin / _end (§5.5c, d),
+//                     the shared-list pass and the synchronous list tail
+//   drain_sink.cpp    ps_sink_set / ps_sink_take and run.cpp's hooks (§5.5e):
+//                     the shared drain behind every window of a run
+//   drain_topics.cpp  ps_drain_topics (§5.5f): a topic's audience as one list
+//                     plus exceptions
+// The state is ps_engine::Drain (engine.hpp), grouped by owner.
+//
+// What the paths rely on, between them and with run.cpp:
+//  - Drain::Tables (seq, p_*): one set of device tables per window, built by
+//    whichever path runs first (drain_tables on the host, drain_tables_async
+//    on the device; the sink always builds its window's) and reused by the others.
+//  - Tables::d_err lives behind the mask words of the device build; it is
+//    created (8 bytes, cleared) on first use when only host builds have run.
+//    The synchronous list tail passes a zero word behind its header instead.
+//  - ps_drain's slabs: ev_copy[k & 1] is waited on before slab k is emitted,
+//    slab k - 1 is copied while slab k is emitted; under timing the copy runs
+//    in line on `stream`.
+//  - Slot::seen / emit_pending / ev_emit and Sink::fence (the last sink emit
+//    over each row set) are read by drain_fence (run.cpp).
+//  - ps_drain_shared_begin and the sink run one pass over their queries
+//    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
+//  - ps_drain_shared and ps_drain_topics run one tail over their list queries
+//    (drain_list_offsets, drain_list_ids) in Drain::Sync; the host numbers the
+//    lists, which is what the tests compare the device assignment against.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "engine.hpp"
+
+namespace psamd {
+
+using Drain = ps_engine::Drain;
+using SharedSort = Drain::SharedSort;
+using hclock = std::chrono::steady_clock;
+
+inline double ms_since(hclock::time_point t0) { return std::chrono::duration<double, std::milli>(hclock::now() - t0).count(); }
+
+// segments (or classify steps) one call may hold: the kernels index them in 32 bits
+constexpr uint64_t kDrainRowLimit = 0x7FFFFFFFull;
+// ids one asynchronous drain may hold at most (its buffers are sized by an
+// upper bound, not by the total): larger drains go through ps_drain's slabs
+constexpr uint64_t kDrainAsyncMaxIds = 1ull << 30;
+// drain_shared_sort's mark on a verdict the host gives (no classify pass)
+constexpr uint32_t kOnHost = 0x80000000u;
+
+inline size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+// PSAMD_DRAIN_TIMING: one phase on stream s between the two timing events,
+// waited for at its end.  Off: nothing is recorded and nothing waits.
+struct PhaseTimer {
+  const hipEvent_t* ev;
+  hipStream_t s;
+  bool on;
+  hipError_t begin() const { return on ? hipEventRecord(ev[0], s) : hipSuccess; }
+  hipError_t end(float& ms) const {
+    if (!on) return hipSuccess;
+    hipError_t r = hipEventRecord(ev[1], s);
+    if (r == hipSuccess) r = hipEventSynchronize(ev[1]);
+    float t = 0;
+    if (r == hipSuccess) r = hipEventElapsedTime(&t, ev[0], ev[1]);
+    ms += t;
+    return r;
+  }
+};
+
+// ---- drain_tables.cpp (each is described where it is defined) ------------------
+
+hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need);
+hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out);
+
+// Where one call stages its input: a slot's pinned h_in, all of it (one call
+// takes once), or a region of a sink result's arena
+struct Staging {
+  Drain::Slot* slot;
+  Drain::Sink::Res* arena;
+  hipError_t take(size_t bytes, uint8_t** out) const {
+    if (arena) return sink_stage(*arena, bytes, out);
+    const hipError_t rc = pinned_ensure(&slot->h_in, nullptr, &slot->in_cap, bytes);
+    *out = slot->h_in;
+    return rc;
+  }
+};
+
+// The state checks of a call on the last window, tested in this order; a null
+// message: the call has no such check
+struct DrainEntry {
+  const char* multi_rank;  // PS_E_STATE on a multi-rank engine (ps_drain serves them)
+  const char* no_window;   // PS_E_NOTREADY before the first run
+  const char* slots_full;  // PS_E_STATE with two drains outstanding (the begin calls)
+  // the twin is joined before the queries are read (the synchronous calls);
+  // the begin calls join it in drain_begin_slot, behind their limits
+  bool join;
+};
+// (ps_drain_topics takes no (topic, peer) query: it checks its topics itself)
+int drain_enter(ps_engine* e, const DrainEntry& c, const uint32_t* topic = nullptr, const uint32_t* peer = nullptr,
+                size_t n = 0);
+int drain_ready(ps_engine* e);
+int drain_check_queries(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n);
+int drain_tables(ps_engine* e);
+int drain_tables_async(ps_engine* e, const Staging& st, size_t tail, bool timed, size_t* used, uint8_t** tail_out);
+int drain_err_word(ps_engine* e, hipStream_t s);
+uint64_t drain_resolve(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n, DrainQuery* out,
+                       uint64_t* bound);
+DrainArgs drain_args(const ps_engine* e, const Drain::Tables& T);
+int drain_count_scan(ps_engine* e, DrainArgs& a, uint32_t n_segs, Drain::Scratch& B, const DrainQuery* queries,
+                     size_t n_queries, hipStream_t s, const PhaseTimer& tm, float& count_ms);
+
+// The node query (t, peer) reads, kNone where its answer is empty: a topic
+// idle in the window, the root, a peer not subscribed or another rank's.
+// `map`: topic t's peer map once looked up (a caller may keep it per topic).
+// (Inline: the resolution and the sort call it once per query.)
+inline uint32_t drain_node(ps_engine* e, uint32_t t, uint32_t peer, const uint32_t*& map) {
+  if (!e->drain.tab.topics[t].n_pos) return kNone;
+  if (!map) map = peer_node_map(e, t, e->last_topics[t]).data();
+  return map[peer];
+}
+
+// ---- drain.cpp: what the two asynchronous forms share around their slots -------
+
+int drain_begin_slot(ps_engine* e, size_t tail, bool timed, Drain::Slot** slot, size_t* used, uint8_t** tail_out);
+int drain_give_up(ps_engine* e, bool staged, int code, const char* what);
+int drain_slot_host_view(ps_engine* e, Drain::Slot& S, bool staged);
+int drain_view_status(ps_engine* e, uint64_t err, uint32_t over);
+int drain_slot_enqueued(ps_engine* e, Drain::Slot& S, size_t res_bytes, bool to_host);
+int drain_slot_complete(ps_engine* e, Drain::Slot& S);
+
+// ---- drain_shared.cpp -----------------------------------------------------------
+
+// The shared-list pass's input, one block and one upload: queries | initial
+// verdicts | sorted queries | bins
+struct SharedLayout {
+  size_t n;
+  uint32_t nt;
+  size_t o_v, o_cq, o_bins, tail;
+  SharedLayout(size_t n_queries, uint32_t n_topics)
+      : n(n_queries),
+        nt(n_topics),
+        o_v(align256(n * sizeof(DrainQuery))),
+        o_cq(o_v + align256(n * 4)),
+        o_bins(o_cq + align256(n * sizeof(DrainClassQuery))),
+        tail(o_bins + align256(nt * sizeof(DrainClassBin))) {}
+};
+
+// the shared-list pass: ps_drain_shared_begin's, and the sink's per window
+int shared_stage(ps_engine* e, const uint32_t* topic, const uint32_t* peer, const SharedLayout& L, uint8_t* c,
+                 SharedSort* R);
+bool shared_caps(const Drain& D, const SharedSort& R, size_t n, bool own, size_t* list_cap, size_t* id_cap,
+                 uint32_t* seg_bound);
+int shared_pass(ps_engine* e, Drain::ListBufs& B, const SharedLayout& L, const uint8_t* h, const SharedSort& R,
+                size_t list_cap, uint32_t seg_bound, uint32_t* list_of_query, const PhaseTimer& tm, float* ms,
+                DrainArgs* args, DrainCtl** ctl_out);
+// the synchronous list tail: ps_drain_shared's, and ps_drain_topics'
+int drain_list_offsets(ps_engine* e, DrainArgs& a, const std::vector<DrainQuery>& lists, uint32_t n_segs,
+                       std::vector<uint64_t>& hdr, const PhaseTimer& tm, float& count_ms, float& scan_ms);
+int drain_list_ids(ps_engine* e, const DrainArgs& a, uint32_t n_segs, uint64_t total, void* out, const PhaseTimer& tm,
+                   float& emit_ms, float& copy_ms);
+
+}  // namespace psamd

@@ -10,7 +10,9 @@
 //   run.cpp    one window as a list of stages over a WindowRun (plan uploads,
 //              streams and row sets, window start, level or compaction
 //              rounds, finish), and ps_run* / ps_wait around it
-//   drain.cpp  the batched drain of the last window (ps_drain*), host side
+//   drain_*.cpp  the batched drain of the last window (ps_drain*, the sink),
+//              host side, one file per call family over drain_tables.cpp
+//              (drain_impl.hpp)
 //   api.cpp    the remaining C ABI (lifecycle, topics, membership, reads,
 //              multi-GPU)
 #pragma once
@@ -475,51 +477,101 @@ struct ps_engine {
   std::vector<uint64_t> peer_node_epoch;                 // graph_epoch each map was built for
   uint64_t window_seq = 0;  // bumped whenever last_* change (a new last window)
 
-  // ps_drain: the last window's drain tables (per topic: bit ->
-  // message id, message mask or arrival order), built on the first drain
-  // after a window; count / offset / query staging; two output slabs
+  // The batched drain of the last window (host code:
+  // drain_*.cpp, drain_impl.hpp).  The fields are grouped by what owns them;
+  // copy_stream and ev_t serve every call.
   struct Drain {
     // one call's queries on the device, the ids per segment, their offsets
     // (the scan of the counts) and the scan's temporary storage
     struct Scratch {
       psamd::DevBuf d_queries, d_cnt, d_off, d_scan;
     };
-    // the shared-list pass's device buffers (drain.cpp: shared_pass; DESIGN.md
-    // §5.5d): the lists and their counts, the input block (queries, verdicts,
-    // sorted queries, bins), the numbering scan's keys and their sums, the
-    // control block with the topics' first full queries behind it
+    // the shared-list pass's device buffers (drain_shared.cpp: shared_pass;
+    // DESIGN.md §5.5d): the lists and their counts, the input block (queries,
+    // verdicts, sorted queries, bins), the numbering scan's keys and their
+    // sums, the control block with the topics' first full queries behind it
     struct ListBufs {
       Scratch scratch;
       psamd::DevBuf d_in, d_key, d_aux;
     };
-    uint64_t seq = ~0ull;  // window_seq the tables on the device were built for
-    std::vector<psamd::DrainTopic> topics;
-    psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order, d_slab[2];
-    Scratch scratch;  // of ps_drain and ps_drain_shared (synchronous: one call at a time)
-    std::vector<psamd::DrainQuery> queries;
-    std::vector<uint64_t> off;  // host copy of the segment offsets
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_emit[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};  // per slab
-    hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around one phase
-    uint64_t slab_ids = 64ull << 20;  // ids per slab (A/B: PSAMD_DRAIN_SLAB_IDS, at least one segment)
-    bool staged = true;               // LDS-staged emit (A/B: PSAMD_DRAIN_EMIT=direct)
-    bool timing = false;              // PSAMD_DRAIN_TIMING=1: phases run apart, times to stderr
-    // the tables the device holds for `seq`, wherever they were built (the
-    // synchronous build above, or ps_drain_begin's blocks below); every use
-    // is ordered on `stream`
-    const psamd::DrainTopic* p_topics = nullptr;
-    const psamd::DrainGroup* p_groups = nullptr;
-    const uint32_t* p_ids = nullptr;
-    const uint64_t* p_mask = nullptr;
-    const uint32_t* p_order = nullptr;
 
-    // ps_drain_begin / ps_drain_end.  The window's tables:
-    // one uploaded block (topics, groups, the build's message arrays, a
-    // gather topic's order), the id table (device-built positions, then the
-    // gather topics' ids), the mask words with the error word behind them,
-    // the check's keys.
-    psamd::DevBuf d_ablock, d_aids, d_amask, d_akeys;
-    uint32_t* d_err = nullptr;  // the last device build's error word (in d_amask)
+    // The window's tables (per topic: bit -> message id, message mask or
+    // arrival order), one set per window: whichever call drains a window
+    // first builds them (drain_tables.cpp) and every other call, the sink
+    // included, reads them through p_*.  Every use is ordered on `stream`.
+    struct Tables {
+      uint64_t seq = ~0ull;  // window_seq the tables on the device were built for
+      std::vector<psamd::DrainTopic> topics;
+      // the host build (drain_tables: the synchronous calls)
+      psamd::DevBuf d_topics, d_groups, d_ids, d_mask, d_order;
+      // the device build (drain_tables_async: the begin calls and the sink;
+      // DESIGN.md §5.5b): one uploaded block (topics, groups, the build's
+      // message arrays, a gather topic's order), the id table (device-built
+      // positions, then the gather topics' ids), the mask words with the
+      // error word behind them, the check's keys
+      psamd::DevBuf d_ablock, d_aids, d_amask, d_akeys;
+      // the device build's error word (in d_amask), read by the kernels of the
+      // begin calls and the sink; made on first use where only host builds ran
+      uint32_t* d_err = nullptr;
+      // the tables the device holds for `seq`, wherever they were built
+      const psamd::DrainTopic* p_topics = nullptr;
+      const psamd::DrainGroup* p_groups = nullptr;
+      const uint32_t* p_ids = nullptr;
+      const uint64_t* p_mask = nullptr;
+      const uint32_t* p_order = nullptr;
+    } tab;
+
+    // The synchronous calls' buffers (ps_drain, ps_drain_shared,
+    // ps_drain_topics: one call at a time, each waits for its own work).
+    struct Sync {
+      Scratch scratch;  // all three
+      std::vector<psamd::DrainQuery> queries;  // ps_drain, ps_drain_shared: the resolved queries
+      // ps_drain: the host copy of the segment offsets, the two output slabs
+      // and, per slab, the events behind its emit and its copy
+      std::vector<uint64_t> off;
+      psamd::DevBuf d_slab[2];
+      hipEvent_t ev_emit[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
+      // ps_drain_shared: the classify pass's bins, sorted
+      // queries and verdicts
+      psamd::DevBuf d_cbins, d_cqueries, d_verdict;
+      // ps_drain_shared, ps_drain_topics (the synchronous list tail): the
+      // list queries' offsets header, with a zero error word behind it, and
+      // their ids; ps_drain_shared's host copy of the header
+      psamd::DevBuf d_hdr, d_lists;
+      std::vector<uint64_t> hdr;
+    } sync;
+
+    // The sort's host scratch (drain_shared.cpp: drain_shared_sort), filled by
+    // ps_drain_shared and, through shared_stage, by ps_drain_shared_begin and
+    // the sink: every query's host verdict and the classified queries by topic
+    struct Sort {
+      std::vector<uint32_t> verdict;
+      std::vector<psamd::DrainClassQuery> cqueries;
+      // what the sort leaves beside them
+      struct SharedSort {
+        std::vector<psamd::DrainClassBin> bins;
+        uint32_t n_class = 0, n_waves = 0;
+        uint32_t n_rows = 0, n_gather = 0;  // queries with a row; those of kDrainGather topics
+        uint64_t row_ids = 0, gather_ids = 0, bin_ids = 0;  // window messages: per such query; per bin
+        uint32_t max_segs = 0;  // segments of the widest topic with a row queried
+      };
+    } sort;
+    using SharedSort = Sort::SharedSort;
+
+    // The switches read from the environment at ps_create (api.cpp: read_switches)
+    struct Switches {
+      uint64_t slab_ids = 64ull << 20;  // ps_drain: ids per slab (A/B: PSAMD_DRAIN_SLAB_IDS, at least one segment)
+      bool staged = true;       // the synchronous calls: LDS-staged emit (A/B: PSAMD_DRAIN_EMIT=direct)
+      bool timing = false;      // every call: PSAMD_DRAIN_TIMING=1, phases run apart, times to stderr
+      bool mapped_out = false;  // ps_drain_begin: emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)
+      // the shared calls, ps_drain_topics and the sink: full rows share their topic's list (A/B: PSAMD_DRAIN_SHARED=private)
+      bool share = true;
+    } env;
+
+    hipStream_t copy_stream = nullptr;        // results leave on it, beside whatever `stream` runs next
+    hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around one phase
+
+    // ps_drain_begin / ps_drain_end.
     // Two drains may be outstanding, in slots that alternate.  A slot owns
     // its pinned input staging (queries and, when it builds them, the
     // window's table block), its count / offset / scan / result buffers and
@@ -547,23 +599,6 @@ struct ps_engine {
       size_t o_off = 0, o_lq = 0, o_ids = 0;
     } slot[2];
     uint32_t slot_head = 0, slot_count = 0;
-    bool mapped_out = false;  // emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)
-
-    // ps_drain_shared: the classify pass's bins, sorted
-    // queries and verdicts; the list queries' offsets header and ids
-    psamd::DevBuf d_cbins, d_cqueries, d_verdict, d_hdr, d_lists;
-    std::vector<psamd::DrainClassQuery> cqueries;
-    std::vector<uint32_t> verdict;
-    std::vector<uint64_t> hdr;
-    bool share = true;  // full rows share their topic's list (A/B: PSAMD_DRAIN_SHARED=private)
-    // what drain_shared_sort (drain.cpp) leaves beside the sorted queries
-    struct SharedSort {
-      std::vector<psamd::DrainClassBin> bins;
-      uint32_t n_class = 0, n_waves = 0;
-      uint32_t n_rows = 0, n_gather = 0;  // queries with a row; those of kDrainGather topics
-      uint64_t row_ids = 0, gather_ids = 0, bin_ids = 0;  // window messages: per such query; per bin
-      uint32_t max_segs = 0;  // segments of the widest topic with a row queried
-    };
 
     // ps_drain_topics: the strips, verdict bytes and strip
     // counts on the device, the exception records behind them, and the
@@ -761,9 +796,9 @@ int twin_join(ps_engine* e);
 // & co.), waits for every pending ps_drain_begin emit that reads that set (a
 // no-op when none is pending, or for `stream`, which the drains run on)
 int drain_fence(ps_engine* e, hipStream_t s);
-// drain.cpp: frees the drain's stream, events and pinned memory (ps_destroy)
+// drain_tables.cpp: frees the drain's stream, events and pinned memory (ps_destroy)
 void drain_destroy(ps_engine* e);
-// drain.cpp, the sink (ps_sink_set; all no-ops while none is set).  A run
+// drain_sink.cpp, the sink (ps_sink_set; all no-ops while none is set).  A run
 // asks sink_precheck before it touches the pending messages (both results
 // untaken, or an answer that may pass 2^30 ids), opens a result, calls
 // sink_window behind every window it remembered and closes the result behind

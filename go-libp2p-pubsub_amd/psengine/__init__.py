@@ -265,6 +265,23 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def _queries(topics, peers):
+    """A drain's queries as the C calls take them: the two contiguous uint32
+    arrays (kept alive by the caller) and their pointers."""
+    t = np.ascontiguousarray(topics, dtype=np.uint32)
+    p = np.ascontiguousarray(peers, dtype=np.uint32)
+    if t.ndim != 1 or t.shape != p.shape:
+        raise ValueError("topics and peers must be 1-d arrays of one length")
+    return t, p, _p(t, C.c_uint32), _p(p, C.c_uint32)
+
+
+def _view(ptr, shape, dtype) -> np.ndarray:
+    """The engine's memory at ptr as an array of `shape` (an int: 1-d); an
+    empty array of `dtype` where it holds no element (ptr is not read)."""
+    shape = shape if isinstance(shape, tuple) else (shape,)
+    return np.ctypeslib.as_array(ptr, shape=shape) if all(shape) else np.empty(shape, dtype=dtype)
+
+
 class Engine:
     """One engine = one GPU's worth of topics (NewTopicManager, pubsub.go:26-31)."""
 
@@ -459,14 +476,11 @@ class Engine:
         """client.Messages() of many subscribers at once (ps_drain): query q =
         (topics[q], peers[q]); returns (off: uint64[n + 1], ids: uint32[total]),
         query q's message ids, in arrival order, being ids[off[q]:off[q + 1]]."""
-        t = np.ascontiguousarray(topics, dtype=np.uint32)
-        p = np.ascontiguousarray(peers, dtype=np.uint32)
-        if t.ndim != 1 or t.shape != p.shape:
-            raise ValueError("topics and peers must be 1-d arrays of one length")
+        t, p, tp, pp = _queries(topics, peers)
         n = t.size
         off = np.empty(n + 1, dtype=np.uint64)
         total = C.c_uint64()
-        tp, pp, op = _p(t, C.c_uint32), _p(p, C.c_uint32), _p(off, C.c_uint64)
+        op = _p(off, C.c_uint64)
         rc = self._L.ps_drain(self._h, tp, pp, n, op, None, 0, C.byref(total))  # the sizing call
         if rc != -7 or total.value == 0:
             self._check(rc)
@@ -480,15 +494,12 @@ class Engine:
         returns (list_of_query: uint32[n], list_off: uint64[n_lists + 1],
         ids: uint32[total]); query q's ids are list l = list_of_query[q],
         ids[list_off[l]:list_off[l + 1]], or nothing when l == NONE."""
-        t = np.ascontiguousarray(topics, dtype=np.uint32)
-        p = np.ascontiguousarray(peers, dtype=np.uint32)
-        if t.ndim != 1 or t.shape != p.shape:
-            raise ValueError("topics and peers must be 1-d arrays of one length")
+        t, p, tp, pp = _queries(topics, peers)
         n = t.size
         lists = np.empty(n, dtype=np.uint32)
         off = np.zeros(1, dtype=np.uint64)
         n_lists, total = C.c_uint32(), C.c_uint64()
-        tp, pp, lp = _p(t, C.c_uint32), _p(p, C.c_uint32), _p(lists, C.c_uint32)
+        lp = _p(lists, C.c_uint32)
         rc = self._L.ps_drain_shared(self._h, tp, pp, n, lp, _p(off, C.c_uint64), 0, None, 0, C.byref(n_lists),
                                      C.byref(total))  # the sizing call
         if rc != -7 or n_lists.value == 0:
@@ -505,11 +516,8 @@ class Engine:
         """Enqueues drain(topics, peers) of the last window of the last run
         enqueued (ps_drain_begin) and returns without waiting for it; at most
         two may be outstanding.  drain_end() completes the oldest."""
-        t = np.ascontiguousarray(topics, dtype=np.uint32)
-        p = np.ascontiguousarray(peers, dtype=np.uint32)
-        if t.ndim != 1 or t.shape != p.shape:
-            raise ValueError("topics and peers must be 1-d arrays of one length")
-        self._check(self._L.ps_drain_begin(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size))
+        t, p, tp, pp = _queries(topics, peers)
+        self._check(self._L.ps_drain_begin(self._h, tp, pp, t.size))
         self._drain_n.append((False, t.size))
 
     def drain_end(self, copy: bool = True):
@@ -522,8 +530,7 @@ class Engine:
         if rc != -8 and self._drain_n and not self._drain_n[0][0]:
             n = self._drain_n.pop(0)[1]
         self._check(rc)
-        off = np.ctypeslib.as_array(op, shape=(n + 1,))
-        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        off, ids = _view(op, n + 1, np.uint64), _view(mp, total.value, np.uint32)
         return (off.copy(), ids.copy()) if copy else (off, ids)
 
     def drain_shared_begin(self, topics, peers, list_cap: int = 0, id_cap: int = 0):
@@ -532,12 +539,8 @@ class Engine:
         it; it shares drain_begin's two slots.  list_cap = id_cap = 0: the
         engine's caps, the size of the answer.  drain_shared_end() completes
         the oldest."""
-        t = np.ascontiguousarray(topics, dtype=np.uint32)
-        p = np.ascontiguousarray(peers, dtype=np.uint32)
-        if t.ndim != 1 or t.shape != p.shape:
-            raise ValueError("topics and peers must be 1-d arrays of one length")
-        self._check(self._L.ps_drain_shared_begin(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size, list_cap,
-                                                  id_cap))
+        t, p, tp, pp = _queries(topics, peers)
+        self._check(self._L.ps_drain_shared_begin(self._h, tp, pp, t.size, list_cap, id_cap))
         self._drain_n.append((True, t.size))
 
     def drain_shared_end(self, copy: bool = True):
@@ -553,20 +556,16 @@ class Engine:
         if rc != -8 and self._drain_n and self._drain_n[0][0]:
             n = self._drain_n.pop(0)[1]
         self._check(rc)
-        lists = np.ctypeslib.as_array(lp, shape=(n,)) if n else np.empty(0, dtype=np.uint32)
-        off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
-        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        lists = _view(lp, n, np.uint32)
+        off, ids = _view(op, n_lists.value + 1, np.uint64), _view(mp, total.value, np.uint32)
         return (lists.copy(), off.copy(), ids.copy()) if copy else (lists, off, ids)
 
     def sink_set(self, topics, peers, list_cap: int = 0, id_cap: int = 0):
         """Registers standing queries (ps_sink_set): from now on every window
         of every run is drained for them, one result per run (sink_take).  No
         query clears the sink; results not yet taken are discarded."""
-        t = np.ascontiguousarray(topics, dtype=np.uint32)
-        p = np.ascontiguousarray(peers, dtype=np.uint32)
-        if t.ndim != 1 or t.shape != p.shape:
-            raise ValueError("topics and peers must be 1-d arrays of one length")
-        self._check(self._L.ps_sink_set(self._h, _p(t, C.c_uint32), _p(p, C.c_uint32), t.size, list_cap, id_cap))
+        t, p, tp, pp = _queries(topics, peers)
+        self._check(self._L.ps_sink_set(self._h, tp, pp, t.size, list_cap, id_cap))
         self._sink_n = t.size
 
     def sink_take(self, copy: bool = True):
@@ -579,9 +578,8 @@ class Engine:
         self._check(self._L.ps_sink_take(self._h, C.byref(wp), C.byref(op), C.byref(mp), C.byref(n_windows),
                                          C.byref(n_lists), C.byref(total)))
         n, nw = self._sink_n, n_windows.value
-        wl = np.ctypeslib.as_array(wp, shape=(nw, n)) if nw and n else np.empty((nw, n), dtype=np.uint32)
-        off = np.ctypeslib.as_array(op, shape=(n_lists.value + 1,))
-        ids = np.ctypeslib.as_array(mp, shape=(total.value,)) if total.value else np.empty(0, dtype=np.uint32)
+        wl = _view(wp, (nw, n), np.uint32)
+        off, ids = _view(op, n_lists.value + 1, np.uint64), _view(mp, total.value, np.uint32)
         return (wl.copy(), off.copy(), ids.copy()) if copy else (wl, off, ids)
 
     def drain_topics(self, topics) -> dict:
@@ -605,7 +603,7 @@ class Engine:
                                             C.byref(n_lists), C.byref(total)))
 
         def arr(p, k, dt):
-            return np.ctypeslib.as_array(p, shape=(k,)).copy() if k else np.empty(0, dtype=dt)
+            return _view(p, k, dt).copy()
 
         exc_off = arr(eo, n + 1, np.uint64)
         n_exc = int(exc_off[n])

@@ -12,9 +12,10 @@ LIB = os.path.join(LIBDIR, "libpsengine.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "pull.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp", "drain.cpp",
+SOURCES = ["kernels.hip", "pull.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp",
+           "drain_tables.cpp", "drain.cpp", "drain_shared.cpp", "drain_sink.cpp", "drain_topics.cpp",
            "tree.cpp", "dist.cpp", "codec.cpp", "pubsub.cpp"]
-HEADERS = ["kernels.hpp", "devutil.hpp", "gbuild.hpp", "tree.hpp", "dist.hpp", "engine.hpp"]
+HEADERS = ["kernels.hpp", "devutil.hpp", "gbuild.hpp", "tree.hpp", "dist.hpp", "engine.hpp", "drain_impl.hpp"]
 
 
 def _stale() -> bool:
