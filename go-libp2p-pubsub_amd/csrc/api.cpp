@@ -73,30 +73,6 @@ int dist_streams(ps_engine* e) {
 
 namespace {
 
-ps_plan_opts current_opts(const ps_engine* e) {
-  ps_plan_opts o{};
-  o.flood_top_bytes = e->flood_top_bytes;
-  o.overlap_min_bytes = e->overlap_min_bytes;
-  o.launch_bytes = static_cast<uint64_t>(e->launch_bytes);
-  o.flood = e->flood_on ? 1 : 0;
-  o.chain_max = e->chain_max;
-  o.chain_max_groups = e->chain_max_groups;
-  o.chain_tail = e->chain_tail ? 1 : 0;
-  o.chain_words = e->chain_words;
-  o.flood_words = e->flood_words;
-  o.pad_words = e->pad_words;
-  o.overlap = e->overlap_on ? 1 : 0;
-  o.overlap_min_rounds = e->overlap_min_rounds;
-  o.xchg_overlap = e->xchg_overlap_env;
-  o.gpu_build = e->gpu_build_on ? 1 : 0;
-  o.flood_spin_ticks = e->flood_spin_ticks;
-  o.chain_nt = e->chain_nt ? 1 : 0;
-  o.chain_waves = e->chain_waves;
-  o.flood_min_rounds = e->flood_min_rounds;
-  o.align_groups = e->align_groups ? 1 : 0;
-  return o;
-}
-
 const char* check_opts(const ps_plan_opts& o) {
   if (o.chain_max < 1 || o.chain_max > kChainLevels || o.chain_max_groups < 1 || o.chain_max_groups > kChainLevels)
     return "chain_max / chain_max_groups out of 1..6";
@@ -114,30 +90,7 @@ const char* check_opts(const ps_plan_opts& o) {
 // the exchange stream of a multi-rank engine: forced by the options, or
 // (auto) on whenever the transport copies the records
 void refresh_xchg_overlap(ps_engine* e) {
-  if (e->transport) e->xchg_overlap = e->xchg_overlap_env < 0 ? !e->transport->zero_copy() : e->xchg_overlap_env != 0;
-}
-
-void apply_opts(ps_engine* e, const ps_plan_opts& o) {
-  e->flood_top_bytes = o.flood_top_bytes;
-  e->overlap_min_bytes = o.overlap_min_bytes;
-  e->launch_bytes = static_cast<double>(o.launch_bytes);
-  e->flood_on = o.flood != 0;
-  e->chain_max = o.chain_max;
-  e->chain_max_groups = o.chain_max_groups;
-  e->chain_tail = o.chain_tail != 0;
-  e->chain_words = o.chain_words;
-  e->flood_words = o.flood_words;
-  e->pad_words = o.pad_words;
-  e->overlap_on = o.overlap != 0;
-  e->overlap_min_rounds = o.overlap_min_rounds;
-  e->xchg_overlap_env = o.xchg_overlap;
-  e->gpu_build_on = o.gpu_build != 0;
-  e->flood_spin_ticks = o.flood_spin_ticks;
-  e->chain_nt = o.chain_nt != 0;
-  e->chain_waves = o.chain_waves;
-  e->flood_min_rounds = o.flood_min_rounds;
-  e->align_groups = o.align_groups != 0;
-  refresh_xchg_overlap(e);
+  if (e->transport) e->xchg_overlap = e->opts.xchg_overlap < 0 ? !e->transport->zero_copy() : e->opts.xchg_overlap != 0;
 }
 
 }  // namespace
@@ -174,67 +127,77 @@ int ps_abi_check(uint32_t abi_version, size_t config_size, size_t stats_size, si
   return PS_E_INVAL;
 }
 
+// One environment variable each: a 0 / 1 flag, an unsigned value clamped to
+// lo..hi, a 64-bit value (strtoull's base).  Unset: the current value.
+static bool env_flag(const char* name, bool cur) {
+  const char* v = std::getenv(name);
+  return v ? std::atoi(v) != 0 : cur;
+}
+static uint32_t env_u32(const char* name, int lo, int hi, uint32_t cur) {
+  const char* v = std::getenv(name);
+  return v ? static_cast<uint32_t>(std::min(hi, std::max(lo, std::atoi(v)))) : cur;
+}
+static uint64_t env_u64(const char* name, int base, uint64_t cur) {
+  const char* v = std::getenv(name);
+  return v ? std::strtoull(v, nullptr, base) : cur;
+}
+
 // Debug switches read at creation (host phase times, per-wave profiles: they
 // change no plan).  The plan options come from ps_set_plan_opts; only A/B
 // tools that also set PSAMD_AB=1 may override them from the environment.
 static void read_switches(ps_engine* e) {
-  if (const char* v = std::getenv("PSAMD_HOST_TIMING")) e->host_timing = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_FLOOD_PROFILE")) e->flood_profile = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_CHAIN_PROFILE")) e->chain_prof_path = v;
-  if (const char* v = std::getenv("PSAMD_DRAIN_TIMING")) e->drain.env.timing = std::atoi(v) != 0;
-  const char* ab = std::getenv("PSAMD_AB");
-  if (!ab || std::atoi(ab) == 0) return;
-  if (const char* v = std::getenv("PSAMD_DRAIN_SLAB_IDS"))  // (a slab holds at least one segment)
-    e->drain.env.slab_ids = std::max<uint64_t>(kDrainSegBits, std::strtoull(v, nullptr, 10));
-  if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) e->drain.env.staged = std::strcmp(v, "direct") != 0;
-  if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) e->drain.env.mapped_out = std::strcmp(v, "mapped") == 0;
-  if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) e->drain.env.share = std::strcmp(v, "private") != 0;
-  if (const char* v = std::getenv("PSAMD_TWIN")) e->twin_on = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_NARROW")) e->expand_opts = std::atoi(v) == 0 ? kExpandNoNarrow : 0u;
-  if (const char* v = std::getenv("PSAMD_CHAIN_WORDS_LEAD"))
-    e->chain_words_lead = static_cast<uint32_t>(std::min(1 << 20, std::max(0, std::atoi(v))));
-  ps_plan_opts o = current_opts(e);
-  if (const char* v = std::getenv("PSAMD_GPU_BUILD")) o.gpu_build = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_FLOOD")) o.flood = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_PULL_PAIR"))  // 0: one k_pull launch per round
-    if (std::atoi(v) == 0) o.chain_max = o.chain_max_groups = 1;
-  if (const char* v = std::getenv("PSAMD_XCHG_OVERLAP")) o.xchg_overlap = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_CHAIN"))  // rounds per launch at most: 1 (k_pull only), 2 (pairs), 3..6
-    o.chain_max = o.chain_max_groups =
-        static_cast<uint32_t>(std::max(1, std::min(static_cast<int>(kChainLevels), std::atoi(v))));
-  if (const char* v = std::getenv("PSAMD_OVERLAP")) o.overlap = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_OVERLAP_ROUNDS"))
-    o.overlap_min_rounds = static_cast<uint32_t>(std::max(2, std::atoi(v)));
-  if (const char* v = std::getenv("PSAMD_OVERLAP_BYTES")) o.overlap_min_bytes = std::strtoull(v, nullptr, 10);
-  if (const char* v = std::getenv("PSAMD_PAD_WORDS")) o.pad_words = static_cast<uint32_t>(std::max(2, std::atoi(v)));
-  if (const char* v = std::getenv("PSAMD_CHAIN_TAIL")) o.chain_tail = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_LAUNCH_BYTES")) o.launch_bytes = static_cast<uint64_t>(std::max(0.0, std::atof(v)));
-  if (const char* v = std::getenv("PSAMD_CHAIN_WORDS"))
-    o.chain_words = static_cast<uint32_t>(std::min(1 << 20, std::max(256, std::atoi(v))));
-  if (const char* v = std::getenv("PSAMD_FLOOD_WORDS"))
-    o.flood_words = static_cast<uint32_t>(std::min(1 << 16, std::max(64, std::atoi(v))));
-  if (const char* v = std::getenv("PSAMD_FLOOD_SPIN_TICKS")) o.flood_spin_ticks = static_cast<uint32_t>(std::strtoul(v, nullptr, 0));
-  if (const char* v = std::getenv("PSAMD_FLOOD_TOP_BYTES")) o.flood_top_bytes = std::strtoull(v, nullptr, 0);
-  if (const char* v = std::getenv("PSAMD_UPLOAD_REUSE")) e->upload_reuse = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_SIG_WINDOWS")) e->sig_windows = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_FUSE_REDUCE")) e->fuse_reduce = std::atoi(v) != 0;
-  if (const char* v = std::getenv("PSAMD_FLOOD_MIN_ROUNDS"))
-    o.flood_min_rounds = static_cast<uint32_t>(std::max(1, std::atoi(v)));
-  if (const char* v = std::getenv("PSAMD_CHAIN_WAVES"))
-    o.chain_waves = static_cast<uint32_t>(std::max(0, std::min(16, std::atoi(v))));
-  if (!check_opts(o)) apply_opts(e, o);
+  constexpr int kAny = 0x7FFFFFFF;  // (no upper bound)
+  auto& s = e->env;
+  auto& d = e->drain.env;
+  s.host_timing = env_flag("PSAMD_HOST_TIMING", s.host_timing);
+  s.flood_profile = env_flag("PSAMD_FLOOD_PROFILE", s.flood_profile);
+  if (const char* v = std::getenv("PSAMD_CHAIN_PROFILE")) s.chain_prof_path = v;
+  d.timing = env_flag("PSAMD_DRAIN_TIMING", d.timing);
+  if (!env_flag("PSAMD_AB", false)) return;
+  // (a slab holds at least one segment)
+  d.slab_ids = std::max<uint64_t>(kDrainSegBits, env_u64("PSAMD_DRAIN_SLAB_IDS", 10, d.slab_ids));
+  if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) d.staged = std::strcmp(v, "direct") != 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) d.mapped_out = std::strcmp(v, "mapped") == 0;
+  if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) d.share = std::strcmp(v, "private") != 0;
+  s.twin = env_flag("PSAMD_TWIN", s.twin);
+  s.expand_opts = env_flag("PSAMD_NARROW", true) ? 0u : kExpandNoNarrow;
+  s.chain_words_lead = env_u32("PSAMD_CHAIN_WORDS_LEAD", 0, 1 << 20, s.chain_words_lead);
+  s.upload_reuse = env_flag("PSAMD_UPLOAD_REUSE", s.upload_reuse);
+  s.sig_windows = env_flag("PSAMD_SIG_WINDOWS", s.sig_windows);
+  s.fuse_reduce = env_flag("PSAMD_FUSE_REDUCE", s.fuse_reduce);
+  ps_plan_opts o = e->opts;
+  o.gpu_build = env_flag("PSAMD_GPU_BUILD", o.gpu_build);
+  o.flood = env_flag("PSAMD_FLOOD", o.flood);
+  if (!env_flag("PSAMD_PULL_PAIR", true)) o.chain_max = o.chain_max_groups = 1;  // 0: one k_pull launch per round
+  if (const char* v = std::getenv("PSAMD_XCHG_OVERLAP")) o.xchg_overlap = std::atoi(v) != 0;  // (unset: -1, auto)
+  // rounds per launch at most: 1 (k_pull only), 2 (pairs), 3..6
+  o.chain_max = env_u32("PSAMD_CHAIN", 1, kChainLevels, o.chain_max);
+  o.chain_max_groups = env_u32("PSAMD_CHAIN", 1, kChainLevels, o.chain_max_groups);
+  o.overlap = env_flag("PSAMD_OVERLAP", o.overlap);
+  o.overlap_min_rounds = env_u32("PSAMD_OVERLAP_ROUNDS", 2, kAny, o.overlap_min_rounds);
+  o.overlap_min_bytes = env_u64("PSAMD_OVERLAP_BYTES", 10, o.overlap_min_bytes);
+  o.pad_words = env_u32("PSAMD_PAD_WORDS", 2, kAny, o.pad_words);
+  o.chain_tail = env_flag("PSAMD_CHAIN_TAIL", o.chain_tail);
+  if (const char* v = std::getenv("PSAMD_LAUNCH_BYTES"))  // (a float: 16e6)
+    o.launch_bytes = static_cast<uint64_t>(std::max(0.0, std::atof(v)));
+  o.chain_words = env_u32("PSAMD_CHAIN_WORDS", 256, 1 << 20, o.chain_words);
+  o.flood_words = env_u32("PSAMD_FLOOD_WORDS", 64, 1 << 16, o.flood_words);
+  o.flood_spin_ticks = static_cast<uint32_t>(env_u64("PSAMD_FLOOD_SPIN_TICKS", 0, o.flood_spin_ticks));
+  o.flood_top_bytes = env_u64("PSAMD_FLOOD_TOP_BYTES", 0, o.flood_top_bytes);
+  o.flood_min_rounds = env_u32("PSAMD_FLOOD_MIN_ROUNDS", 1, kAny, o.flood_min_rounds);
+  o.chain_waves = env_u32("PSAMD_CHAIN_WAVES", 0, 16, o.chain_waves);
+  if (!check_opts(o)) e->opts = o;
 }
 
 int ps_plan_opts_default(ps_plan_opts* out) {
   if (!out) return PS_E_INVAL;
-  const ps_engine fresh;  // (the member initialisers are the defaults)
-  *out = current_opts(&fresh);
+  *out = default_plan_opts();
   return PS_OK;
 }
 
 int ps_get_plan_opts(const ps_engine* e, ps_plan_opts* out) {
   if (!e || !out) return PS_E_INVAL;
-  *out = current_opts(e);
+  *out = e->opts;
   return PS_OK;
 }
 
@@ -242,11 +205,11 @@ int ps_set_plan_opts(ps_engine* e, const ps_plan_opts* o) {
   if (!e || !o) return PS_E_INVAL;
   if (const char* why = check_opts(*o)) return e->fail(PS_E_INVAL, why);
   if (e->infl_count) return e->fail(PS_E_STATE, "asynchronous runs pending: ps_wait first");
-  const ps_plan_opts old = current_opts(e);
-  apply_opts(e, *o);
   // a changed node-space build or row padding re-plans everything; the plan
   // keys cover the rest (chain lengths, words, tail, launch price, k_flood split)
-  if (old.gpu_build != o->gpu_build || old.pad_words != o->pad_words) e->graph_dirty = true;
+  if (e->opts.gpu_build != o->gpu_build || e->opts.pad_words != o->pad_words) e->graph_dirty = true;
+  e->opts = *o;
+  refresh_xchg_overlap(e);
   e->pull.key.clear();
   e->pair.key.clear();
   e->flood.key.clear();
@@ -296,7 +259,7 @@ int ps_create(const ps_config* cfg, ps_engine** out) {
     delete e;
     return PS_E_DEVICE;
   }
-  for (auto& f : e->infl) {
+  for (auto& f : e->slot) {
     void* h = nullptr;
     if (hipEventCreateWithFlags(&f.ev0, kStartEvent) != hipSuccess || hipEventCreate(&f.ev1) != hipSuccess ||
         hipHostMalloc(&h, 2 * (PS_MAX_ROUNDS + 1) * kNumCtr * 8 + 64, hipHostMallocMapped | hipHostMallocCoherent) !=
@@ -333,31 +296,25 @@ void ps_destroy(ps_engine* e) {
     return;
   }
   (void)hipSetDevice(e->cfg.device);
+  const hipStream_t side[5] = {e->xstream, e->pstream, e->rstream, e->qstream, e->tstream};
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  if (e->xstream) (void)hipStreamSynchronize(e->xstream);
-  if (e->pstream) (void)hipStreamSynchronize(e->pstream);
-  if (e->rstream) (void)hipStreamSynchronize(e->rstream);
-  if (e->qstream) (void)hipStreamSynchronize(e->qstream);
-  if (e->tstream) (void)hipStreamSynchronize(e->tstream);
+  for (hipStream_t x : side)
+    if (x) (void)hipStreamSynchronize(x);
   drain_destroy(e);
   for (auto ev : e->ev_k) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : {e->ev_run0, e->ev_run1, e->ev_round, e->ev_xchg, e->ev_gate[0], e->ev_gate[1], e->ev_pre, e->ev_end,
-                      e->ev_tend, e->ev_e2t})
+  for (hipEvent_t ev : {e->ev_run0, e->ev_run1, e->ev_round, e->ev_xchg, e->slot[0].ev_gate, e->slot[1].ev_gate, e->ev_pre,
+                      e->ev_end, e->ev_tend, e->ev_e2t})
     if (ev) (void)hipEventDestroy(ev);
-  for (auto& f : e->infl) {
+  for (auto& f : e->slot) {
     if (f.ev0) (void)hipEventDestroy(f.ev0);
     if (f.ev1) (void)hipEventDestroy(f.ev1);
     if (f.hs) (void)hipHostFree(f.hs);
+    if (f.stg.h) (void)hipHostFree(f.stg.h);
   }
-  for (auto& g : e->stg)
-    if (g.h) (void)hipHostFree(g.h);
   if (e->pairs_pinned) (void)hipHostFree(e->pairs_pinned);
   e->transport.reset();  // (a communicator before its streams)
-  if (e->xstream) (void)hipStreamDestroy(e->xstream);
-  if (e->pstream) (void)hipStreamDestroy(e->pstream);
-  if (e->rstream) (void)hipStreamDestroy(e->rstream);
-  if (e->qstream) (void)hipStreamDestroy(e->qstream);
-  if (e->tstream) (void)hipStreamDestroy(e->tstream);
+  for (hipStream_t x : side)
+    if (x) (void)hipStreamDestroy(x);
   if (e->stream) (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -634,12 +591,12 @@ int ps_read_delivered(ps_engine* e, uint32_t msg, uint8_t* out) {
         break;
       }
   if (d.n_nodes)
-    HIP_TRY(hipMemcpy2DAsync(col.data(), 8, e->d_seen.as<uint64_t>() + phys_word(d, G, 0, b >> 6), stride * 8ull, 8,
+    HIP_TRY(hipMemcpy2DAsync(col.data(), 8, e->rows.seen.as<uint64_t>() + phys_word(d, G, 0, b >> 6), stride * 8ull, 8,
                              d.n_nodes, hipMemcpyDeviceToHost, e->stream),
             "read seen");
   std::vector<uint8_t> gen(d.n_nodes);
   if (d.n_nodes)
-    HIP_TRY(hipMemcpyAsync(gen.data(), e->d_gen.as<uint8_t>() + d.nbase, d.n_nodes, hipMemcpyDeviceToHost, e->stream),
+    HIP_TRY(hipMemcpyAsync(gen.data(), e->rows.gen.as<uint8_t>() + d.nbase, d.n_nodes, hipMemcpyDeviceToHost, e->stream),
             "read generations");
   HIP_TRY(hipStreamSynchronize(e->stream), "sync");
   const bool mesh = (d.flags & kTopicMesh) != 0;
@@ -648,7 +605,7 @@ int ps_read_delivered(ps_engine* e, uint32_t msg, uint8_t* out) {
   // recipient; on another rank node 0 is an ordinary node
   const uint32_t u0 = (d.flags & kTopicRootLocal) ? 1 : 0;
   for (uint32_t u = u0; u < d.n_nodes; ++u)
-    if ((mesh || gen[u] == e->gen_cur) && (col[u] & bit)) out[e->node_peer[d.nbase + u]] = 1;
+    if ((mesh || gen[u] == e->rows.gen_cur) && (col[u] & bit)) out[e->node_peer[d.nbase + u]] = 1;
   return PS_OK;
 }
 
@@ -671,18 +628,18 @@ int ps_read_peer_messages(ps_engine* e, uint32_t topic, uint32_t peer, uint32_t*
   uint8_t g = 0;
   if (d.flags & kTopicGroups) {  // the row's blocks, one per start group
     for (const StartGroup& sg : e->last_groups[topic])
-      HIP_TRY(hipMemcpyAsync(row.data() + sg.w0, e->d_seen.as<uint64_t>() + phys_word(d, e->last_groups[topic], u, sg.w0),
+      HIP_TRY(hipMemcpyAsync(row.data() + sg.w0, e->rows.seen.as<uint64_t>() + phys_word(d, e->last_groups[topic], u, sg.w0),
                              sg.wn * 8ull, hipMemcpyDeviceToHost, e->stream),
               "read seen row");
   } else {
-    HIP_TRY(hipMemcpyAsync(row.data(), e->d_seen.as<uint64_t>() + d.wbase + static_cast<uint64_t>(u) * d.W, d.W * 8ull,
+    HIP_TRY(hipMemcpyAsync(row.data(), e->rows.seen.as<uint64_t>() + d.wbase + static_cast<uint64_t>(u) * d.W, d.W * 8ull,
                            hipMemcpyDeviceToHost, e->stream),
             "read seen row");
   }
-  HIP_TRY(hipMemcpyAsync(&g, e->d_gen.as<uint8_t>() + d.nbase + u, 1, hipMemcpyDeviceToHost, e->stream),
+  HIP_TRY(hipMemcpyAsync(&g, e->rows.gen.as<uint8_t>() + d.nbase + u, 1, hipMemcpyDeviceToHost, e->stream),
           "read generation");
   HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  if (!(d.flags & kTopicMesh) && g != e->gen_cur) return PS_OK;  // stale row: saw nothing
+  if (!(d.flags & kTopicMesh) && g != e->rows.gen_cur) return PS_OK;  // stale row: saw nothing
   // window slot li -> message
   const WinSlice w = window_slice(e, topic);
   const uint32_t* bits = window_bits(e, topic);
@@ -715,11 +672,9 @@ int ps_seen_digest(ps_engine* e, uint64_t* digest_out) {
   // time, the yardstick of the audience classify pass -- DESIGN.md §5.5f)
   const bool timed = e->drain.env.timing && e->drain.ev_t[0];
   if (timed) HIP_TRY(hipEventRecord(e->drain.ev_t[0], e->stream), "event");
-  HIP_TRY(launch_digest(e->d_seen.as<uint64_t>(), e->d_gen.as<uint8_t>(), e->gen_cur, e->d_node_peer.as<uint32_t>(),
+  HIP_TRY(launch_digest(e->rows.seen.as<uint64_t>(), e->rows.gen.as<uint8_t>(), e->rows.gen_cur, e->d_node_peer.as<uint32_t>(),
                         e->d_node_topic.as<uint16_t>(),
-                        (e->last_slot ? e->d_topics1 : e->d_topics).as<TopicDev>(),
-                        (e->last_slot ? e->d_groups1 : e->d_groups).as<GroupDev>(),
-                        e->n_nodes, e->d_digest.as<uint64_t>(), e->stream),
+                        e->last_slot->topics.as<TopicDev>(), e->last_slot->groups.as<GroupDev>(), e->n_nodes, e->d_digest.as<uint64_t>(), e->stream),
           "digest");
   if (timed) HIP_TRY(hipEventRecord(e->drain.ev_t[1], e->stream), "event");
   HIP_TRY(hipMemcpyAsync(digest_out, e->d_digest.p, 8, hipMemcpyDeviceToHost, e->stream), "read digest");
@@ -861,7 +816,7 @@ int ps_plan_create(uint32_t n_peers, uint32_t n_topics, const uint32_t* roots, c
   e->topics.resize(n_topics);
   e->live.assign(n_peers, 1);
   read_switches(e);
-  e->gpu_build_on = false;
+  e->opts.gpu_build = 0;
   for (uint32_t t = 0; t < n_topics; ++t) {
     int rc = ps_topic_set_tree(e, t, roots[t], parents + static_cast<size_t>(t) * n_peers);
     if (rc) {

@@ -74,7 +74,7 @@ int drain_slot_enqueued(ps_engine* e, Drain::Slot& S, size_t res_bytes, bool to_
   auto& D = e->drain;
   hipStream_t s = e->stream;
   HIP_TRY(hipEventRecord(S.ev_emit, s), "event");
-  S.seen = e->d_seen.p;
+  S.seen = e->rows.seen.p;
   S.emit_pending = true;
   S.enqueued = true;
   ++D.slot_count;

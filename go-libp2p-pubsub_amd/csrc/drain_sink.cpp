@@ -197,13 +197,13 @@ int psamd::sink_window(ps_engine* e) {
   // the entry of this row set, else one whose row set is gone
   Drain::Sink::Fence* F = nullptr;
   for (auto& f : K.fence)
-    if (f.seen == e->d_seen.p) F = &f;
+    if (f.seen == e->rows.seen.p) F = &f;
   for (auto& f : K.fence)
-    if (!F && (!f.seen || f.seen != e->d_seen_b.p)) F = &f;
+    if (!F && (!f.seen || f.seen != e->rows_other.seen.p)) F = &f;
   if (!F) return e->fail(PS_E_STATE, "sink: no fence entry for the row set");
   if (!F->ev) HIP_TRY(hipEventCreateWithFlags(&F->ev, kStreamEvent), "sink event");
   HIP_TRY(hipEventRecord(F->ev, s), "event");
-  F->seen = e->d_seen.p;
+  F->seen = e->rows.seen.p;
   F->run = R.run;
   K.last_ev = F->ev;
   R.windows = w + 1;

@@ -389,9 +389,9 @@ uint64_t drain_resolve(ps_engine* e, const uint32_t* topic, const uint32_t* peer
 // (all but the queries: the engine's current row set over the window's tables)
 DrainArgs drain_args(const ps_engine* e, const Drain::Tables& T) {
   DrainArgs a{};
-  a.seen = e->d_seen.as<uint64_t>();
-  a.gen = e->d_gen.as<uint8_t>();
-  a.gen_cur = e->gen_cur;
+  a.seen = e->rows.seen.as<uint64_t>();
+  a.gen = e->rows.gen.as<uint8_t>();
+  a.gen_cur = e->rows.gen_cur;
   a.topics = T.p_topics;
   a.groups = T.p_groups;
   a.mask = T.p_mask;

@@ -202,7 +202,7 @@ struct WindowLayout {
 // enqueue the window that the host can work out without the device.  The
 // level plans themselves stay engine members (pull, pair, flood, ghost: cached
 // across windows), as do the reduce descriptors, slot offsets and round kinds
-// (desc_host, woff_host, round_kind: later code and Inflight read them).
+// (desc_host, woff_host, round_kind: later code and the RunSlot read them).
 struct WindowSchedule {
   std::vector<SeedDev> seeds;                  // root injections, grouped by round:
   std::vector<uint32_t> seed_off;              // round r's are [seed_off[r], seed_off[r + 1])
@@ -271,6 +271,50 @@ struct GhostPlan {
   uint64_t recv_words = 0;
 };
 
+// The default plan options (ps_plan_opts_default; a new engine's `opts`): the
+// one place the numbers stand, each with the measurement that chose it.
+inline ps_plan_opts default_plan_opts() {
+  ps_plan_opts o{};
+  // k_flood (DESIGN.md §5.2): a single-rank level window's leading rounds in
+  // one persistent launch; PSAMD_FLOOD=0 runs per-round launches instead
+  o.flood = 1;
+  o.flood_words = kFloodWords;  // row words per task (PSAMD_FLOOD_WORDS)
+  // k_flood runs the leading rounds writing at most this many row bytes (with
+  // chains after it: 4 MB; 16 MB was best before them, profiles/r03/ab_flood_top.txt)
+  o.flood_top_bytes = 4ull << 20;
+  o.flood_min_rounds = 4;  // k_flood only for at least this many leading rounds
+  o.align_groups = 1;      // one-rank start-group windows run level-aligned
+  o.flood_spin_ticks = 200000000u;  // dependency-wait bound: 2 s of s_memrealtime (100 MHz); PSAMD_FLOOD_SPIN_TICKS
+  // rounds per launch at most (chain_max, 1..kChainLevels): 1 = one k_pull
+  // per round, 2 = pairs (k_pull_pair), 3..6 chains.
+  // Defaults by measurement (profiles/r03/ab_chain_v2.txt):
+  // 4 for single-start windows (cfg3 burst 1.016 vs 1.033 ms at 6), 6 for
+  // windows with start groups (paced cfg3 1.363 vs 1.443 ms at 4)
+  o.chain_max = 4;
+  o.chain_max_groups = 6;
+  o.pad_words = 16;         // rows of at least this many words padded to even (PSAMD_PAD_WORDS)
+  o.chain_tail = 1;         // a chain ending at the last round may be one round longer (PSAMD_CHAIN_TAIL)
+  o.launch_bytes = 16000000;  // planner: a launch's ramp and tail as row bytes (PSAMD_LAUNCH_BYTES)
+  o.chain_words = 4096;     // row words per chain wave, the planner's target (8192 until r05: cfg4 0.444 -> 0.404, cfg3 -0.5..1 %, profiles/r05/ab/)
+  o.chain_waves = 12;       // chain launches: resident waves per CU at most
+  o.chain_nt = 1;           // chain launches: level 0 and the inner levels stored non-temporally
+  // cross-window overlap (PSAMD_OVERLAP=0: off) of windows
+  // with at least these rounds and row bytes (PSAMD_OVERLAP_BYTES)
+  o.overlap = 1;
+  o.overlap_min_rounds = 12;
+  o.overlap_min_bytes = 512ull << 20;
+  // the exchange on its own stream beside the round's locally fed chunks
+  // (-1 = auto): a transport that copies the records (RCCL; the loopback
+  // with PS_DIST_F_COPY) yes; the zero-copy loopback no -- there it only
+  // contends for the same GPU (4 loopback ranks, cfg4: 7.06 vs 6.32 ms/step,
+  // profiles/r03/loopback)
+  o.xchg_overlap = -1;
+  // GPU rebuild of the node space (DESIGN.md §4.1): on by default for one
+  // rank and tree topics (PSAMD_GPU_BUILD=0: host build)
+  o.gpu_build = 1;
+  return o;
+}
+
 }  // namespace psamd
 
 struct ps_engine {
@@ -280,20 +324,32 @@ struct ps_engine {
   hipStream_t xstream = nullptr;  // multi-GPU: the exchange, beside the round's local chunks
   hipEvent_t ev_run0 = nullptr, ev_run1 = nullptr;
   hipEvent_t ev_round = nullptr, ev_xchg = nullptr;  // multi-GPU: round boundary, exchange done
-  // the exchange on its own stream beside the round's locally fed chunks
-  // (ps_plan_opts.xchg_overlap, -1 = auto): a transport that copies the
-  // records (RCCL; the loopback with PS_DIST_F_COPY) yes; the zero-copy
-  // loopback no -- there it only contends for the same GPU (4 loopback
-  // ranks, cfg4: 7.06 vs 6.32 ms/step, profiles/r03/loopback)
-  int xchg_overlap_env = -1;
-  bool xchg_overlap = true;
+  // the plan options (ps_get_plan_opts / ps_set_plan_opts; the A/B
+  // environment through api.cpp: read_switches)
+  ps_plan_opts opts = psamd::default_plan_opts();
+  bool xchg_overlap = true;  // opts.xchg_overlap resolved against the transport (api.cpp: refresh_xchg_overlap)
+  // The A/B and debug switches that are no plan options, read from the
+  // environment at creation (api.cpp: read_switches)
+  struct Switches {
+    bool host_timing = false;    // PSAMD_HOST_TIMING=1: host phase times to stderr
+    bool flood_profile = false;  // PSAMD_FLOOD_PROFILE=1: per-wave phase times of k_flood to stderr (sync runs)
+    // PSAMD_CHAIN_PROFILE=<file>: per-wave start / end / words of every
+    // k_pull_chain launch of blocking windows, appended to <file> (debug)
+    std::string chain_prof_path;
+    bool twin = true;          // twin windows (PSAMD_TWIN=0: off)
+    bool sig_windows = true;   // pipelined one-rank windows end with a pinned flag, not an event (A/B: PSAMD_SIG_WINDOWS=0)
+    // a signalled window's reduce is held back (pend_reduce) to run in the
+    // next window's first launch (A/B: PSAMD_FUSE_REDUCE=0)
+    bool fuse_reduce = true;
+    bool upload_reuse = true;  // the upload shadows below (A/B: PSAMD_UPLOAD_REUSE=0)
+    uint32_t expand_opts = 0;       // ExpandArgs::opts (A/B only: PSAMD_NARROW=0 -> kExpandNoNarrow)
+    uint32_t chain_words_lead = 0;  // A/B only (PSAMD_CHAIN_WORDS_LEAD): opts.chain_words for all but the last launch
+  } env;
   std::vector<hipEvent_t> ev_k;  // pairs around expand launches
   uint32_t n_cus = 256, expand_grid = 2048;
   bool host_only = false;        // a planner probe (psengine_plan.h): no device
   psamd::WindowLayout probe;     // the probe's last planned window
   psamd::WindowSchedule probe_sched;  // ... and its schedule (PS_PLAN_SCHEDULE)
-  bool host_timing = false;      // PSAMD_HOST_TIMING=1: host phase times to stderr
-  bool sig_windows = true;        // pipelined one-rank windows end with a pinned flag, not an event (A/B: PSAMD_SIG_WINDOWS=0)
   // per-window uploads (topic table, seeds, descriptors) kept on the device:
   // the bytes last staged into each buffer, skipped when a window repeats them
   struct UploadShadow {
@@ -301,21 +357,15 @@ struct ps_engine {
     std::vector<uint8_t> data;
   };
   std::map<const psamd::DevBuf*, UploadShadow> upload_shadow;
-  bool upload_reuse = true;  // (A/B: PSAMD_UPLOAD_REUSE=0)
   bool defer_into_signalled = false;  // the window being enqueued raises its flag in its reduce
   uint64_t sig_seq = 0;
   // a signalled window's reduce, held back to run in the next window's first
   // launch (k_window_turn) -- or alone, from ps_wait, if none comes first
-  // (A/B: PSAMD_FUSE_REDUCE=0)
-  bool fuse_reduce = true;
   struct PendingReduce {
     bool valid = false;
-    const void* owner = nullptr;  // the Inflight slot whose flag it raises
+    const void* owner = nullptr;  // the RunSlot whose flag it raises
     psamd::ReduceArgs args{};
   } pend_reduce;
-  // GPU rebuild of the node space (DESIGN.md §4.1): on by default for one
-  // rank and tree topics (PSAMD_GPU_BUILD=0: host build)
-  bool gpu_build_on = true;
   bool gpu_graph = false;     // the current node space was built on the GPU
   bool mirrors_valid = true;  // host copies of node_peer / flags / CSR are current
   std::vector<uint32_t> pairs_host, gstat_host, roots_host;
@@ -348,30 +398,17 @@ struct ps_engine {
     bool launched = false, ready = false;
   };
   std::vector<EarlyQuery> early_q;
-  // k_flood (DESIGN.md §5.2): a single-rank level window's leading rounds in
-  // one persistent launch; PSAMD_FLOOD=0 runs per-round launches instead
-  bool flood_on = true;
+  // k_flood (opts.flood and the flood_* options)
   bool flood_broken = false;  // a dependency wait timed out once: per-level launches from then on
   uint32_t flood_grid = 0;    // resident blocks (0: k_flood unavailable)
-  uint32_t flood_words = psamd::kFloodWords;  // row words per task (PSAMD_FLOOD_WORDS)
   uint32_t pull_words = psamd::kPullWords;    // row words per k_pull chunk (512..4096 measured: 1024 best)
-  // k_flood runs the leading rounds writing at most this many row bytes (with
-  // chains after it: 4 MB; 16 MB was best before them, profiles/r03/ab_flood_top.txt)
-  uint64_t flood_top_bytes = 4ull << 20;
-  uint32_t flood_min_rounds = 4;  // k_flood only for at least this many leading rounds (ps_plan_opts)
-  bool align_groups = true;       // one-rank start-group windows run level-aligned (ps_plan_opts)
   uint32_t flood_epoch = 0;   // granule tag of the last launch (granules are never reset)
-  uint32_t flood_spin_ticks = 200000000u;  // dependency-wait bound: 2 s of s_memrealtime (100 MHz); PSAMD_FLOOD_SPIN_TICKS
   psamd::FloodPlan flood;
   uint64_t flood_up = ~0ull;  // plan version of the tasks on the device
   psamd::DevBuf d_flood_tasks, d_flood_segs, d_flood_gran;
-  bool flood_profile = false;  // PSAMD_FLOOD_PROFILE=1: per-wave phase times of k_flood to stderr (sync runs)
-  psamd::DevBuf d_flood_prof;
+  psamd::DevBuf d_flood_prof;  // env.flood_profile
   uint32_t flood_prof_waves = 0;
-  // PSAMD_CHAIN_PROFILE=<file>: per-wave start / end / words of every
-  // k_pull_chain launch of blocking windows, appended to <file> (debug)
-  std::string chain_prof_path;
-  psamd::DevBuf d_chain_prof;
+  psamd::DevBuf d_chain_prof;  // env.chain_prof_path
 
   std::vector<psamd::TopicHost> topics;
   std::vector<uint8_t> live;
@@ -379,8 +416,8 @@ struct ps_engine {
   uint64_t graph_epoch = 0, flags_epoch = 0;  // bumped by every upload
 
   // level mode, per-round counter slots and their reduce descriptors
+  // (on the device: the run slot's woff)
   std::vector<uint32_t> woff_host, desc_host;
-  psamd::DevBuf d_woff;
   // level-aligned windows: the (topic, level) pieces of k_level_reach, cached
   // per node space and active topic set
   psamd::DevBuf d_reach;
@@ -391,21 +428,8 @@ struct ps_engine {
   psamd::PullPlan pull;
   psamd::DevBuf d_pull;
   uint64_t pull_up = ~0ull;  // plan version of the chunks on the device
-  // rounds per launch at most (ps_plan_opts.chain_max, 1..kChainLevels): 1 =
-  // one k_pull per round, 2 = pairs (k_pull_pair), 3..6 chains.
-  // Defaults by measurement (profiles/r03/ab_chain_v2.txt):
-  // 4 for single-start windows (cfg3 burst 1.016 vs 1.033 ms at 6), 6 for
-  // windows with start groups (paced cfg3 1.363 vs 1.443 ms at 4)
-  uint32_t chain_max = 4, chain_max_groups = 6;
+  // pair and chain launches (the opts.chain_* options)
   psamd::DevBuf d_chain;
-  uint32_t pad_words = 16;        // rows of at least this many words padded to even (PSAMD_PAD_WORDS)
-  bool chain_tail = true;         // a chain ending at the last round may be one round longer (PSAMD_CHAIN_TAIL)
-  double launch_bytes = 16e6;     // planner: a launch's ramp and tail as row bytes (PSAMD_LAUNCH_BYTES)
-  uint32_t chain_words = 4096;    // row words per chain wave, the planner's target (8192 until r05: cfg4 0.444 -> 0.404, cfg3 -0.5..1 %, profiles/r05/ab/)
-  uint32_t chain_words_lead = 0;  // A/B only (PSAMD_CHAIN_WORDS_LEAD): the same for all but the last launch
-  uint32_t expand_opts = 0;       // ExpandArgs::opts (A/B only: PSAMD_NARROW=0 -> kExpandNoNarrow)
-  uint32_t chain_waves = 12;      // chain launches: resident waves per CU at most (ps_plan_opts)
-  bool chain_nt = true;           // chain launches: level 0 and the inner levels stored non-temporally
   std::vector<uint64_t> chain_fail_key;  // a pair plan whose chain ranges overflowed the level tables: no chains
   psamd::DevBuf d_chain_ovf;
   psamd::DevBuf d_chain_meta, d_chain_cnt, d_chain_scan;  // the chunks' node entries (k_chain_meta)
@@ -427,9 +451,21 @@ struct ps_engine {
 
   psamd::DevBuf d_row_ptr, d_col, d_node_topic, d_node_flags, d_node_peer, d_node_parent;
   psamd::DevBuf d_ext0, d_ext1;  // compaction mode, one rank: arrival extents (ExpandArgs::ext_cur)
-  psamd::DevBuf d_seen, d_arr0, d_arr1, d_hop, d_flags, d_blk, d_gen, d_frontier, d_nfront, d_wgcount,
-      d_partials, d_stats, d_topics, d_seeds, d_digest, d_groups;
-  uint32_t gen_cur = 0;  // window generation stamped into d_gen (1..255)
+  // A row set: the seen rows, the two arrival rows and the nodes' generation
+  // bytes.  `rows` always names the set the last window wrote, rows_other the
+  // set a twin or alternating window writes next (they swap: §5.3d below).
+  struct RowSet {
+    psamd::DevBuf seen, arr0, arr1, gen;
+    uint32_t gen_cur = 0;  // window generation stamped into gen (1..255)
+    void swap(RowSet& o) {
+      seen.swap(o.seen);
+      arr0.swap(o.arr0);
+      arr1.swap(o.arr1);
+      gen.swap(o.gen);
+      std::swap(gen_cur, o.gen_cur);
+    }
+  } rows, rows_other;
+  psamd::DevBuf d_hop, d_flags, d_blk, d_frontier, d_nfront, d_wgcount, d_stats, d_digest;
   psamd::DevBuf d_remote_fed, d_send, d_recv, d_apply_stats;
   // multi-GPU level mode: ghost parents
   std::vector<uint32_t> ghost_ref;  // per node: remote parent's rank << 27 | record index, or kNone
@@ -663,10 +699,30 @@ struct ps_engine {
     } sink;
   } drain;
 
-  // asynchronous runs (ps_run_async / ps_wait): the last window of a run may
-  // leave its stats on the stream (pinned readback) so that the host plans
-  // the next run while this one's kernels execute
-  struct Inflight {
+  // per-window uploads (topic table, seeds, reduce descriptors) go through
+  // pinned staging: a copy from pageable memory blocks the host until the
+  // stream has drained, so the next batch's launches would only be issued
+  // once the previous batch had finished (a ~35 us bubble per pipelined
+  // step).  Two slots alternate; a slot is rewritten only after the copies
+  // of its previous use have completed: slot i belongs to asynchronous run
+  // slot i (synchronous runs use slot 0 with nothing in flight).
+  struct Staging {
+    uint8_t* h = nullptr;
+    uint8_t* d = nullptr;  // the slot's device-mapped address
+    size_t cap = 0;
+  };
+  // A run slot.  Asynchronous runs (ps_run_async / ps_wait): the last window
+  // of a run may leave its stats on the stream (pinned readback) so that the
+  // host plans the next run while this one's kernels execute; two runs may
+  // be in flight, in slots that alternate.  A slot owns what a window of its
+  // run must not share with a window of the other: the pinned counters and
+  // flag, the upload staging, the per-window tables on the device and the
+  // gate event (§5.3 below).  Synchronous runs use slot 0's staging and
+  // tables with the engine's own ev_run0 / ev_run1.
+  struct RunSlot {
+    Staging stg;
+    psamd::DevBuf topics, woff, groups, partials, seeds;  // the per-window tables (upload_shadow keys: stable addresses)
+    hipEvent_t ev_gate = nullptr;
     ps_stats st{};
     bool deferred = false;
     uint32_t r = 0, launches = 0;
@@ -688,25 +744,13 @@ struct ps_engine {
     std::vector<uint8_t> kinds;  // round_kind of the window
     hipStream_t stream = nullptr;  // the stream the window's kernels ran on
   };
-  Inflight infl[2];
-  uint32_t infl_head = 0, infl_count = 0;
-
-  // per-window uploads (topic table, seeds, reduce descriptors) go through
-  // pinned staging: a copy from pageable memory blocks the host until the
-  // stream has drained, so the next batch's launches would only be issued
-  // once the previous batch had finished (a ~35 us bubble per pipelined
-  // step).  Two slots alternate; a slot is rewritten only after the copies
-  // of its previous use have completed: slot i belongs to asynchronous run
-  // slot i (synchronous runs use slot 0 with nothing in flight).
-  struct Staging {
-    uint8_t* h = nullptr;
-    uint8_t* d = nullptr;  // the slot's device-mapped address
-    size_t cap = 0;
-  };
-  Staging stg[2];
+  RunSlot slot[2];
+  uint32_t infl_head = 0, infl_count = 0;  // the runs in flight: slot[infl_head] the oldest
   bool defer_phase = false;  // the current phase may defer its last window's stats
   bool defer_last = false;   // ... and this window is that last window
-  Inflight* defer_into = nullptr;
+  RunSlot* defer_into = nullptr;  // the slot of the asynchronous run being enqueued
+  // the slot whose staging and tables the window being enqueued uses
+  RunSlot& run_slot() { return defer_into ? *defer_into : slot[0]; }
 
   // Cross-window overlap.  A deep single-rank window (at
   // least overlap_min_rounds rounds, one start round) plans no k_flood; its
@@ -717,49 +761,36 @@ struct ps_engine {
   // prefix on pstream once that predecessor's gate is done, beside the
   // predecessor's remaining launches: they touch only levels > P + 1, and the
   // per-window tables (topics, seeds, reduce descriptors, partial slots) are
-  // per slot.  PSAMD_OVERLAP=0: off.
-  bool overlap_on = true;
-  uint32_t overlap_min_rounds = 12;
-  uint64_t overlap_min_bytes = 512ull << 20;  // row bytes of the window at least (PSAMD_OVERLAP_BYTES)
+  // per slot.  opts.overlap = 0 (PSAMD_OVERLAP=0): off.
   hipStream_t pstream = nullptr;
   hipStream_t rstream = nullptr;  // a pipelined window's counter reduce, beside the next window
   // the lazy prune's reach queries: they read the node space of the window
   // just enqueued (its build is complete), not its rows, so they run beside
   // the window's kernels instead of behind them
   hipStream_t qstream = nullptr;
-  hipEvent_t ev_gate[2] = {nullptr, nullptr}, ev_pre = nullptr, ev_end = nullptr;
+  hipEvent_t ev_pre = nullptr, ev_end = nullptr;
   bool gate_valid = false;
-  uint32_t gate_slot = 0;
+  RunSlot* gate_slot = slot;       // the slot whose ev_gate the last gate was recorded on
   std::vector<uint64_t> gate_key;  // plan versions, node-space epochs and P of the gate's window
   uint64_t overlapped = 0;         // windows whose prefix ran beside their predecessor (stats)
-  uint32_t last_slot = 0;          // the slot of the last enqueued window's tables
-  psamd::DevBuf d_topics1, d_woff1, d_groups1, d_partials1, d_seeds1;  // slot 1's tables
+  RunSlot* last_slot = slot;       // the slot of the last enqueued window's tables
 
   // Twin windows.  A pipelined one-rank level window whose
   // plan is already on the device runs ENTIRELY beside its predecessor: on
   // the other of two streams (stream / tstream), into the other of two row
-  // sets (seen + arrivals + generation bytes, swapped so that d_seen & co.
-  // always name the last window's), with its own slot's tables and signal
+  // sets (seen + arrivals + generation bytes, swapped so that `rows`
+  // always names the last window's), with its own slot's tables and signal
   // counter.  Nothing the two share is written by either (node space, plan
   // tables, reach pieces are read-only; uploads make a window a non-twin).
   // Work on `stream` that changes shared state first waits for tstream's
   // last window (twin_join); a twin window on tstream first waits for work
-  // `stream` did since tstream last followed it (e_seq).  PSAMD_TWIN=0: off.
-  bool twin_on = true;
+  // `stream` did since tstream last followed it (e_seq).  env.twin = false
+  // (PSAMD_TWIN=0): off.
   hipStream_t tstream = nullptr;
   hipEvent_t ev_tend = nullptr, ev_e2t = nullptr;
   bool t_pending = false;            // tstream ran a window `stream` has not waited for
   uint64_t e_seq = 1, t_seq = 0;     // shared-state work on `stream` / the last that tstream followed
   hipStream_t last_win_stream = nullptr;
-  psamd::DevBuf d_seen_b, d_arr0_b, d_arr1_b, d_gen_b;  // the other row set
-  uint32_t gen_cur_b = 0;
-  void swap_row_sets() {
-    d_seen.swap(d_seen_b);
-    d_arr0.swap(d_arr0_b);
-    d_arr1.swap(d_arr1_b);
-    d_gen.swap(d_gen_b);
-    std::swap(gen_cur, gen_cur_b);
-  }
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -792,7 +823,7 @@ int upload_graph(ps_engine* e);
 // run.cpp: the engine stream waits for tstream's last twin window (a no-op
 // when none is pending); every change of shared device state goes after it
 int twin_join(ps_engine* e);
-// run.cpp: stream s, about to start a window into the current row set (d_seen
+// run.cpp: stream s, about to start a window into the current row set (rows.seen
 // & co.), waits for every pending ps_drain_begin emit that reads that set (a
 // no-op when none is pending, or for `stream`, which the drains run on)
 int drain_fence(ps_engine* e, hipStream_t s);
@@ -855,7 +886,7 @@ bool deep_window(const ps_engine* e, const WindowLayout& L);
 // planner probe and run.cpp both plan a window through it.  Fills
 // e->round_kind, desc_host and woff_host; writes every topic's round-0 seed
 // range into L.tab.  No HIP call -- but on N ranks with in-place rows the
-// ghost plan hands this rank's row-set address (d_seen.p) to the others, so
+// ghost plan hands this rank's row-set address (rows.seen.p) to the others, so
 // run.cpp allocates the window's row set before it plans the schedule.
 int plan_window_schedule(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& win,
                          WindowLayout& L, WindowSchedule& S);

@@ -405,7 +405,7 @@ int ensure_mirrors(ps_engine* e) {
 namespace {
 
 bool can_gpu_build(const ps_engine* e) {
-  if (!e->gpu_build_on || e->world != 1 || e->cfg.n_peers >= (1u << kBuildPeerBits)) return false;
+  if (!e->opts.gpu_build || e->world != 1 || e->cfg.n_peers >= (1u << kBuildPeerBits)) return false;
   bool any = false;
   for (const auto& T : e->topics) {
     if (!T.exists) continue;
@@ -733,7 +733,7 @@ int gpu_build_graph(ps_engine* e, bool* fallback) {
   const uint32_t nn = na ? tb[2 * na] : 0u;
   e->n_nodes = nn;
   e->n_pad = std::max<uint32_t>(16, ((nn + 15) / 16) * 16);
-  if (e->host_timing) {
+  if (e->env.host_timing) {
     auto ms = [](auto x, auto y) { return std::chrono::duration<double, std::milli>(y - x).count(); };
     std::fprintf(stderr, "[psengine] gpu build: deltas %.3f ms (%zu), scratch %.3f ms, child lists + placement "
                  "+ readback %.3f ms\n", ms(tb0, tb1), pairs.size() / 2, ms(tb1, tb2), ms(tb2, tb3));
@@ -841,15 +841,15 @@ int upload_graph(ps_engine* e) {
     const size_t n_blk = ceil_div(e->n_pad, kFlagsPerBlock);
     HIP_TRY(e->d_blk.ensure(n_blk), "alloc block flags");
     HIP_TRY(hipMemsetAsync(e->d_blk.p, 0, e->d_blk.bytes, e->stream), "clear block flags");
-    HIP_TRY(e->d_gen.ensure(e->n_pad + 16), "alloc generations");
+    HIP_TRY(e->rows.gen.ensure(e->n_pad + 16), "alloc generations");
     e->n_remote_fed = static_cast<uint32_t>(e->remote_fed.size());
     HIP_TRY(e->d_remote_fed.ensure(std::max<size_t>(e->remote_fed.size(), 1) * 4), "alloc remote list");
     if (!e->remote_fed.empty())
       HIP_TRY(hipMemcpyAsync(e->d_remote_fed.p, e->remote_fed.data(), e->remote_fed.size() * 4,
                              hipMemcpyHostToDevice, e->stream),
               "upload remote list");
-    HIP_TRY(hipMemsetAsync(e->d_gen.p, 0, e->d_gen.bytes, e->stream), "clear generations");
-    e->gen_cur = 0;  // node ids changed: every row is stale
+    HIP_TRY(hipMemsetAsync(e->rows.gen.p, 0, e->rows.gen.bytes, e->stream), "clear generations");
+    e->rows.gen_cur = 0;  // node ids changed: every row is stale
     HIP_TRY(e->d_frontier.ensure(std::max<size_t>(nn, 1) * 4), "alloc frontier");
     HIP_TRY(e->d_wgcount.ensure(static_cast<size_t>(ceil_div(e->n_pad, kFlagsPerBlock)) * 4),
             "alloc wg_count");

@@ -58,7 +58,7 @@ int plan_window_layout(ps_engine* e, const std::vector<RunMsg>& msgs, const std:
   // reach rows ride in the window's counter reduce and must fit a run
   // slot's pinned rows.
   bool align = false;
-  if (e->world == 1 && e->align_groups && !e->run_zero_start && !(e->cfg.flags & PS_F_COMPACT)) {
+  if (e->world == 1 && e->opts.align_groups && !e->run_zero_start && !(e->cfg.flags & PS_F_COMPACT)) {
     bool multi = false, mesh = false;
     uint64_t segs = 0;
     uint32_t depth = 0;
@@ -124,7 +124,7 @@ int plan_window_layout(ps_engine* e, const std::vector<RunMsg>& msgs, const std:
       // -> 1.003 ms/step, the 4-rank cfg4 loopback's 63-word rows 2.49x ->
       // 2.32x; profiles/r03/ab_pad.txt)
       // (16-word alignment measured no faster: profiles/r04/ab/NOTES.md)
-      if (d.W >= e->pad_words) d.W = (d.W + 1) & ~1u;
+      if (d.W >= e->opts.pad_words) d.W = (d.W + 1) & ~1u;
       L.groups[t].push_back(StartGroup{s_lo, 0, d.W});
     } else {
       // Start groups (a tree's messages entering at different rounds): the
@@ -318,20 +318,20 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
   const auto& xchg = e->ghost.rounds;
   std::vector<uint64_t> key = e->pull.key;  // (graph, flags, rounds, row widths, start groups)
   key.push_back(first);
-  key.push_back(e->chain_max);
-  key.push_back(e->chain_max_groups);
-  key.push_back(e->chain_words);
-  key.push_back(e->chain_words_lead);
-  key.push_back(static_cast<uint64_t>(e->launch_bytes));
-  key.push_back(e->chain_tail ? 1 : 0);
+  key.push_back(e->opts.chain_max);
+  key.push_back(e->opts.chain_max_groups);
+  key.push_back(e->opts.chain_words);
+  key.push_back(e->env.chain_words_lead);
+  key.push_back(e->opts.launch_bytes);
+  key.push_back(e->opts.chain_tail ? 1 : 0);
   for (size_t q = 0; q < xchg.size(); ++q) key.push_back(xchg[q].any);
   PairPlan& PP = e->pair;
   if (key == PP.key) return false;
   PP.key = key;
   constexpr uint32_t stage = kPairWords;
-  const double kLaunchBytes = e->launch_bytes;  // ~3 us of launch ramp and tail at ~5.5 TB/s
+  const double kLaunchBytes = static_cast<double>(e->opts.launch_bytes);  // ~3 us of launch ramp and tail at ~5.5 TB/s
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
-  const uint32_t chain_max = L.multi ? e->chain_max_groups : e->chain_max;
+  const uint32_t chain_max = L.multi ? e->opts.chain_max_groups : e->opts.chain_max;
   const uint32_t max_len = std::max<uint32_t>(1, std::min<uint32_t>(chain_max, kChainLevels));
   auto& kind = PP.kind;
   kind.assign(rounds + 2, PS_K_NONE);
@@ -427,10 +427,10 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
     if (e->pull.bytes[q]) last_r = q;
   // (A/B: the launches before the window's last one sized by chain_words_lead)
   auto words_of = [&](uint32_t q, uint32_t len) {
-    return e->chain_words_lead && q + len - 1 < last_r ? e->chain_words_lead : e->chain_words;
+    return e->env.chain_words_lead && q + len - 1 < last_r ? e->env.chain_words_lead : e->opts.chain_words;
   };
   auto can_chain = [&](uint32_t q, uint32_t len) {
-    const bool tail = e->chain_tail && len == max_len + 1 && q + len - 1 == last_r && max_len >= 3;
+    const bool tail = e->opts.chain_tail && len == max_len + 1 && q + len - 1 == last_r && max_len >= 3;
     if (!chains_ok || (len > max_len && !tail) || len > kChainLevels || q + len - 1 > rounds || exch(q)) return false;
     for (uint32_t k = 1; k <= len; ++k)
       if (exch(q + k)) return false;
@@ -586,13 +586,13 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
 // (Windows under overlap_min_bytes never overlap -- run.cpp's byte floor --
 // so they keep k_flood: a small deep tree has nothing to gain from chains.)
 bool deep_window(const ps_engine* e, const WindowLayout& L) {
-  if (!(e->overlap_on && L.level && e->world == 1 && !L.any_mesh && !(e->cfg.flags & PS_F_RECORD_HOPS) &&
-        !L.multi && L.planned0 >= e->overlap_min_rounds))
+  if (!(e->opts.overlap && L.level && e->world == 1 && !L.any_mesh && !(e->cfg.flags & PS_F_RECORD_HOPS) &&
+        !L.multi && L.planned0 >= e->opts.overlap_min_rounds))
     return false;
   uint64_t rows = 0;  // the window's row bytes, as run.cpp's floor counts them
   for (uint32_t t = 0; t < L.tab.size(); ++t)
     rows += static_cast<uint64_t>(L.tab[t].n_nodes) * L.tab[t].W * 8;
-  return rows >= e->overlap_min_bytes;
+  return rows >= e->opts.overlap_min_bytes;
 }
 
 // (Fewer than flood_min_rounds leading rounds cost less as a chain launch:
@@ -601,8 +601,8 @@ bool deep_window(const ps_engine* e, const WindowLayout& L) {
 // 0.457 without; profiles/r04/ab/NOTES.md.)
 uint32_t plan_flood_rounds(const ps_engine* e, const WindowLayout& L) {
   uint32_t r = 0;
-  while (r < L.planned0 && e->pull.bytes[r + 1] <= e->flood_top_bytes) ++r;
-  return r >= e->flood_min_rounds ? r : 0;
+  while (r < L.planned0 && e->pull.bytes[r + 1] <= e->opts.flood_top_bytes) ++r;
+  return r >= e->opts.flood_min_rounds ? r : 0;
 }
 
 // One persistent launch (k_flood, flood.hip): every level of every active
@@ -617,7 +617,7 @@ uint32_t plan_flood_rounds(const ps_engine* e, const WindowLayout& L) {
 bool plan_flood_tasks(ps_engine* e, const WindowLayout& L, uint32_t rounds) {
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
   const auto& tab = L.tab;
-  std::vector<uint64_t> key{e->graph_epoch, rounds, e->flood_words};
+  std::vector<uint64_t> key{e->graph_epoch, rounds, e->opts.flood_words};
   for (uint32_t t = 0; t < nt; ++t) {
     key.push_back(tab[t].W ? L.groups[t].size() : ~0ull);
     key.push_back(tab[t].W);
@@ -651,7 +651,7 @@ bool plan_flood_tasks(ps_engine* e, const WindowLayout& L, uint32_t rounds) {
         if (d + 1 >= T.level_off.size()) continue;
         const uint32_t lo = T.level_off[d], hi = T.level_off[d + 1];
         if (lo == hi) continue;
-        uint32_t per = std::max<uint32_t>(1, std::min<uint32_t>(kFloodMaxNodes, e->flood_words / W));
+        uint32_t per = std::max<uint32_t>(1, std::min<uint32_t>(kFloodMaxNodes, e->opts.flood_words / W));
         const uint32_t gsz = std::min(per, kFloodGranule);
         per -= per % gsz;  // whole granules per task
         const uint32_t pseg = d == 1 ? kNone : seg_prev[t][gi];  // level 1: the seeded root
@@ -852,9 +852,9 @@ int plan_ghost(ps_engine* e, const WindowLayout& L, bool* changed) {
   // the same ghost key, so all of them reach this exchange together)
   if (e->inplace && e->transport && !G.segs.empty()) {
     Transport::Share mine;
-    mine.seen = e->d_seen.p;
-    mine.gen = e->d_gen.p;
-    mine.gen_cur = e->gen_cur;
+    mine.seen = e->rows.seen.p;
+    mine.gen = e->rows.gen.p;
+    mine.gen_cur = e->rows.gen_cur;
     for (uint32_t t = 0; t < nt; ++t) {
       const TopicDev& d = L.tab[t];
       mine.topics.insert(mine.topics.end(), {d.wbase, d.n_nodes, d.nbase, d.flags});
@@ -864,7 +864,7 @@ int plan_ghost(ps_engine* e, const WindowLayout& L, bool* changed) {
     if (e->transport->share(mine, all, &xerr) != hipSuccess) return e->fail(PS_E_DEVICE, xerr);
     e->rrows_host.assign(kMaxRanks, RankRows{nullptr, nullptr});
     for (int32_t a = 0; a < world; ++a) {
-      if (all[a].gen_cur != e->gen_cur || all[a].topics.size() != mine.topics.size())
+      if (all[a].gen_cur != e->rows.gen_cur || all[a].topics.size() != mine.topics.size())
         return e->fail(PS_E_STATE, "in-place rows: the ranks' windows differ");
       e->rrows_host[a] = RankRows{static_cast<const uint64_t*>(all[a].seen), static_cast<const uint8_t*>(all[a].gen)};
     }
@@ -1109,8 +1109,8 @@ void plan_schedule_pairs(ps_engine* e, const WindowLayout& L, WindowSchedule& S)
   // sets (engine.hpp, twin windows): a window's prefix then writes no row its
   // predecessor's last launch still reads, so the prefix may hold every
   // launch but the last (the gate: recorded before that launch)
-  S.alt_plan = e->twin_on && L.level && e->world == 1 && S.deep && flood_rounds == 0 &&
-               S.total >= e->overlap_min_bytes;
+  S.alt_plan = e->env.twin && L.level && e->world == 1 && S.deep && flood_rounds == 0 &&
+               S.total >= e->opts.overlap_min_bytes;
   // the prefix (deep windows): leading launches of at most 1/64 of the
   // window's row bytes, rounds 1..pre_P, followed by a launch starting at
   // round pre_P + 1 (the gate) and at least one more
@@ -1161,7 +1161,7 @@ int plan_window_schedule(ps_engine* e, const std::vector<RunMsg>& msgs, const st
   // deep single-start windows: per-round launches from round 1 (their first
   // few form the prefix that may overlap the previous window)
   S.deep = deep_window(e, L);
-  S.flood_ok = !S.deep && L.level && e->world == 1 && e->flood_on && !e->flood_broken && e->flood_grid > 0 &&
+  S.flood_ok = !S.deep && L.level && e->world == 1 && e->opts.flood && !e->flood_broken && e->flood_grid > 0 &&
                e->n_nodes < 0x80000000u;  // k_flood marks node ids with bit 31
   // level-aligned windows: counter rows of the reach counts after the rounds'
   S.reach_rows =

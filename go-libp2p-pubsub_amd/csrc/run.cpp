@@ -180,11 +180,11 @@ int twin_join(ps_engine* e) {
 int drain_fence(ps_engine* e, hipStream_t s) {
   if (s == e->stream) return PS_OK;  // (the drains are enqueued on it: ordered already)
   for (auto& S : e->drain.slot)
-    if (S.emit_pending && S.seen == e->d_seen.p) HIP_TRY(hipStreamWaitEvent(s, S.ev_emit, 0), "wait for a pending drain");
+    if (S.emit_pending && S.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, S.ev_emit, 0), "wait for a pending drain");
   // ... and the sink's: the last emit it enqueued over this row set, in this run or one not yet seen complete
   const auto& K = e->drain.sink;
   for (const auto& F : K.fence)
-    if (F.run > K.runs_done && F.seen == e->d_seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending sink drain");
+    if (F.run > K.runs_done && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending sink drain");
   return PS_OK;
 }
 
@@ -200,7 +200,7 @@ int stage_uploads(ps_engine* e, const Upload* ups, size_t n, hipStream_t s, Stag
   bool keep[8] = {};
   for (size_t i = 0; i < n && i < 8; ++i) {
     const Upload& u = ups[i];
-    if (!u.buf || !u.bytes || !e->upload_reuse) continue;
+    if (!u.buf || !u.bytes || !e->env.upload_reuse) continue;
     auto& sh = e->upload_shadow[u.buf];
     if (sh.gen == u.buf->gen && sh.data.size() == u.bytes && std::memcmp(sh.data.data(), u.src, u.bytes) == 0) {
       keep[i] = true;
@@ -216,7 +216,7 @@ int stage_uploads(ps_engine* e, const Upload* ups, size_t n, hipStream_t s, Stag
   // the slot of the asynchronous run being enqueued (its previous user was
   // waited for before the run slot was reused); synchronous runs start with
   // nothing in flight
-  ps_engine::Staging& g = e->stg[e->defer_into ? e->defer_into - e->infl : 0];
+  ps_engine::Staging& g = e->run_slot().stg;
   if (need > g.cap) {
     if (g.h) HIP_TRY(hipHostFree(g.h), "free staging");
     g.h = nullptr;
@@ -306,7 +306,7 @@ void chain_profile_dump(ps_engine* e, uint32_t planned0) {
     out.insert(out.end(), {K[i].topic, K[i].W, K[i].S,
                            static_cast<uint64_t>(K[i].node_end - K[i].node_begin) << 8 | K[i].levels});
   }
-  if (FILE* f = std::fopen(e->chain_prof_path.c_str(), "ab")) {
+  if (FILE* f = std::fopen(e->env.chain_prof_path.c_str(), "ab")) {
     std::fwrite(out.data(), 8, out.size(), f);
     std::fclose(f);
   }
@@ -327,9 +327,8 @@ struct WindowRun {
   WindowLayout L;
   WindowSchedule S;
   uint32_t nt = 0;
-  uint32_t slot = 0;      // the run slot whose per-window tables this window uses
+  ps_engine::RunSlot* slot = nullptr;  // the run slot whose staging and per-window tables this window uses
   uint64_t epochs0 = 0;   // the node-space epochs before this window's upload_graph
-  DevBuf *d_topics = nullptr, *d_woff = nullptr, *d_groups = nullptr, *d_partials = nullptr, *d_seeds = nullptr;
   hipStream_t s = nullptr;  // the stream the next launch goes to
   bool record = false, timed = false;
   bool plain = false;     // a one-rank tree window in level mode with lazy seen rows, neither recorded nor timed
@@ -370,23 +369,23 @@ struct WindowRun {
   }
 
   int ensure_row_sets() {
-    HIP_TRY(e->d_seen.ensure(L.wtot * 8), "alloc seen");
-    HIP_TRY(e->d_arr0.ensure(L.wtot * 8), "alloc arrivals");
-    HIP_TRY(e->d_arr1.ensure(L.wtot * 8), "alloc arrivals");
+    HIP_TRY(e->rows.seen.ensure(L.wtot * 8), "alloc seen");
+    HIP_TRY(e->rows.arr0.ensure(L.wtot * 8), "alloc arrivals");
+    HIP_TRY(e->rows.arr1.ensure(L.wtot * 8), "alloc arrivals");
     return PS_OK;
   }
 
   // This window into the row set the last one did not write (its generation
   // bytes cleared on s when newly allocated).
   int switch_sets(bool* fresh_gen = nullptr) {
-    const size_t gen_bytes = e->d_gen.bytes;
-    e->swap_row_sets();
+    const size_t gen_bytes = e->rows.gen.bytes;
+    e->rows.swap(e->rows_other);
     if (const int rc = ensure_row_sets()) return rc;
     bool gfresh = false;
-    HIP_TRY(e->d_gen.ensure(gen_bytes, &gfresh), "alloc generations");
+    HIP_TRY(e->rows.gen.ensure(gen_bytes, &gfresh), "alloc generations");
     if (gfresh) {
-      HIP_TRY(hipMemsetAsync(e->d_gen.p, 0, e->d_gen.bytes, s), "clear generations");
-      e->gen_cur = 0;
+      HIP_TRY(hipMemsetAsync(e->rows.gen.p, 0, e->rows.gen.bytes, s), "clear generations");
+      e->rows.gen_cur = 0;
     }
     if (fresh_gen) *fresh_gen = gfresh;
     return PS_OK;
@@ -422,7 +421,7 @@ struct WindowRun {
   hipError_t seed_round(uint32_t r, uint64_t* into) {
     if (r > L.max_start) return hipSuccess;
     const bool level = L.level;
-    return launch_seed(d_seeds->as<SeedDev>(), S.seed_off[r], S.seed_off[r + 1], into, a.seen,
+    return launch_seed(slot->seeds.as<SeedDev>(), S.seed_off[r], S.seed_off[r + 1], into, a.seen,
                        level ? nullptr : a.next_flag, level ? nullptr : a.blk_flag, s);
   }
 
@@ -463,7 +462,7 @@ struct WindowRun {
     fa.err = reinterpret_cast<uint32_t*>(partials);  // slot 0, reduced into row 0
     fa.n_tasks = static_cast<uint32_t>(e->flood.tasks.size());
     fa.gen_cur = a.gen_cur;
-    fa.spin_ticks = e->flood_spin_ticks;
+    fa.spin_ticks = e->opts.flood_spin_ticks;
     return fa;
   }
 
@@ -509,17 +508,12 @@ struct WindowRun {
     // the per-window device tables of this run's slot: a pipelined window's
     // leading launches may run beside the previous window's last ones (the
     // other slot), see `overlap` in choose_streams
-    slot = e->defer_into ? static_cast<uint32_t>(e->defer_into - e->infl) : 0u;
-    d_topics = slot ? &e->d_topics1 : &e->d_topics;
-    d_woff = slot ? &e->d_woff1 : &e->d_woff;
-    d_groups = slot ? &e->d_groups1 : &e->d_groups;
-    d_partials = slot ? &e->d_partials1 : &e->d_partials;
-    d_seeds = slot ? &e->d_seeds1 : &e->d_seeds;
+    slot = &e->run_slot();
     nt = static_cast<uint32_t>(e->topics.size());
     record = (e->cfg.flags & PS_F_RECORD_HOPS) != 0;
     timed = (e->cfg.flags & PS_F_TIME_KERNELS) != 0;
     t_w0 = Clock::now();
-    if (e->host_timing)
+    if (e->env.host_timing)
       std::fprintf(stderr, "[psengine] graph upload/build %.3f ms (%s)\n",
                    std::chrono::duration<double, std::milli>(t_w0 - t_g0).count(), e->gpu_graph ? "gpu" : "host");
     return plan_window_layout(e, msgs, win, L);
@@ -527,23 +521,23 @@ struct WindowRun {
 
   // Buffers: the allocations sized by the layout (grow-only: nothing is
   // enqueued).  They come before the schedule: on N ranks with in-place rows
-  // the ghost plan hands the row set's address (d_seen) to the other ranks.
+  // the ghost plan hands the row set's address (rows.seen) to the other ranks.
   // Leaves n_waves and stats_rows.
   int ensure_window_buffers() {
     if (const int rc = ensure_row_sets()) return rc;
     if (record) HIP_TRY(e->d_hop.ensure(L.wtot * 64 * 2), "alloc hop record");
     n_waves = e->expand_grid * (kBlock / 64);
     // staged + direct kernel counters side by side
-    HIP_TRY(d_partials->ensure(static_cast<size_t>(2) * n_waves * kNumCtr * 8), "alloc partials");
+    HIP_TRY(slot->partials.ensure(static_cast<size_t>(2) * n_waves * kNumCtr * 8), "alloc partials");
     // per-round counter rows: the planned rounds plus slack, grown (content kept)
     // if a mesh path outlives them
     stats_rows =
         std::min<uint32_t>(L.round_cap, std::max<uint32_t>(kMaxRoundsCap, L.max_depth + L.max_start + 32));
     HIP_TRY(e->d_stats.ensure(static_cast<size_t>(stats_rows + 1) * kNumCtr * 8), "alloc stats");
     HIP_TRY(e->d_apply_stats.ensure(static_cast<size_t>(stats_rows + 1) * kNumCtr * 8), "alloc apply stats");
-    HIP_TRY(d_topics->ensure(L.tab.size() * sizeof(TopicDev)), "alloc topics");
+    HIP_TRY(slot->topics.ensure(L.tab.size() * sizeof(TopicDev)), "alloc topics");
     HIP_TRY(e->d_nfront.ensure(4), "alloc n_front");
-    HIP_TRY(d_groups->ensure(std::max<size_t>(L.gtab.size(), 1) * sizeof(GroupDev)), "alloc groups");
+    HIP_TRY(slot->groups.ensure(std::max<size_t>(L.gtab.size(), 1) * sizeof(GroupDev)), "alloc groups");
     return PS_OK;
   }
 
@@ -577,11 +571,11 @@ struct WindowRun {
 
   // Buffers, second part: the allocations sized by the schedule.
   int ensure_schedule_buffers() {
-    HIP_TRY(d_seeds->ensure(S.seeds.size() * sizeof(SeedDev)), "alloc seeds");
+    HIP_TRY(slot->seeds.ensure(S.seeds.size() * sizeof(SeedDev)), "alloc seeds");
     if (L.level) {
-      HIP_TRY(d_partials->ensure(static_cast<size_t>(std::max<uint32_t>(S.n_slots, 1)) * kNumCtr * 8),
+      HIP_TRY(slot->partials.ensure(static_cast<size_t>(std::max<uint32_t>(S.n_slots, 1)) * kNumCtr * 8),
               "alloc level partials");
-      HIP_TRY(d_woff->ensure(e->desc_host.size() * 4), "alloc reduce descriptors");
+      HIP_TRY(slot->woff.ensure(e->desc_host.size() * 4), "alloc reduce descriptors");
     } else if (e->world > 1) {
       HIP_TRY(e->d_send.ensure(S.max_send), "alloc send regions");
       HIP_TRY(e->d_recv.ensure(S.max_recv), "alloc recv regions");
@@ -661,10 +655,10 @@ struct WindowRun {
     // windows side by side only share HBM and the MALL (paced cfg3 1.058 vs
     // 1.015, cfg4 0.4437 vs 0.4432 ms/step: profiles/r05/ab/twin_*.json) --
     // those keep the prefix overlap
-    twin = e->twin_on && e->sig_windows && plain && S.flood_rounds == 0 && e->defer_last && e->defer_into &&
-             planned0 <= PS_MAX_ROUNDS && fresh && !reach_up && e->chain_prof_path.empty() &&
-             S.total < e->overlap_min_bytes;
-    pcap = !twin && e->overlap_on && plain && !L.multi && S.total >= e->overlap_min_bytes && S.deep;
+    twin = e->env.twin && e->env.sig_windows && plain && S.flood_rounds == 0 && e->defer_last && e->defer_into &&
+             planned0 <= PS_MAX_ROUNDS && fresh && !reach_up && e->env.chain_prof_path.empty() &&
+             S.total < e->opts.overlap_min_bytes;
+    pcap = !twin && e->opts.overlap && plain && !L.multi && S.total >= e->opts.overlap_min_bytes && S.deep;
     if (!twin) {
       if ((rc = twin_join(e))) return rc;  // (it reuses the last window's row set)
       ++e->e_seq;
@@ -690,7 +684,7 @@ struct WindowRun {
     if (alt_sets && (rc = switch_sets(&sets_fresh))) return rc;
     if (pcap && !e->pstream) {  // (created on first use: multi-rank engines never need them)
       HIP_TRY(hipStreamCreateWithFlags(&e->pstream, hipStreamNonBlocking), "prefix stream");
-      for (hipEvent_t* ev : {&e->ev_gate[0], &e->ev_gate[1], &e->ev_pre})
+      for (hipEvent_t* ev : {&e->slot[0].ev_gate, &e->slot[1].ev_gate, &e->ev_pre})
         HIP_TRY(hipEventCreateWithFlags(ev, kStreamEvent), "overlap events");
     }
     if (pcap)
@@ -698,7 +692,7 @@ struct WindowRun {
                 S.flood_rounds, L.wtot, planned0};
     overlap = pcap && fresh && !sets_fresh && e->defer_into && e->gate_valid && e->gate_slot != slot &&
                 e->gate_key == gkey && epochs0 == (e->graph_epoch ^ (e->flags_epoch << 32)) &&
-                e->gen_cur + 1 <= 255;
+                e->rows.gen_cur + 1 <= 255;
     e->gate_valid = false;  // (this window records its own gate in the round loop)
     // the window's effective plan (ps_stats diagnostics)
     st->prefix_rounds = pcap ? S.pre_P : 0;
@@ -709,7 +703,7 @@ struct WindowRun {
       for (uint32_t q = S.flood_rounds + 1; q <= planned0 && q < e->pair.len.size(); ++q)
         st->plan_max_rounds = std::max(st->plan_max_rounds, e->pair.len[q]);
     if (overlap) {
-      HIP_TRY(hipStreamWaitEvent(e->pstream, e->ev_gate[e->gate_slot], 0), "wait for the previous gate");
+      HIP_TRY(hipStreamWaitEvent(e->pstream, e->gate_slot->ev_gate, 0), "wait for the previous gate");
       s = e->pstream;
       ++e->overlapped;
     }
@@ -734,23 +728,23 @@ struct WindowRun {
     // mode without meshes; the eager seen clear below would erase the seeds)
     fold = level && !any_mesh && !(e->cfg.flags & PS_F_NO_LAZY_SEEN);
     {  // (desc_host holds this window's descriptors: the upload shadow compares against the last window's)
-      const Upload ups[4] = {{d_topics->p, L.tab.data(), L.tab.size() * sizeof(TopicDev), d_topics},
-                             {d_seeds->p, S.seeds.data(), S.seeds.size() * sizeof(SeedDev), d_seeds},
-                             {d_woff->p, e->desc_host.data(), level ? e->desc_host.size() * 4 : 0, d_woff},
-                             {d_groups->p, L.gtab.data(), L.gtab.size() * sizeof(GroupDev), d_groups}};
+      const Upload ups[4] = {{slot->topics.p, L.tab.data(), L.tab.size() * sizeof(TopicDev), &slot->topics},
+                             {slot->seeds.p, S.seeds.data(), S.seeds.size() * sizeof(SeedDev), &slot->seeds},
+                             {slot->woff.p, e->desc_host.data(), level ? e->desc_host.size() * 4 : 0, &slot->woff},
+                             {slot->groups.p, L.gtab.data(), L.gtab.size() * sizeof(GroupDev), &slot->groups}};
       const int rcu = stage_uploads(e, ups, 4, s, fold ? &ws.copy : nullptr, staged);
       if (rcu) return rcu;
     }
     if (fold) {
       if (S.seed_off[1] > 0) ws.seeds = static_cast<const SeedDev*>(staged[1]);
-      ws.zero = d_partials->as<uint64_t>();
+      ws.zero = slot->partials.as<uint64_t>();
       ws.zero_words = static_cast<uint64_t>(S.n_slots) * kNumCtr;
     }
     // a pipelined one-rank window on the main stream alone ends with a pinned
     // flag and timestamps instead of events (ps_wait polls the flag): no event
     // record between consecutive windows.  (Not the plain-window predicate: a
     // mesh or eager-seen window may end signalled too.)
-    sigwin = e->sig_windows && e->defer_last && e->defer_into && level && e->world == 1 && !record &&
+    sigwin = e->env.sig_windows && e->defer_last && e->defer_into && level && e->world == 1 && !record &&
                !timed && !pcap && L.planned0 <= PS_MAX_ROUNDS;
     e->defer_into_signalled = false;
     if (sigwin)
@@ -759,9 +753,9 @@ struct WindowRun {
       HIP_TRY(hipEventRecord(e->ev_run0, s), "event");
     t_first = Clock::now();
     // new window generation: every tree row from older windows becomes stale
-    if (++e->gen_cur > 255) {
-      HIP_TRY(hipMemsetAsync(e->d_gen.p, 0, e->d_gen.bytes, s), "clear generations");
-      e->gen_cur = 1;
+    if (++e->rows.gen_cur > 255) {
+      HIP_TRY(hipMemsetAsync(e->rows.gen.p, 0, e->rows.gen.bytes, s), "clear generations");
+      e->rows.gen_cur = 1;
     }
     // the previous window's held-back reduce: in this launch when both run on
     // the main stream, else on its own first
@@ -773,48 +767,48 @@ struct WindowRun {
     if (turn) {
       e->pend_reduce.valid = false;
       HIP_TRY(launch_window_turn(e->pend_reduce.args, static_cast<const TopicDev*>(staged[0]), nt,
-                                 e->d_seen.as<uint64_t>(), e->d_arr0.as<uint64_t>(), e->d_arr1.as<uint64_t>(),
-                                 e->d_gen.as<uint8_t>(), e->gen_cur, any_mesh, ws, s),
+                                 e->rows.seen.as<uint64_t>(), e->rows.arr0.as<uint64_t>(), e->rows.arr1.as<uint64_t>(),
+                                 e->rows.gen.as<uint8_t>(), e->rows.gen_cur, any_mesh, ws, s),
               "reduce + window init");
     } else {
-      HIP_TRY(launch_window_init(static_cast<const TopicDev*>(fold ? staged[0] : d_topics->p), nt,
-                                 e->d_seen.as<uint64_t>(), e->d_arr0.as<uint64_t>(), e->d_arr1.as<uint64_t>(),
-                                 e->d_gen.as<uint8_t>(), e->gen_cur, any_mesh, ws, s),
+      HIP_TRY(launch_window_init(static_cast<const TopicDev*>(fold ? staged[0] : slot->topics.p), nt,
+                                 e->rows.seen.as<uint64_t>(), e->rows.arr0.as<uint64_t>(), e->rows.arr1.as<uint64_t>(),
+                                 e->rows.gen.as<uint8_t>(), e->rows.gen_cur, any_mesh, ws, s),
               "window init");
     }
     if (e->n_remote_fed && !level)
       HIP_TRY(launch_init_nodes(e->d_remote_fed.as<uint32_t>(), e->n_remote_fed, e->d_node_topic.as<uint16_t>(),
-                                d_topics->as<TopicDev>(), e->d_seen.as<uint64_t>(), e->d_arr0.as<uint64_t>(),
-                                e->d_arr1.as<uint64_t>(), e->d_gen.as<uint8_t>(), e->gen_cur, !level, s),
+                                slot->topics.as<TopicDev>(), e->rows.seen.as<uint64_t>(), e->rows.arr0.as<uint64_t>(),
+                                e->rows.arr1.as<uint64_t>(), e->rows.gen.as<uint8_t>(), e->rows.gen_cur, !level, s),
               "init remote-fed rows");
     if (e->cfg.flags & PS_F_NO_LAZY_SEEN) {
       // eager variant: clear every row and mark every node current, so the
       // expand kernel reads each child's seen word before it tests and sets it
-      HIP_TRY(hipMemsetAsync(e->d_seen.p, 0, L.wtot * 8, s), "clear seen");
-      HIP_TRY(hipMemsetAsync(e->d_gen.p, static_cast<int>(e->gen_cur), e->d_gen.bytes, s), "stamp generations");
+      HIP_TRY(hipMemsetAsync(e->rows.seen.p, 0, L.wtot * 8, s), "clear seen");
+      HIP_TRY(hipMemsetAsync(e->rows.gen.p, static_cast<int>(e->rows.gen_cur), e->rows.gen.bytes, s), "stamp generations");
     }
     if (record) HIP_TRY(hipMemsetAsync(e->d_hop.p, 0xFF, L.wtot * 64 * 2, s), "clear hop record");
     if (e->world > 1)  // (level mode: stays zero; the pull kernels count every delivery)
       HIP_TRY(hipMemsetAsync(e->d_apply_stats.p, 0, static_cast<size_t>(L.planned0 + 1) * kNumCtr * 8, s),
               "clear apply stats");
     a.frontier = e->d_frontier.as<uint32_t>();
-    a.opts = e->expand_opts;
+    a.opts = e->env.expand_opts;
     a.n_front = e->d_nfront.as<uint32_t>();
     a.row_ptr = e->d_row_ptr.as<uint32_t>();
     a.col = e->d_col.as<uint32_t>();
     a.node_topic = e->d_node_topic.as<uint16_t>();
     a.node_flags = e->d_node_flags.as<uint8_t>();
-    a.topics = d_topics->as<TopicDev>();
-    a.seen = e->d_seen.as<uint64_t>();
-    a.gen = e->d_gen.as<uint8_t>();
-    a.gen_cur = e->gen_cur;
+    a.topics = slot->topics.as<TopicDev>();
+    a.seen = e->rows.seen.as<uint64_t>();
+    a.gen = e->rows.gen.as<uint8_t>();
+    a.gen_cur = e->rows.gen_cur;
     a.next_flag = e->d_flags.as<uint8_t>();
     a.blk_flag = e->d_blk.as<uint8_t>();
     a.hop_rec = record ? e->d_hop.as<uint16_t>() : nullptr;
     a.send = e->d_send.as<uint8_t>();
-    partials = d_partials->as<uint64_t>();
-    arr[0] = e->d_arr0.as<uint64_t>();
-    arr[1] = e->d_arr1.as<uint64_t>();
+    partials = slot->partials.as<uint64_t>();
+    arr[0] = e->rows.arr0.as<uint64_t>();
+    arr[1] = e->rows.arr1.as<uint64_t>();
     stats = e->d_stats.as<uint64_t>();
     return PS_OK;
   }
@@ -837,7 +831,7 @@ struct WindowRun {
     for (uint32_t q = 1; q <= L.planned0; ++q) pairs |= e->round_kind[q] == PS_K_PAIR || e->round_kind[q] == PS_K_CHAIN;
     upfront = S.flood_rounds > 0 || L.multi || pairs;  // (a pair launch's plain level-1 runs read roots)
     if (upfront && L.max_start > 0)
-      HIP_TRY(launch_seed(d_seeds->as<SeedDev>(), S.seed_off[1], S.seed_off[L.max_start + 1], arr[0], a.seen,
+      HIP_TRY(launch_seed(slot->seeds.as<SeedDev>(), S.seed_off[1], S.seed_off[L.max_start + 1], arr[0], a.seen,
                           nullptr, nullptr, s),
               "seed");
     return PS_OK;
@@ -851,7 +845,7 @@ struct WindowRun {
     if (++e->flood_epoch == 0) ++e->flood_epoch;  // granules of older launches carry older epochs
     fa.epoch = e->flood_epoch;
     const uint32_t flood_blocks = std::min<uint32_t>(e->flood_grid, ceil_div(fa.n_tasks, kBlock / 64));
-    if (e->flood_profile) {
+    if (e->env.flood_profile) {
       HIP_TRY(e->d_flood_prof.ensure(static_cast<size_t>(flood_blocks) * 4 * kFloodProf * 8), "alloc flood profile");
       fa.prof = e->d_flood_prof.as<uint64_t>();
       fa.prof_split = S.flood_rounds * 2 / 3;
@@ -878,7 +872,7 @@ struct WindowRun {
     pa = pull_args();
     zero_copy = e->world > 1 && e->transport->zero_copy();
     // debug: the chain launches' per-wave profile (blocking windows only)
-    cprof = !e->chain_prof_path.empty() && !(e->defer_last && e->defer_into) && !e->pair.chain.empty();
+    cprof = !e->env.chain_prof_path.empty() && !(e->defer_last && e->defer_into) && !e->pair.chain.empty();
     if (cprof) HIP_TRY(e->d_chain_prof.ensure(e->pair.chain.size() * kChainProf * 8), "alloc chain profile");
     return PS_OK;
   }
@@ -946,11 +940,11 @@ struct WindowRun {
     uint64_t* const prof = cprof ? e->d_chain_prof.as<uint64_t>() : nullptr;
     pa.prof = prof ? prof + static_cast<size_t>(e->pair.lo[r]) * kChainProf : nullptr;
     HIP_TRY(launch_pull_chain(pa, e->d_chain.as<ChainChunk>() + e->pair.lo[r], e->pair.gsplit[r] - e->pair.lo[r], r,
-                              record, ntc, false, e->chain_nt, e->chain_waves, s),
+                              record, ntc, false, e->opts.chain_nt, e->opts.chain_waves, s),
             "pull chain");
     pa.prof = prof ? prof + static_cast<size_t>(e->pair.gsplit[r]) * kChainProf : nullptr;
     HIP_TRY(launch_pull_chain(pa, e->d_chain.as<ChainChunk>() + e->pair.gsplit[r], e->pair.hi[r] - e->pair.gsplit[r],
-                              r, record, ntc, true, e->chain_nt, e->chain_waves, s),
+                              r, record, ntc, true, e->opts.chain_nt, e->opts.chain_waves, s),
             "pull chain (column slices)");
     pa.prof = nullptr;
     HIP_TRY(time_mark(false), "event");
@@ -1021,7 +1015,7 @@ struct WindowRun {
     // the gate launch is enqueued (alternating sets: the gate is recorded
     // before the window's last launch)
     if (pcap && !gate_done && r > (alt_sets ? pre_P : pre_P + 1)) {
-      HIP_TRY(hipEventRecord(e->ev_gate[slot], e->stream), "event");
+      HIP_TRY(hipEventRecord(slot->ev_gate, e->stream), "event");
       e->gate_valid = true;
       e->gate_slot = slot;
       e->gate_key = gkey;
@@ -1095,22 +1089,22 @@ struct WindowRun {
         if (s != e->stream) HIP_TRY(hipStreamSynchronize(s), "sync");  // (before `stream`'s windows use it)
       }
       wsig.flag = e->defer_into->sig_dev;
-      wsig.ctr = e->d_sigctr.as<uint32_t>() + 32 * slot;
+      wsig.ctr = e->d_sigctr.as<uint32_t>() + 32 * (slot - e->slot);
       wsig.seq = ++e->sig_seq;
       e->defer_into->seq = wsig.seq;
     }
     // (beside other windows it writes only the slot's pinned rows, not the shared device rows)
-    if (wsig.flag && e->fuse_reduce && planned0 > 0 && !twin) {
+    if (wsig.flag && e->env.fuse_reduce && planned0 > 0 && !twin) {
       // held back for the next window's first launch (k_window_turn); only
       // this slot's buffers and the pinned rows: the shared device stats rows
       // may be reallocated by then, and nobody reads a deferred window's
       e->pend_reduce.valid = true;
       e->pend_reduce.owner = e->defer_into;
-      e->pend_reduce.args = ReduceArgs{partials, d_woff->as<uint32_t>(), planned0 + S.reach_rows, nullptr,
+      e->pend_reduce.args = ReduceArgs{partials, slot->woff.as<uint32_t>(), planned0 + S.reach_rows, nullptr,
                                        e->defer_into->hs_dev, wsig};
     } else {
       // (twin windows reduce side by side: neither writes the shared device rows)
-      HIP_TRY(launch_reduce_rounds(partials, d_woff->as<uint32_t>(), planned0 + S.reach_rows,
+      HIP_TRY(launch_reduce_rounds(partials, slot->woff.as<uint32_t>(), planned0 + S.reach_rows,
                                    (reduce_side || twin) ? nullptr : stats,
                                    direct ? e->defer_into->hs_dev : nullptr, wsig, rs),
               "reduce rounds");
@@ -1287,9 +1281,9 @@ struct WindowRun {
   // memory (level mode: written there by the reduce itself); the window's end
   // event -- on s, or on rstream behind the reduce -- marks their arrival
   // unless the window ends signalled; ps_wait accumulates them.  Fills the
-  // Inflight slot.
+  // run slot.
   int finish_deferred() {
-    ps_engine::Inflight& f = *e->defer_into;
+    ps_engine::RunSlot& f = *e->defer_into;
     if (!host_stats_written)
       HIP_TRY(hipMemcpyAsync(f.hs, stats, static_cast<size_t>(r + 1 + S.reach_rows) * kNumCtr * 8,
                              hipMemcpyDeviceToHost, s),
@@ -1315,7 +1309,7 @@ struct WindowRun {
     f.kinds = e->round_kind;
     f.stream = s;
     remember_window();
-    if (e->host_timing) {
+    if (e->env.host_timing) {
       char tail[80];
       std::snprintf(tail, sizeof tail, ", prefix P %u%s", S.pre_P, overlap ? " (beside the previous window)" : "");
       host_timing_line("async window", tail);
@@ -1376,7 +1370,7 @@ struct WindowRun {
               "read apply stats");
     }
     HIP_TRY(hipStreamSynchronize(s), "sync");
-    if (S.mode == PS_MODE_FLOOD && e->flood_profile && e->flood_prof_waves) flood_profile_report(e);
+    if (S.mode == PS_MODE_FLOOD && e->env.flood_profile && e->flood_prof_waves) flood_profile_report(e);
     if (cprof) chain_profile_dump(e, planned0);
     if (std::string why; L.aligned && !split_aligned_window(st, hs.data(), r, L.true_rounds, L.split, &why))
       return e->fail(PS_E_DEVICE, "level-aligned window: reach counts disagree with the per-level counters (" + why + ")");
@@ -1388,10 +1382,10 @@ struct WindowRun {
       // fresh generation, and keep those from now on.
       e->flood_broken = true;
       *st = keep;
-      if (e->host_timing) std::fprintf(stderr, "[psengine] k_flood timed out: window re-run per round\n");
+      if (e->env.host_timing) std::fprintf(stderr, "[psengine] k_flood timed out: window re-run per round\n");
       return run_window(e, msgs, win, st);
     }
-    if (e->host_timing) {
+    if (e->env.host_timing) {
       char tail[80];
       std::snprintf(tail, sizeof tail, ", wait %.3f ms, tail %.3f ms",
                     std::chrono::duration<double, std::milli>(t_sync - t_enq).count(),
@@ -1669,7 +1663,7 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer) {
     }
     // the prune's questions, asked with this phase's rebuild (graph.cpp)
     e->early_q.clear();
-    if (any && e->graph_dirty && e->gpu_build_on)
+    if (any && e->graph_dirty && e->opts.gpu_build)
       for (uint32_t t = 0; t < nt; ++t) {
         TopicHost& T = e->topics[t];
         if (!(T.exists && T.kind == Kind::Join && rest[t].n && T.tree.parts_only_pass())) continue;
@@ -1700,7 +1694,7 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer) {
           if (eq.ready && eq.topic == static_cast<uint32_t>(&T - e->topics.data()) && eq.peers.size() == k &&
               std::equal(peers.begin(), peers.end(), eq.peers.begin())) {
             outv = eq.out;
-            if (e->host_timing) std::fprintf(stderr, "[psengine] prune reach query: %u parents, from the rebuild\n", k);
+            if (e->env.host_timing) std::fprintf(stderr, "[psengine] prune reach query: %u parents, from the rebuild\n", k);
             return PS_OK;
           }
         // (its own stream: the GPU build ended with a stream sync, so the node
@@ -1718,7 +1712,7 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer) {
                 "reach query");
         HIP_TRY(hipMemcpyAsync(outv.data(), dout, k, hipMemcpyDeviceToHost, qs), "read reach query");
         HIP_TRY(hipStreamSynchronize(qs), "sync");
-        if (e->host_timing)
+        if (e->env.host_timing)
           std::fprintf(stderr, "[psengine] prune reach query: %u parents, done at %.3f ms\n", k,
                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - e->t_run0).count());
         return PS_OK;
@@ -1730,7 +1724,7 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer) {
   }
   e->early_q.clear();
   e->have_hops = record;
-  if (e->host_timing)
+  if (e->env.host_timing)
     std::fprintf(stderr, "[psengine] after-message prune %.3f ms (started at %.3f ms)\n",
                  std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_am).count(),
                  std::chrono::duration<double, std::milli>(t_am - e->t_run0).count());
@@ -1762,7 +1756,7 @@ int ps_run_async(ps_engine* e) {
   if (!e) return PS_E_INVAL;
   if (e->host_only) return e->fail(PS_E_STATE, "planner probe: no device");
   if (e->infl_count >= 2) return e->fail(PS_E_STATE, "two runs in flight: ps_wait first");
-  ps_engine::Inflight& f = e->infl[(e->infl_head + e->infl_count) % 2];
+  ps_engine::RunSlot& f = e->slot[(e->infl_head + e->infl_count) % 2];
   f.st = ps_stats{};
   f.deferred = false;
   f.stream = nullptr;
@@ -1794,7 +1788,7 @@ int ps_run_async(ps_engine* e) {
 int ps_wait(ps_engine* e, ps_stats* out) {
   if (!e) return PS_E_INVAL;
   if (!e->infl_count) return e->fail(PS_E_NOTREADY, "no asynchronous run pending");
-  ps_engine::Inflight& f = e->infl[e->infl_head];
+  ps_engine::RunSlot& f = e->slot[e->infl_head];
   e->infl_head = (e->infl_head + 1) % 2;
   --e->infl_count;
   if (e->pend_reduce.valid && e->pend_reduce.owner == &f) {

@@ -628,6 +628,42 @@ def test_plan_opts_defaults_pinned():
         PL.Plan(parent[None, :], [0]).set_plan(chain_max=7)
 
 
+def test_plan_opts_round_trip_every_field():
+    """Every ps_plan_opts field, set alone to a legal non-default value, reads
+    back as set and leaves the others alone; one value outside each range
+    check_opts states is refused with PS_E_INVAL and changes nothing.  The
+    field list is PlanOpts._fields_: a new option without a case fails here."""
+    legal = {"flood_top_bytes": 1 << 20, "overlap_min_bytes": 1 << 30, "launch_bytes": (1 << 53) + 1,
+             "flood": 0, "chain_max": 2, "chain_max_groups": 3, "chain_tail": 0, "chain_words": 8192,
+             "flood_words": 1024, "pad_words": 8, "overlap": 0, "overlap_min_rounds": 5, "xchg_overlap": 1,
+             "gpu_build": 1, "flood_spin_ticks": 1_000_000, "chain_nt": 0, "chain_waves": 0,
+             "flood_min_rounds": 2, "align_groups": 0}
+    # one value outside each range of check_opts (the three byte counts and the
+    # spin bound have none)
+    illegal = {"chain_max": [0, 7], "chain_max_groups": [0, 7], "chain_words": [255, (1 << 20) + 1],
+               "flood_words": [63, (1 << 16) + 1], "pad_words": [1], "overlap_min_rounds": [1],
+               "xchg_overlap": [-2, 2], "flood": [2], "chain_tail": [2], "overlap": [2], "gpu_build": [2],
+               "chain_nt": [2], "chain_waves": [17], "flood_min_rounds": [0], "align_groups": [2]}
+    fields = [k for k, _ in PE.PlanOpts._fields_]
+    assert sorted(legal) == sorted(fields), "a plan option without a case"
+    assert set(illegal) <= set(fields)
+    parent = np.full(64, NONE, dtype=np.uint32)
+    parent[1:] = (np.arange(1, 64) - 1) // 2
+    for k in fields:
+        p = PL.Plan(parent[None, :], [0])
+        before = p.set_plan()  # (a probe: the defaults with gpu_build = 0)
+        assert before == {**PE.default_plan_opts(), "gpu_build": 0}
+        assert legal[k] != before[k], k
+        assert p.set_plan(**{k: legal[k]}) == {**before, k: legal[k]}, k
+        after = p.set_plan()
+        for bad in illegal.get(k, []):
+            with pytest.raises(PE.EngineError) as ei:
+                p.set_plan(**{k: bad})
+            assert ei.value.code == -1, (k, bad)  # PS_E_INVAL
+            assert p.set_plan() == after, (k, bad)
+        p.close()
+
+
 def wide_span_tree():
     """Level 1: 200 nodes; level 2: 700 children each (140,000 nodes), of
     which only the first and the last have children (2 each); levels 4 and 5
