@@ -1,6 +1,7 @@
 // drain.cpp -- the plain drain (drain_impl.hpp):
 // ps_drain, ps_drain_begin / ps_drain_end, and the two slots the asynchronous
-// calls of either kind (this one, ps_drain_shared_begin) wait in.
+// calls of every kind (this one, ps_drain_shared_begin, ps_drain_topics_begin)
+// wait in.
 #include "drain_impl.hpp"
 
 using namespace psamd;
@@ -62,7 +63,10 @@ int drain_view_status(ps_engine* e, uint64_t err, uint32_t over) {
   if (err)
     return e->fail(PS_E_STATE, err & kDrainErrBit ? "drain tables: a window message bit past the row or shared"
                                                   : "drain tables: row bits do not ascend in arrival order");
-  if (over) return e->fail(PS_E_RANGE, over & kDrainOverLists ? "more lists than list_cap" : "more ids than id_cap");
+  if (over)
+    return e->fail(PS_E_RANGE, over & kDrainOverExc     ? "more exceptions than exc_cap"
+                               : over & kDrainOverLists ? "more lists than list_cap"
+                                                        : "more ids than id_cap");
   return PS_OK;
 }
 
@@ -227,7 +231,7 @@ int ps_drain_begin(ps_engine* e, const uint32_t* topic, const uint32_t* peer, si
   hipStream_t s = e->stream;
   // (written once the tables stand, not before their build: nothing reads a slot that is not taken)
   S.n = n;
-  S.shared = false;
+  S.kind = Drain::Slot::kPlain;
 
   // the queries, resolved straight into the slot's staging behind the tables
   DrainQuery* hq = reinterpret_cast<DrainQuery*>(h);
@@ -271,7 +275,9 @@ int ps_drain_end(ps_engine* e, const uint64_t** off_out, const uint32_t** msg_ou
   auto& D = e->drain;
   if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
   auto& S = D.slot[D.slot_head];
-  if (S.shared) return e->fail(PS_E_STATE, "the oldest drain is a shared one: ps_drain_shared_end");
+  if (S.kind != Drain::Slot::kPlain)
+    return e->fail(PS_E_STATE, S.kind == Drain::Slot::kShared ? "the oldest drain is a shared one: ps_drain_shared_end"
+                                                               : "the oldest drain is a topics one: ps_drain_topics_end");
   if (const int rc = drain_slot_complete(e, S)) return rc;
   const uint64_t* hdr = reinterpret_cast<const uint64_t*>(S.h_res);
   *off_out = hdr;

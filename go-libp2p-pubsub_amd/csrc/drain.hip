@@ -23,6 +23,11 @@
 //   k_audience_classify   one streaming pass over a topic's rows: a verdict
 //                         byte per node, the full and other nodes per strip
 //   k_audience_emit       the nodes that are not full, in node order
+// and, for ps_drain_topics_begin (§5.5g), which may not wait:
+//   k_audience_totals / _keys / _lists  per-topic totals from the strips'
+//                         counts, the lists numbered in request order and
+//                         their segments laid out, around two scans (the host
+//                         loop of ps_drain_topics on the device)
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -391,6 +396,123 @@ __global__ __launch_bounds__(kAudBlock) void k_audience_emit(AudArgs g, AudEmit 
   }
 }
 
+// ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
+// What the host loop of ps_drain_topics does between its waits.
+
+// the entry whose records hold record k: the last i < n with exc_off[i] <= k
+// (k below exc_off[n]: that entry is not empty)
+__device__ __forceinline__ uint32_t aud_entry_of(const uint64_t* __restrict__ exc_off, uint32_t n, uint64_t k) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (exc_off[mid] <= k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo - 1;  // (exc_off[0] = 0 <= k)
+}
+
+constexpr uint32_t kAudTotalsPer = 8;  // strip counts a thread has in flight
+
+// One block per entry (and one behind the last): the full nodes of its strips
+// summed -- a strided read, a wave sum, one LDS word per wave --, its first
+// record, and its key: it creates the topic's shared list if a node holds it.
+__global__ __launch_bounds__(kAudBlock) void k_audience_totals(AudAssign g) {
+  __shared__ uint64_t part[kAudBlock / kWave];
+  const uint32_t i = blockIdx.x;
+  if (i == g.n) {
+    if (threadIdx.x == 0) {
+      g.exc_off[i] = g.strip_off[g.n_strips];
+      g.ekey[i] = 0;
+    }
+    return;
+  }
+  const AudEntry E = g.entries[i];
+  const uint32_t s1 = g.entries[i + 1].strip0;
+  uint64_t sum = 0;
+  // (kAudTotalsPer loads in flight: a hot topic has 10^5 strips, and one load
+  // a turn leaves the block waiting on memory latency 400 times over)
+  for (uint32_t s0 = E.strip0 + threadIdx.x; s0 < s1; s0 += kAudBlock * kAudTotalsPer) {
+    uint32_t v[kAudTotalsPer];
+#pragma unroll
+    for (uint32_t k = 0; k < kAudTotalsPer; ++k) {
+      const uint32_t s = s0 + k * kAudBlock;
+      v[k] = s < s1 ? g.strip_full[s] : 0u;
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kAudTotalsPer; ++k) sum += v[k];
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) sum += shfl_u64(sum, static_cast<int>((threadIdx.x & (kWave - 1)) ^ m));
+  if ((threadIdx.x & (kWave - 1)) == 0) part[threadIdx.x / kWave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t full = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kAudBlock / kWave; ++w) full += part[w];
+    g.n_full[i] = full;
+    g.exc_off[i] = g.strip_off[E.strip0];
+    g.ekey[i] = full ? 1ull << 32 | E.segs : 0ull;
+  }
+}
+
+// One thread per record slot up to exc_cap (and one behind): a record that
+// holds a message creates a private list of its topic's segments
+__global__ __launch_bounds__(kAudBlock) void k_audience_keys(AudAssign g) {
+  const uint32_t k = blockIdx.x * kAudBlock + threadIdx.x;
+  if (k > g.exc_cap) return;
+  const uint64_t n_exc = g.strip_off[g.n_strips];
+  uint64_t key = 0;
+  if (k < g.exc_cap && k < n_exc && (g.rec_verdict[k] & kDrainRowAny))
+    key = 1ull << 32 | g.entries[aud_entry_of(g.exc_off, g.n, k)].segs;
+  g.rkey[k] = key;
+}
+
+// One thread per entry and per record slot: the list numbers and first
+// segments from the two sums.  Entry i's lists start behind the shared lists of
+// the entries before and the private lists of the records before its first;
+// record k's list lies behind its entry's shared one and the private lists of
+// the records before k.  Thread 0 leaves the counts in the control block.
+__global__ __launch_bounds__(kAudBlock) void k_audience_lists(AudAssign g) {
+  const uint32_t x = blockIdx.x * kAudBlock + threadIdx.x;
+  const uint64_t n_exc = g.strip_off[g.n_strips];
+  const uint32_t used = static_cast<uint32_t>(n_exc < g.exc_cap ? n_exc : g.exc_cap);
+  if (x < g.n) {
+    uint32_t mine = 0xFFFFFFFFu;  // (PS_NONE)
+    if (g.ekey[x]) {
+      const uint64_t e0 = g.exc_off[x];
+      const uint64_t at = g.ekey_off[x] + g.rkey_off[e0 < used ? e0 : used];
+      mine = static_cast<uint32_t>(at >> 32);
+      if (mine < g.list_cap) g.lists[mine] = DrainQuery{g.entries[x].topic, kDrainMaskRow, static_cast<uint32_t>(at), 0};
+    }
+    g.topic_list[x] = mine;
+  }
+  if (x < g.exc_cap) {
+    uint32_t mine = 0xFFFFFFFFu, peer = 0xFFFFFFFFu;
+    if (x < used) {
+      peer = g.rec_peer[x];
+      if (g.rkey[x]) {
+        const uint32_t i = aud_entry_of(g.exc_off, g.n, x);
+        const uint64_t at = g.ekey_off[i + 1] + g.rkey_off[x];
+        mine = static_cast<uint32_t>(at >> 32);
+        if (mine < g.list_cap) g.lists[mine] = DrainQuery{g.entries[i].topic, g.rec_node[x], static_cast<uint32_t>(at), 0};
+      }
+    }
+    g.exc_peer[x] = peer;
+    g.exc_list[x] = mine;
+  }
+  if (x == 0) {
+    const uint64_t all = g.ekey_off[g.n] + g.rkey_off[used];
+    DrainCtl c{};
+    c.n_lists = static_cast<uint32_t>(all >> 32);
+    c.n_segs = static_cast<uint32_t>(all);
+    c.over = (n_exc > g.exc_cap ? kDrainOverExc : 0u) |
+             (c.n_lists > g.list_cap || c.n_segs > g.seg_bound ? kDrainOverLists : 0u);
+    c.use_lists = c.over ? 0u : c.n_lists;
+    c.use_segs = c.over ? 0u : c.n_segs;
+    *g.ctl = c;
+  }
+}
+
 // ---- the window's drain tables built on the device (ps_drain_begin) ----------
 
 constexpr uint32_t kTabBlock = 256;
@@ -735,6 +857,23 @@ hipError_t launch_audience_emit(const AudArgs& g, const AudEmit& o, hipStream_t 
   if (g.n_strips == 0) return hipSuccess;
   const uint32_t per = kAudBlock / kWave;
   hipLaunchKernelGGL(k_audience_emit, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_assign(const AudAssign& g, hipStream_t s) {
+  const dim3 block(kAudBlock);
+  hipLaunchKernelGGL(k_audience_totals, dim3(g.n + 1), block, 0, s, g);
+  hipLaunchKernelGGL(k_audience_keys, dim3((g.exc_cap + 1 + kAudBlock - 1) / kAudBlock), block, 0, s, g);
+  hipError_t rc = hipGetLastError();
+  if (rc != hipSuccess) return rc;
+  size_t bytes = g.scan_bytes;
+  rc = hipcub::DeviceScan::ExclusiveSum(g.scan_temp, bytes, g.rkey, g.rkey_off, g.exc_cap + 1, s);
+  if (rc != hipSuccess) return rc;
+  bytes = g.scan_bytes;
+  rc = hipcub::DeviceScan::ExclusiveSum(g.scan_temp, bytes, g.ekey, g.ekey_off, g.n + 1, s);
+  if (rc != hipSuccess) return rc;
+  const uint32_t threads = g.n > g.exc_cap ? g.n : g.exc_cap;
+  hipLaunchKernelGGL(k_audience_lists, dim3((threads + kAudBlock - 1) / kAudBlock), block, 0, s, g);
   return hipGetLastError();
 }
 

@@ -8,7 +8,8 @@
 //   drain_sink.cpp    ps_sink_set / ps_sink_take and run.cpp's hooks (§5.5e):
 //                     the shared drain behind every window of a run
 //   drain_topics.cpp  ps_drain_topics (§5.5f): a topic's audience as one list
-//                     plus exceptions
+//                     plus exceptions; ps_drain_topics_begin / _end (§5.5g):
+//                     that answer behind a running batch
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -28,6 +29,12 @@
 //  - ps_drain_shared and ps_drain_topics run one tail over their list queries
 //    (drain_list_offsets, drain_list_ids) in Drain::Sync; the host numbers the
 //    lists, which is what the tests compare the device assignment against.
+//  - The three begin calls share the two slots (Slot::kind names the end call
+//    that completes one) and what surrounds them: drain_begin_slot,
+//    drain_give_up, drain_slot_host_view, drain_slot_enqueued, drain_slot_complete.
+//    ps_drain_topics_begin keeps its strips' verdicts, counts and records in
+//    the slot, not in Drain::Audience: a synchronous ps_drain_topics may run
+//    beside two outstanding drains.
 #pragma once
 #include <algorithm>
 #include <cstdio>

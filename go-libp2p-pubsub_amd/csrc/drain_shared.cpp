@@ -389,7 +389,7 @@ int ps_drain_shared_begin(ps_engine* e, const uint32_t* topic, const uint32_t* p
   if (!rows_fit) return drain_give_up(e, used, PS_E_RANGE, "too many rows in one drain");
 
   S.n = n;
-  S.shared = true;
+  S.kind = Drain::Slot::kShared;
   S.list_cap = list_cap;
   S.id_cap = id_cap;
   S.o_off = align256(sizeof(DrainSharedHdr));
@@ -440,7 +440,9 @@ int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t*
   auto& D = e->drain;
   if (D.slot_count == 0) return e->fail(PS_E_NOTREADY, "no drain outstanding");
   auto& S = D.slot[D.slot_head];
-  if (!S.shared) return e->fail(PS_E_STATE, "the oldest drain is not a shared one: ps_drain_end");
+  if (S.kind != Drain::Slot::kShared)
+    return e->fail(PS_E_STATE, S.kind == Drain::Slot::kPlain ? "the oldest drain is not a shared one: ps_drain_end"
+                                                              : "the oldest drain is a topics one: ps_drain_topics_end");
   if (const int rc = drain_slot_complete(e, S)) return rc;
   const DrainSharedHdr* hdr = reinterpret_cast<const DrainSharedHdr*>(S.h_res);
   *list_out = reinterpret_cast<const uint32_t*>(S.h_res + S.o_lq);

@@ -630,9 +630,18 @@ struct ps_engine {
       // ps_drain_shared_begin takes the same slots.  Its
       // view: a DrainSharedHdr, then list_off[list_cap + 1], list_of_query[n]
       // and ids[id_cap] at o_*
-      bool shared = false;
+      enum Kind { kPlain, kShared, kTopics } kind = kPlain;  // whose end call completes it
       size_t list_cap = 0, id_cap = 0;
       size_t o_off = 0, o_lq = 0, o_ids = 0;
+      // ps_drain_topics_begin too.  Its view: a
+      // DrainSharedHdr, then topic_list[n], n_full[n], exc_off[n + 1],
+      // exc_peer[exc_cap], exc_list[exc_cap], list_off[list_cap + 1] (o_off)
+      // and ids[id_cap] (o_ids); behind what the device writes, n_nodes[n]
+      // from the host.  The strips' verdicts, counts and records are the
+      // slot's own: two drains may be outstanding beside a synchronous call.
+      size_t exc_cap = 0;
+      size_t o_tl = 0, o_nf = 0, o_eo = 0, o_ep = 0, o_el = 0, o_nn = 0;
+      psamd::DevBuf d_verdict, d_exc, d_full, d_rec;
     } slot[2];
     uint32_t slot_head = 0, slot_count = 0;
 

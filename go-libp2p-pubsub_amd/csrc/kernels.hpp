@@ -667,6 +667,7 @@ hipError_t launch_drain_classify(const DrainArgs& a, const DrainClassBin* bins, 
 // counts read from a control block -- the host knows only the caps.
 constexpr uint32_t kDrainOverLists = 1;  // DrainCtl.over: more lists than list_cap
 constexpr uint32_t kDrainOverIds = 2;    // ... more ids than id_cap
+constexpr uint32_t kDrainOverExc = 4;    // ... more exception records than exc_cap (ps_drain_topics_begin)
 struct DrainCtl {
   uint32_t n_lists, n_segs;  // exact, whatever the caps
   uint32_t use_lists, use_segs;  // what the passes behind run over: the above, or 0 past list_cap
@@ -757,6 +758,53 @@ struct AudEmit {
   uint64_t cap;
 };
 hipError_t launch_audience_emit(const AudArgs& g, const AudEmit& o, hipStream_t s);
+// the exception records ps_drain_topics brings with its first copy; the most
+// ps_drain_topics_begin's own exc_cap holds
+constexpr uint64_t kAudPrefix = 1ull << 16;
+
+// ---- a topic's audience in two halves (ps_drain_topics_begin) --
+// What ps_drain_topics does on the host between its waits, on the device: the
+// per-topic totals from the strips' counts, then the lists numbered in request
+// order -- entry i's shared list if a node holds it, then a private one per
+// "any" record of [exc_off[i], exc_off[i + 1]) -- and their segments laid out,
+// around two exclusive sums of creates << 32 | segments keys (as k_drain_keys):
+// one over the entries, one over the first exc_cap records.  The lists then go
+// through k_drain_count_dev / _offsets_dev / _emit_dev.
+struct AudEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t segs;    // segments of one of the topic's lists
+  uint32_t pad;
+};
+struct AudAssign {
+  const AudEntry* entries;     // [n + 1]
+  uint32_t n, n_strips;
+  const uint32_t* strip_full;  // [n_strips] AudArgs::n_full
+  const uint64_t* strip_off;   // [n_strips + 1] the exclusive sum of AudArgs::n_exc
+  const uint32_t* rec_peer;    // the records k_audience_emit wrote
+  const uint32_t* rec_node;
+  const uint8_t* rec_verdict;
+  uint32_t exc_cap, list_cap;
+  uint32_t seg_bound;          // segments list_cap lists hold at most
+  uint64_t* ekey;              // [n + 1] an entry's key (a shared list); ekey_off: its exclusive sum
+  uint64_t* ekey_off;
+  uint64_t* rkey;              // [exc_cap + 1] a record's key (a private list), zero from the record count on
+  uint64_t* rkey_off;
+  void* scan_temp;
+  size_t scan_bytes;
+  uint32_t* topic_list;        // the view: [n]
+  uint64_t* n_full;            // [n]
+  uint64_t* exc_off;           // [n + 1]
+  uint32_t* exc_peer;          // [exc_cap]
+  uint32_t* exc_list;          // [exc_cap]
+  DrainQuery* lists;           // [list_cap]
+  DrainCtl* ctl;
+};
+// k_audience_totals, k_audience_keys, the two scans, k_audience_lists: n_full
+// and exc_off exact whatever the caps; exc_peer / exc_list for the records
+// below exc_cap (PS_NONE behind the count); nothing stored past a cap; the
+// control block with kDrainOverExc / kDrainOverLists.
+hipError_t launch_audience_assign(const AudAssign& g, hipStream_t s);
 
 // ---- the sink: every window of a run into one result (ps_sink_set) --
 // The run cursor: what the windows so far have added to the result.  Two of

@@ -164,6 +164,10 @@ PROTOTYPES = [
     ("ps_drain_topics", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p),
                                   C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p),
                                   C.POINTER(_u32p), _u32p, _u64p]),
+    ("ps_drain_topics_begin", C.c_int, [_P, _u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    ("ps_drain_topics_end", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p), C.POINTER(_u64p),
+                                      C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p,
+                                      _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -306,7 +310,7 @@ class Engine:
             raise EngineError(rc, "ps_create failed (is a GPU visible?)")
         self._h = h
         self._L = L
-        self._drain_n = []  # (shared, query count) of the drains begun and not ended
+        self._drain_n = []  # (kind: 0 plain, 1 shared, 2 topics; entries) of the drains begun and not ended
         self._sink_n = 0  # standing queries (sink_set)
         if plan:
             self.set_plan(**plan)
@@ -518,7 +522,7 @@ class Engine:
         two may be outstanding.  drain_end() completes the oldest."""
         t, p, tp, pp = _queries(topics, peers)
         self._check(self._L.ps_drain_begin(self._h, tp, pp, t.size))
-        self._drain_n.append((False, t.size))
+        self._drain_n.append((0, t.size))
 
     def drain_end(self, copy: bool = True):
         """(off, ids) of the oldest drain_begin, as drain() returns them
@@ -526,8 +530,8 @@ class Engine:
         valid until the next drain_begin."""
         op, mp, total = _u64p(), _u32p(), C.c_uint64()
         rc = self._L.ps_drain_end(self._h, C.byref(op), C.byref(mp), C.byref(total))
-        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is a shared one)
-        if rc != -8 and self._drain_n and not self._drain_n[0][0]:
+        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is of another kind)
+        if rc != -8 and self._drain_n and self._drain_n[0][0] == 0:
             n = self._drain_n.pop(0)[1]
         self._check(rc)
         off, ids = _view(op, n + 1, np.uint64), _view(mp, total.value, np.uint32)
@@ -541,7 +545,7 @@ class Engine:
         the oldest."""
         t, p, tp, pp = _queries(topics, peers)
         self._check(self._L.ps_drain_shared_begin(self._h, tp, pp, t.size, list_cap, id_cap))
-        self._drain_n.append((True, t.size))
+        self._drain_n.append((1, t.size))
 
     def drain_shared_end(self, copy: bool = True):
         """(list_of_query, list_off, ids) of the oldest drain_shared_begin, as
@@ -552,8 +556,8 @@ class Engine:
         n_lists, total = C.c_uint32(), C.c_uint64()
         rc = self._L.ps_drain_shared_end(self._h, C.byref(lp), C.byref(op), C.byref(mp), C.byref(n_lists),
                                          C.byref(total))
-        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is not a shared one)
-        if rc != -8 and self._drain_n and self._drain_n[0][0]:
+        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is of another kind)
+        if rc != -8 and self._drain_n and self._drain_n[0][0] == 1:
             n = self._drain_n.pop(0)[1]
         self._check(rc)
         lists = _view(lp, n, np.uint32)
@@ -605,6 +609,52 @@ class Engine:
         def arr(p, k, dt):
             return _view(p, k, dt).copy()
 
+        exc_off = arr(eo, n + 1, np.uint64)
+        n_exc = int(exc_off[n])
+        return {"topic_list": arr(tl, n, np.uint32), "n_nodes": arr(nn, n, np.uint64), "n_full": arr(nf, n, np.uint64),
+                "exc_off": exc_off, "exc_peer": arr(ep, n_exc, np.uint32), "exc_list": arr(el, n_exc, np.uint32),
+                "list_off": arr(lo, n_lists.value + 1, np.uint64), "ids": arr(mp, total.value, np.uint32)}
+
+    def drain_topics_begin(self, topics, exc_cap: int = 0, list_cap: int = 0, id_cap: int = 0):
+        """Enqueues drain_topics(topics) of the last window of the last run
+        enqueued (ps_drain_topics_begin) and returns without waiting for it;
+        it shares drain_begin's two slots.  A cap of 0: the engine's own.
+        drain_topics_end() completes the oldest."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_drain_topics_begin(self._h, _p(t, C.c_uint32), t.size, exc_cap, list_cap, id_cap))
+        self._drain_n.append((2, t.size))
+
+    def drain_topics_end(self, copy: bool = True) -> dict:
+        """The oldest drain_topics_begin's answer, the dict drain_topics()
+        returns (ps_drain_topics_end).  copy=False: views of the engine's
+        pinned memory, valid until the next begin of any kind.  When the
+        answer exceeded a cap the EngineError (PS_E_RANGE) carries `partial`:
+        n_nodes, n_full and exc_off, exact whatever the caps, and n_lists and
+        total, exact when the exceptions and the lists fit."""
+        tl, ep, el, mp = _u32p(), _u32p(), _u32p(), _u32p()
+        nn, nf, eo, lo = _u64p(), _u64p(), _u64p(), _u64p()
+        n_lists, total = C.c_uint32(), C.c_uint64()
+        rc = self._L.ps_drain_topics_end(self._h, C.byref(tl), C.byref(nn), C.byref(nf), C.byref(eo), C.byref(ep),
+                                         C.byref(el), C.byref(lo), C.byref(mp), C.byref(n_lists), C.byref(total))
+        # (no slot was completed: PS_E_NOTREADY, or the oldest drain is of another kind)
+        done = rc != -8 and self._drain_n and self._drain_n[0][0] == 2
+        if done:
+            n = self._drain_n.pop(0)[1]
+
+        def arr(p, k, dt):
+            v = _view(p, k, dt)
+            return v.copy() if copy else v
+
+        if rc == -7 and done and tl:
+            err = EngineError(rc, self._L.ps_last_error(self._h).decode())
+            err.partial = {"n_nodes": _view(nn, n, np.uint64).copy(), "n_full": _view(nf, n, np.uint64).copy(),
+                           "exc_off": _view(eo, n + 1, np.uint64).copy(),
+                           # (exact when the exceptions and the lists fit)
+                           "n_lists": n_lists.value, "total": total.value}
+            raise err
+        self._check(rc)
         exc_off = arr(eo, n + 1, np.uint64)
         n_exc = int(exc_off[n])
         return {"topic_list": arr(tl, n, np.uint32), "n_nodes": arr(nn, n, np.uint64), "n_full": arr(nf, n, np.uint64),

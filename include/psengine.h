@@ -456,6 +456,50 @@ int ps_drain_topics(ps_engine* e, const uint32_t* topic, size_t n,
                     const uint64_t** list_off_out,    /* [n_lists + 1]       */
                     const uint32_t** msg_out,         /* [total]             */
                     uint32_t* n_lists_out, uint64_t* total_out);
+/* ps_drain_topics in two halves, for pipelined batches: ps_drain_topics'
+ * answer for the window ps_drain_begin reads (the last window of the last run
+ * enqueued, whether or not ps_wait has returned for it), enqueued behind that
+ * run with no wait in between -- the per-topic totals and the list numbering
+ * are computed on the GPU.  ps_drain_topics_end completes the oldest drain
+ * begun and lends the ten outputs from pinned memory the engine owns, entry
+ * for entry what ps_drain_topics returns for that window; they stay valid
+ * until the next begin call of any kind, or ps_destroy.
+ *   The view is sized by caps, since the host cannot know the counts without
+ * waiting: at most exc_cap exception records, list_cap lists and id_cap ids.
+ * A cap of zero selects the engine's own (all three zero: the engine's caps):
+ * exc_cap = the non-root nodes of the named topics that have window messages,
+ * 65,536 at most; list_cap = one list per named topic with window messages
+ * plus one per non-root node of a named mesh topic whose window has several
+ * start rounds; id_cap = those lists' window message counts, summed -- the
+ * size of the answer while every reached row is full.  An id cap above 2^30
+ * returns PS_E_RANGE, as does list_cap x the widest named topic's segments at
+ * or above 2^31 - 1: use ps_drain_topics.  When the answer exceeds a cap
+ * nothing is written past it, no id is emitted and ps_drain_topics_end
+ * returns PS_E_RANGE; n_nodes, n_full and exc_off are exact then, whatever
+ * the caps (retry with exc_cap = exc_off[n]), exc_peer and exc_list are exact
+ * for the records below exc_cap, and *n_lists_out, list_off and *total_out are
+ * exact when the exceptions and the lists fit.
+ *   The two slots are ps_drain_begin's: at most two drains of any kind are
+ * outstanding, completed oldest first, each by the end call of its kind (the
+ * others return PS_E_STATE and complete nothing).  A third begin returns
+ * PS_E_STATE; an end with none outstanding and a begin before any run return
+ * PS_E_NOTREADY.  PS_E_INVAL for a NULL output, n > 0 without topic, or a
+ * topic named twice; PS_E_RANGE for a topic out of range, with nothing
+ * enqueued and no slot taken; PS_E_STATE on a multi-rank engine; n == 0 is a
+ * valid drain; ps_drain_topics_end returns PS_E_STATE when the device-side
+ * check of the window's tables failed. */
+int ps_drain_topics_begin(ps_engine* e, const uint32_t* topic, size_t n, size_t exc_cap, size_t list_cap,
+                          size_t id_cap);
+int ps_drain_topics_end(ps_engine* e,
+                        const uint32_t** topic_list_out,  /* [n]                 */
+                        const uint64_t** n_nodes_out,     /* [n]                 */
+                        const uint64_t** n_full_out,      /* [n]                 */
+                        const uint64_t** exc_off_out,     /* [n + 1]             */
+                        const uint32_t** exc_peer_out,    /* [min(exc_off[n], exc_cap)] */
+                        const uint32_t** exc_list_out,    /* [min(exc_off[n], exc_cap)] */
+                        const uint64_t** list_off_out,    /* [n_lists + 1]       */
+                        const uint32_t** msg_out,         /* [total]             */
+                        uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -57,6 +57,17 @@ every subscription in the node space as explicit queries -- both wall clocks,
 the host share of each, and that the expanded answers agree -- and (b) the
 device time of k_digest (ps_seen_digest), which reads the same rows once under
 the same generation test.  Writes DIR/drain_topics_bench.json.
+
+--pipelined --topics: the audience drain in two halves (ps_drain_topics_begin /
+ps_drain_topics_end) over every topic inside the pipelined step loop, three
+loops alternating in one process, --reps timings each: (i) no drain, (ii)
+ps_run then ps_drain_topics, (iii) publish, ps_run_async,
+ps_drain_topics_begin, ps_wait and ps_drain_topics_end of the previous; wall
+ms/step, the host time inside the begin call, the view's and the upload's
+bytes, ps_overlapped_windows(), the answers of (ii) and (iii) compared entry
+for entry, and whether (iii) beats (ii) by more than (ii)'s own spread; then,
+on a quiet engine with PSAMD_DRAIN_TIMING=1, the device time of the passes.
+Writes DIR/drain_topics_async_bench.json.
 """
 from __future__ import annotations
 
@@ -657,6 +668,105 @@ def topics_main(a, wl):
         with open(os.path.join(a.out, "drain_topics_bench.json"), "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
 
+TOPIC_KEYS = ("topic_list", "n_nodes", "n_full", "exc_off", "exc_peer", "exc_list", "list_off")
+
+
+def loop_topics_serial(eng, wl, n, topics):
+    r = None
+    for _ in range(n):
+        eng.publish(wl.msg_topics)
+        eng.run()
+        r = eng.drain_topics(topics)
+    return r
+
+
+def loop_topics_async(eng, wl, n, topics, exc_cap, begin_s):
+    """Loop (iii) with ps_drain_topics_begin / _end.  Returns the last view (copies)."""
+    L, h = eng._L, eng._h
+    tp = topics.ctypes.data_as(C.POINTER(C.c_uint32))
+    r = None
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        eng.run_async()
+        t0 = time.perf_counter()
+        rc = L.ps_drain_topics_begin(h, tp, topics.size, exc_cap, 0, 0)
+        begin_s.append(time.perf_counter() - t0)
+        assert rc == 0, rc
+        eng._drain_n.append((2, topics.size))
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            r = eng.drain_topics_end(copy=False)
+    eng.wait()
+    r = eng.drain_topics_end()
+    return r
+
+
+def pipelined_topics_main(a, wl):
+    topics = np.arange(len(wl.topics), dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": int(topics.size),
+           "steps": a.steps, "warmup": a.warmup, "reps": a.reps}
+    # the passes' device time, each run apart and waited for (not a wall figure)
+    eng = fresh_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        with StderrCapture():
+            exc_cap = max(int(eng.drain_topics(topics)["exc_off"][-1]), 1)  # (every step publishes the same batch)
+        rows = []
+        for _ in range(a.reps + 1):  # (the first call allocates; each builds its window's tables)
+            eng.publish(wl.msg_topics)
+            eng.run()
+            with StderrCapture() as cap:
+                eng.drain_topics_begin(topics, exc_cap=exc_cap)
+                want = eng.drain_topics_end()
+            row = phase_line(cap.text, "drain_topics_begin")
+            for k in ("strips", "nodes", "row_bytes", "exc_cap", "list_cap", "id_cap", "seg_bound", "upload_bytes", "view_bytes"):
+                row[k] = int(re.search(rf"\b{k} (\d+)", cap.text).group(1))
+            row["host_us"] = float(re.search(r"host_us ([0-9.]+)", cap.text).group(1))
+            rows.append(row)
+        res["device_phases"] = rows[1:]
+        with StderrCapture():
+            sync = eng.drain_topics(topics)
+        assert all(np.array_equal(want[k], sync[k]) for k in TOPIC_KEYS) and np.array_equal(want["ids"], sync["ids"])
+    res.update(exceptions=int(want["exc_off"][-1]), lists=int(want["list_off"].size - 1), ids=int(want["ids"].size),
+               view_bytes=rows[-1]["view_bytes"], upload_bytes=rows[-1]["upload_bytes"])
+    eng = fresh_engine(wl, {})
+    with eng:
+        loop_plain(eng, wl, a.warmup)
+        loop_topics_serial(eng, wl, a.warmup, topics)
+        loop_topics_async(eng, wl, a.warmup, topics, exc_cap, [])
+        plain, serial, asyn, begin_us, over = [], [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            loop_plain(eng, wl, a.steps)
+            plain.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            t0 = time.perf_counter()
+            rs = loop_topics_serial(eng, wl, a.steps, topics)
+            serial.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            o0 = eng.overlapped_windows()
+            begin_s = []
+            t0 = time.perf_counter()
+            ra = loop_topics_async(eng, wl, a.steps, topics, exc_cap, begin_s)
+            asyn.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            over.append(eng.overlapped_windows() - o0)
+            begin_us.append({"median": 1e6 * float(np.median(begin_s)), "max": 1e6 * float(np.max(begin_s))})
+            # entry for entry (every step publishes the same batch under new ids)
+            assert all(np.array_equal(ra[k], rs[k]) for k in TOPIC_KEYS), "loop (iii) differs from loop (ii)"
+            assert np.array_equal(norm(ra["ids"]), norm(rs["ids"])), "loop (iii) differs from loop (ii)"
+    res.update(plain_ms_per_step=plain, serial_ms_per_step=serial, async_ms_per_step=asyn, begin_host_us=begin_us,
+               async_overlapped_windows=over, answers_agree=True)
+    res["serial_spread_ms"] = max(serial) - min(serial)
+    res["serial_minus_async_ms"] = float(np.median(serial) - np.median(asyn))
+    res["async_faster_than_serial_by_more_than_its_spread"] = bool(res["serial_minus_async_ms"] > res["serial_spread_ms"])
+    res["async_minus_plain_ms"] = float(np.median(asyn) - np.median(plain))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "drain_topics_async_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
 
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
@@ -801,6 +911,8 @@ def main():
     ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.pipelined and a.topics:
+        return pipelined_topics_main(a, wl)
     if a.topics:
         return topics_main(a, wl)
     if a.sink:
