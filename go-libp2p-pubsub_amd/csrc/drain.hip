@@ -769,7 +769,60 @@ __global__ __launch_bounds__(kWave) void k_sink_emit(DrainArgs a, const DrainCtl
   emit_segment<true>(a, blockIdx.x, off, 0, out + base, id_cap - base, stage);
 }
 
+// The audience sink's commit (ps_sink_set_topics): k_sink_commit's part for the
+// window's lists, and the window's audience view into the run's -- row w of
+// topic_list (rebased, PS_NONE kept) and n_full, exc_off[w * n + i] from the
+// run's exact record count (the entry behind the row too: the next window
+// writes the same value there), the records below the window's cap at that
+// count, exc_list rebased.  Every thread reads cur[w & 1]; thread 0 alone
+// writes cur[(w + 1) & 1].  Plain loads and stores; nothing past a cap.
+__global__ __launch_bounds__(kTabBlock) void k_audience_sink_commit(AudSinkCommit c) {
+  const uint32_t i = blockIdx.x * kTabBlock + threadIdx.x;
+  const SinkCursor C = c.cur[c.w & 1];
+  const DrainCtl ctl = *c.ctl;
+  const uint64_t total = c.seg_off[ctl.use_segs];
+  const uint64_t n_exc = c.win_exc_off[c.n];
+  const uint64_t row = static_cast<uint64_t>(c.w) * c.n;
+  if (i <= ctl.use_lists && i <= c.win_list_cap) {
+    const uint64_t at = static_cast<uint64_t>(C.lists) + i;
+    if (at <= c.list_cap) c.list_off[at] = C.ids + (i < ctl.use_lists ? c.seg_off[c.lists[i].seg0] : total);
+  }
+  if (i < c.n) {
+    const uint32_t v = c.win_topic_list[i];
+    c.topic_list[row + i] = v == 0xFFFFFFFFu ? v : C.lists + v;  // (PS_NONE stays)
+    c.n_full[row + i] = c.win_n_full[i];
+  }
+  if (i <= c.n) c.exc_off[row + i] = C.exc + c.win_exc_off[i];
+  if (i < c.win_exc_cap && i < n_exc) {
+    const uint64_t at = C.exc + i;
+    if (at < c.exc_cap) {
+      const uint32_t v = c.win_exc_list[i];
+      c.exc_peer[at] = c.win_exc_peer[i];
+      c.exc_list[at] = v == 0xFFFFFFFFu ? v : C.lists + v;
+    }
+  }
+  if (i == 0) {
+    SinkCursor N{};
+    N.ids = C.ids + total;
+    N.lists = C.lists + ctl.n_lists;
+    N.windows = C.windows + 1;
+    N.exc = C.exc + n_exc;
+    N.over = C.over | ctl.over | (static_cast<uint64_t>(C.lists) + ctl.n_lists > c.list_cap ? kDrainOverLists : 0u) |
+             (C.ids + total > c.id_cap ? kDrainOverIds : 0u) | (N.exc > c.exc_cap ? kDrainOverExc : 0u);
+    N.err = C.err | *c.err;
+    c.cur[(c.w + 1) & 1] = N;
+  }
+}
+
 }  // namespace
+
+hipError_t launch_audience_sink_commit(const AudSinkCommit& c, hipStream_t s) {
+  uint32_t threads = c.n + 1;
+  if (c.win_list_cap + 1 > threads) threads = c.win_list_cap + 1;
+  if (c.win_exc_cap > threads) threads = c.win_exc_cap;
+  hipLaunchKernelGGL(k_audience_sink_commit, dim3((threads + kTabBlock - 1) / kTabBlock), dim3(kTabBlock), 0, s, c);
+  return hipGetLastError();
+}
 
 hipError_t launch_sink_commit(const SinkCommit& c, hipStream_t s) {
   const uint32_t threads = c.win_list_cap + 1 > c.n ? c.win_list_cap + 1 : c.n;

@@ -6,7 +6,9 @@
 //   drain_shared.cpp  ps_drain_shared, ps_drain_shared_begin / _end (§5.5c, d),
 //                     the shared-list pass and the synchronous list tail
 //   drain_sink.cpp    ps_sink_set / ps_sink_take and run.cpp's hooks (§5.5e):
-//                     the shared drain behind every window of a run
+//                     the shared drain behind every window of a run; and
+//                     ps_sink_set_topics / ps_sink_take_topics (§5.5h): the
+//                     audience drain behind every window, through the same hooks
 //   drain_topics.cpp  ps_drain_topics (§5.5f): a topic's audience as one list
 //                     plus exceptions; ps_drain_topics_begin / _end (§5.5g):
 //                     that answer behind a running batch
@@ -26,6 +28,10 @@
 //    over each row set) are read by drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
+//  - ps_drain_topics_begin and the audience sink run one pass over their topics
+//    (aud_stage, aud_caps, aud_pass), each with buffers of its own; the sink
+//    keeps its entries and strips on the device between windows of one shape
+//    (Sink::strip_key), the begin call uploads them per call.
 //  - ps_drain_shared and ps_drain_topics run one tail over their list queries
 //    (drain_list_offsets, drain_list_ids) in Drain::Sync; the host numbers the
 //    lists, which is what the tests compare the device assignment against.
@@ -46,6 +52,7 @@ namespace psamd {
 
 using Drain = ps_engine::Drain;
 using SharedSort = Drain::SharedSort;
+using AudShape = Drain::AudShape;
 using hclock = std::chrono::steady_clock;
 
 inline double ms_since(hclock::time_point t0) { return std::chrono::duration<double, std::milli>(hclock::now() - t0).count(); }
@@ -169,5 +176,42 @@ int drain_list_offsets(ps_engine* e, DrainArgs& a, const std::vector<DrainQuery>
                        std::vector<uint64_t>& hdr, const PhaseTimer& tm, float& count_ms, float& scan_ms);
 int drain_list_ids(ps_engine* e, const DrainArgs& a, uint32_t n_segs, uint64_t total, void* out, const PhaseTimer& tm,
                    float& emit_ms, float& copy_ms);
+
+
+// ---- drain_topics.cpp -------------------------------------------------------------
+
+// the checks every topics call makes on its topics: range, then repeats
+int aud_check_topics(ps_engine* e, const uint32_t* topic, size_t n);
+// topic t's non-root nodes in the last window: the first one and their number
+uint32_t aud_nodes(const ps_engine* e, uint32_t t, uint32_t* u0);
+
+// the bytes one window's entries and strips take at most, before its tables
+// stand: entries | strips (the strips from *o_strips)
+size_t aud_stage_bytes(ps_engine* e, const uint32_t* topic, size_t n, size_t* o_strips, uint64_t* strips_max);
+// The audience pass: ps_drain_topics_begin's, and the audience sink's per
+// window.  aud_stage cuts the entry table and the strips from the named topics'
+// node ranges in the last window into `entries` [n + 1] and `strips`
+// [strips_max] (false: more strips than staged; both null: the shape alone); aud_caps settles the three caps
+// (zero: the engine's) and the segment bound (false: too many rows); aud_pass
+// enqueues classify through the segment scan over entries and strips on the
+// device, into `view` (window-local) and the buffers' control block.
+bool aud_stage(ps_engine* e, const uint32_t* topic, size_t n, AudEntry* entries, AudStrip* strips, uint64_t strips_max,
+               AudShape* out);
+bool aud_caps(const AudShape& A, size_t n, size_t* exc_cap, size_t* list_cap, size_t* id_cap, uint32_t* seg_bound);
+struct AudBufs {
+  Drain::ListBufs* lb;  // d_key, d_aux (the control block), scratch: the lists, their counts, offsets, the scans' temporary
+  DevBuf *d_verdict, *d_exc, *d_full, *d_rec;
+};
+struct AudView {
+  uint32_t* topic_list;  // [n]
+  uint64_t* n_full;      // [n]
+  uint64_t* exc_off;     // [n + 1]
+  uint32_t* exc_peer;    // [exc_cap]
+  uint32_t* exc_list;    // [exc_cap]
+};
+// ms: classify, strip scan, records, assign, count, segment scan (PSAMD_DRAIN_TIMING)
+int aud_pass(ps_engine* e, const AudBufs& B, const AudEntry* d_entries, const AudStrip* d_strips, size_t n,
+             const AudShape& A, size_t exc_cap, size_t list_cap, uint32_t seg_bound, const AudView& view,
+             const PhaseTimer& tm, float* ms, DrainArgs* args, DrainCtl** ctl_out);
 
 }  // namespace psamd

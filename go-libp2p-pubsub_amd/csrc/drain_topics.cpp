@@ -21,8 +21,11 @@ uint32_t aud_strip_nodes(bool gather, uint32_t words) {
   return std::max(1u, kAudStripBytes / (lanes * 8));
 }
 
-// the checks both calls make on their topics, behind drain_enter
-int aud_check_topics(ps_engine* e, const uint32_t* topic, size_t n) {
+}  // namespace
+
+// ---- what the topics calls share ------------------------------------------------
+
+int psamd::aud_check_topics(ps_engine* e, const uint32_t* topic, size_t n) {
   const uint32_t nt = static_cast<uint32_t>(e->topics.size());
   for (size_t i = 0; i < n; ++i)
     if (topic[i] >= nt) return e->fail(PS_E_RANGE, "topic out of range");
@@ -32,14 +35,192 @@ int aud_check_topics(ps_engine* e, const uint32_t* topic, size_t n) {
   return PS_OK;
 }
 
-// topic t's non-root nodes in the last window: the first one and their number
-uint32_t aud_nodes(const ps_engine* e, uint32_t t, uint32_t* u0) {
+uint32_t psamd::aud_nodes(const ps_engine* e, uint32_t t, uint32_t* u0) {
   const TopicDev& d = e->last_topics[t];
   *u0 = (d.flags & kTopicRootLocal) ? 1 : 0;
   return d.n_nodes > *u0 ? d.n_nodes - *u0 : 0;
 }
 
-}  // namespace
+// ---- the audience pass (ps_drain_topics_begin, the audience sink) ---------------
+
+// The strips at most, before the tables stand (a staging is taken once, with
+// them): a topic's rows counted at the mask words its highest window bit
+// gives, as both table builds lay a mask out; an arrival-order topic's strips
+// are longer, so it takes fewer.
+size_t psamd::aud_stage_bytes(ps_engine* e, const uint32_t* topic, size_t n, size_t* o_strips, uint64_t* strips_max) {
+  uint64_t most = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t t = topic[i], cnt = e->last_cnt[t];
+    const TopicDev& d = e->last_topics[t];
+    uint32_t u0 = 0;
+    const uint32_t nn = aud_nodes(e, t, &u0);
+    if (!d.W || !cnt || !nn) continue;
+    const uint32_t* bits = window_bits(e, t);
+    const uint32_t top = bits ? *std::max_element(bits, bits + cnt) : cnt - 1;
+    const uint32_t per = aud_strip_nodes(false, std::min<uint32_t>(top >> 6, d.W - 1) + 1);
+    most += ceil_div(nn, per);
+  }
+  *strips_max = most;
+  *o_strips = align256((n + 1) * sizeof(AudEntry));
+  return *o_strips + most * sizeof(AudStrip);
+}
+
+bool psamd::aud_stage(ps_engine* e, const uint32_t* topic, size_t n, AudEntry* entries, AudStrip* strips,
+                      uint64_t strips_max, AudShape* out) {
+  const auto& D = e->drain;
+  AudShape A;
+  uint64_t ns64 = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t t = topic[i];
+    const DrainTopic& T = D.tab.topics[t];
+    uint32_t u0 = 0;
+    const uint32_t nn = aud_nodes(e, t, &u0);
+    const uint32_t segs = ceil_div(T.n_pos, kDrainSegBits);
+    if (entries) entries[i] = AudEntry{t, static_cast<uint32_t>(ns64), segs, 0};
+    if (!T.n_pos || !nn) continue;
+    const bool gather = T.flags & kDrainGather;
+    if (!gather) A.row_bytes += static_cast<uint64_t>(nn) * (T.n_pos / 64) * 8;
+    const uint32_t per = aud_strip_nodes(gather, T.n_pos / 64);
+    if (ns64 + ceil_div(nn, per) > strips_max) return false;
+    if (!strips) {
+      ns64 += ceil_div(nn, per);
+      A.n_verdicts += nn;
+    }
+    for (uint32_t k = 0; strips && k < nn; k += per) {
+      const uint32_t c = std::min(per, nn - k);
+      strips[ns64++] = AudStrip{t, u0 + k, c, e->last_topics[t].nbase, A.n_verdicts};
+      A.n_verdicts += c;
+    }
+    A.max_segs = std::max(A.max_segs, segs);
+    // the topic's shared list and a private one per node of an arrival-order
+    // topic; every node's where full rows do not share
+    const uint64_t lists = D.env.share ? 1 + (gather ? nn : 0) : nn;
+    A.own_lists += lists;
+    A.own_ids += lists * e->last_cnt[t];
+  }
+  A.ns = static_cast<uint32_t>(ns64);
+  if (entries) entries[n] = AudEntry{0, A.ns, 0, 0};
+  A.own_exc = std::max<uint64_t>(std::min<uint64_t>(A.n_verdicts, kAudPrefix), 1);
+  A.own_lists = std::max<uint64_t>(A.own_lists, 1);
+  *out = A;
+  return true;
+}
+
+bool psamd::aud_caps(const AudShape& A, size_t n, size_t* exc_cap, size_t* list_cap, size_t* id_cap, uint32_t* seg_bound) {
+  if (!*exc_cap) *exc_cap = A.own_exc;
+  if (!*list_cap) *list_cap = A.own_lists;
+  if (!*id_cap) *id_cap = A.own_ids;
+  const uint64_t bound = static_cast<uint64_t>(*list_cap) * A.max_segs;
+  // (the numbering scans keep the segments in the low half of their keys)
+  if (*list_cap >= 0x7FFFFFFFull || *exc_cap >= 0x7FFFFFFFull || bound >= kDrainRowLimit ||
+      (static_cast<uint64_t>(*exc_cap) + n) * A.max_segs >= kDrainRowLimit)
+    return false;
+  *seg_bound = static_cast<uint32_t>(bound);
+  return true;
+}
+
+int psamd::aud_pass(ps_engine* e, const AudBufs& B, const AudEntry* d_entries, const AudStrip* d_strips, size_t n,
+                    const AudShape& A, size_t exc_cap, size_t list_cap, uint32_t seg_bound, const AudView& view,
+                    const PhaseTimer& tm, float* ms, DrainArgs* args, DrainCtl** ctl_out) {
+  auto& D = e->drain;
+  hipStream_t s = e->stream;
+  auto& C = B.lb->scratch;
+  const uint32_t ns = A.ns;
+  const uint64_t n_verdicts = A.n_verdicts;
+  const size_t o_node = align256(n_verdicts * 4), o_v = 2 * o_node;
+  const size_t n_off = static_cast<size_t>(seg_bound) + 1;
+  HIP_TRY(B.lb->d_key.ensure(2 * (n + 1 + exc_cap + 1) * 8), "alloc drain keys");
+  HIP_TRY(B.lb->d_aux.ensure(align256(sizeof(DrainCtl))), "alloc drain control");
+  HIP_TRY(B.d_verdict->ensure(n_verdicts), "alloc audience verdicts");
+  HIP_TRY(B.d_exc->ensure(2 * (static_cast<size_t>(ns) + 1) * 8), "alloc audience counts");
+  HIP_TRY(B.d_full->ensure(static_cast<size_t>(ns) * 4), "alloc audience counts");
+  HIP_TRY(B.d_rec->ensure(o_v + n_verdicts), "alloc audience records");
+  HIP_TRY(C.d_queries.ensure(list_cap * sizeof(DrainQuery)), "alloc drain lists");
+  HIP_TRY(C.d_cnt.ensure(n_off * 8), "alloc drain counts");
+  HIP_TRY(C.d_off.ensure(n_off * 8), "alloc drain offsets");
+  uint64_t* const strip_cnt = B.d_exc->as<uint64_t>();
+  uint64_t* const strip_off = strip_cnt + ns + 1;
+  uint64_t* const ekey = B.lb->d_key.as<uint64_t>();
+  uint64_t* const rkey = ekey + 2 * (n + 1);
+  uint64_t* const cnt = C.d_cnt.as<uint64_t>();
+  uint64_t* const off = C.d_off.as<uint64_t>();
+  size_t scan_bytes = 0;  // one temporary for the four scans
+  for (const uint32_t len : {ns + 1, static_cast<uint32_t>(exc_cap) + 1, static_cast<uint32_t>(n) + 1, seg_bound + 1}) {
+    size_t b = 0;
+    HIP_TRY(drain_scan(nullptr, &b, cnt, off, len, s), "size drain scan");
+    scan_bytes = std::max(scan_bytes, b);
+  }
+  HIP_TRY(C.d_scan.ensure(scan_bytes), "alloc drain scan");
+
+  uint8_t* const rec = B.d_rec->as<uint8_t>();
+  DrainCtl* const ctl = B.lb->d_aux.as<DrainCtl>();
+  DrainArgs a = drain_args(e, D.tab);
+  AudArgs g{};
+  g.strips = d_strips;
+  g.n_strips = ns;
+  g.share = D.env.share;
+  g.verdict = B.d_verdict->as<uint8_t>();
+  g.n_exc = strip_cnt;
+  g.n_full = B.d_full->as<uint32_t>();
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
+  HIP_TRY(tm.end(ms[0]), "event");
+  HIP_TRY(tm.begin(), "event");
+  size_t sb = C.d_scan.bytes;
+  HIP_TRY(drain_scan(C.d_scan.p, &sb, strip_cnt, strip_off, ns + 1, s), "drain scan");
+  HIP_TRY(tm.end(ms[1]), "event");
+  AudEmit o{};
+  o.node_peer = e->d_node_peer.as<uint32_t>();
+  o.off = strip_off;
+  o.peer = reinterpret_cast<uint32_t*>(rec);
+  o.node = reinterpret_cast<uint32_t*>(rec + o_node);
+  o.verdict = rec + o_v;
+  o.cap = n_verdicts;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_emit(g, o, s), "k_audience_emit");
+  HIP_TRY(tm.end(ms[2]), "event");
+
+  AudAssign q{};
+  q.entries = d_entries;
+  q.n = static_cast<uint32_t>(n);
+  q.n_strips = ns;
+  q.strip_full = g.n_full;
+  q.strip_off = strip_off;
+  q.rec_peer = o.peer;
+  q.rec_node = o.node;
+  q.rec_verdict = o.verdict;
+  q.exc_cap = static_cast<uint32_t>(exc_cap);
+  q.list_cap = static_cast<uint32_t>(list_cap);
+  q.seg_bound = seg_bound;
+  q.ekey = ekey;
+  q.ekey_off = ekey + n + 1;
+  q.rkey = rkey;
+  q.rkey_off = rkey + exc_cap + 1;
+  q.scan_temp = C.d_scan.p;
+  q.scan_bytes = C.d_scan.bytes;
+  q.topic_list = view.topic_list;
+  q.n_full = view.n_full;
+  q.exc_off = view.exc_off;
+  q.exc_peer = view.exc_peer;
+  q.exc_list = view.exc_list;
+  q.lists = C.d_queries.as<DrainQuery>();
+  q.ctl = ctl;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_assign(q, s), "audience list assignment");
+  HIP_TRY(tm.end(ms[3]), "event");
+  a.queries = q.lists;
+  a.n_queries = 0;  // (the kernels read it from the control block)
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, cnt, s), "k_drain_count_dev");
+  HIP_TRY(tm.end(ms[4]), "event");
+  HIP_TRY(tm.begin(), "event");
+  sb = C.d_scan.bytes;
+  HIP_TRY(drain_scan(C.d_scan.p, &sb, cnt, off, seg_bound + 1, s), "drain scan");
+  HIP_TRY(tm.end(ms[5]), "event");
+  *args = a;
+  *ctl_out = ctl;
+  return PS_OK;
+}
 
 extern "C" {
 
@@ -260,77 +441,30 @@ int ps_drain_topics_begin(ps_engine* e, const uint32_t* topic, size_t n, size_t 
   auto& D = e->drain;
   const auto t_host0 = hclock::now();
 
-  // The strips at most, before the tables stand (the staging is taken once,
-  // with them): a topic's rows counted at the mask words its highest window
-  // bit gives, as both table builds lay a mask out; an arrival-order topic's
-  // strips are longer, so it takes fewer.
-  uint64_t strips_max = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t t = topic[i], cnt = e->last_cnt[t];
-    const TopicDev& d = e->last_topics[t];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, t, &u0);
-    if (!d.W || !cnt || !nn) continue;
-    const uint32_t* bits = window_bits(e, t);
-    const uint32_t top = bits ? *std::max_element(bits, bits + cnt) : cnt - 1;
-    const uint32_t per = aud_strip_nodes(false, std::min<uint32_t>(top >> 6, d.W - 1) + 1);
-    strips_max += ceil_div(nn, per);
-  }
-  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-
   // staged in the slot's pinned input, behind the table block where one is
-  // built: the entry table, then the strips.  From here to the slot's taking
-  // a failure gives the slot up.
-  const size_t o_strips = align256((n + 1) * sizeof(AudEntry));
+  // built: the entry table, then the strips (sized before the tables stand).
+  // From here to the slot's taking a failure gives the slot up.
+  size_t o_strips = 0;
+  uint64_t strips_max = 0;
+  const size_t stage_bytes = aud_stage_bytes(e, topic, n, &o_strips, &strips_max);
+  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
   Drain::Slot* slot = nullptr;
   size_t used = 0;
   uint8_t* h = nullptr;
-  int rc = drain_begin_slot(e, o_strips + strips_max * sizeof(AudStrip), D.env.timing, &slot, &used, &h);
+  int rc = drain_begin_slot(e, stage_bytes, D.env.timing, &slot, &used, &h);
   if (rc) return rc;
   auto& S = *slot;
   hipStream_t s = e->stream;
-  AudEntry* const entries = reinterpret_cast<AudEntry*>(h);
-  AudStrip* const strips = reinterpret_cast<AudStrip*>(h + o_strips);
-  uint64_t ns64 = 0, n_verdicts = 0, row_bytes = 0;
-  uint64_t own_lists = 0, own_ids = 0;  // the engine's caps
-  uint32_t max_segs = 0;
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t t = topic[i];
-    const DrainTopic& T = D.tab.topics[t];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, t, &u0);
-    entries[i] = AudEntry{t, static_cast<uint32_t>(ns64), ceil_div(T.n_pos, kDrainSegBits), 0};
-    if (!T.n_pos || !nn) continue;
-    const bool gather = T.flags & kDrainGather;
-    if (!gather) row_bytes += static_cast<uint64_t>(nn) * (T.n_pos / 64) * 8;
-    const uint32_t per = aud_strip_nodes(gather, T.n_pos / 64);
-    if (ns64 + ceil_div(nn, per) > strips_max) return drain_give_up(e, used, PS_E_STATE, "audience: more strips than staged");
-    for (uint32_t k = 0; k < nn; k += per) {
-      const uint32_t c = std::min(per, nn - k);
-      strips[ns64++] = AudStrip{t, u0 + k, c, e->last_topics[t].nbase, n_verdicts};
-      n_verdicts += c;
-    }
-    max_segs = std::max(max_segs, entries[i].segs);
-    // the topic's shared list and a private one per node of an arrival-order
-    // topic; every node's where full rows do not share
-    const uint64_t lists = D.env.share ? 1 + (gather ? nn : 0) : nn;
-    own_lists += lists;
-    own_ids += lists * e->last_cnt[t];
-  }
-  const uint32_t ns = static_cast<uint32_t>(ns64);
-  entries[n] = AudEntry{0, ns, 0, 0};
+  AudShape A;
+  if (!aud_stage(e, topic, n, reinterpret_cast<AudEntry*>(h), reinterpret_cast<AudStrip*>(h + o_strips), strips_max, &A))
+    return drain_give_up(e, used, PS_E_STATE, "audience: more strips than staged");
+  const uint32_t ns = A.ns;
 
   // the caps: the engine's where the caller names none
-  if (!exc_cap) exc_cap = std::max<uint64_t>(std::min<uint64_t>(n_verdicts, kAudPrefix), 1);
-  if (!list_cap) list_cap = std::max<uint64_t>(own_lists, 1);
-  if (!id_cap) id_cap = own_ids;
+  uint32_t seg_bound = 0;
+  const bool rows_fit = aud_caps(A, n, &exc_cap, &list_cap, &id_cap, &seg_bound);
   if (id_cap > kDrainAsyncMaxIds) return drain_give_up(e, used, PS_E_RANGE, "drain may exceed 2^30 ids: use ps_drain_topics");
-  const uint64_t bound = static_cast<uint64_t>(list_cap) * max_segs;
-  // (the numbering scans keep the segments in the low half of their keys)
-  if (list_cap >= 0x7FFFFFFFull || exc_cap >= 0x7FFFFFFFull || bound >= kDrainRowLimit ||
-      (static_cast<uint64_t>(exc_cap) + n) * max_segs >= kDrainRowLimit)
-    return drain_give_up(e, used, PS_E_RANGE, "too many rows in one drain");
-  const uint32_t seg_bound = static_cast<uint32_t>(bound);
+  if (!rows_fit) return drain_give_up(e, used, PS_E_RANGE, "too many rows in one drain");
 
   S.n = n;
   S.kind = Drain::Slot::kTopics;
@@ -363,103 +497,24 @@ int ps_drain_topics_begin(ps_engine* e, const uint32_t* topic, size_t n, size_t 
   // (PSAMD_DRAIN_TIMING: the phases run apart and are waited for; else nothing here waits)
   float ms[7] = {0, 0, 0, 0, 0, 0, 0};  // classify, scan, emit, assign, count, scan + offsets, emit
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
-  auto& C = S.lb.scratch;
   const size_t in_bytes = o_strips + static_cast<size_t>(ns) * sizeof(AudStrip);
-  const size_t o_node = align256(n_verdicts * 4), o_v = 2 * o_node;
-  const size_t n_off = static_cast<size_t>(seg_bound) + 1;
   HIP_TRY(S.d_res.ensure(res_bytes), "alloc drain result");
   HIP_TRY(S.lb.d_in.ensure(in_bytes), "alloc drain input");
-  HIP_TRY(S.lb.d_key.ensure(2 * (n + 1 + exc_cap + 1) * 8), "alloc drain keys");
-  HIP_TRY(S.lb.d_aux.ensure(align256(sizeof(DrainCtl))), "alloc drain control");
-  HIP_TRY(S.d_verdict.ensure(n_verdicts), "alloc audience verdicts");
-  HIP_TRY(S.d_exc.ensure(2 * (static_cast<size_t>(ns) + 1) * 8), "alloc audience counts");
-  HIP_TRY(S.d_full.ensure(static_cast<size_t>(ns) * 4), "alloc audience counts");
-  HIP_TRY(S.d_rec.ensure(o_v + n_verdicts), "alloc audience records");
-  HIP_TRY(C.d_queries.ensure(list_cap * sizeof(DrainQuery)), "alloc drain lists");
-  HIP_TRY(C.d_cnt.ensure(n_off * 8), "alloc drain counts");
-  HIP_TRY(C.d_off.ensure(n_off * 8), "alloc drain offsets");
-  uint64_t* const strip_cnt = S.d_exc.as<uint64_t>();
-  uint64_t* const strip_off = strip_cnt + ns + 1;
-  uint64_t* const ekey = S.lb.d_key.as<uint64_t>();
-  uint64_t* const rkey = ekey + 2 * (n + 1);
-  uint64_t* const cnt = C.d_cnt.as<uint64_t>();
-  uint64_t* const off = C.d_off.as<uint64_t>();
-  size_t scan_bytes = 0;  // one temporary for the four scans
-  for (const uint32_t len : {ns + 1, static_cast<uint32_t>(exc_cap) + 1, static_cast<uint32_t>(n) + 1, seg_bound + 1}) {
-    size_t b = 0;
-    HIP_TRY(drain_scan(nullptr, &b, cnt, off, len, s), "size drain scan");
-    scan_bytes = std::max(scan_bytes, b);
-  }
-  HIP_TRY(C.d_scan.ensure(scan_bytes), "alloc drain scan");
-
   uint8_t* const din = S.lb.d_in.as<uint8_t>();
   uint8_t* const res = S.d_res.as<uint8_t>();
-  uint8_t* const rec = S.d_rec.as<uint8_t>();
-  DrainCtl* const ctl = S.lb.d_aux.as<DrainCtl>();
   HIP_TRY(hipMemcpyAsync(din, h, in_bytes, hipMemcpyHostToDevice, s), "upload audience strips");
   if ((rc = drain_err_word(e, s))) return rc;
-  DrainArgs a = drain_args(e, D.tab);
-  AudArgs g{};
-  g.strips = reinterpret_cast<const AudStrip*>(din + o_strips);
-  g.n_strips = ns;
-  g.share = D.env.share;
-  g.verdict = S.d_verdict.as<uint8_t>();
-  g.n_exc = strip_cnt;
-  g.n_full = S.d_full.as<uint32_t>();
+  const AudBufs bufs{&S.lb, &S.d_verdict, &S.d_exc, &S.d_full, &S.d_rec};
+  const AudView view{reinterpret_cast<uint32_t*>(res + S.o_tl), reinterpret_cast<uint64_t*>(res + S.o_nf),
+                     reinterpret_cast<uint64_t*>(res + S.o_eo), reinterpret_cast<uint32_t*>(res + S.o_ep),
+                     reinterpret_cast<uint32_t*>(res + S.o_el)};
+  DrainArgs a{};
+  DrainCtl* ctl = nullptr;
+  if ((rc = aud_pass(e, bufs, reinterpret_cast<const AudEntry*>(din), reinterpret_cast<const AudStrip*>(din + o_strips), n,
+                     A, exc_cap, list_cap, seg_bound, view, tm, ms, &a, &ctl)))
+    return rc;
+  const uint64_t* const off = S.lb.scratch.d_off.as<uint64_t>();
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
-  HIP_TRY(tm.end(ms[0]), "event");
-  HIP_TRY(tm.begin(), "event");
-  size_t sb = C.d_scan.bytes;
-  HIP_TRY(drain_scan(C.d_scan.p, &sb, strip_cnt, strip_off, ns + 1, s), "drain scan");
-  HIP_TRY(tm.end(ms[1]), "event");
-  AudEmit o{};
-  o.node_peer = e->d_node_peer.as<uint32_t>();
-  o.off = strip_off;
-  o.peer = reinterpret_cast<uint32_t*>(rec);
-  o.node = reinterpret_cast<uint32_t*>(rec + o_node);
-  o.verdict = rec + o_v;
-  o.cap = n_verdicts;
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_audience_emit(g, o, s), "k_audience_emit");
-  HIP_TRY(tm.end(ms[2]), "event");
-
-  AudAssign q{};
-  q.entries = reinterpret_cast<const AudEntry*>(din);
-  q.n = static_cast<uint32_t>(n);
-  q.n_strips = ns;
-  q.strip_full = g.n_full;
-  q.strip_off = strip_off;
-  q.rec_peer = o.peer;
-  q.rec_node = o.node;
-  q.rec_verdict = o.verdict;
-  q.exc_cap = static_cast<uint32_t>(exc_cap);
-  q.list_cap = static_cast<uint32_t>(list_cap);
-  q.seg_bound = seg_bound;
-  q.ekey = ekey;
-  q.ekey_off = ekey + n + 1;
-  q.rkey = rkey;
-  q.rkey_off = rkey + exc_cap + 1;
-  q.scan_temp = C.d_scan.p;
-  q.scan_bytes = C.d_scan.bytes;
-  q.topic_list = reinterpret_cast<uint32_t*>(res + S.o_tl);
-  q.n_full = reinterpret_cast<uint64_t*>(res + S.o_nf);
-  q.exc_off = reinterpret_cast<uint64_t*>(res + S.o_eo);
-  q.exc_peer = reinterpret_cast<uint32_t*>(res + S.o_ep);
-  q.exc_list = reinterpret_cast<uint32_t*>(res + S.o_el);
-  q.lists = C.d_queries.as<DrainQuery>();
-  q.ctl = ctl;
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_audience_assign(q, s), "audience list assignment");
-  HIP_TRY(tm.end(ms[3]), "event");
-  a.queries = q.lists;
-  a.n_queries = 0;  // (the kernels read it from the control block)
-  HIP_TRY(tm.begin(), "event");
-  HIP_TRY(launch_drain_count_dev(a, ctl, seg_bound, cnt, s), "k_drain_count_dev");
-  HIP_TRY(tm.end(ms[4]), "event");
-  HIP_TRY(tm.begin(), "event");
-  sb = C.d_scan.bytes;
-  HIP_TRY(drain_scan(C.d_scan.p, &sb, cnt, off, seg_bound + 1, s), "drain scan");
   HIP_TRY(launch_drain_offsets_dev(a.queries, ctl, static_cast<uint32_t>(list_cap), off, id_cap, D.tab.d_err,
                                    reinterpret_cast<DrainSharedHdr*>(res), reinterpret_cast<uint64_t*>(res + S.o_off), s),
           "k_drain_offsets_dev");
@@ -476,7 +531,7 @@ int ps_drain_topics_begin(ps_engine* e, const uint32_t* topic, size_t n, size_t 
                  "psamd drain_topics_begin: topics %zu strips %u nodes %llu row_bytes %llu exc_cap %zu list_cap %zu id_cap %zu "
                  "seg_bound %u tables %s classify_ms %.4f strip_scan_ms %.4f records_ms %.4f assign_ms %.4f count_ms %.4f "
                  "scan_ms %.4f emit_ms %.4f upload_bytes %zu view_bytes %zu host_us %.1f\n",
-                 n, ns, static_cast<unsigned long long>(n_verdicts), static_cast<unsigned long long>(row_bytes), exc_cap,
+                 n, ns, static_cast<unsigned long long>(A.n_verdicts), static_cast<unsigned long long>(A.row_bytes), exc_cap,
                  list_cap, id_cap, seg_bound, used ? "built" : "kept", ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6],
                  in_bytes, res_bytes, 1e3 * ms_since(t_host0));
   return PS_OK;

@@ -665,10 +665,25 @@ struct ps_engine {
     // its pinned view and the pinned staging of its run's windows.  The
     // per-window passes share one set of device buffers: they all run on
     // `stream`, one window after the other.
+    // What the audience pass's stage step leaves beside the entries and the
+    // strips (drain_topics.cpp: aud_stage): the shape its buffers and grids
+    // are sized by, and the engine's own caps for the window
+    struct AudShape {
+      uint32_t ns = 0;                          // strips
+      uint64_t n_verdicts = 0, row_bytes = 0;   // nodes with a row to classify; the row bytes read
+      uint32_t max_segs = 0;                    // segments of the widest named topic with a row
+      uint64_t own_exc = 0, own_lists = 0, own_ids = 0;
+    };
+
     struct Sink {
       bool on = false;
+      // one sink of one kind: standing (topic, peer) queries (ps_sink_set), or
+      // standing topics drained as ps_drain_topics does (ps_sink_set_topics,
+      // `peer` is empty); the take call of the kind completes it
+      enum Kind { kQueries, kTopics } kind = kQueries;
       std::vector<uint32_t> topic, peer;
       size_t list_cap = 0, id_cap = 0;  // the caller's (both zero: the engine's, summed over the windows)
+      size_t exc_cap = 0;               // kTopics: the caller's (there each cap that is zero is the engine's)
       struct Chunk {
         uint8_t* h = nullptr;
         size_t cap = 0;
@@ -685,6 +700,15 @@ struct ps_engine {
         size_t list_cap = 0, id_cap = 0;     // as far as the last window
         size_t o_wl = 0, o_off = 0, o_ids = 0;  // the view: a SinkCursor, then these
         uint64_t run = 0;                    // the run's number (drain_fence)
+        // kTopics: d_wl holds the topic_list rows; the n_full and exc_off rows
+        // and the exception records beside it, grown with their contents kept;
+        // n_nodes rows from the host, written into the view (o_nn) behind what
+        // the copies bring.  The view: a SinkCursor, topic_list (o_wl), n_full,
+        // exc_off, exc_peer, exc_list, list_off (o_off), ids (o_ids), n_nodes.
+        psamd::DevBuf d_nf, d_eo, d_ep, d_el;
+        std::vector<uint64_t> n_nodes;
+        size_t exc_cap = 0;
+        size_t o_nf = 0, o_eo = 0, o_ep = 0, o_el = 0, o_nn = 0;
       } res[2];
       uint32_t head = 0, count = 0;  // untaken results, oldest first
       Res* open = nullptr;           // the run being enqueued
@@ -705,6 +729,13 @@ struct ps_engine {
       std::vector<uint64_t> sort_key;
       std::vector<uint8_t> sort_tail;
       SharedSort sort_r;
+      // kTopics: the entry table and the strips on the device, kept while
+      // what they are cut from stays (strip_key: graph_epoch and each standing
+      // topic's table flags, n_pos, node range); the window's verdicts, strip
+      // counts, records and window-local view (one set: all on `stream`)
+      psamd::DevBuf d_strips, d_verdict, d_exc, d_full, d_rec, d_view;
+      std::vector<uint64_t> strip_key;
+      size_t strip_bytes = 0;  // PSAMD_DRAIN_TIMING: the bytes the open run's windows uploaded for them
     } sink;
   } drain;
 

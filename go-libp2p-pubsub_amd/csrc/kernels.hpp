@@ -818,8 +818,9 @@ struct SinkCursor {
   uint32_t windows;  // windows so far
   uint32_t over;     // kDrainOver*, sticky: no id is emitted from the first overflow on
   uint32_t err;      // the windows' table error words (kDrainErr*)
-  uint32_t pad[2];
+  uint64_t exc;      // the audience sink's exception records so far: exact, whatever the caps (else 0)
 };
+static_assert(sizeof(SinkCursor) == 32, "two cursors alternate in the result's first 64 bytes");
 struct SinkCommit {
   const DrainQuery* lists;      // the window's lists (k_drain_lists)
   const DrainCtl* ctl;          // ... and their counts
@@ -840,5 +841,36 @@ hipError_t launch_sink_commit(const SinkCommit& c, hipStream_t s);
 // the verdict on the caps from cur[(w + 1) & 1]
 hipError_t launch_sink_emit(const DrainArgs& a, const DrainCtl* ctl, const SinkCursor* cur, uint32_t w,
                             uint32_t seg_bound, const uint64_t* off, uint32_t* out, uint64_t id_cap, hipStream_t s);
+
+// ---- the audience sink: ps_drain_topics behind every window (ps_sink_set_topics) --
+// The window's audience view as launch_audience_assign left it (window-local
+// list numbers, exc_off from 0), its lists and control block, the scanned
+// segment counts -- and the run's result they go into at the run cursor.
+struct AudSinkCommit {
+  const DrainQuery* lists;      // the window's lists (k_audience_lists)
+  const DrainCtl* ctl;          // ... and their counts
+  const uint64_t* seg_off;      // the window's scanned segment counts
+  const uint32_t* win_topic_list;  // [n] the window's view
+  const uint64_t* win_n_full;      // [n]
+  const uint64_t* win_exc_off;     // [n + 1]
+  const uint32_t* win_exc_peer;    // [win_exc_cap]
+  const uint32_t* win_exc_list;    // [win_exc_cap]
+  const uint32_t* err;          // the window's table error word
+  SinkCursor* cur;              // [2]
+  uint64_t* list_off;           // [list_cap + 1] the run's
+  uint32_t* topic_list;         // [windows x n] the run's
+  uint64_t* n_full;             // [windows x n]
+  uint64_t* exc_off;            // [windows x n + 1]
+  uint32_t* exc_peer;           // [exc_cap]
+  uint32_t* exc_list;           // [exc_cap]
+  uint32_t w, n;                // the window's number in the run; topics
+  uint32_t win_list_cap, win_exc_cap;  // what this window's passes were sized for
+  uint32_t list_cap, exc_cap;   // the run's caps as far as this window
+  uint64_t id_cap;
+};
+// k_audience_sink_commit: list_off[base + l], rows w of topic_list / n_full /
+// exc_off, the window's records at the run's record count, the next cursor.
+// Nothing is stored past a cap.  k_sink_emit follows it as it follows k_sink_commit.
+hipError_t launch_audience_sink_commit(const AudSinkCommit& c, hipStream_t s);
 
 }  // namespace psamd

@@ -168,6 +168,10 @@ PROTOTYPES = [
     ("ps_drain_topics_end", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p), C.POINTER(_u64p),
                                       C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p,
                                       _u64p]),
+    ("ps_sink_set_topics", C.c_int, [_P, _u32p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    ("ps_sink_take_topics", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p), C.POINTER(_u64p),
+                                      C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p,
+                                      _u32p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -660,6 +664,60 @@ class Engine:
         return {"topic_list": arr(tl, n, np.uint32), "n_nodes": arr(nn, n, np.uint64), "n_full": arr(nf, n, np.uint64),
                 "exc_off": exc_off, "exc_peer": arr(ep, n_exc, np.uint32), "exc_list": arr(el, n_exc, np.uint32),
                 "list_off": arr(lo, n_lists.value + 1, np.uint64), "ids": arr(mp, total.value, np.uint32)}
+
+    def sink_set_topics(self, topics, exc_cap: int = 0, list_cap: int = 0, id_cap: int = 0):
+        """Registers standing topics (ps_sink_set_topics): from now on every
+        window of every run is drained for them as drain_topics does, one
+        result per run (sink_take_topics).  It replaces a query sink; no topic
+        clears the sink; results not yet taken are discarded.  A cap of 0: the
+        engine's own, summed over the run's windows."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_sink_set_topics(self._h, _p(t, C.c_uint32), t.size, exc_cap, list_cap, id_cap))
+        self._sink_n = t.size
+
+    def sink_take_topics(self, copy: bool = True) -> dict:
+        """The oldest run not yet taken (ps_sink_take_topics): drain_topics'
+        dict over the run's windows plus n_windows -- topic_list, n_nodes and
+        n_full as [n_windows, n] arrays, exc_off[n_windows * n + 1] cumulative
+        over the run, exc_peer / exc_list, list_off and ids run-wide.
+        copy=False: views of the engine's pinned memory, valid until the
+        second run after its own.  When the answer exceeded a cap the
+        EngineError (PS_E_RANGE) carries `partial`: n_windows, n_nodes, n_full
+        and exc_off, exact whatever the caps, and n_lists and total."""
+        tl, ep, el, mp = _u32p(), _u32p(), _u32p(), _u32p()
+        nn, nf, eo, lo = _u64p(), _u64p(), _u64p(), _u64p()
+        n_windows, n_lists, total = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        rc = self._L.ps_sink_take_topics(self._h, C.byref(tl), C.byref(nn), C.byref(nf), C.byref(eo), C.byref(ep),
+                                         C.byref(el), C.byref(lo), C.byref(mp), C.byref(n_windows), C.byref(n_lists),
+                                         C.byref(total))
+        n, nw = self._sink_n, n_windows.value
+
+        def arr(p, k, dt):
+            v = _view(p, k, dt)
+            return v.copy() if copy else v
+
+        if rc == -7 and tl:
+            err = EngineError(rc, self._L.ps_last_error(self._h).decode())
+            err.partial = {"n_windows": nw, "n_nodes": _view(nn, (nw, n), np.uint64).copy(),
+                           "n_full": _view(nf, (nw, n), np.uint64).copy(),
+                           "exc_off": _view(eo, nw * n + 1, np.uint64).copy(),
+                           # (exact for the windows before the first that overflowed)
+                           "topic_list": _view(tl, (nw, n), np.uint32).copy(),
+                           "n_lists": n_lists.value, "total": total.value}
+            # the first k records / list offsets / ids, for a caller who knows its caps
+            ptrs = {"exc_peer": (ep, np.uint32), "exc_list": (el, np.uint32), "list_off": (lo, np.uint64),
+                    "ids": (mp, np.uint32)}
+            err.partial["head"] = lambda name, k: _view(ptrs[name][0], int(k), ptrs[name][1]).copy()
+            raise err
+        self._check(rc)
+        exc_off = arr(eo, nw * n + 1, np.uint64)
+        n_exc = int(exc_off[nw * n])
+        return {"n_windows": nw, "topic_list": arr(tl, (nw, n), np.uint32), "n_nodes": arr(nn, (nw, n), np.uint64),
+                "n_full": arr(nf, (nw, n), np.uint64), "exc_off": exc_off, "exc_peer": arr(ep, n_exc, np.uint32),
+                "exc_list": arr(el, n_exc, np.uint32), "list_off": arr(lo, n_lists.value + 1, np.uint64),
+                "ids": arr(mp, total.value, np.uint32)}
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

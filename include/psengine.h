@@ -385,7 +385,8 @@ int ps_drain_shared_end(ps_engine* e, const uint32_t** list_out, const uint64_t*
  * may be NULL).  A topic or peer out of range returns PS_E_RANGE and the
  * previous sink stays.  PS_E_STATE with a run in flight and on a multi-rank
  * engine; ps_dist_init* on an engine whose sink is set returns PS_E_STATE.
- * Setting or clearing discards results not yet taken.
+ * Setting or clearing discards results not yet taken, and replaces or clears
+ * a topics sink too (ps_sink_set_topics below): an engine has one sink.
  *   While a sink is set, every window of every ps_run / ps_run_async enqueues
  * behind itself the shared drain of ps_drain_shared_begin for the standing
  * queries, resolved against the node space that window ran on, and the run's
@@ -500,6 +501,63 @@ int ps_drain_topics_end(ps_engine* e,
                         const uint64_t** list_off_out,    /* [n_lists + 1]       */
                         const uint32_t** msg_out,         /* [total]             */
                         uint32_t* n_lists_out, uint64_t* total_out);
+/* The audience sink: standing TOPICS the engine drains itself behind EVERY
+ * window of a run, as ps_drain_topics does, into one answer per run -- what
+ * ps_sink_set is to ps_drain_shared, for ps_drain_topics.
+ *   ps_sink_set_topics registers the n distinct topics (copied; n == 0 clears
+ * the sink, topic may be NULL then).  An engine has one sink, of one kind:
+ * with n > 0 this call replaces a query sink and ps_sink_set replaces a
+ * topics sink; either call discards results not yet taken, and either with
+ * n == 0 clears whatever sink is set.  PS_E_INVAL for n > 0 without topic or a
+ * topic named twice, PS_E_RANGE for a topic out of range (the previous sink
+ * stays in both cases); PS_E_STATE with a run in flight and on a multi-rank
+ * engine; ps_dist_init* on an engine whose sink is set returns PS_E_STATE.
+ *   While the sink is set, every window of every ps_run / ps_run_async
+ * enqueues behind itself ps_drain_topics_begin's passes over the standing
+ * topics, against the node space that window ran on, and the run's windows
+ * accumulate.  Entry (w, i) lies at index w * n + i: n_nodes, n_full and
+ * topic_list are window w's values for topic[i], a topic_list entry shifted
+ * by the lists of the windows before (PS_NONE stays).  exc_off is ONE
+ * cumulative array over the run: the exceptions of (w, i) are records
+ * exc_off[w * n + i] .. exc_off[w * n + i + 1], dense, in window order, then
+ * request order, then node order; exc_list is shifted like topic_list.  Lists
+ * are numbered run-wide, window by window, within a window as ps_drain_topics
+ * numbers them; list l is msg[list_off[l] .. list_off[l + 1]), total =
+ * list_off[n_lists].  A topic with no message in a window has n_full = 0, no
+ * exception and PS_NONE in that window's row.  A topic's deliveries of the
+ * run are its windows' lists in window order, which is arrival order.
+ * Windows that run nothing do not count; a run without a window gives
+ * n_windows = 0, exc_off = {0}, list_off = {0}.
+ *   Caps as ps_drain_topics_begin's three, for the run: a cap of zero selects
+ * the engine's own -- that call's own cap of each window, summed as the
+ * windows come (exc_cap: the non-root nodes of the named topics with window
+ * messages, 65,536 at most, per window).  ps_run / ps_run_async return
+ * PS_E_RANGE before touching the pending messages when the engine's id cap
+ * for the run may pass 2^30.  Overflow is sticky: from the first window whose
+ * answer passes a cap no id is emitted and ps_sink_take_topics returns
+ * PS_E_RANGE; n_windows, n_nodes, n_full and exc_off are exact then for every
+ * window, whatever the caps (retry with exc_cap = exc_off[n_windows * n]);
+ * exc_peer, exc_list, topic_list, n_lists, list_off and total are exact for
+ * the windows before the first that overflowed and unspecified from there
+ * on.  Nothing is stored past a cap.
+ *   ps_sink_take_topics completes the oldest untaken run's result and lends
+ * it from pinned memory.  The two result slots, the PS_E_STATE refusal of a
+ * run with both untaken, the view lifetime and "a failed run gives up its
+ * slot" are ps_sink_set's.  The take call of the other kind returns
+ * PS_E_STATE and completes nothing.  PS_E_INVAL for a NULL output;
+ * PS_E_NOTREADY with nothing outstanding; PS_E_STATE when a window's
+ * device-side table check failed. */
+int ps_sink_set_topics(ps_engine* e, const uint32_t* topic, size_t n, size_t exc_cap, size_t list_cap, size_t id_cap);
+int ps_sink_take_topics(ps_engine* e,
+                        const uint32_t** topic_list_out,  /* [n_windows * n]      */
+                        const uint64_t** n_nodes_out,     /* [n_windows * n]      */
+                        const uint64_t** n_full_out,      /* [n_windows * n]      */
+                        const uint64_t** exc_off_out,     /* [n_windows * n + 1]  */
+                        const uint32_t** exc_peer_out,    /* [min(exc_off[last], exc_cap)] */
+                        const uint32_t** exc_list_out,    /* same                 */
+                        const uint64_t** list_off_out,    /* [n_lists + 1]        */
+                        const uint32_t** msg_out,         /* [total]              */
+                        uint32_t* n_windows_out, uint32_t* n_lists_out, uint64_t* total_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -68,6 +68,18 @@ bytes, ps_overlapped_windows(), the answers of (ii) and (iii) compared entry
 for entry, and whether (iii) beats (ii) by more than (ii)'s own spread; then,
 on a quiet engine with PSAMD_DRAIN_TIMING=1, the device time of the passes.
 Writes DIR/drain_topics_async_bench.json.
+
+--pipelined --topics --sink: the audience sink (ps_sink_set_topics /
+ps_sink_take_topics) over every topic: the sink-topics loop -- publish,
+ps_run_async, ps_wait and ps_sink_take_topics of the previous -- beside loops
+(i) and (iii) of --pipelined --topics, the three alternating in one process,
+--reps timings each: wall ms/step, the host time inside ps_run_async (with the
+begin call in loop (iii)), ps_overlapped_windows(), the results of the two
+drained loops compared entry for entry, and whether the sink loop is slower
+than loop (iii) by more than loop (iii)'s own spread; the sink's host time and
+whether the strips were kept, per run, from PSAMD_DRAIN_TIMING's line; one
+case with msg_window cut so that the largest topic takes three windows per
+step.  Writes DIR/sink_topics_bench.json.
 """
 from __future__ import annotations
 
@@ -768,6 +780,145 @@ def pipelined_topics_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def loop_sink_topics(eng, wl, n, run_s):
+    """publish; ps_run_async; ps_wait of the previous; ps_sink_take_topics of
+    the previous (a topics sink is set).  Returns the last view (copies)."""
+    view = None
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        t0 = time.perf_counter()
+        eng.run_async()
+        run_s.append(time.perf_counter() - t0)
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            view = eng.sink_take_topics(copy=False)
+    eng.wait()
+    view = eng.sink_take_topics(copy=False)
+    return {k: (v.copy() if k != "n_windows" else v) for k, v in view.items()}
+
+
+def loop_topics_async_timed(eng, wl, n, topics, exc_cap, run_s):
+    """loop_topics_async with the host time of ps_run_async + ps_drain_topics_begin per step."""
+    r = None
+    eng.publish(wl.msg_topics)
+    for i in range(n):
+        t0 = time.perf_counter()
+        eng.run_async()
+        eng.drain_topics_begin(topics, exc_cap=exc_cap)
+        run_s.append(time.perf_counter() - t0)
+        if i + 1 < n:
+            eng.publish(wl.msg_topics)
+        if i:
+            eng.wait()
+            r = eng.drain_topics_end(copy=False)
+    eng.wait()
+    r = eng.drain_topics_end()
+    return r
+
+
+def sink_topics_main(a, wl):
+    topics = np.arange(len(wl.topics), dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": int(topics.size),
+           "steps": a.steps, "warmup": a.warmup, "reps": a.reps}
+
+    def engine(env, msg_window=65536):
+        os.environ.update(env)
+        e = PE.Engine(wl.n_peers, len(wl.topics), seed=wl.seed, msg_window=msg_window)
+        WL.build_engine_topics(e, wl)
+        for k in env:
+            os.environ.pop(k, None)
+        return e
+
+    def us(xs):
+        return {"median": 1e6 * float(np.median(xs)), "max": 1e6 * float(np.max(xs))}
+
+    with engine({}) as eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        exc_cap = max(int(eng.drain_topics(topics)["exc_off"][-1]), 1)  # (every step publishes the same batch)
+        loop_plain(eng, wl, a.warmup)
+        loop_topics_async_timed(eng, wl, a.warmup, topics, exc_cap, [])
+        eng.sink_set_topics(topics, exc_cap=exc_cap)
+        loop_sink_topics(eng, wl, a.warmup, [])
+        eng.sink_set_topics([])
+        plain, asyn, sink, asyn_us, sink_us, over_a, over_s = [], [], [], [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            loop_plain(eng, wl, a.steps)
+            plain.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            o0, run_s = eng.overlapped_windows(), []
+            t0 = time.perf_counter()
+            ra = loop_topics_async_timed(eng, wl, a.steps, topics, exc_cap, run_s)
+            asyn.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            over_a.append(eng.overlapped_windows() - o0)
+            asyn_us.append(us(run_s))
+            eng.sink_set_topics(topics, exc_cap=exc_cap)
+            o0, run_s = eng.overlapped_windows(), []
+            t0 = time.perf_counter()
+            rk = loop_sink_topics(eng, wl, a.steps, run_s)
+            sink.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            over_s.append(eng.overlapped_windows() - o0)
+            sink_us.append(us(run_s))
+            eng.sink_set_topics([])
+            # entry for entry (one window a step; every step publishes the same batch under new ids)
+            assert rk["n_windows"] == 1
+            for k in TOPIC_KEYS:
+                got = rk[k][0] if k in ("topic_list", "n_nodes", "n_full") else rk[k]
+                assert np.array_equal(got, ra[k]), ("the sink-topics loop differs from loop (iii)", k)
+            assert np.array_equal(norm(rk["ids"]), norm(ra["ids"])), "the sink-topics loop differs from loop (iii)"
+        res.update(exc_cap=exc_cap, exceptions=int(rk["exc_off"][-1]), lists=int(rk["list_off"].size - 1),
+                   ids=int(rk["ids"].size))
+    res.update(plain_ms_per_step=plain, async_ms_per_step=asyn, sink_ms_per_step=sink, async_run_host_us=asyn_us,
+               sink_run_host_us=sink_us, async_overlapped_windows=over_a, sink_overlapped_windows=over_s, answers_agree=True)
+    res["async_spread_ms"] = max(asyn) - min(asyn)
+    res["sink_minus_async_ms"] = float(np.median(sink) - np.median(asyn))
+    res["sink_slower_than_async_by_more_than_its_spread"] = bool(res["sink_minus_async_ms"] > res["async_spread_ms"])
+    res["sink_minus_plain_ms"] = float(np.median(sink) - np.median(plain))
+
+    # the sink's own host time and upload per run (PSAMD_DRAIN_TIMING's line; the timed build of the
+    # tables waits in no sink window), and three windows a step for the record
+    def timed_runs(msg_window, runs):
+        rows = []
+        with engine({"PSAMD_DRAIN_TIMING": "1"}, msg_window) as eng:
+            eng.sink_set_topics(topics, exc_cap=exc_cap * 3)
+            for _ in range(runs):
+                eng.publish(wl.msg_topics)
+                with StderrCapture() as cap:
+                    eng.run()
+                    r = eng.sink_take_topics(copy=False)
+                m = re.search(r"psamd sink_topics: .*", cap.text).group(0)
+                rows.append({"windows": int(re.search(r"windows (\d+)", m).group(1)),
+                             "strips": re.search(r"strips (\w+)", m).group(1),
+                             "upload_bytes": int(re.search(r"upload_bytes (\d+)", m).group(1)),
+                             "view_bytes": int(re.search(r"view_bytes (\d+)", m).group(1)),
+                             "host_us": float(re.search(r"host_us ([0-9.]+)", m).group(1)),
+                             "lists": int(r["list_off"].size - 1), "ids": int(r["ids"].size)})
+        return rows
+
+    res["sink_runs_timed"] = timed_runs(65536, a.reps + 2)
+    res["three_windows_runs_timed"] = timed_runs(7040, a.reps + 2)
+    with engine({}, 7040) as eng:
+        loop_plain(eng, wl, a.warmup)
+        eng.sink_set_topics(topics, exc_cap=exc_cap * 3)
+        loop_sink_topics(eng, wl, a.warmup, [])
+        t0 = time.perf_counter()
+        rk = loop_sink_topics(eng, wl, a.steps, [])
+        t_sink = 1e3 * (time.perf_counter() - t0) / a.steps
+        eng.sink_set_topics([])
+        t0 = time.perf_counter()
+        loop_plain(eng, wl, a.steps)
+        res["three_windows"] = {"msg_window": 7040, "windows_per_step": int(rk["n_windows"]), "sink_ms_per_step": t_sink,
+                                "plain_ms_per_step": 1e3 * (time.perf_counter() - t0) / a.steps,
+                                "lists": int(rk["list_off"].size - 1), "ids": int(rk["ids"].size)}
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "sink_topics_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -911,6 +1062,8 @@ def main():
     ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.topics and a.sink:
+        return sink_topics_main(a, wl)
     if a.pipelined and a.topics:
         return pipelined_topics_main(a, wl)
     if a.topics:
