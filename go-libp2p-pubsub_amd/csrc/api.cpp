@@ -38,6 +38,8 @@ int dist_common(ps_engine* e, const ps_dist_config* dc) {
     return e->fail(PS_E_INVAL, "PS_DIST_F_INPLACE reads rows in place: not with PS_DIST_F_COPY");
   if (!e->pending.empty()) return e->fail(PS_E_STATE, "messages pending");
   if (e->drain.sink.on) return e->fail(PS_E_STATE, "a sink is set (one rank only): clear it with ps_sink_set first");
+  if (e->drain.load.on)
+    return e->fail(PS_E_STATE, "per-peer load is tracked (one rank only): clear it with ps_load_track first");
   // (every check above passed: the mode changes together with rank and world)
   e->inplace = dc->world > 1 && (dc->flags & PS_DIST_F_INPLACE) != 0;
   e->rank = dc->rank;
@@ -159,6 +161,7 @@ static void read_switches(ps_engine* e) {
   if (const char* v = std::getenv("PSAMD_DRAIN_EMIT")) d.staged = std::strcmp(v, "direct") != 0;
   if (const char* v = std::getenv("PSAMD_DRAIN_ASYNC_OUT")) d.mapped_out = std::strcmp(v, "mapped") == 0;
   if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) d.share = std::strcmp(v, "private") != 0;
+  if (const char* v = std::getenv("PSAMD_LOAD_COUNT")) d.load_rows = std::strcmp(v, "rows") == 0;
   s.twin = env_flag("PSAMD_TWIN", s.twin);
   s.expand_opts = env_flag("PSAMD_NARROW", true) ? 0u : kExpandNoNarrow;
   s.chain_words_lead = env_u32("PSAMD_CHAIN_WORDS_LEAD", 0, 1 << 20, s.chain_words_lead);

@@ -28,6 +28,9 @@
 //                         counts, the lists numbered in request order and
 //                         their segments laid out, around two scans (the host
 //                         loop of ps_drain_topics on the device)
+// and, for ps_peer_load / ps_load_track (§5.5i), per-peer traffic:
+//   k_audience_load       behind k_audience_classify: a node's verdict, peer and
+//                         CSR children into recv / sent sums in peer space
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -393,6 +396,88 @@ __global__ __launch_bounds__(kAudBlock) void k_audience_emit(AudArgs g, AudEmit 
       o.verdict[to] = static_cast<uint8_t>(v);
     }
     at += __popcll(b);
+  }
+}
+
+// ---- per-peer load (ps_peer_load, ps_load_track) -------------------------------
+
+// the topic's window messages the row of node u holds (wave-uniform): the row
+// words under the message mask, lanes across words; an arrival-order topic's
+// bits through its order table, lanes across positions
+__device__ __forceinline__ uint32_t load_count_row(const DrainArgs& a, const DrainTopic& T, uint32_t u, uint32_t lane) {
+  if (!(T.flags & kTopicMesh) && a.gen[T.nbase + u] != static_cast<uint8_t>(a.gen_cur)) return 0;
+  uint32_t c = 0;
+  if (!(T.flags & kDrainGather)) {
+    const uint32_t words = T.n_pos / 64;
+    for (uint32_t w0 = 0; w0 < words; w0 += kWave) {
+      const uint32_t w = w0 + lane;
+      if (w < words) {
+        const uint64_t at = row_word_at(a, T, u, w);
+        if (at != kNoWord) c += __popcll(a.seen[at] & a.mask[T.aux0 + w]);
+      }
+    }
+    return wave_sum_u32(c);
+  }
+  for (uint32_t p0 = 0; p0 < T.n_pos; p0 += kWave) {
+    const uint32_t p = p0 + lane;
+    bool set = false;
+    if (p < T.n_pos) {
+      const uint32_t b = a.order[T.aux0 + p];
+      const uint64_t at = row_word_at(a, T, u, b >> 6);
+      set = at != kNoWord && (a.seen[at] >> (b & 63) & 1ull);
+    }
+    c += __popcll(__ballot(set));
+  }
+  return c;
+}
+
+// One wave per strip, one node per lane: the verdict byte, the node's peer and
+// its two CSR bounds, then at most two 64-bit atomic adds in peer space.  The
+// rows the verdict does not settle go through load_count_row one at a time.
+// The wave of an entry's first strip adds the root's share.
+__global__ __launch_bounds__(kAudBlock) void k_audience_load(DrainArgs a, LoadArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const LoadEntry E = g.entries[lo - 1];
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  unsigned long long* const recv = reinterpret_cast<unsigned long long*>(g.recv);
+  unsigned long long* const sent = reinterpret_cast<unsigned long long*>(g.sent);
+  for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+    const uint32_t i = i0 + lane;
+    const bool in = i < S.n;
+    const uint32_t u = S.nbase + S.u0 + min(i, S.n - 1);
+    const uint32_t v = vin[min(i, S.n - 1)];
+    const uint32_t peer = g.node_peer[u];
+    const uint32_t deg = g.row_ptr[u + 1] - g.row_ptr[u];
+    const bool full = !gather && v == kDrainRowAny;
+    const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+    uint32_t k = in && full && !count ? E.c_t : 0u;
+    uint64_t todo = __ballot(count);
+    while (todo) {
+      const uint32_t j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t c = load_count_row(a, T, S.u0 + i0 + j, lane);
+      if (lane == j) k = c;
+    }
+    if (k) {
+      atomicAdd(recv + peer, static_cast<unsigned long long>(k));
+      if (deg) atomicAdd(sent + peer, static_cast<unsigned long long>(k) * deg);
+    }
+  }
+  if (E.strip0 == s && lane == 0 && E.root != kLoadNoRoot && E.c_t) {
+    const uint32_t deg = g.row_ptr[E.root + 1] - g.row_ptr[E.root];
+    if (deg) atomicAdd(sent + g.node_peer[E.root], static_cast<unsigned long long>(E.c_t) * deg);
   }
 }
 
@@ -910,6 +995,13 @@ hipError_t launch_audience_emit(const AudArgs& g, const AudEmit& o, hipStream_t 
   if (g.n_strips == 0) return hipSuccess;
   const uint32_t per = kAudBlock / kWave;
   hipLaunchKernelGGL(k_audience_emit, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g, o);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_load(const DrainArgs& a, const LoadArgs& g, hipStream_t s) {
+  if (g.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_load, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
   return hipGetLastError();
 }
 

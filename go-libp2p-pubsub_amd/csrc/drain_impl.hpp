@@ -12,6 +12,9 @@
 //   drain_topics.cpp  ps_drain_topics (§5.5f): a topic's audience as one list
 //                     plus exceptions; ps_drain_topics_begin / _end (§5.5g):
 //                     that answer behind a running batch
+//   drain_load.cpp    ps_peer_load, ps_load_track / ps_load_take and run.cpp's
+//                     hooks (§5.5i): per-peer recv / sent sums from the audience
+//                     pass's strips and verdicts, with buffers of their own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -24,8 +27,9 @@
 //  - ps_drain's slabs: ev_copy[k & 1] is waited on before slab k is emitted,
 //    slab k - 1 is copied while slab k is emitted; under timing the copy runs
 //    in line on `stream`.
-//  - Slot::seen / emit_pending / ev_emit and Sink::fence (the last sink emit
-//    over each row set) are read by drain_fence (run.cpp).
+//  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
+//    over each row set) and Load::fence (the last standing load pass over
+//    each) are read by drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics

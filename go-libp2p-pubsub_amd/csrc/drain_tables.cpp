@@ -447,6 +447,14 @@ void drain_destroy(ps_engine* e) {
     for (uint8_t* h : {sl.h_in, sl.h_res})
       if (h) (void)hipHostFree(h);
   if (D.aud.h_ids) (void)hipHostFree(D.aud.h_ids);
+  if (D.load.h_out) (void)hipHostFree(D.load.h_out);
+  for (auto& a : D.load.arena) {
+    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
+    if (a.ev) (void)hipEventDestroy(a.ev);
+  }
+  for (auto& f : D.load.fence)
+    if (f.ev) (void)hipEventDestroy(f.ev);
+  if (D.load.ev_take) (void)hipEventDestroy(D.load.ev_take);
 }
 
 }  // namespace psamd

@@ -602,6 +602,8 @@ struct ps_engine {
       bool mapped_out = false;  // ps_drain_begin: emit straight into the pinned view (A/B: PSAMD_DRAIN_ASYNC_OUT=mapped)
       // the shared calls, ps_drain_topics and the sink: full rows share their topic's list (A/B: PSAMD_DRAIN_SHARED=private)
       bool share = true;
+      // ps_peer_load, ps_load_track: a full row is counted from its words like a partial one (A/B: PSAMD_LOAD_COUNT=rows)
+      bool load_rows = false;
     } env;
 
     hipStream_t copy_stream = nullptr;        // results leave on it, beside whatever `stream` runs next
@@ -737,6 +739,56 @@ struct ps_engine {
       std::vector<uint64_t> strip_key;
       size_t strip_bytes = 0;  // PSAMD_DRAIN_TIMING: the bytes the open run's windows uploaded for them
     } sink;
+
+    // ps_peer_load / ps_load_track / ps_load_take (host code:
+    // drain_load.cpp): per-peer recv / sent sums from the audience pass's
+    // verdicts, k_audience_load behind k_audience_classify.  The blocking
+    // call and the standing pass each own their entries and strips, verdict
+    // bytes and strip counts; nothing here is the sinks'.
+    struct Load {
+      // one pass's device buffers: entries | strips in one block, the verdict
+      // bytes, the two strip counts classify leaves beside them
+      struct Pass {
+        psamd::DevBuf d_in, d_verdict, d_exc, d_full;
+      };
+      // ps_peer_load: its pass, recv | sent on the device, their pinned copy
+      Pass sync;
+      psamd::DevBuf d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+      // ps_load_track: the standing topics and the totals since the last take
+      // or track call, recv | sent in peer space
+      bool on = false;
+      std::vector<uint32_t> topic;
+      Pass track;
+      psamd::DevBuf d_acc;
+      uint64_t windows = 0;  // windows counted since the last take or track call
+      // the entries and strips on the device while what they are cut from
+      // stays (graph_epoch, each standing topic's table shape, node range and
+      // window messages)
+      std::vector<uint64_t> strip_key;
+      uint32_t ns = 0;
+      uint64_t n_verdicts = 0;
+      // Pinned staging, one arena per run in turn (run k: arena[k & 1]): every
+      // window of the run takes a region of its own, and the arena is reused
+      // once the last pass of the run two before is complete (ev)
+      struct Arena {
+        Sink::Res mem;  // (its arena alone: drain_tables.cpp sink_stage)
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+      } arena[2];
+      uint64_t runs = 0;
+      Arena* open = nullptr;  // the run being enqueued
+      // the last pass per row set: a window about to write the set on another
+      // stream waits for it (run.cpp: drain_fence)
+      struct Fence {
+        const void* seen = nullptr;
+        hipEvent_t ev = nullptr;
+        bool pending = false;
+      } fence[2];
+      hipEvent_t ev_take = nullptr;
+    } load;
   } drain;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
@@ -879,6 +931,13 @@ int sink_open(ps_engine* e);
 int sink_window(ps_engine* e);
 int sink_close(ps_engine* e);
 void sink_abort(ps_engine* e);
+// drain_load.cpp, the standing load pass (ps_load_track; all no-ops while
+// nothing is tracked).  A run opens it (its pinned staging), calls load_window
+// behind every window it remembered, where it calls sink_window, and
+// load_abort when it fails.
+int load_open(ps_engine* e);
+int load_window(ps_engine* e);
+void load_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

@@ -873,4 +873,35 @@ struct AudSinkCommit {
 // Nothing is stored past a cap.  k_sink_emit follows it as it follows k_sink_commit.
 hipError_t launch_audience_sink_commit(const AudSinkCommit& c, hipStream_t s);
 
+// ---- per-peer load (ps_peer_load, ps_load_track) --------------
+// The audience pass's verdicts turned into per-peer sums, in peer space: a
+// non-root node whose row holds k of its topic's c_t window messages adds k to
+// recv[its peer] and k * its CSR children to sent[its peer]; the root, no
+// recipient, adds c_t * its children to sent.  The entry table of the strips
+// (AudEntry's shape: request order, entry n closes the table) carries what the
+// strips do not: the topic's window messages and its root's node.
+constexpr uint32_t kLoadNoRoot = 0xFFFFFFFFu;
+struct LoadEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window
+  uint32_t root;    // the root's node (node space), kLoadNoRoot: none on this rank
+};
+struct LoadArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const LoadEntry* entries;  // [n + 1]
+  uint32_t n;
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint32_t* node_peer;
+  const uint32_t* row_ptr;
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  uint64_t* recv;            // [n_peers] added into
+  uint64_t* sent;            // [n_peers]
+};
+// k_audience_load: one wave per strip behind k_audience_classify.  A full row
+// counts c_t, an empty or stale one nothing; any other row, and every row of a
+// kDrainGather topic, is counted by the wave, one row at a time.
+hipError_t launch_audience_load(const DrainArgs& a, const LoadArgs& g, hipStream_t s);
+
 }  // namespace psamd

@@ -185,6 +185,9 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   const auto& K = e->drain.sink;
   for (const auto& F : K.fence)
     if (F.run > K.runs_done && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending sink drain");
+  // ... and the standing load pass's (ps_load_track): the last one over this row set
+  for (const auto& F : e->drain.load.fence)
+    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending load pass");
   return PS_OK;
 }
 
@@ -1447,7 +1450,7 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
     int rc = run_window(e, msgs, win, st);
     e->defer_last = false;
     // (the window that was remembered: after a k_flood timeout, its re-run)
-    if (!rc && e->window_seq != seq0) rc = sink_window(e);
+    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e))) rc = load_window(e);
     if (rc) return rc;
   }
   return PS_OK;
@@ -1563,12 +1566,16 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer);
 
 // The run with the sink's result around it (ps_sink_set; nothing while none
 // is set): refused before the pending messages are touched, opened, closed
-// behind the last window, given up when the run fails.
+// behind the last window, given up when the run fails.  And with the standing
+// load pass's staging around it (ps_load_track; nothing while none is set).
 int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
   int rc = sink_precheck(e);
   if (rc || (rc = sink_open(e))) return rc;
-  if (!(rc = run_windows(e, stp, may_defer))) rc = sink_close(e);
-  if (rc) sink_abort(e);
+  if (!(rc = load_open(e)) && !(rc = run_windows(e, stp, may_defer))) rc = sink_close(e);
+  if (rc) {
+    sink_abort(e);
+    load_abort(e);
+  }
   return rc;
 }
 

@@ -172,6 +172,9 @@ PROTOTYPES = [
     ("ps_sink_take_topics", C.c_int, [_P, C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u64p), C.POINTER(_u64p),
                                       C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u64p), C.POINTER(_u32p), _u32p,
                                       _u32p, _u64p]),
+    ("ps_peer_load", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p]),
+    ("ps_load_track", C.c_int, [_P, _u32p, C.c_size_t]),
+    ("ps_load_take", C.c_int, [_P, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -718,6 +721,38 @@ class Engine:
                 "n_full": arr(nf, (nw, n), np.uint64), "exc_off": exc_off, "exc_peer": arr(ep, n_exc, np.uint32),
                 "exc_list": arr(el, n_exc, np.uint32), "list_off": arr(lo, n_lists.value + 1, np.uint64),
                 "ids": arr(mp, total.value, np.uint32)}
+
+    def peer_load(self, topics) -> tuple[np.ndarray, np.ndarray]:
+        """Per-peer traffic of the last window over the named distinct topics
+        (ps_peer_load): (recv, sent), uint64 [n_peers] each -- the messages a
+        peer received as a non-root node, and the copies it wrote to its
+        children (live or not)."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        recv = np.empty(self.n_peers, dtype=np.uint64)
+        sent = np.empty(self.n_peers, dtype=np.uint64)
+        self._check(self._L.ps_peer_load(self._h, _p(t, C.c_uint32), t.size, _p(recv, C.c_uint64), _p(sent, C.c_uint64)))
+        return recv, sent
+
+    def load_track(self, topics):
+        """Registers standing topics (ps_load_track): from now on every window
+        of every run adds its per-peer traffic over them into totals on the
+        device (load_take).  No topic clears the tracking; setting or clearing
+        zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_load_track(self._h, _p(t, C.c_uint32), t.size))
+
+    def load_take(self) -> tuple[np.ndarray, np.ndarray, int]:
+        """The totals since the last take or track call (ps_load_take):
+        (recv, sent, n_windows); the totals and the count start again at 0."""
+        recv = np.empty(self.n_peers, dtype=np.uint64)
+        sent = np.empty(self.n_peers, dtype=np.uint64)
+        nw = C.c_uint64()
+        self._check(self._L.ps_load_take(self._h, _p(recv, C.c_uint64), _p(sent, C.c_uint64), C.byref(nw)))
+        return recv, sent, nw.value
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -558,6 +558,47 @@ int ps_sink_take_topics(ps_engine* e,
                         const uint64_t** list_off_out,    /* [n_lists + 1]        */
                         const uint32_t** msg_out,         /* [total]              */
                         uint32_t* n_windows_out, uint32_t* n_lists_out, uint64_t* total_out);
+/* Per-peer load: how much each peer carried, summed over the named topics (one
+ * rank).  Per window and per topic t with c_t > 0 messages in
+ * it, on the node space that window ran on: a non-root node of peer p whose
+ * row holds k of t's window messages -- the k ids ps_drain_shared would list
+ * for (t, p); 0 for a tree node the window did not reach -- adds k to recv[p]
+ * and k * deg to sent[p], deg its children in the topic's tree (or mesh: a
+ * mesh node forwards each message once, on first receipt).  The root is no
+ * recipient: it adds nothing to recv and c_t * deg(root) to sent.  Children
+ * count whether live or not: the parent writes to them, as forwardMessage
+ * does.  A topic with no message in the window adds nothing; peers outside the
+ * node space (unattached, orphans) get nothing, as in every other read.
+ *   ps_peer_load answers for the last window of the last run, blocking, with
+ * ps_drain_topics' window, stream-ordering and twin-join rules.  The n topics
+ * are distinct; both arrays ([n_peers], either may be NULL) are written in
+ * full: peers in no named topic read 0, and n == 0 gives all zeros.
+ * PS_E_INVAL for a NULL engine, n > 0 without topic, both outputs NULL or a
+ * topic named twice; PS_E_RANGE, nothing written, for a topic out of range;
+ * PS_E_NOTREADY before any run; PS_E_STATE on a multi-rank engine.
+ *   ps_load_track registers n standing topics (copied; n == 0 clears the
+ * tracking and frees the totals).  PS_E_INVAL / PS_E_RANGE as above, the
+ * previous tracking stays; PS_E_STATE with a run in flight and on a
+ * multi-rank engine; ps_dist_init* on an engine that is tracking returns
+ * PS_E_STATE.  Setting or clearing zeroes the totals.  Tracking is
+ * independent of the sinks: an engine may have a sink and tracking at once.
+ * While it is set, every window of every ps_run / ps_run_async that runs
+ * something enqueues the pass behind itself -- the window is neither planned
+ * nor launched differently -- and the pass adds into two totals on the
+ * device, recv[n_peers] and sent[n_peers], in peer space: they survive
+ * node-space rebuilds, joins, leaves and drops between windows.
+ *   ps_load_take waits for the passes enqueued so far, copies the totals since
+ * the last take or track call (each array may be NULL), zeroes them in front
+ * of whatever runs next, sets *n_windows_out to the windows counted and
+ * resets that count.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with
+ * a run in flight (complete the runs with ps_wait first); PS_E_INVAL for a
+ * NULL engine or n_windows_out.  After a failed ps_run / ps_wait the totals
+ * are unspecified until the next take or track call. */
+int ps_peer_load(ps_engine* e, const uint32_t* topic, size_t n,
+                 uint64_t* recv_out, uint64_t* sent_out);          /* [n_peers] each, either may be NULL */
+int ps_load_track(ps_engine* e, const uint32_t* topic, size_t n);
+int ps_load_take(ps_engine* e, uint64_t* recv_out, uint64_t* sent_out, /* [n_peers], nullable */
+                 uint64_t* n_windows_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

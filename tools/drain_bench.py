@@ -80,6 +80,15 @@ than loop (iii) by more than loop (iii)'s own spread; the sink's host time and
 whether the strips were kept, per run, from PSAMD_DRAIN_TIMING's line; one
 case with msg_window cut so that the largest topic takes three windows per
 step.  Writes DIR/sink_topics_bench.json.
+
+--load: per-peer load (ps_peer_load) over every topic after one step, --reps
+repetitions in one process: its wall and device phases (classify, load, copy)
+beside ps_drain_topics' phases; the derivation a caller has without it --
+ps_drain_topics + ps_topic_get_parents per topic + numpy -- and its wall, the
+two answers compared array for array; then the pipelined step with every
+topic tracked (ps_load_track, one ps_load_take per loop) against the step with
+the audience sink over the same topics and the plain step, the three
+alternating in one process.  Writes DIR/load_bench.json.
 """
 from __future__ import annotations
 
@@ -919,6 +928,144 @@ def sink_topics_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def host_peer_load(eng, wl, topics):
+    """Per-peer load as a caller derives it without ps_peer_load: the audience
+    answer, every topic's parent array, numpy.  (A Join topic's parents name
+    the members: a peer with no upstream is outside the node space.)"""
+    r = eng.drain_topics(topics)
+    n = wl.n_peers
+    recv = np.zeros(n, dtype=np.uint64)
+    sent = np.zeros(n, dtype=np.uint64)
+    sizes = np.diff(r["list_off"]).astype(np.uint64)
+    c_all = np.bincount(wl.msg_topics, minlength=len(wl.topics))
+    for i, t in enumerate(topics):
+        c = int(c_all[t])
+        if not c:
+            continue
+        par = eng.parents(int(t))
+        kid = np.nonzero(par != 0xFFFFFFFF)[0]
+        n_child = np.bincount(par[kid], minlength=n).astype(np.uint64)
+        k = np.zeros(n, dtype=np.uint64)
+        k[kid] = c
+        lo, hi = int(r["exc_off"][i]), int(r["exc_off"][i + 1])
+        if hi > lo:  # the nodes that are not full: their private list's length, or nothing
+            el = r["exc_list"][lo:hi].astype(np.int64)
+            have = el != 0xFFFFFFFF
+            ke = np.zeros(hi - lo, dtype=np.uint64)
+            ke[have] = sizes[el[have]]
+            k[r["exc_peer"][lo:hi]] = ke
+        root = wl.topics[int(t)].root
+        k[root] = 0
+        recv += k
+        sent += k * n_child
+        sent[root] += np.uint64(c) * n_child[root]
+    return recv, sent
+
+
+def loop_track(eng, wl, n):
+    """publish; ps_run_async; ps_wait of the previous (topics are tracked);
+    one ps_load_take behind the last."""
+    loop_plain(eng, wl, n)
+    return eng.load_take()
+
+
+def load_main(a, wl):
+    """--load: ps_peer_load over every topic after one step: its phases
+    (PSAMD_DRAIN_TIMING) beside ps_drain_topics' in one process, its wall
+    against the host derivation (ps_drain_topics + ps_topic_get_parents per
+    topic + numpy), the two answers compared array for array; then the step
+    of the pipelined loop with every topic tracked (ps_load_track) against
+    the step with the audience sink over the same topics and the plain step,
+    alternating in one process.  Writes DIR/load_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": a.steps, "warmup": a.warmup}
+    eng, st = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        rows = []
+        for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+            with StderrCapture() as cap:
+                recv, sent = eng.peer_load(topics)
+            row = phase_line(cap.text, "peer_load")
+            for k in ("strips", "nodes", "row_bytes"):
+                row[k] = int(re.search(rf"\b{k} (\d+)", cap.text).group(1))
+            rows.append(row)
+        res["load_phases"] = rows[1:]
+        rows = []
+        for _ in range(a.reps + 1):
+            with StderrCapture() as cap:
+                eng.drain_topics(topics)
+            rows.append(phase_line(cap.text, "drain_topics"))
+        res["topics_phases"] = rows[1:]
+        assert int(recv.sum()) == st.deliveries, (int(recv.sum()), st.deliveries)
+        res.update(deliveries=int(st.deliveries), recv_sum=int(recv.sum()), sent_sum=int(sent.sum()),
+                   peers_receiving=int((recv > 0).sum()), peers_sending=int((sent > 0).sum()),
+                   sent_max=int(sent.max()), recv_max=int(recv.max()))
+    eng, _ = stepped_engine(wl, {})
+    with eng:
+        walls = {"load": [], "host": [], "topics": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.peer_load(topics)
+            walls["load"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            want = host_peer_load(eng, wl, topics)
+            walls["host"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.drain_topics(topics)
+            walls["topics"].append(1e3 * (time.perf_counter() - t0))
+            assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "ps_peer_load differs from the host derivation"
+    res["load_wall_ms"], res["host_derivation_wall_ms"], res["topics_wall_ms"] = (walls[k][1:] for k in ("load", "host", "topics"))
+    res["answers_agree"] = True
+    res["host_over_load_wall"] = float(np.median(res["host_derivation_wall_ms"]) / np.median(res["load_wall_ms"]))
+    lp = res["load_phases"]
+    res["load_over_classify_device"] = float(np.median([p["load_ms"] for p in lp]) / np.median([p["classify_ms"] for p in lp]))
+
+    # tracking in the pipelined loop, beside the audience sink and the plain step
+    for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING"):
+        os.environ.pop(k, None)
+    eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    with eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        exc_cap = max(int(eng.drain_topics(topics)["exc_off"][-1]), 1)
+        loop_plain(eng, wl, a.warmup)
+        eng.sink_set_topics(topics, exc_cap=exc_cap)
+        loop_sink_topics(eng, wl, a.warmup, [])
+        eng.sink_set_topics([])
+        eng.load_track(topics)
+        loop_track(eng, wl, a.warmup)
+        eng.load_track([])
+        plain, sink, track, over = [], [], [], []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            loop_plain(eng, wl, a.steps)
+            plain.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            eng.sink_set_topics(topics, exc_cap=exc_cap)
+            t0 = time.perf_counter()
+            loop_sink_topics(eng, wl, a.steps, [])
+            sink.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            eng.sink_set_topics([])
+            eng.load_track(topics)
+            o0 = eng.overlapped_windows()
+            t0 = time.perf_counter()
+            r, s, nw = loop_track(eng, wl, a.steps)
+            track.append(1e3 * (time.perf_counter() - t0) / a.steps)
+            over.append(eng.overlapped_windows() - o0)
+            eng.load_track([])
+            assert nw == a.steps and np.array_equal(r, recv * np.uint64(a.steps)) and np.array_equal(s, sent * np.uint64(a.steps))
+    res.update(plain_ms_per_step=plain, sink_topics_ms_per_step=sink, track_ms_per_step=track, track_overlapped_windows=over,
+               track_minus_plain_ms=float(np.median(track) - np.median(plain)),
+               sink_minus_plain_ms=float(np.median(sink) - np.median(plain)), tracked_totals_agree=True)
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "load_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -1060,8 +1207,11 @@ def main():
     ap.add_argument("--large-queries", type=int, default=262144)
     ap.add_argument("--sink", action="store_true", help="the sink in the pipelined loop against ps_drain_shared_begin's")
     ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
+    ap.add_argument("--load", action="store_true", help="ps_peer_load against the host derivation; tracking in the pipelined loop")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.load:
+        return load_main(a, wl)
     if a.topics and a.sink:
         return sink_topics_main(a, wl)
     if a.pipelined and a.topics:
