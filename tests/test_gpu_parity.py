@@ -9,6 +9,7 @@ subtree.forwardMessage (subtree.go:319-354), client.processMessages
 import numpy as np
 import pytest
 
+import mesh_ref as MR
 import oracle as O
 import psengine as PE
 from psengine import workloads as WL
@@ -121,6 +122,7 @@ def test_mesh_parity_dedup(seed):
         st = eng.run()
         total = check_topic(eng, first, list(range(n_msgs)), rp, cl, root, live)
         assert st.deliveries == total
+        assert st.duplicates == n_msgs * MR.flood(rp, cl, root, live).duplicates
 
 
 def test_multi_topic_fused_and_windows():
