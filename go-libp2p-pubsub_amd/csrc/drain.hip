@@ -31,6 +31,11 @@
 // and, for ps_peer_load / ps_load_track (§5.5i), per-peer traffic:
 //   k_audience_load       behind k_audience_classify: a node's verdict, peer and
 //                         CSR children into recv / sent sums in peer space
+// and, for ps_topic_hops / ps_hops_track (§5.5j), deliveries by hop per topic:
+//   k_audience_hops       behind k_audience_classify: per (strip, level) the
+//                         nodes reached and the messages they hold
+//   k_audience_hops_sum   each (topic, column)'s partials into its row: one
+//                         writer per word, no atomics
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -478,6 +483,132 @@ __global__ __launch_bounds__(kAudBlock) void k_audience_load(DrainArgs a, LoadAr
   if (E.strip0 == s && lane == 0 && E.root != kLoadNoRoot && E.c_t) {
     const uint32_t deg = g.row_ptr[E.root + 1] - g.row_ptr[E.root];
     if (deg) atomicAdd(sent + g.node_peer[E.root], static_cast<unsigned long long>(E.c_t) * deg);
+  }
+}
+
+// ---- deliveries by hop per topic (ps_topic_hops, ps_hops_track) ----------------
+
+constexpr uint32_t kHopsSumBlock = 1024;
+constexpr uint32_t kHopsSumPer = 4;  // partial pairs a thread has in flight
+
+// One wave per strip: the level of the strip's first node by bisection of the
+// topic's level table, then level by level to the strip's end -- the level's
+// nodes of the strip a lane each, their verdict bytes (full: c_t, none: 0,
+// anything else, and under the seam every full row, through load_count_row),
+// a wave sum, one partial pair per (strip, level).  Where classify counted no
+// exception in the strip, every node is full: the partials follow from the
+// level bounds and no verdict byte is read.
+__global__ __launch_bounds__(kAudBlock) void k_audience_hops(DrainArgs a, HopsArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const HopsEntry E = g.entries[lo - 1];
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  lo = 1, hi = E.depth + 1;  // the last level whose first node is <= u0: the first node's
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (lv[mid] <= S.u0) lo = mid + 1;
+    else hi = mid;
+  }
+  uint32_t d = lo - 1;
+  if (d == 0) return;  // (a strip holds no root)
+  const bool all_full = !g.count_rows && g.n_exc[s] == 0;
+  const uint32_t end = S.u0 + S.n;
+  uint32_t slot = E.part0 + (s - E.strip0) + (d - 1);
+  for (uint32_t u = S.u0; u < end && d <= E.depth; ++d, ++slot) {
+    const uint32_t ue = min(end, max(lv[d + 1], u + 1));
+    uint32_t reached = 0;  // (wave-uniform)
+    uint64_t deliv = 0;
+    if (all_full) {
+      reached = ue - u;
+      deliv = static_cast<uint64_t>(reached) * E.c_t;
+    } else {
+      for (uint32_t i0 = u; i0 < ue; i0 += kWave) {
+        const uint32_t i = i0 + lane;
+        const bool in = i < ue;
+        const uint32_t v = vin[min(i, ue - 1) - S.u0];
+        const bool full = !gather && v == kDrainRowAny;
+        const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+        uint32_t k = in && full && !count ? E.c_t : 0u;
+        uint64_t todo = __ballot(count);
+        while (todo) {
+          const uint32_t j = __builtin_ctzll(todo);
+          todo &= todo - 1;
+          const uint32_t c = load_count_row(a, T, i0 + j, lane);
+          if (lane == j) k = c;
+        }
+        reached += __popcll(__ballot(k != 0));
+        deliv += wave_sum_u32(k);
+      }
+    }
+    if (lane == 0) {
+      g.part_reached[slot] = reached;
+      g.part_deliv[slot] = deliv;
+    }
+    u = ue;
+  }
+}
+
+// One block per (entry, column): the strips that meet level d are those of its
+// first to its last node, their slots a run with stride one; the last column
+// takes every level from its own on.  The block's two sums and the levels'
+// nodes are added to the entry's row by one thread: nobody else writes there
+// in this pass, and the passes follow each other on one stream.
+__global__ __launch_bounds__(kHopsSumBlock) void k_audience_hops_sum(HopsArgs g) {
+  __shared__ uint64_t part[2][kHopsSumBlock / kWave];
+  const uint32_t h = blockIdx.y + 1;
+  const HopsEntry E = g.entries[blockIdx.x];
+  if (!E.c_t || h > min(E.depth, kHopsCols - 1) || g.entries[blockIdx.x + 1].strip0 == E.strip0) return;
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  const uint32_t d_hi = h == kHopsCols - 1 ? E.depth : h;
+  uint64_t r = 0, dl = 0;
+  for (uint32_t d = h; d <= d_hi; ++d) {
+    const uint32_t sa = (lv[d] - lv[1]) / E.per, sb = (lv[d + 1] - 1 - lv[1]) / E.per;  // (relative to strip0)
+    const uint32_t p0 = E.part0 + (d - 1);
+    for (uint32_t s0 = sa + threadIdx.x; s0 <= sb; s0 += kHopsSumBlock * kHopsSumPer) {
+      uint32_t vr[kHopsSumPer];
+      uint64_t vd[kHopsSumPer];
+#pragma unroll
+      for (uint32_t k = 0; k < kHopsSumPer; ++k) {
+        const uint32_t sk = s0 + k * kHopsSumBlock;
+        vr[k] = sk <= sb ? g.part_reached[p0 + sk] : 0u;
+        vd[k] = sk <= sb ? g.part_deliv[p0 + sk] : 0ull;
+      }
+#pragma unroll
+      for (uint32_t k = 0; k < kHopsSumPer; ++k) {
+        r += vr[k];
+        dl += vd[k];
+      }
+    }
+  }
+  r = dev::wave_sum_u64(r);
+  dl = dev::wave_sum_u64(dl);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    part[0][threadIdx.x / kWave] = r;
+    part[1][threadIdx.x / kWave] = dl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    r = dl = 0;
+    for (uint32_t w = 0; w < kHopsSumBlock / kWave; ++w) {
+      r += part[0][w];
+      dl += part[1][w];
+    }
+    const size_t at = static_cast<size_t>(E.row) * kHopsCols + h;
+    g.nodes[at] += lv[d_hi + 1] - lv[h];
+    g.reached[at] += r;
+    g.deliv[at] += dl;
   }
 }
 
@@ -1002,6 +1133,19 @@ hipError_t launch_audience_load(const DrainArgs& a, const LoadArgs& g, hipStream
   if (g.n_strips == 0) return hipSuccess;
   const uint32_t per = kAudBlock / kWave;
   hipLaunchKernelGGL(k_audience_load, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_hops(const DrainArgs& a, const HopsArgs& g, hipStream_t s) {
+  if (g.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_hops, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_hops_sum(const HopsArgs& g, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0 || g.max_cols == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_audience_hops_sum, dim3(g.n, g.max_cols), dim3(kHopsSumBlock), 0, s, g);
   return hipGetLastError();
 }
 

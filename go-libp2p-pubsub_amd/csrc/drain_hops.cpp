@@ -1,0 +1,398 @@
+// drain_hops.cpp -- deliveries by hop per topic (drain_impl.hpp; DESIGN.md
+// §5.5j): for each named tree topic, by BFS level, how many nodes the level
+// has, how many of them the window reached and how many messages they hold.
+// ps_topic_hops answers for the last window, blocking; ps_hops_track registers
+// standing topics whose pass run.cpp's hooks enqueue behind every window of a
+// run, into totals that ps_hops_take copies and clears.  Both cut the topics
+// into the audience pass's strips (aud_stage), run the unchanged
+// k_audience_classify over them and k_audience_hops / k_audience_hops_sum
+// behind it, with buffers of their own.  A node's level comes from the host's
+// level tables (TopicHost::level_off), which every node-space build leaves --
+// the GPU rebuild from the readback it makes anyway -- so nothing is read back
+// for this pass.
+#include "drain_impl.hpp"
+
+using namespace psamd;
+
+namespace {
+
+using Hops = Drain::Hops;
+
+static_assert(kHopsCols == PS_MAX_ROUNDS, "a column per round of ps_stats");
+
+// The tree topics of a request with their positions in it: a mesh topic of
+// the window's node space takes no part in the pass
+struct Req {
+  std::vector<uint32_t> topic, row;
+  size_t n_lvl = 0;  // level-table words of the topics with rows to read
+};
+
+bool hops_is_mesh(const ps_engine* e, uint32_t t) { return (e->last_topics[t].flags & kTopicMesh) != 0; }
+
+// topic t has rows to read in the last window (its drain table stands)
+bool hops_active(ps_engine* e, uint32_t t) {
+  uint32_t u0 = 0;
+  return e->drain.tab.topics[t].n_pos && aud_nodes(e, t, &u0);
+}
+
+// The level table of an active topic is the last window's: one root, every
+// level from 1 on non-empty, n_nodes behind the last.  It is written by the
+// node-space build alone, and a build drops the last window, so it can only
+// differ after the topic was set anew over another kind (its record starts
+// afresh, the table empty) with no run since.
+int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t t = topic[i];
+    if (hops_is_mesh(e, t)) continue;
+    R->topic.push_back(t);
+    R->row.push_back(static_cast<uint32_t>(i));
+    if (!hops_active(e, t)) continue;
+    uint32_t u0 = 0;
+    (void)aud_nodes(e, t, &u0);
+    const auto& lv = e->topics[t].level_off;
+    // (lv[1] == u0: the strips start at the first node of level 1, which is
+    // what k_audience_hops_sum's (lv[d] - lv[1]) / per counts strips from)
+    bool ok = lv.size() >= 3 && lv[0] == 0 && lv[1] == u0 && u0 == 1 && lv.back() == e->last_topics[t].n_nodes;
+    for (size_t d = 1; ok && d + 1 < lv.size(); ++d) ok = lv[d] < lv[d + 1];
+    if (!ok) return e->fail(PS_E_STATE, "hops: a topic was set anew since the last window: run first");
+    R->n_lvl += lv.size();
+  }
+  return PS_OK;
+}
+
+// where the parts of the pass's input block lie: entries | levels | strips
+void hops_layout(const Req& R, Hops::Shape* K) {
+  K->n = R.topic.size();
+  K->o_lvl = align256((K->n + 1) * sizeof(HopsEntry));
+  K->o_strips = K->o_lvl + align256(std::max<size_t>(R.n_lvl, 1) * 4);
+}
+
+// aud_stage's entries [n + 1] as the hop pass's, into he; the level tables
+// into lv where it is given; the shape's counts
+void hops_entries(ps_engine* e, const Req& R, const AudEntry* ae, const AudShape& A, HopsEntry* he, uint32_t* lv,
+                  Hops::Shape* K) {
+  const size_t n = R.topic.size();
+  uint32_t lvl0 = 0;
+  uint64_t part0 = 0;
+  K->max_cols = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t t = R.topic[i];
+    HopsEntry h{t, ae[i].strip0, 0, R.row[i], 0, 0, 1, static_cast<uint32_t>(part0)};
+    if (hops_active(e, t)) {
+      const DrainTopic& T = e->drain.tab.topics[t];
+      const auto& src = e->topics[t].level_off;
+      h.c_t = e->last_cnt[t];
+      h.lvl0 = lvl0;
+      h.depth = static_cast<uint32_t>(src.size()) - 2;
+      h.per = aud_strip_nodes(T.flags & kDrainGather, T.n_pos / 64);
+      if (lv) std::copy(src.begin(), src.end(), lv + lvl0);
+      lvl0 += static_cast<uint32_t>(src.size());
+      part0 += static_cast<uint64_t>(ae[i + 1].strip0 - ae[i].strip0) + h.depth;
+      K->max_cols = std::max(K->max_cols, std::min(h.depth, kHopsCols - 1));
+    }
+    he[i] = h;
+  }
+  he[n] = HopsEntry{0, A.ns, 0, 0, 0, 0, 1, static_cast<uint32_t>(part0)};
+  K->ns = A.ns;
+  K->n_verdicts = A.n_verdicts;
+  K->row_bytes = A.row_bytes;
+  K->n_parts = part0;
+}
+
+// classify, then the two hop kernels, over the block `din` on `stream`, into
+// the three [rows][PS_MAX_ROUNDS] arrays.  ms: classify, hops, sum (PSAMD_DRAIN_TIMING)
+int hops_pass(ps_engine* e, Hops::Pass& P, const uint8_t* din, const Hops::Shape& K, uint64_t* nodes, uint64_t* reached,
+              uint64_t* deliv, const PhaseTimer& tm, float* ms) {
+  if (K.ns == 0) return PS_OK;  // no row to read: nothing to add
+  auto& D = e->drain;
+  hipStream_t s = e->stream;
+  if (K.n_parts >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one hop pass");
+  HIP_TRY(P.d_verdict.ensure(K.n_verdicts), "alloc hop verdicts");
+  HIP_TRY(P.d_exc.ensure((static_cast<size_t>(K.ns) + 1) * 8), "alloc hop counts");
+  HIP_TRY(P.d_full.ensure(static_cast<size_t>(K.ns) * 4), "alloc hop counts");
+  HIP_TRY(P.d_part_r.ensure(K.n_parts * 4), "alloc hop partials");
+  HIP_TRY(P.d_part_d.ensure(K.n_parts * 8), "alloc hop partials");
+  const DrainArgs a = drain_args(e, D.tab);
+  AudArgs g{};
+  g.strips = reinterpret_cast<const AudStrip*>(din + K.o_strips);
+  g.n_strips = K.ns;
+  g.share = D.env.share;
+  g.verdict = P.d_verdict.as<uint8_t>();
+  g.n_exc = P.d_exc.as<uint64_t>();
+  g.n_full = P.d_full.as<uint32_t>();
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
+  HIP_TRY(tm.end(ms[0]), "event");
+  HopsArgs h{};
+  h.strips = g.strips;
+  h.n_strips = K.ns;
+  h.entries = reinterpret_cast<const HopsEntry*>(din);
+  h.n = static_cast<uint32_t>(K.n);
+  h.levels = reinterpret_cast<const uint32_t*>(din + K.o_lvl);
+  h.verdict = g.verdict;
+  h.n_exc = g.n_exc;
+  h.count_rows = D.env.load_rows;
+  h.max_cols = K.max_cols;
+  h.part_reached = P.d_part_r.as<uint32_t>();
+  h.part_deliv = P.d_part_d.as<uint64_t>();
+  h.nodes = nodes;
+  h.reached = reached;
+  h.deliv = deliv;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_hops(a, h, s), "k_audience_hops");
+  HIP_TRY(tm.end(ms[1]), "event");
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_audience_hops_sum(h, s), "k_audience_hops_sum");
+  HIP_TRY(tm.end(ms[2]), "event");
+  return PS_OK;
+}
+
+// every pass enqueued so far is complete: nothing waits for one any more
+void hops_settled(Hops& H) {
+  for (auto& f : H.fence) f.pending = false;
+  for (auto& a : H.arena) a.pending = false;
+}
+
+size_t hops_total_bytes(size_t n) { return 3 * n * kHopsCols * 8; }
+
+// The topic as it is defined now builds into a mesh (graph.cpp's rule: a node
+// with two parents, or the root with one, among those the root reaches).
+// Only child lists can: a parent array and a join tree give one parent each.
+bool hops_child_lists_mesh(const TopicHost& T) {
+  if (!T.exists || T.kind != Kind::Children || T.rp.empty()) return false;
+  std::vector<uint8_t> met(T.rp.size() - 1, 0);
+  std::vector<uint32_t> todo{T.root};
+  met[T.root] = 1;
+  while (!todo.empty()) {
+    const uint32_t p = todo.back();
+    todo.pop_back();
+    for (uint32_t k = T.rp[p]; k < T.rp[p + 1]; ++k) {
+      if (met[T.cl[k]]++) return true;
+      todo.push_back(T.cl[k]);
+    }
+  }
+  return false;
+}
+
+}  // namespace
+
+// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
+
+int psamd::hops_open(ps_engine* e) {
+  auto& H = e->drain.hops;
+  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
+}
+
+void psamd::hops_abort(ps_engine* e) {
+  auto& H = e->drain.hops;
+  if (!H.open) return;
+  // what the run's windows staged must have left the staging
+  (void)hipStreamSynchronize(e->stream);
+  H.open = nullptr;
+}
+
+// The window just remembered, added to the totals: its tables (built here
+// where nobody has), the entry table -- per window: it carries the window's
+// message counts --, and the level tables and strips, read where the last
+// window left them on the device while what they are cut from stays, then
+// classify and the two hop kernels.  All on `stream`, behind the window and in
+// front of the next node-space rebuild, which `stream` runs too; nothing
+// waits.  The level tables are the host's of the node space this window ran
+// on: the run built it before its first window, and nothing but a build
+// writes them.
+int psamd::hops_window(ps_engine* e) {
+  auto& D = e->drain;
+  auto& H = D.hops;
+  if (!H.on || !H.open) return PS_OK;
+  auto& R = H.open->mem;
+  if (const int rj = twin_join(e)) return rj;
+  hipStream_t s = e->stream;
+  size_t used = 0;
+  uint8_t* h = nullptr;
+  int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
+  if (rc) return rc;
+  Req Q;
+  if ((rc = hops_plan(e, H.topic.data(), H.topic.size(), &Q))) return rc;
+  const size_t n = Q.topic.size();
+  const uint32_t* const topic = Q.topic.data();
+
+  std::vector<uint64_t> key{e->graph_epoch, n, Q.n_lvl};
+  for (size_t i = 0; i < n; ++i) {
+    const DrainTopic& T = D.tab.topics[topic[i]];
+    uint32_t u0 = 0;
+    const uint32_t nn = aud_nodes(e, topic[i], &u0);
+    key.push_back(static_cast<uint64_t>(T.flags) << 32 | T.n_pos);
+    key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
+    key.push_back(static_cast<uint64_t>(Q.row[i]) << 32 | topic[i]);
+  }
+  Hops::Shape K;
+  hops_layout(Q, &K);
+  std::vector<AudEntry> ae(n + 1);
+  AudShape A;
+  uint8_t* hs = nullptr;
+  if (key == H.strip_key) {
+    HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc hop staging");
+    aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);
+    hops_entries(e, Q, ae.data(), A, reinterpret_cast<HopsEntry*>(hs), nullptr, &K);
+    if (K.ns != H.kept.ns || K.n_verdicts != H.kept.n_verdicts || K.n_parts != H.kept.n_parts || K.o_strips != H.kept.o_strips)
+      return e->fail(PS_E_STATE, "hops: the kept strips are not the window's");
+    K.bytes = H.kept.bytes;
+    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, (n + 1) * sizeof(HopsEntry), hipMemcpyHostToDevice, s), "upload hop entries");
+  } else {
+    H.strip_key.clear();
+    size_t o = 0;
+    uint64_t strips_max = 0;
+    (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
+    if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one hop window");
+    HIP_TRY(sink_stage(R, K.o_strips + strips_max * sizeof(AudStrip), &hs), "alloc hop staging");
+    if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
+      return e->fail(PS_E_STATE, "hops: more strips than staged");
+    hops_entries(e, Q, ae.data(), A, reinterpret_cast<HopsEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl), &K);
+    K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
+    HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc hop strips");
+    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload hop strips");
+    H.kept = K;
+    H.strip_key = key;
+  }
+  const PhaseTimer untimed{D.ev_t, s, false};
+  float none[3] = {0, 0, 0};
+  uint64_t* const acc = H.d_acc.as<uint64_t>();
+  const size_t rows = H.topic.size() * kHopsCols;
+  if ((rc = hops_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, acc, acc + rows, acc + 2 * rows, untimed, none))) return rc;
+  // classify and the counted rows read the window's row set: the events are
+  // recorded whether or not a row was read
+  if ((rc = pass_fence(e, H.fence, "hops"))) return rc;
+  HIP_TRY(hipEventRecord(H.open->ev, s), "event");
+  H.open->pending = true;
+  H.windows += 1;
+  H.skipped += H.topic.size() - n;  // the mesh topics of this window
+  return PS_OK;
+}
+
+extern "C" {
+
+// ---- ps_topic_hops ---------------------------------------------
+
+int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes_out, uint64_t* reached_out,
+                  uint64_t* deliv_out) {
+  if (!e || (n && !topic) || (!nodes_out && !reached_out && !deliv_out)) return PS_E_INVAL;
+  if (const int rc = drain_enter(e, {"ps_topic_hops on a multi-rank engine", "no completed run", nullptr, true})) return rc;
+  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_topic_hops: a mesh topic has no hop per node");
+  if (n == 0) return PS_OK;
+  auto& D = e->drain;
+  auto& H = D.hops;
+  const auto t_host0 = hclock::now();
+  int rc = drain_ready(e);
+  if (!rc) rc = drain_tables(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  float ms[4] = {0, 0, 0, 0};  // classify, hops, sum, copy (PSAMD_DRAIN_TIMING)
+  const PhaseTimer tm{D.ev_t, s, D.env.timing};
+
+  Req Q;
+  if ((rc = hops_plan(e, topic, n, &Q))) return rc;
+  Hops::Shape K;
+  hops_layout(Q, &K);
+  size_t o = 0;
+  uint64_t strips_max = 0;
+  (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
+  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  uint8_t* const hs = H.stage.data();
+  std::vector<AudEntry> ae(n + 1);
+  AudShape A;
+  if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
+    return e->fail(PS_E_STATE, "hops: more strips than staged");
+  hops_entries(e, Q, ae.data(), A, reinterpret_cast<HopsEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl), &K);
+  K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
+  const double host_ms = ms_since(t_host0);
+
+  const size_t rows = n * kHopsCols, out_bytes = hops_total_bytes(n);
+  HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc hop strips");
+  HIP_TRY(H.d_out.ensure(out_bytes), "alloc hop sums");
+  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes), "alloc hop view");
+  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s), "clear hop sums");
+  if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload hop strips");
+  if ((rc = hops_pass(e, H.sync, H.sync.d_in.as<uint8_t>(), K, out, out + rows, out + 2 * rows, tm, ms))) return rc;
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(hipMemcpyAsync(H.h_out, out, out_bytes, hipMemcpyDeviceToHost, s), "read hop sums");
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  HIP_TRY(tm.end(ms[3]), "event");
+  if (nodes_out) std::memcpy(nodes_out, H.h_out, rows * 8);
+  if (reached_out) std::memcpy(reached_out, H.h_out + rows * 8, rows * 8);
+  if (deliv_out) std::memcpy(deliv_out, H.h_out + 2 * rows * 8, rows * 8);
+  if (D.env.timing)
+    std::fprintf(stderr,
+                 "psamd topic_hops: topics %zu strips %u nodes %llu row_bytes %llu partials %llu classify_ms %.4f hops_ms %.4f "
+                 "sum_ms %.4f copy_ms %.4f host_strips_ms %.4f\n",
+                 n, K.ns, static_cast<unsigned long long>(K.n_verdicts), static_cast<unsigned long long>(K.row_bytes),
+                 static_cast<unsigned long long>(K.n_parts), ms[0], ms[1], ms[2], ms[3], host_ms);
+  return PS_OK;
+}
+
+// ---- ps_hops_track / ps_hops_take ------------------------------
+
+int ps_hops_track(ps_engine* e, const uint32_t* topic, size_t n) {
+  if (!e || (n && !topic)) return PS_E_INVAL;
+  if (e->world > 1) return e->fail(PS_E_STATE, "ps_hops_track on a multi-rank engine");
+  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
+  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (hops_child_lists_mesh(e->topics[topic[i]]))
+      return e->fail(PS_E_STATE, "ps_hops_track: a mesh topic has no hop per node");
+  auto& H = e->drain.hops;
+  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  // whatever still adds into the totals ends first
+  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
+  hops_settled(H);
+  H.open = nullptr;
+  H.strip_key.clear();
+  H.windows = H.skipped = 0;
+  H.topic.assign(topic, topic + n);
+  H.on = n > 0;
+  if (!H.on) {
+    H.d_acc.release();
+    H.track.d_in.release();
+    H.track.d_verdict.release();
+    H.track.d_exc.release();
+    H.track.d_full.release();
+    H.track.d_part_r.release();
+    H.track.d_part_d.release();
+    return PS_OK;
+  }
+  HIP_TRY(H.d_acc.ensure(hops_total_bytes(n)), "alloc hop totals");
+  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, hops_total_bytes(n), e->stream), "clear hop totals");
+  return PS_OK;
+}
+
+int ps_hops_take(ps_engine* e, uint64_t* nodes_out, uint64_t* reached_out, uint64_t* deliv_out, uint64_t* n_windows_out,
+                 uint64_t* n_skipped_out) {
+  if (!e || !n_windows_out || !n_skipped_out) return PS_E_INVAL;
+  auto& H = e->drain.hops;
+  if (!H.on) return e->fail(PS_E_NOTREADY, "no hops are tracked");
+  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
+  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  const size_t rows = H.topic.size() * kHopsCols, bytes = hops_total_bytes(H.topic.size());
+  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, bytes), "alloc hop view");
+  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "hop event");
+  // every pass ran on `stream`: the copy behind them, the clearing behind the
+  // copy and in front of whatever runs next, one wait
+  hipStream_t s = e->stream;
+  HIP_TRY(hipMemcpyAsync(H.h_out, H.d_acc.p, bytes, hipMemcpyDeviceToHost, s), "read hop totals");
+  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, s), "clear hop totals");
+  HIP_TRY(hipEventRecord(H.ev_take, s), "event");
+  HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the hop totals");
+  hops_settled(H);
+  if (nodes_out) std::memcpy(nodes_out, H.h_out, rows * 8);
+  if (reached_out) std::memcpy(reached_out, H.h_out + rows * 8, rows * 8);
+  if (deliv_out) std::memcpy(deliv_out, H.h_out + 2 * rows * 8, rows * 8);
+  *n_windows_out = H.windows;
+  *n_skipped_out = H.skipped;
+  H.windows = H.skipped = 0;
+  return PS_OK;
+}
+
+}  // extern "C"

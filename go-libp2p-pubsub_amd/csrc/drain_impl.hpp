@@ -15,6 +15,10 @@
 //   drain_load.cpp    ps_peer_load, ps_load_track / ps_load_take and run.cpp's
 //                     hooks (§5.5i): per-peer recv / sent sums from the audience
 //                     pass's strips and verdicts, with buffers of their own
+//   drain_hops.cpp    ps_topic_hops, ps_hops_track / ps_hops_take and run.cpp's
+//                     hooks (§5.5j): per tree topic, nodes / reached / deliv by
+//                     BFS level from the same strips and verdicts and the
+//                     host's level tables, with buffers of their own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -29,7 +33,8 @@
 //    in line on `stream`.
 //  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
 //    over each row set) and Load::fence (the last standing load pass over
-//    each) are read by drain_fence (run.cpp).
+//    each) and Hops::fence (the last standing hop pass) are read by
+//    drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics
@@ -93,6 +98,10 @@ struct PhaseTimer {
 
 hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need);
 hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out);
+// the standing passes (load, hops): a run's pinned staging, arena[run & 1];
+// the event behind the last pass over the current row set
+int pass_arena_open(ps_engine* e, Drain::PassArena (&arena)[2], uint64_t* runs, Drain::PassArena** open);
+int pass_fence(ps_engine* e, Drain::PassFence (&fence)[2], const char* who);
 
 // Where one call stages its input: a slot's pinned h_in, all of it (one call
 // takes once), or a region of a sink result's arena
@@ -188,6 +197,9 @@ int drain_list_ids(ps_engine* e, const DrainArgs& a, uint32_t n_segs, uint64_t t
 int aud_check_topics(ps_engine* e, const uint32_t* topic, size_t n);
 // topic t's non-root nodes in the last window: the first one and their number
 uint32_t aud_nodes(const ps_engine* e, uint32_t t, uint32_t* u0);
+
+// nodes of every strip but a topic's last (the hop pass finds a level's strips by it)
+uint32_t aud_strip_nodes(bool gather, uint32_t words);
 
 // the bytes one window's entries and strips take at most, before its tables
 // stand: entries | strips (the strips from *o_strips)

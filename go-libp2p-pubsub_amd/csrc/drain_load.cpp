@@ -70,23 +70,6 @@ int load_pass(ps_engine* e, Load::Pass& P, const uint8_t* din, size_t o_strips, 
   return PS_OK;
 }
 
-// The last pass over the window's rows on `stream` (run.cpp: drain_fence),
-// recorded behind it: the entry of this row set, else one whose row set is gone
-int load_fence(ps_engine* e) {
-  auto& L = e->drain.load;
-  Load::Fence* F = nullptr;
-  for (auto& f : L.fence)
-    if (f.seen == e->rows.seen.p) F = &f;
-  for (auto& f : L.fence)
-    if (!F && (!f.seen || f.seen != e->rows_other.seen.p)) F = &f;
-  if (!F) return e->fail(PS_E_STATE, "load: no fence entry for the row set");
-  if (!F->ev) HIP_TRY(hipEventCreateWithFlags(&F->ev, kStreamEvent), "load event");
-  HIP_TRY(hipEventRecord(F->ev, e->stream), "event");
-  F->seen = e->rows.seen.p;
-  F->pending = true;
-  return PS_OK;
-}
-
 // every pass enqueued so far is complete: nothing waits for one any more
 void load_settled(Load& L) {
   for (auto& f : L.fence) f.pending = false;
@@ -99,28 +82,7 @@ void load_settled(Load& L) {
 
 int psamd::load_open(ps_engine* e) {
   auto& L = e->drain.load;
-  if (!L.on) return PS_OK;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  auto& A = L.arena[L.runs++ & 1];
-  // the arena's last run lies two back: its passes have left the staging, or do so soon
-  if (A.pending) HIP_TRY(hipEventSynchronize(A.ev), "wait for a load pass");
-  A.pending = false;
-  auto& R = A.mem;
-  if (R.arena.size() > 1) {
-    size_t cap = 0;
-    for (auto& c : R.arena) {
-      cap += c.cap;
-      (void)hipHostFree(c.h);
-    }
-    R.arena.clear();
-    uint8_t* h = nullptr;
-    R.arena_used = 0;
-    HIP_TRY(sink_stage(R, cap, &h), "alloc load staging");
-  }
-  R.arena_used = 0;
-  if (!A.ev) HIP_TRY(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming), "load event");
-  L.open = &A;
-  return PS_OK;
+  return L.on ? pass_arena_open(e, L.arena, &L.runs, &L.open) : PS_OK;
 }
 
 void psamd::load_abort(ps_engine* e) {
@@ -196,7 +158,7 @@ int psamd::load_window(ps_engine* e) {
     return rc;
   // classify and the counted rows read the window's row set: the events are
   // recorded whether or not a row was read
-  if ((rc = load_fence(e))) return rc;
+  if ((rc = pass_fence(e, L.fence, "load"))) return rc;
   HIP_TRY(hipEventRecord(L.open->ev, s), "event");
   L.open->pending = true;
   L.windows += 1;

@@ -7,12 +7,10 @@
 
 using namespace psamd;
 
-namespace {
-
 // nodes one strip holds of rows `words` mask words wide (kernels.hpp,
 // AudStrip): a row counted at the lanes it takes in a load, one for the rows
 // of an arrival-order topic, which are not read
-uint32_t aud_strip_nodes(bool gather, uint32_t words) {
+uint32_t psamd::aud_strip_nodes(bool gather, uint32_t words) {
   uint32_t lanes = 1;
   if (!gather) {
     while (lanes < words && lanes < 64) lanes *= 2;
@@ -20,8 +18,6 @@ uint32_t aud_strip_nodes(bool gather, uint32_t words) {
   }
   return std::max(1u, kAudStripBytes / (lanes * 8));
 }
-
-}  // namespace
 
 // ---- what the topics calls share ------------------------------------------------
 

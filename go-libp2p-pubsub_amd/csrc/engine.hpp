@@ -740,6 +740,24 @@ struct ps_engine {
       size_t strip_bytes = 0;  // PSAMD_DRAIN_TIMING: the bytes the open run's windows uploaded for them
     } sink;
 
+    // What the standing passes behind a run's windows (ps_load_track,
+    // ps_hops_track) keep alike (drain_tables.cpp: pass_arena_open, pass_fence).
+    // Pinned staging, one arena per run in turn (run k: arena[k & 1]): every
+    // window of the run takes a region of its own, and the arena is reused
+    // once the last pass of the run two before is complete (ev)
+    struct PassArena {
+      Sink::Res mem;  // (its arena alone: drain_tables.cpp sink_stage)
+      hipEvent_t ev = nullptr;
+      bool pending = false;
+    };
+    // the last pass per row set: a window about to write the set on another
+    // stream waits for it (run.cpp: drain_fence)
+    struct PassFence {
+      const void* seen = nullptr;
+      hipEvent_t ev = nullptr;
+      bool pending = false;
+    };
+
     // ps_peer_load / ps_load_track / ps_load_take (host code:
     // drain_load.cpp): per-peer recv / sent sums from the audience pass's
     // verdicts, k_audience_load behind k_audience_classify.  The blocking
@@ -770,25 +788,59 @@ struct ps_engine {
       std::vector<uint64_t> strip_key;
       uint32_t ns = 0;
       uint64_t n_verdicts = 0;
-      // Pinned staging, one arena per run in turn (run k: arena[k & 1]): every
-      // window of the run takes a region of its own, and the arena is reused
-      // once the last pass of the run two before is complete (ev)
-      struct Arena {
-        Sink::Res mem;  // (its arena alone: drain_tables.cpp sink_stage)
-        hipEvent_t ev = nullptr;
-        bool pending = false;
-      } arena[2];
+      // pinned staging per run and the last pass per row set (PassArena, PassFence)
+      PassArena arena[2];
       uint64_t runs = 0;
-      Arena* open = nullptr;  // the run being enqueued
-      // the last pass per row set: a window about to write the set on another
-      // stream waits for it (run.cpp: drain_fence)
-      struct Fence {
-        const void* seen = nullptr;
-        hipEvent_t ev = nullptr;
-        bool pending = false;
-      } fence[2];
+      PassArena* open = nullptr;  // the run being enqueued
+      PassFence fence[2];
       hipEvent_t ev_take = nullptr;
     } load;
+
+    // ps_topic_hops / ps_hops_track / ps_hops_take (host
+    // code: drain_hops.cpp): per tree topic, nodes / reached / deliv by BFS
+    // level from the audience pass's verdicts, k_audience_hops and
+    // k_audience_hops_sum behind k_audience_classify.  Shaped as Load: the
+    // blocking call and the standing pass each own their buffers, and nothing
+    // here is the sinks' or the load pass's.
+    struct Hops {
+      // one pass's device buffers: entries | levels | strips in one block, the
+      // verdict bytes and strip counts of classify, the (strip, level) partials
+      struct Pass {
+        psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_part_r, d_part_d;
+      };
+      // what hops_stage leaves beside the block: where its parts lie and what
+      // the grids and buffers are sized by
+      struct Shape {
+        size_t n = 0;                 // tree topics: the entries
+        size_t o_lvl = 0, o_strips = 0, bytes = 0;
+        uint32_t ns = 0, max_cols = 0;
+        uint64_t n_verdicts = 0, n_parts = 0, row_bytes = 0;
+      };
+      // ps_topic_hops: its pass, nodes | reached | deliv on the device, their pinned copy
+      Pass sync;
+      psamd::DevBuf d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+      // ps_hops_track: the standing topics and the totals since the last take
+      // or track call, nodes | reached | deliv, [n][PS_MAX_ROUNDS] each by
+      // request position
+      bool on = false;
+      std::vector<uint32_t> topic;
+      Pass track;
+      psamd::DevBuf d_acc;
+      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out, since the last take or track call
+      // the levels and strips on the device while what they are cut from
+      // stays (graph_epoch, each standing topic's table shape and node range)
+      std::vector<uint64_t> strip_key;
+      Shape kept;
+      // pinned staging per run and the last pass per row set (PassArena, PassFence)
+      PassArena arena[2];
+      uint64_t runs = 0;
+      PassArena* open = nullptr;  // the run being enqueued
+      PassFence fence[2];
+      hipEvent_t ev_take = nullptr;
+    } hops;
   } drain;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
@@ -938,6 +990,11 @@ void sink_abort(ps_engine* e);
 int load_open(ps_engine* e);
 int load_window(ps_engine* e);
 void load_abort(ps_engine* e);
+// drain_hops.cpp, the standing hop pass (ps_hops_track; all no-ops while
+// nothing is tracked): called where the load pass's hooks are
+int hops_open(ps_engine* e);
+int hops_window(ps_engine* e);
+void hops_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

@@ -904,4 +904,52 @@ struct LoadArgs {
 // kDrainGather topic, is counted by the wave, one row at a time.
 hipError_t launch_audience_load(const DrainArgs& a, const LoadArgs& g, hipStream_t s);
 
+// ---- deliveries by hop per topic (ps_topic_hops, ps_hops_track) --
+// The audience pass's verdicts turned into three histograms per tree topic, by
+// BFS level: a non-root node of level d whose row holds k of its topic's c_t
+// window messages adds 1 to nodes, (k > 0) to reached and k to deliv, in
+// column min(d, kHopsCols - 1) of the topic's row.  The strips are the
+// audience pass's, cut with no regard to levels; the entry table (request
+// order among the tree topics, entry n closes it) carries the topic's level
+// table -- levels[lvl0 + d], d in [0, depth + 1]: the first node of level d,
+// topic-relative, n_nodes behind the last -- and its strip length, so that a
+// level's strips follow from its node range.  Strip s of an entry leaves one
+// partial per level d it meets, in slot part0 + (s - strip0) + (d - 1): strips
+// and levels both ascend along a topic's nodes, so no two pairs share a slot.
+constexpr uint32_t kHopsCols = 256;  // PS_MAX_ROUNDS
+struct HopsEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window
+  uint32_t row;     // the topic's row of the outputs: its position in the request
+  uint32_t lvl0;    // the topic's level table in HopsArgs::levels
+  uint32_t depth;   // its deepest level
+  uint32_t per;     // nodes of every strip of the entry but the last
+  uint32_t part0;   // the entry's first partial slot (it owns strips + depth of them)
+};
+struct HopsArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const HopsEntry* entries;  // [n + 1]
+  uint32_t n;
+  const uint32_t* levels;
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint64_t* n_exc;     // AudArgs::n_exc: 0 = every node of the strip is full
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  uint32_t max_cols;         // columns 1 .. max_cols are summed: the deepest entry's, kHopsCols - 1 at most
+  uint32_t* part_reached;    // per (strip, level) slot
+  uint64_t* part_deliv;
+  uint64_t* nodes;           // [rows][kHopsCols] each, added into
+  uint64_t* reached;
+  uint64_t* deliv;
+};
+// k_audience_hops: one wave per strip behind k_audience_classify, a node per
+// lane, level by level; a strip without exceptions takes its partials from the
+// level bounds alone.  k_audience_hops_sum: one block per (entry, column) adds
+// the column's run of partials -- the last column every level from
+// kHopsCols - 1 on -- and the level's size into the three outputs: one writer
+// per word, plain loads and stores.
+hipError_t launch_audience_hops(const DrainArgs& a, const HopsArgs& g, hipStream_t s);
+hipError_t launch_audience_hops_sum(const HopsArgs& g, hipStream_t s);
+
 }  // namespace psamd

@@ -175,6 +175,9 @@ PROTOTYPES = [
     ("ps_peer_load", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p]),
     ("ps_load_track", C.c_int, [_P, _u32p, C.c_size_t]),
     ("ps_load_take", C.c_int, [_P, _u64p, _u64p, _u64p]),
+    ("ps_topic_hops", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p]),
+    ("ps_hops_track", C.c_int, [_P, _u32p, C.c_size_t]),
+    ("ps_hops_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -319,6 +322,7 @@ class Engine:
         self._L = L
         self._drain_n = []  # (kind: 0 plain, 1 shared, 2 topics; entries) of the drains begun and not ended
         self._sink_n = 0  # standing queries (sink_set)
+        self._hops_n = 0  # standing topics (hops_track): the rows hops_take's arrays hold
         if plan:
             self.set_plan(**plan)
 
@@ -753,6 +757,44 @@ class Engine:
         nw = C.c_uint64()
         self._check(self._L.ps_load_take(self._h, _p(recv, C.c_uint64), _p(sent, C.c_uint64), C.byref(nw)))
         return recv, sent, nw.value
+
+    def topic_hops(self, topics) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Deliveries by hop of the last window for the named distinct tree
+        topics (ps_topic_hops): (nodes, reached, deliv), uint64 [n, MAX_ROUNDS]
+        each, row i for topics[i] -- per BFS level the topic's nodes, those the
+        window reached, and the messages they received; the last column holds
+        every level from MAX_ROUNDS - 1 on."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        out = [np.zeros((t.size, MAX_ROUNDS), dtype=np.uint64) for _ in range(3)]
+        self._check(self._L.ps_topic_hops(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out)))
+        return out[0], out[1], out[2]
+
+    def hops_track(self, topics):
+        """Registers standing tree topics (ps_hops_track): from now on every
+        window of every run adds its deliveries by hop over them into totals on
+        the device (hops_take).  No topic clears the tracking; setting or
+        clearing zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_hops_track(self._h, _p(t, C.c_uint32), t.size))
+        self._hops_n = int(t.size)
+
+    def hops_take(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, int, int]:
+        """The totals since the last take or track call (ps_hops_take):
+        (nodes, reached, deliv, n_windows, n_skipped), the arrays uint64
+        [n_tracked, MAX_ROUNDS]; n_skipped counts the (topic, window) pairs
+        left out because the topic was a mesh there.  The totals and both
+        counts start again at 0.  (The arrays are sized by the last hops_track
+        made through this object: track through it, not through the raw
+        library handle.)"""
+        n = self._hops_n
+        out = [np.zeros((n, MAX_ROUNDS), dtype=np.uint64) for _ in range(3)]
+        nw, nsk = C.c_uint64(), C.c_uint64()
+        self._check(self._L.ps_hops_take(self._h, *(_p(a, C.c_uint64) for a in out), C.byref(nw), C.byref(nsk)))
+        return out[0], out[1], out[2], nw.value, nsk.value
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -599,6 +599,62 @@ int ps_peer_load(ps_engine* e, const uint32_t* topic, size_t n,
 int ps_load_track(ps_engine* e, const uint32_t* topic, size_t n);
 int ps_load_take(ps_engine* e, uint64_t* recv_out, uint64_t* sent_out, /* [n_peers], nullable */
                  uint64_t* n_windows_out);
+/* Deliveries by hop per topic: how deep a topic's messages travel (one rank;
+ * DESIGN.md 5.5j).  Per window and per named tree topic t with c_t > 0
+ * messages in it, on the node space that window ran on: a non-root node u has
+ * BFS level d(u) in [1, depth_t], and its row holds k(u) of t's window
+ * messages -- ps_peer_load's k: 0 for a tree node the window did not reach.
+ * Column h = min(d(u), PS_MAX_ROUNDS - 1) of the topic's row gets
+ *   nodes[h] += 1, reached[h] += (k(u) > 0), deliv[h] += k(u).
+ * On a tree the path is unique: every message a node receives arrives at hop
+ * d(u), whatever its start round (ps_publish_at: hop = round - start), so
+ * deliv[h] is the topic's deliveries at hop h.  Column 0 stays 0: the root is
+ * no recipient.  The last column collects hop PS_MAX_ROUNDS - 1 and more, so
+ * row sums stay exact for trees deeper than the array.  A topic with no
+ * message in the window adds nothing, not even nodes; peers outside the node
+ * space add nothing: both as in ps_peer_load.
+ *   Mesh topics are refused: a mesh node's hop is its first-arrival round,
+ * which no row records.  A tree topic that shares a window with a mesh is
+ * answered as any other.
+ *   ps_topic_hops answers for the last window of the last run, blocking, with
+ * ps_peer_load's window, stream-ordering and twin-join rules.  The n topics
+ * are distinct; row i of each array ([n * PS_MAX_ROUNDS]; any may be NULL, not
+ * all three) belongs to topic[i] and is written in full: unused columns and
+ * idle topics read 0.  n == 0 is valid and writes nothing.  PS_E_INVAL for a
+ * NULL engine, n > 0 without topic, all three outputs NULL or a topic named
+ * twice; PS_E_RANGE, nothing written, for a topic out of range; PS_E_NOTREADY
+ * before any run; PS_E_STATE, nothing written, on a multi-rank engine, when a
+ * named topic is a mesh in that window's node space, and for a topic that was
+ * set anew over another kind since the window (its levels are gone: run first).
+ *   ps_hops_track registers n standing topics (copied; n == 0 clears the
+ * tracking and frees the totals).  PS_E_INVAL / PS_E_RANGE as above, and
+ * PS_E_STATE for a topic whose child lists make a mesh: the previous tracking
+ * stays.  PS_E_STATE with a run in flight and on a multi-rank engine;
+ * ps_dist_init* on an engine that is tracking hops returns PS_E_STATE.
+ * Setting or clearing zeroes the totals.  Tracking is independent of both
+ * sinks and of ps_load_track: all three may be set at once.  While it is set,
+ * every window of every ps_run / ps_run_async that runs something enqueues
+ * the pass behind itself -- the window is neither planned nor launched
+ * differently -- and the pass adds into three totals on the device,
+ * [n][PS_MAX_ROUNDS] each, indexed by request position: they survive
+ * node-space rebuilds, joins, leaves and drops between windows.  A tracked
+ * topic that is a mesh in a window's node space adds nothing for that window;
+ * each such (topic, window) pair is counted.
+ *   ps_hops_take waits for the passes enqueued so far, copies the totals since
+ * the last take or track call (each array may be NULL), zeroes them in front
+ * of whatever runs next, sets *n_windows_out to the windows counted and
+ * *n_skipped_out to the (mesh topic, window) pairs left out, and resets both
+ * counts.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with a run in
+ * flight (complete the runs with ps_wait first); PS_E_INVAL for a NULL engine
+ * or count pointer.  After a failed ps_run / ps_wait the totals are
+ * unspecified until the next take or track call. */
+int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n,
+                  uint64_t* nodes_out, uint64_t* reached_out, uint64_t* deliv_out);
+                  /* [n * PS_MAX_ROUNDS] each, row i = topic[i]; any may be NULL, not all three */
+int ps_hops_track(ps_engine* e, const uint32_t* topic, size_t n);
+int ps_hops_take(ps_engine* e, uint64_t* nodes_out, uint64_t* reached_out, uint64_t* deliv_out,
+                 /* [n_tracked * PS_MAX_ROUNDS], nullable */
+                 uint64_t* n_windows_out, uint64_t* n_skipped_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -89,6 +89,16 @@ two answers compared array for array; then the pipelined step with every
 topic tracked (ps_load_track, one ps_load_take per loop) against the step with
 the audience sink over the same topics and the plain step, the three
 alternating in one process.  Writes DIR/load_bench.json.
+
+--hops: deliveries by hop per topic (ps_topic_hops) over every topic after one
+step, --reps repetitions in one process: its wall and device phases (classify,
+hops, sum, copy) beside ps_peer_load's and ps_drain_topics' phases and walls;
+the derivation a caller has without it -- ps_drain_topics +
+ps_topic_get_parents per topic + numpy depths -- and its wall, the two answers
+compared array for array; then the pipelined step plain, with hops tracked
+(ps_hops_track, one ps_hops_take per loop), with load tracked, with both and
+with the audience sink beside both, the five alternating in one process, the
+totals against steps x the blocking answer.  Writes DIR/hops_bench.json.
 """
 from __future__ import annotations
 
@@ -1066,6 +1076,167 @@ def load_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def host_topic_hops(eng, wl, topics):
+    """Deliveries by hop as a caller derives them without ps_topic_hops: the
+    audience answer, every topic's parent array, depths by numpy (level d + 1 =
+    the peers whose upstream stands at level d)."""
+    r = eng.drain_topics(topics)
+    n, cols = wl.n_peers, PE.MAX_ROUNDS
+    out = [np.zeros((len(topics), cols), dtype=np.uint64) for _ in range(3)]
+    sizes = np.diff(r["list_off"]).astype(np.uint64)
+    c_all = np.bincount(wl.msg_topics, minlength=len(wl.topics))
+    for i, t in enumerate(topics):
+        c = int(c_all[t])
+        if not c:
+            continue
+        par = eng.parents(int(t))
+        root = wl.topics[int(t)].root
+        kid = np.nonzero(par != 0xFFFFFFFF)[0]
+        kid = kid[kid != root]
+        depth = np.full(n, -1, dtype=np.int64)
+        depth[root] = 0
+        todo, d = kid, 0
+        while todo.size:
+            at = depth[par[todo]] == d
+            if not at.any():
+                break
+            d += 1
+            depth[todo[at]] = d
+            todo = todo[~at]
+        k = np.zeros(n, dtype=np.uint64)
+        k[kid] = c
+        lo, hi = int(r["exc_off"][i]), int(r["exc_off"][i + 1])
+        if hi > lo:  # the nodes that are not full: their private list's length, or nothing
+            el = r["exc_list"][lo:hi].astype(np.int64)
+            have = el != 0xFFFFFFFF
+            ke = np.zeros(hi - lo, dtype=np.uint64)
+            ke[have] = sizes[el[have]]
+            k[r["exc_peer"][lo:hi]] = ke
+        k[root] = 0
+        m = kid[depth[kid] > 0]
+        col = np.minimum(depth[m], cols - 1)
+        out[0][i] = np.bincount(col, minlength=cols).astype(np.uint64)
+        out[1][i] = np.bincount(col[k[m] > 0], minlength=cols).astype(np.uint64)
+        out[2][i] = np.bincount(col, weights=k[m].astype(np.float64), minlength=cols).astype(np.uint64)
+    return tuple(out)
+
+
+def hops_main(a, wl):
+    """--hops (see the module text).  Writes DIR/hops_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": a.steps, "warmup": a.warmup}
+    eng, st = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for tag, call, key in (("topic_hops", eng.topic_hops, "hops_phases"), ("peer_load", eng.peer_load, "load_phases"),
+                               ("drain_topics", eng.drain_topics, "topics_phases")):
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+                with StderrCapture() as cap:
+                    got = call(topics)
+                row = phase_line(cap.text, tag)
+                for k in ("strips", "nodes", "row_bytes", "partials"):
+                    m = re.search(rf"\b{k} (\d+)", cap.text)
+                    if m:
+                        row[k] = int(m.group(1))
+                rows.append(row)
+            res[key] = rows[1:]
+            if tag == "topic_hops":
+                blocking = got
+        assert int(blocking[2].sum()) == st.deliveries, (int(blocking[2].sum()), st.deliveries)
+        depth = [int(np.nonzero(blocking[0][i])[0].max()) if blocking[0][i].any() else 0 for i in range(nt)]
+        res.update(deliveries=int(st.deliveries), deliv_sum=int(blocking[2].sum()), nodes_sum=int(blocking[0].sum()),
+                   reached_sum=int(blocking[1].sum()), max_depth=max(depth),
+                   deliv_by_hop=blocking[2].sum(axis=0)[:max(depth) + 1].tolist())
+    eng, _ = stepped_engine(wl, {})
+    with eng:
+        walls = {"hops": [], "host": [], "topics": [], "load": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.topic_hops(topics)
+            walls["hops"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            want = host_topic_hops(eng, wl, topics)
+            walls["host"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.drain_topics(topics)
+            walls["topics"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.peer_load(topics)
+            walls["load"].append(1e3 * (time.perf_counter() - t0))
+            for g, w, name in zip(got, want, ("nodes", "reached", "deliv")):
+                assert np.array_equal(g, w), f"ps_topic_hops {name} differs from the host derivation"
+    res["hops_wall_ms"], res["host_derivation_wall_ms"], res["topics_wall_ms"], res["load_wall_ms"] = \
+        (walls[k][1:] for k in ("hops", "host", "topics", "load"))
+    res["answers_agree"] = True
+    res["host_over_hops_wall"] = float(np.median(res["host_derivation_wall_ms"]) / np.median(res["hops_wall_ms"]))
+    hp, lp = res["hops_phases"], res["load_phases"]
+    res["hops_kernels_over_load_kernel"] = float(np.median([p["hops_ms"] + p["sum_ms"] for p in hp]) /
+                                                 np.median([p["load_ms"] for p in lp]))
+
+    # tracking in the pipelined loop: plain, hops, load, both
+    for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING"):
+        os.environ.pop(k, None)
+    eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    none = np.zeros(0, dtype=np.uint32)
+    # (hops tracked, load tracked, the audience sink set)
+    modes = {"plain": (False, False, False), "hops": (True, False, False), "load": (False, True, False),
+             "both": (True, True, False), "all_three": (True, True, True)}
+
+    def timed(hops, load, sink, steps):
+        eng.hops_track(topics if hops else none)
+        eng.load_track(topics if load else none)
+        if sink:
+            eng.sink_set_topics(topics, exc_cap=exc_cap)
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        if sink:
+            loop_sink_topics(eng, wl, steps, [])
+        else:
+            loop_plain(eng, wl, steps)
+        th = eng.hops_take() if hops else None
+        tl = eng.load_take() if load else None
+        ms = 1e3 * (time.perf_counter() - t0) / steps
+        if sink:
+            eng.sink_set_topics([])
+        return ms, eng.overlapped_windows() - o0, th, tl
+
+    with eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        load0 = eng.peer_load(topics)
+        exc_cap = max(int(eng.drain_topics(topics)["exc_off"][-1]), 1)
+        for mode in modes.values():
+            timed(*mode, a.warmup)
+        ms = {k: [] for k in modes}
+        over = {k: [] for k in modes}
+        for _ in range(a.reps):
+            for name, (hops, load, sink) in modes.items():
+                t, o, th, tl = timed(hops, load, sink, a.steps)
+                ms[name].append(t)
+                over[name].append(int(o))
+                if hops:
+                    assert th[3:] == (a.steps, 0)
+                    for g, w in zip(th[:3], blocking):
+                        assert np.array_equal(g, w * np.uint64(a.steps)), "tracked hop totals differ"
+                if load:
+                    assert tl[2] == a.steps and np.array_equal(tl[0], load0[0] * np.uint64(a.steps))
+        eng.hops_track(none)
+        eng.load_track(none)
+    res.update(ms_per_step=ms, overlapped_windows=over, tracked_totals_agree=True,
+               hops_minus_plain_ms=float(np.median(ms["hops"]) - np.median(ms["plain"])),
+               load_minus_plain_ms=float(np.median(ms["load"]) - np.median(ms["plain"])),
+               both_minus_plain_ms=float(np.median(ms["both"]) - np.median(ms["plain"])),
+               all_three_minus_plain_ms=float(np.median(ms["all_three"]) - np.median(ms["plain"])))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "hops_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -1208,8 +1379,11 @@ def main():
     ap.add_argument("--sink", action="store_true", help="the sink in the pipelined loop against ps_drain_shared_begin's")
     ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
     ap.add_argument("--load", action="store_true", help="ps_peer_load against the host derivation; tracking in the pipelined loop")
+    ap.add_argument("--hops", action="store_true", help="ps_topic_hops against the host derivation; tracking in the pipelined loop")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.hops:
+        return hops_main(a, wl)
     if a.load:
         return load_main(a, wl)
     if a.topics and a.sink:
