@@ -36,6 +36,12 @@
 //                         nodes reached and the messages they hold
 //   k_audience_hops_sum   each (topic, column)'s partials into its row: one
 //                         writer per word, no atomics
+// and, for ps_peer_downstream / ps_downstream_track (§5.5k), the audience behind each peer:
+//   k_audience_weights    behind k_audience_classify: the messages a node's row holds
+//   k_downstream_level    one launch per BFS level, bottom-up: a node's subtree
+//                         size and subtree messages from its children's, and
+//                         what lies below it into its peer's two sums
+//   k_downstream_top      the narrow levels under a root in one block
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -612,6 +618,140 @@ __global__ __launch_bounds__(kHopsSumBlock) void k_audience_hops_sum(HopsArgs g)
   }
 }
 
+// ---- audience behind each peer (ps_peer_downstream, ps_downstream_track) -------
+
+// One wave per strip, one node per lane: the messages the node's row holds
+// into k -- full: c_t, none: 0, anything else, and under the seam every full
+// row, through load_count_row.  Where classify counted no exception in the
+// strip every node is full and no verdict byte is read.  The wave of an
+// entry's first strip writes the root's 0.
+__global__ __launch_bounds__(kAudBlock) void k_audience_weights(DrainArgs a, DownArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const DownEntry E = g.entries[lo - 1];
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  uint32_t* __restrict__ kout = g.k + E.n0;
+  const bool all_full = !g.count_rows && g.n_exc[s] == 0;
+  for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+    const uint32_t i = i0 + lane;
+    const bool in = i < S.n;
+    uint32_t k = E.c_t;
+    if (!all_full) {
+      const uint32_t v = vin[min(i, S.n - 1)];
+      const bool full = !gather && v == kDrainRowAny;
+      const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+      k = full && !count ? E.c_t : 0u;
+      uint64_t todo = __ballot(count);
+      while (todo) {
+        const uint32_t j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint32_t c = load_count_row(a, T, S.u0 + i0 + j, lane);
+        if (lane == j) k = c;
+      }
+    }
+    if (in) kout[S.u0 + i] = k;
+  }
+  if (E.strip0 == s && lane == 0) kout[0] = 0;
+}
+
+// The nodes [lo, hi) of level d < depth of entry E, thread tid of nt (whole
+// waves) a node each: the node's children are the CSR range's length of nodes
+// of level d + 1, from that level's first node plus what the level's nodes
+// before it have.  A lane sums its node's children; a node with more than a
+// wave's worth is summed by the wave, lanes across its children.  Children of
+// the deepest level are leaves: (1, k).  Then the node's two words, and what
+// lies strictly below it into its peer's sums.
+__device__ __forceinline__ void down_nodes(const DownArgs& g, const DownEntry& E, const uint32_t* __restrict__ lv,
+                                           uint32_t d, uint32_t lo, uint32_t hi, uint32_t tid, uint32_t nt) {
+  const uint32_t lane = tid & (kWave - 1);
+  const uint32_t c0 = lv[d + 1], c1 = lv[d + 2];
+  const uint32_t rp0 = g.row_ptr[E.nbase + lv[d]];
+  const bool leaf_kids = d + 1 == E.depth;
+  const uint32_t* const k = g.k + E.n0;
+  uint32_t* const w_n = g.w_n + E.n0;
+  uint64_t* const w_k = g.w_k + E.n0;
+  unsigned long long* const below = reinterpret_cast<unsigned long long*>(g.below);
+  unsigned long long* const carried = reinterpret_cast<unsigned long long*>(g.carried);
+  for (uint32_t u0 = lo + (tid & ~(kWave - 1)); u0 < hi; u0 += nt) {  // (wave-uniform)
+    const bool in = u0 + lane < hi;
+    const uint32_t u = min(u0 + lane, hi - 1);
+    const uint32_t r0 = g.row_ptr[E.nbase + u], r1 = g.row_ptr[E.nbase + u + 1];
+    // (clamped into level d + 1, whatever the CSR says)
+    const uint32_t cb = min(c0 + (r0 - rp0), c1);
+    const uint32_t deg = in ? min(r1 - r0, c1 - cb) : 0u;
+    const bool wide = deg > kWave;
+    uint32_t sn = 0;
+    uint64_t sk = 0;
+    if (!wide) {
+      for (uint32_t j = 0; j < deg; ++j) {
+        sn += leaf_kids ? 1u : w_n[cb + j];
+        sk += leaf_kids ? k[cb + j] : w_k[cb + j];
+      }
+    }
+    uint64_t todo = __ballot(wide);
+    while (todo) {
+      const uint32_t j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t b = __shfl(cb, static_cast<int>(j), 64), n = __shfl(deg, static_cast<int>(j), 64);
+      uint32_t pn = 0;
+      uint64_t pk = 0;
+      for (uint32_t i = lane; i < n; i += kWave) {
+        pn += leaf_kids ? 1u : w_n[b + i];
+        pk += leaf_kids ? k[b + i] : w_k[b + i];
+      }
+      pn = wave_sum_u32(pn);
+      pk = dev::wave_sum_u64(pk);
+      if (lane == j) {
+        sn = pn;
+        sk = pk;
+      }
+    }
+    if (in) {
+      w_n[u] = 1 + sn;
+      w_k[u] = k[u] + sk;
+      const uint32_t peer = g.node_peer[E.nbase + u];
+      if (sn) atomicAdd(below + peer, static_cast<unsigned long long>(sn));
+      if (sk) atomicAdd(carried + peer, static_cast<unsigned long long>(sk));
+    }
+  }
+}
+
+// One block per work item of this launch: a run of nodes of the level that
+// lies as far above its entry's deepest as the launch is behind the first.
+// The words it reads were written by the launch before (or are the deepest
+// level's k): stream order is the only order between the launches' waves.
+__global__ __launch_bounds__(kDownBlock) void k_downstream_level(DownArgs g, uint32_t w0) {
+  const DownWork W = g.work[w0 + blockIdx.x];
+  const DownEntry E = g.entries[W.entry];
+  if (W.level >= E.depth) return;  // (block-uniform; leaves take no work)
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  down_nodes(g, E, lv, W.level, max(W.lo, lv[W.level]), min(W.hi, lv[W.level + 1]), threadIdx.x, kDownBlock);
+}
+
+// One block per entry, behind the last level launch: the levels [0, top),
+// none wider than the block by the host's choice, walked upwards; the barrier
+// between two levels orders the block's own stores and loads.
+__global__ __launch_bounds__(kDownBlock) void k_downstream_top(DownArgs g) {
+  const DownEntry E = g.entries[blockIdx.x];
+  if (!E.c_t || g.entries[blockIdx.x + 1].strip0 == E.strip0) return;  // (block-uniform)
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  for (uint32_t d = min(E.top, E.depth); d-- > 0;) {
+    down_nodes(g, E, lv, d, lv[d], lv[d + 1], threadIdx.x, kDownBlock);
+    __syncthreads();
+  }
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -1146,6 +1286,25 @@ hipError_t launch_audience_hops(const DrainArgs& a, const HopsArgs& g, hipStream
 hipError_t launch_audience_hops_sum(const HopsArgs& g, hipStream_t s) {
   if (g.n_strips == 0 || g.n == 0 || g.max_cols == 0) return hipSuccess;
   hipLaunchKernelGGL(k_audience_hops_sum, dim3(g.n, g.max_cols), dim3(kHopsSumBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_weights(const DrainArgs& a, const DownArgs& g, hipStream_t s) {
+  if (g.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_weights, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_downstream_level(const DownArgs& g, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0) return hipSuccess;
+  hipLaunchKernelGGL(k_downstream_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_downstream_top(const DownArgs& g, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_downstream_top, dim3(g.n), dim3(kDownBlock), 0, s, g);
   return hipGetLastError();
 }
 

@@ -27,19 +27,6 @@ struct Req {
   size_t n_lvl = 0;  // level-table words of the topics with rows to read
 };
 
-bool hops_is_mesh(const ps_engine* e, uint32_t t) { return (e->last_topics[t].flags & kTopicMesh) != 0; }
-
-// topic t has rows to read in the last window (its drain table stands)
-bool hops_active(ps_engine* e, uint32_t t) {
-  uint32_t u0 = 0;
-  return e->drain.tab.topics[t].n_pos && aud_nodes(e, t, &u0);
-}
-
-// The level table of an active topic is the last window's: one root, every
-// level from 1 on non-empty, n_nodes behind the last.  It is written by the
-// node-space build alone, and a build drops the last window, so it can only
-// differ after the topic was set anew over another kind (its record starts
-// afresh, the table empty) with no run since.
 int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
   for (size_t i = 0; i < n; ++i) {
     const uint32_t t = topic[i];
@@ -47,15 +34,8 @@ int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
     R->topic.push_back(t);
     R->row.push_back(static_cast<uint32_t>(i));
     if (!hops_active(e, t)) continue;
-    uint32_t u0 = 0;
-    (void)aud_nodes(e, t, &u0);
-    const auto& lv = e->topics[t].level_off;
-    // (lv[1] == u0: the strips start at the first node of level 1, which is
-    // what k_audience_hops_sum's (lv[d] - lv[1]) / per counts strips from)
-    bool ok = lv.size() >= 3 && lv[0] == 0 && lv[1] == u0 && u0 == 1 && lv.back() == e->last_topics[t].n_nodes;
-    for (size_t d = 1; ok && d + 1 < lv.size(); ++d) ok = lv[d] < lv[d + 1];
-    if (!ok) return e->fail(PS_E_STATE, "hops: a topic was set anew since the last window: run first");
-    R->n_lvl += lv.size();
+    if (!hops_levels_stand(e, t)) return e->fail(PS_E_STATE, "hops: a topic was set anew since the last window: run first");
+    R->n_lvl += e->topics[t].level_off.size();
   }
   return PS_OK;
 }
@@ -155,10 +135,37 @@ void hops_settled(Hops& H) {
 
 size_t hops_total_bytes(size_t n) { return 3 * n * kHopsCols * 8; }
 
+}  // namespace
+
+// ---- what the passes over tree levels ask of a topic (the downstream pass too) --
+
+bool psamd::hops_is_mesh(const ps_engine* e, uint32_t t) { return (e->last_topics[t].flags & kTopicMesh) != 0; }
+
+bool psamd::hops_active(ps_engine* e, uint32_t t) {
+  uint32_t u0 = 0;
+  return e->drain.tab.topics[t].n_pos && aud_nodes(e, t, &u0);
+}
+
+// The level table of an active topic is the last window's: one root, every
+// level from 1 on non-empty, n_nodes behind the last.  It is written by the
+// node-space build alone, and a build drops the last window, so it can only
+// differ after the topic was set anew over another kind (its record starts
+// afresh, the table empty) with no run since.
+bool psamd::hops_levels_stand(ps_engine* e, uint32_t t) {
+  uint32_t u0 = 0;
+  (void)aud_nodes(e, t, &u0);
+  const auto& lv = e->topics[t].level_off;
+  // (lv[1] == u0: the strips start at the first node of level 1, which is
+  // what k_audience_hops_sum's (lv[d] - lv[1]) / per counts strips from)
+  bool ok = lv.size() >= 3 && lv[0] == 0 && lv[1] == u0 && u0 == 1 && lv.back() == e->last_topics[t].n_nodes;
+  for (size_t d = 1; ok && d + 1 < lv.size(); ++d) ok = lv[d] < lv[d + 1];
+  return ok;
+}
+
 // The topic as it is defined now builds into a mesh (graph.cpp's rule: a node
 // with two parents, or the root with one, among those the root reaches).
 // Only child lists can: a parent array and a join tree give one parent each.
-bool hops_child_lists_mesh(const TopicHost& T) {
+bool psamd::hops_child_lists_mesh(const TopicHost& T) {
   if (!T.exists || T.kind != Kind::Children || T.rp.empty()) return false;
   std::vector<uint8_t> met(T.rp.size() - 1, 0);
   std::vector<uint32_t> todo{T.root};
@@ -173,8 +180,6 @@ bool hops_child_lists_mesh(const TopicHost& T) {
   }
   return false;
 }
-
-}  // namespace
 
 // ---- the standing pass's run hooks (run.cpp calls them) -------------------------
 

@@ -19,6 +19,11 @@
 //                     hooks (§5.5j): per tree topic, nodes / reached / deliv by
 //                     BFS level from the same strips and verdicts and the
 //                     host's level tables, with buffers of their own
+//   drain_downstream.cpp  ps_peer_downstream, ps_downstream_track / _take and
+//                     run.cpp's hooks (§5.5k): per peer, the nodes and window
+//                     messages below its nodes, bottom-up over the same level
+//                     tables behind the same strips and verdicts, with buffers
+//                     of their own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -33,8 +38,8 @@
 //    in line on `stream`.
 //  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
 //    over each row set) and Load::fence (the last standing load pass over
-//    each) and Hops::fence (the last standing hop pass) are read by
-//    drain_fence (run.cpp).
+//    each), Hops::fence (the last standing hop pass) and Downstream::fence
+//    (the last standing downstream pass) are read by drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics
@@ -229,5 +234,16 @@ struct AudView {
 int aud_pass(ps_engine* e, const AudBufs& B, const AudEntry* d_entries, const AudStrip* d_strips, size_t n,
              const AudShape& A, size_t exc_cap, size_t list_cap, uint32_t seg_bound, const AudView& view,
              const PhaseTimer& tm, float* ms, DrainArgs* args, DrainCtl** ctl_out);
+
+// ---- drain_hops.cpp: what the passes over tree levels ask of a topic ---------------
+
+// topic t is a mesh in the last window's node space: it has no levels
+bool hops_is_mesh(const ps_engine* e, uint32_t t);
+// topic t has rows to read in the last window (its drain table stands)
+bool hops_active(ps_engine* e, uint32_t t);
+// an active topic's level table is the last window's (false: set anew over another kind since)
+bool hops_levels_stand(ps_engine* e, uint32_t t);
+// the topic as it is defined now builds into a mesh
+bool hops_child_lists_mesh(const TopicHost& T);
 
 }  // namespace psamd

@@ -45,7 +45,7 @@ hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out) {
   return hipSuccess;
 }
 
-// ---- what the standing passes share (ps_load_track, ps_hops_track) ------------
+// ---- what the standing passes share (ps_load_track, ps_hops_track, ps_downstream_track) --
 
 // The last pass over the window's rows on `stream` (run.cpp: drain_fence),
 // recorded behind it: the entry of this row set, else one whose row set is gone
@@ -507,6 +507,14 @@ void drain_destroy(ps_engine* e) {
   for (auto& f : D.hops.fence)
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.hops.ev_take) (void)hipEventDestroy(D.hops.ev_take);
+  if (D.down.h_out) (void)hipHostFree(D.down.h_out);
+  for (auto& a : D.down.arena) {
+    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
+    if (a.ev) (void)hipEventDestroy(a.ev);
+  }
+  for (auto& f : D.down.fence)
+    if (f.ev) (void)hipEventDestroy(f.ev);
+  if (D.down.ev_take) (void)hipEventDestroy(D.down.ev_take);
 }
 
 }  // namespace psamd

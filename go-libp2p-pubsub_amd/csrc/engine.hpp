@@ -841,6 +841,56 @@ struct ps_engine {
       PassFence fence[2];
       hipEvent_t ev_take = nullptr;
     } hops;
+
+    // ps_peer_downstream / ps_downstream_track / ps_downstream_take (DESIGN.md
+    // §5.5k; host code: drain_downstream.cpp): per peer, the nodes and the
+    // window messages strictly below its nodes in the named tree topics, from
+    // the audience pass's verdicts: k_audience_weights behind
+    // k_audience_classify, then one k_downstream_level launch per BFS level,
+    // bottom-up, and k_downstream_top.  Shaped as Hops: the blocking call and
+    // the standing pass each own their buffers, and nothing here is the
+    // sinks', the load pass's or the hop pass's.
+    struct Downstream {
+      // one pass's device buffers: entries | levels | work | strips in one
+      // block, the verdict bytes and strip counts of classify, and the
+      // scratch k | w_n | w_k (16 bytes a node, grow-only)
+      struct Pass {
+        psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_scratch;
+      };
+      // what down_entries leaves beside the block: where its parts lie, what
+      // the grids and buffers are sized by, and the work items of each level
+      // launch: launch j's are [launch[j], launch[j + 1])
+      struct Shape {
+        size_t n = 0;  // tree topics: the entries
+        size_t o_lvl = 0, o_work = 0, o_strips = 0, bytes = 0;
+        uint32_t ns = 0;
+        uint64_t n_verdicts = 0, n_nodes = 0, row_bytes = 0;
+        std::vector<uint32_t> launch;
+      };
+      // ps_peer_downstream: its pass, below | carried on the device, their pinned copy
+      Pass sync;
+      psamd::DevBuf d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+      // ps_downstream_track: the standing topics and the totals since the last
+      // take or track call, below | carried in peer space
+      bool on = false;
+      std::vector<uint32_t> topic;
+      Pass track;
+      psamd::DevBuf d_acc;
+      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out, since the last take or track call
+      // the levels, work list and strips on the device while what they are cut
+      // from stays (graph_epoch, each standing topic's table shape and node range)
+      std::vector<uint64_t> strip_key;
+      Shape kept;
+      // pinned staging per run and the last pass per row set (PassArena, PassFence)
+      PassArena arena[2];
+      uint64_t runs = 0;
+      PassArena* open = nullptr;  // the run being enqueued
+      PassFence fence[2];
+      hipEvent_t ev_take = nullptr;
+    } down;
   } drain;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
@@ -995,6 +1045,11 @@ void load_abort(ps_engine* e);
 int hops_open(ps_engine* e);
 int hops_window(ps_engine* e);
 void hops_abort(ps_engine* e);
+// drain_downstream.cpp, the standing downstream pass (ps_downstream_track; all
+// no-ops while nothing is tracked): called where the hop pass's hooks are
+int downstream_open(ps_engine* e);
+int downstream_window(ps_engine* e);
+void downstream_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

@@ -952,4 +952,62 @@ struct HopsArgs {
 hipError_t launch_audience_hops(const DrainArgs& a, const HopsArgs& g, hipStream_t s);
 hipError_t launch_audience_hops_sum(const HopsArgs& g, hipStream_t s);
 
+// ---- audience behind each peer (ps_peer_downstream, ps_downstream_track) --
+// The audience pass's verdicts turned into two sums per peer, over the subtrees
+// of its nodes: a node u of a tree topic (the root too) adds the nodes strictly
+// below it to below[its peer] and the window messages their rows hold to
+// carried[its peer].  Three kernels over three scratch arrays, an entry's
+// n_nodes words of each from n0 (the root's first): k[u] the messages u's row
+// holds (the root's 0), w_n[u] = 1 + the nodes below u, w_k[u] = k[u] + the k
+// below u.  The entry table (request order among the tree topics, entry n
+// closes it) carries the level table as HopsEntry does; a node's children are
+// its CSR range one level down (BFS numbering: level d + 1 lists the children
+// of level d's nodes in node order).  k_audience_weights writes k over the
+// audience pass's strips.  k_downstream_level, launched once per level from
+// the level above an entry's deepest upwards, sums a level's nodes from their
+// children's words -- the launch before wrote them; the deepest level's nodes
+// are leaves, (1, k), and are read as that -- over a work list of (entry,
+// level, node range) items, a block each.  The levels [0, top) of an entry,
+// from the root down to the first level wider than a block, are walked upwards
+// by one block in k_downstream_top.
+constexpr uint32_t kDownBlock = 256;  // nodes of a work item at most: a thread each
+struct DownEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window
+  uint32_t nbase;   // the topic's first node (its root) in node space
+  uint32_t lvl0;    // the topic's level table in DownArgs::levels
+  uint32_t depth;   // its deepest level
+  uint32_t n0;      // the entry's first word of k / w_n / w_k
+  uint32_t top;     // levels [0, top) are k_downstream_top's, min(top, depth) at most
+};
+struct DownWork {
+  uint32_t entry, level;
+  uint32_t lo, hi;  // topic-relative nodes of that level, at most kDownBlock
+};
+struct DownArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const DownEntry* entries;  // [n + 1]
+  uint32_t n;
+  const uint32_t* levels;
+  const DownWork* work;      // launch by launch
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint64_t* n_exc;     // AudArgs::n_exc: 0 = every node of the strip is full
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  const uint32_t* node_peer;
+  const uint32_t* row_ptr;
+  uint32_t* k;
+  uint32_t* w_n;
+  uint64_t* w_k;
+  uint64_t* below;           // [n_peers] added into
+  uint64_t* carried;         // [n_peers]
+};
+// k_audience_weights: one wave per strip behind k_audience_classify, a node per lane
+hipError_t launch_audience_weights(const DrainArgs& a, const DownArgs& g, hipStream_t s);
+// k_downstream_level over work items [w0, w1): one launch of the bottom-up pass
+hipError_t launch_downstream_level(const DownArgs& g, uint32_t w0, uint32_t w1, hipStream_t s);
+// k_downstream_top: one block per entry, behind the last level launch
+hipError_t launch_downstream_top(const DownArgs& g, hipStream_t s);
+
 }  // namespace psamd

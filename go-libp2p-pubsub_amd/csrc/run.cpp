@@ -191,6 +191,9 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   // ... and the standing hop pass's (ps_hops_track)
   for (const auto& F : e->drain.hops.fence)
     if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending hop pass");
+  // ... and the standing downstream pass's (ps_downstream_track)
+  for (const auto& F : e->drain.down.fence)
+    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending downstream pass");
   return PS_OK;
 }
 
@@ -1453,7 +1456,8 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
     int rc = run_window(e, msgs, win, st);
     e->defer_last = false;
     // (the window that was remembered: after a k_flood timeout, its re-run)
-    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e))) rc = hops_window(e);
+    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e)) && !(rc = hops_window(e)))
+      rc = downstream_window(e);
     if (rc) return rc;
   }
   return PS_OK;
@@ -1570,16 +1574,19 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer);
 // The run with the sink's result around it (ps_sink_set; nothing while none
 // is set): refused before the pending messages are touched, opened, closed
 // behind the last window, given up when the run fails.  And with the standing
-// load pass's and the standing hop pass's staging around it (ps_load_track,
-// ps_hops_track; nothing while none is set).
+// load pass's, the standing hop pass's and the standing downstream pass's
+// staging around it (ps_load_track, ps_hops_track, ps_downstream_track;
+// nothing while none is set).
 int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
   int rc = sink_precheck(e);
   if (rc || (rc = sink_open(e))) return rc;
-  if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = run_windows(e, stp, may_defer))) rc = sink_close(e);
+  if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = downstream_open(e)) && !(rc = run_windows(e, stp, may_defer)))
+    rc = sink_close(e);
   if (rc) {
     sink_abort(e);
     load_abort(e);
     hops_abort(e);
+    downstream_abort(e);
   }
   return rc;
 }

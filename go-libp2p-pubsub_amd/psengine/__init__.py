@@ -178,6 +178,9 @@ PROTOTYPES = [
     ("ps_topic_hops", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p]),
     ("ps_hops_track", C.c_int, [_P, _u32p, C.c_size_t]),
     ("ps_hops_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_peer_downstream", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p]),
+    ("ps_downstream_track", C.c_int, [_P, _u32p, C.c_size_t]),
+    ("ps_downstream_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -795,6 +798,43 @@ class Engine:
         nw, nsk = C.c_uint64(), C.c_uint64()
         self._check(self._L.ps_hops_take(self._h, *(_p(a, C.c_uint64) for a in out), C.byref(nw), C.byref(nsk)))
         return out[0], out[1], out[2], nw.value, nsk.value
+
+    def peer_downstream(self, topics) -> tuple[np.ndarray, np.ndarray]:
+        """The audience behind each peer in the last window over the named
+        distinct tree topics (ps_peer_downstream): (below, carried), uint64
+        [n_peers] each -- the nodes strictly below the peer's nodes, live or
+        not, and the window messages delivered to them: what would have been
+        lost had the peer dropped."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        below = np.empty(self.n_peers, dtype=np.uint64)
+        carried = np.empty(self.n_peers, dtype=np.uint64)
+        self._check(self._L.ps_peer_downstream(self._h, _p(t, C.c_uint32), t.size, _p(below, C.c_uint64),
+                                               _p(carried, C.c_uint64)))
+        return below, carried
+
+    def downstream_track(self, topics):
+        """Registers standing tree topics (ps_downstream_track): from now on
+        every window of every run adds the audience behind each peer over them
+        into totals on the device (downstream_take).  No topic clears the
+        tracking; setting or clearing zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_downstream_track(self._h, _p(t, C.c_uint32), t.size))
+
+    def downstream_take(self) -> tuple[np.ndarray, np.ndarray, int, int]:
+        """The totals since the last take or track call (ps_downstream_take):
+        (below, carried, n_windows, n_skipped); below is a sum of per-window
+        values, n_skipped counts the (topic, window) pairs left out because the
+        topic was a mesh there.  The totals and both counts start again at 0."""
+        below = np.empty(self.n_peers, dtype=np.uint64)
+        carried = np.empty(self.n_peers, dtype=np.uint64)
+        nw, nsk = C.c_uint64(), C.c_uint64()
+        self._check(self._L.ps_downstream_take(self._h, _p(below, C.c_uint64), _p(carried, C.c_uint64), C.byref(nw),
+                                               C.byref(nsk)))
+        return below, carried, nw.value, nsk.value
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

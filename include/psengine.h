@@ -655,6 +655,69 @@ int ps_hops_track(ps_engine* e, const uint32_t* topic, size_t n);
 int ps_hops_take(ps_engine* e, uint64_t* nodes_out, uint64_t* reached_out, uint64_t* deliv_out,
                  /* [n_tracked * PS_MAX_ROUNDS], nullable */
                  uint64_t* n_windows_out, uint64_t* n_skipped_out);
+/* The audience behind each peer: how many subscribers hang below it, and how
+ * many of the window's deliveries went through it and would have been lost
+ * had it dropped (one rank).  Per window and per named tree
+ * topic t with c_t > 0 messages in it, on the node space that window ran on:
+ * every node v carries k(v), ps_peer_load's k -- the number of t's window
+ * messages its row holds; 0 for a tree node the window did not reach -- and
+ * k(root) counts as 0: the root is no recipient.  For every node u of peer p,
+ * the root included:
+ *   below[p]   += |{v : v a strict descendant of u}|
+ *   carried[p] += the sum of k(v) over the strict descendants v of u.
+ * Descendants count whether live or not, as children do in ps_peer_load: an
+ * unreached subtree adds to below and nothing to carried.  A topic with no
+ * message in the window adds nothing, not even to below; peers outside the
+ * node space add nothing: both as in ps_peer_load and ps_topic_hops.
+ *   Three identities follow.  carried[root_t] is topic t's deliveries of the
+ * window, and below[root_t] is n_nodes - 1.  For one named topic, the sum of
+ * below over the peers is the sum over h of h * nodes[h], and the sum of
+ * carried is the sum over h of h * deliv[h], nodes and deliv being
+ * ps_topic_hops' rows: a node at level h lies below h nodes.  The last two
+ * hold while the tree is at most PS_MAX_ROUNDS - 2 levels deep, so that
+ * ps_topic_hops' clamped last column is unused; below and carried themselves
+ * are exact at any depth.
+ *   Mesh topics are refused: a DAG has no subtrees.  A tree topic that shares
+ * a window with a mesh is answered as any other.
+ *   ps_peer_downstream answers for the last window of the last run, blocking,
+ * with ps_peer_load's window, stream-ordering and twin-join rules.  The n
+ * topics are distinct; both arrays ([n_peers], either may be NULL) are written
+ * in full: peers in no named topic read 0, and n == 0 gives all zeros.
+ * PS_E_INVAL for a NULL engine, n > 0 without topic, both outputs NULL or a
+ * topic named twice; PS_E_RANGE, nothing written, for a topic out of range;
+ * PS_E_NOTREADY before any run; PS_E_STATE, nothing written, on a multi-rank
+ * engine, when a named topic is a mesh in that window's node space, and for a
+ * topic that was set anew over another kind since the window (its levels are
+ * gone: run first).
+ *   ps_downstream_track registers n standing topics (copied; n == 0 clears the
+ * tracking and frees the totals).  PS_E_INVAL / PS_E_RANGE as above, and
+ * PS_E_STATE for a topic whose child lists make a mesh: the previous tracking
+ * stays.  PS_E_STATE with a run in flight and on a multi-rank engine;
+ * ps_dist_init* on an engine that is tracking downstream returns PS_E_STATE.
+ * Setting or clearing zeroes the totals.  Tracking is independent of both
+ * sinks, of ps_load_track and of ps_hops_track: all may be set at once.  While
+ * it is set, every window of every ps_run / ps_run_async that runs something
+ * enqueues the pass behind itself -- the window is neither planned nor
+ * launched differently -- and the pass adds into two totals on the device,
+ * below[n_peers] and carried[n_peers], in peer space: they survive node-space
+ * rebuilds, joins, leaves and drops between windows.  Over several windows
+ * below is a sum of per-window values: a peer with s nodes below it in each of
+ * w windows reads w * s.  A tracked topic that is a mesh in a window's node
+ * space adds nothing for that window; each such (topic, window) pair is
+ * counted.
+ *   ps_downstream_take waits for the passes enqueued so far, copies the totals
+ * since the last take or track call (each array may be NULL), zeroes them in
+ * front of whatever runs next, sets *n_windows_out to the windows counted and
+ * *n_skipped_out to the (mesh topic, window) pairs left out, and resets both
+ * counts.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with a run in
+ * flight (complete the runs with ps_wait first); PS_E_INVAL for a NULL engine
+ * or count pointer.  After a failed ps_run / ps_wait the totals are
+ * unspecified until the next take or track call. */
+int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n,
+                       uint64_t* below_out, uint64_t* carried_out);   /* [n_peers] each, either may be NULL */
+int ps_downstream_track(ps_engine* e, const uint32_t* topic, size_t n);
+int ps_downstream_take(ps_engine* e, uint64_t* below_out, uint64_t* carried_out, /* [n_peers], nullable */
+                       uint64_t* n_windows_out, uint64_t* n_skipped_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

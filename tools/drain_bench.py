@@ -99,6 +99,18 @@ compared array for array; then the pipelined step plain, with hops tracked
 (ps_hops_track, one ps_hops_take per loop), with load tracked, with both and
 with the audience sink beside both, the five alternating in one process, the
 totals against steps x the blocking answer.  Writes DIR/hops_bench.json.
+
+--downstream: the audience behind each peer (ps_peer_downstream) over every
+topic after one step, --reps repetitions in one process: its device phases
+(classify, weights, levels + top, copy) with k_audience_load's in the same
+process as the yardstick, and its wall; the derivation a caller has without it
+-- ps_drain_topics + ps_topic_get_parents per topic + numpy depths and a
+bottom-up sum level by level -- and its wall, the two answers compared array
+for array; then the pipelined step plain, with downstream tracked
+(ps_downstream_track, one ps_downstream_take per loop) and beside hops and
+load tracking, the three alternating in one process, with the overlapped
+windows of each, the totals against steps x the blocking answer.  Writes
+DIR/downstream_bench.json.
 """
 from __future__ import annotations
 
@@ -1237,6 +1249,162 @@ def hops_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def host_peer_downstream(eng, wl, topics):
+    """The audience behind each peer as a caller derives it without
+    ps_peer_downstream: the audience answer, every topic's parent array, depths
+    by numpy as in host_topic_hops, then each level's (1, k) pairs added into
+    the parents', the deepest level first."""
+    r = eng.drain_topics(topics)
+    n = wl.n_peers
+    below = np.zeros(n, dtype=np.uint64)
+    carried = np.zeros(n, dtype=np.uint64)
+    sizes = np.diff(r["list_off"]).astype(np.uint64)
+    c_all = np.bincount(wl.msg_topics, minlength=len(wl.topics))
+    for i, t in enumerate(topics):
+        c = int(c_all[t])
+        if not c:
+            continue
+        par = eng.parents(int(t))
+        root = wl.topics[int(t)].root
+        kid = np.nonzero(par != 0xFFFFFFFF)[0]
+        kid = kid[kid != root]
+        depth = np.full(n, -1, dtype=np.int64)
+        depth[root] = 0
+        todo, levels = kid, []
+        while todo.size:
+            at = depth[par[todo]] == len(levels)
+            if not at.any():
+                break
+            levels.append(todo[at])
+            depth[todo[at]] = len(levels)
+            todo = todo[~at]
+        k = np.zeros(n, dtype=np.uint64)
+        k[kid] = c
+        lo, hi = int(r["exc_off"][i]), int(r["exc_off"][i + 1])
+        if hi > lo:  # the nodes that are not full: their private list's length, or nothing
+            el = r["exc_list"][lo:hi].astype(np.int64)
+            have = el != 0xFFFFFFFF
+            ke = np.zeros(hi - lo, dtype=np.uint64)
+            ke[have] = sizes[el[have]]
+            k[r["exc_peer"][lo:hi]] = ke
+        k[root] = 0
+        k[depth < 0] = 0
+        w_n = (depth >= 0).astype(np.uint64)
+        w_k = k.copy()
+        for at in reversed(levels):
+            np.add.at(w_n, par[at], w_n[at])
+            np.add.at(w_k, par[at], w_k[at])
+        member = depth >= 0
+        below[member] += w_n[member] - np.uint64(1)
+        carried[member] += w_k[member] - k[member]
+    return below, carried
+
+
+def downstream_main(a, wl):
+    """--downstream (see the module text).  Writes DIR/downstream_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": a.steps, "warmup": a.warmup}
+    eng, st = stepped_engine(wl, {"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for tag, call, key in (("peer_downstream", eng.peer_downstream, "downstream_phases"),
+                               ("peer_load", eng.peer_load, "load_phases")):
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+                with StderrCapture() as cap:
+                    got = call(topics)
+                row = phase_line(cap.text, tag)
+                for k in ("strips", "nodes", "row_bytes", "work", "launches"):
+                    m = re.search(rf"\b{k} (\d+)", cap.text)
+                    if m:
+                        row[k] = int(m.group(1))
+                rows.append(row)
+            res[key] = rows[1:]
+            if tag == "peer_downstream":
+                blocking = got
+        roots = np.array([ts.root for ts in wl.topics])
+        res.update(deliveries=int(st.deliveries), below_sum=int(blocking[0].sum()), carried_sum=int(blocking[1].sum()),
+                   below_max=int(blocking[0].max()), carried_max=int(blocking[1].max()),
+                   peers_with_audience=int((blocking[0] > 0).sum()), carried_at_roots=int(blocking[1][np.unique(roots)].sum()))
+    eng, _ = stepped_engine(wl, {})
+    with eng:
+        walls = {"downstream": [], "host": [], "load": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.peer_downstream(topics)
+            walls["downstream"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            want = host_peer_downstream(eng, wl, topics)
+            walls["host"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.peer_load(topics)
+            walls["load"].append(1e3 * (time.perf_counter() - t0))
+            for g, w, name in zip(got, want, ("below", "carried")):
+                assert np.array_equal(g, w), f"ps_peer_downstream {name} differs from the host derivation"
+            for g, w in zip(got, blocking):
+                assert np.array_equal(g, w)
+    res["downstream_wall_ms"], res["host_derivation_wall_ms"], res["load_wall_ms"] = \
+        (walls[k][1:] for k in ("downstream", "host", "load"))
+    res["answers_agree"] = True
+    res["host_over_downstream_wall"] = float(np.median(res["host_derivation_wall_ms"]) / np.median(res["downstream_wall_ms"]))
+    dp, lp = res["downstream_phases"], res["load_phases"]
+    res["downstream_kernels_over_load_kernel"] = float(np.median([p["weights_ms"] + p["levels_ms"] for p in dp]) /
+                                                       np.median([p["load_ms"] for p in lp]))
+
+    # tracking in the pipelined loop: plain, downstream, beside hops and load
+    for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING"):
+        os.environ.pop(k, None)
+    eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    none = np.zeros(0, dtype=np.uint32)
+    modes = {"plain": (False, False), "downstream": (True, False), "beside_hops_and_load": (True, True)}
+
+    def timed(down, others, steps):
+        eng.downstream_track(topics if down else none)
+        eng.hops_track(topics if others else none)
+        eng.load_track(topics if others else none)
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        loop_plain(eng, wl, steps)
+        td = eng.downstream_take() if down else None
+        th = eng.hops_take() if others else None
+        tl = eng.load_take() if others else None
+        return 1e3 * (time.perf_counter() - t0) / steps, eng.overlapped_windows() - o0, td, th, tl
+
+    with eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        load0, hops0 = eng.peer_load(topics), eng.topic_hops(topics)
+        for mode in modes.values():
+            timed(*mode, a.warmup)
+        ms = {k: [] for k in modes}
+        over = {k: [] for k in modes}
+        for _ in range(a.reps):
+            for name, (down, others) in modes.items():
+                t, o, td, th, tl = timed(down, others, a.steps)
+                ms[name].append(t)
+                over[name].append(int(o))
+                if down:
+                    assert td[2:] == (a.steps, 0)
+                    for g, w in zip(td[:2], blocking):
+                        assert np.array_equal(g, w * np.uint64(a.steps)), "tracked downstream totals differ"
+                if others:
+                    assert th[3:] == (a.steps, 0) and np.array_equal(th[2], hops0[2] * np.uint64(a.steps))
+                    assert tl[2] == a.steps and np.array_equal(tl[0], load0[0] * np.uint64(a.steps))
+        eng.downstream_track(none)
+        eng.hops_track(none)
+        eng.load_track(none)
+    res.update(ms_per_step=ms, overlapped_windows=over, tracked_totals_agree=True,
+               downstream_minus_plain_ms=float(np.median(ms["downstream"]) - np.median(ms["plain"])),
+               beside_minus_plain_ms=float(np.median(ms["beside_hops_and_load"]) - np.median(ms["plain"])))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "downstream_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -1380,8 +1548,12 @@ def main():
     ap.add_argument("--topics", action="store_true", help="ps_drain_topics against ps_drain_shared and k_digest (see above)")
     ap.add_argument("--load", action="store_true", help="ps_peer_load against the host derivation; tracking in the pipelined loop")
     ap.add_argument("--hops", action="store_true", help="ps_topic_hops against the host derivation; tracking in the pipelined loop")
+    ap.add_argument("--downstream", action="store_true",
+                    help="ps_peer_downstream against the host derivation; tracking in the pipelined loop")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.downstream:
+        return downstream_main(a, wl)
     if a.hops:
         return hops_main(a, wl)
     if a.load:
