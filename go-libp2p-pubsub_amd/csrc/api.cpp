@@ -576,6 +576,12 @@ int ps_read_delivered(ps_engine* e, uint32_t msg, uint8_t* out) {
   const uint32_t i = msg - e->last_first;
   const uint32_t t = e->last_msgs[i].topic;
   const uint32_t rank = e->run_rank[i];
+  // a rank that owns none of the topic's nodes lays out no rows for it (the
+  // window's range of the topic is empty there): nothing was delivered here
+  if (e->world > 1 && t < e->last_topics.size() && e->last_topics[t].n_nodes == 0) {
+    std::memset(out, 0, e->cfg.n_peers);
+    return PS_OK;
+  }
   if (rank < e->last_lo[t] || rank >= e->last_lo[t] + e->last_cnt[t])
     return e->fail(PS_E_NOTREADY, "message not in the last window");
   const uint32_t b = window_bit(window_bits(e, t), rank - e->last_lo[t]);

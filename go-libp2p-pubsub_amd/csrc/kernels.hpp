@@ -161,7 +161,8 @@ struct PullChunk {
   // into); kNoneNode: none
   uint32_t gin, gout;
   uint32_t group;  // host: the start group (index in the topic's groups) whose block the chunk writes
-  uint32_t pad;
+  uint32_t lvl0;   // first node of the chunk's level: the once-per-parent count looks back no further
+                   // (ghost record indices start again at every level)
 };
 constexpr uint32_t kPullMaxKids = 512;
 constexpr uint32_t kNoneNode = 0xFFFFFFFFu;

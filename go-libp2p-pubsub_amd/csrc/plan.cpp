@@ -252,8 +252,8 @@ bool plan_pull_chunks(ps_engine* e, const WindowLayout& L) {
   P.gsplit.assign(rounds + 2, 0);
   P.bytes.assign(rounds + 2, 0);
   std::vector<PullChunk> ghost;
-  auto cut = [&](std::vector<PullChunk>& out, uint32_t t, uint32_t gi, uint32_t u0, uint32_t u1, uint32_t per,
-                 uint32_t W, uint64_t row0) {
+  auto cut = [&](std::vector<PullChunk>& out, uint32_t t, uint32_t gi, uint32_t l0, uint32_t u0, uint32_t u1,
+                 uint32_t per, uint32_t W, uint64_t row0) {
     const TopicHost& T = e->topics[t];
     for (uint32_t u = u0; u < u1; u += per) {
       PullChunk c{};
@@ -267,6 +267,7 @@ bool plan_pull_chunks(ps_engine* e, const WindowLayout& L) {
       c.row0_hi = static_cast<uint32_t>(row0 >> 32);
       c.gin = c.gout = kNoneNode;
       c.group = gi;
+      c.lvl0 = T.nbase + l0;
       out.push_back(c);
     }
   };
@@ -286,8 +287,8 @@ bool plan_pull_chunks(ps_engine* e, const WindowLayout& L) {
         const uint32_t W = block_w(tab[t], g);
         const uint32_t per = std::max<uint32_t>(1, std::min<uint32_t>(kPullMaxKids, e->pull_words / W));
         P.bytes[q] += static_cast<uint64_t>(hi - lo) * W * 8;
-        cut(P.chunks, t, gi, lo, lo + nl, per, W, block_row0(tab[t], g));
-        cut(ghost, t, gi, lo + nl, hi, per, W, block_row0(tab[t], g));
+        cut(P.chunks, t, gi, lo, lo, lo + nl, per, W, block_row0(tab[t], g));
+        cut(ghost, t, gi, lo, lo + nl, hi, per, W, block_row0(tab[t], g));
       }
     }
     P.gsplit[q] = static_cast<uint32_t>(P.chunks.size());
@@ -566,6 +567,7 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
             c.c_lo = late ? kNoneNode : 0;  // children: filled in on the device
             c.gin = c.gout = kNoneNode;
             c.group = gi;
+            c.lvl0 = T.nbase + lo;
             (part ? ghost : C).push_back(c);
           }
         }

@@ -113,11 +113,16 @@ __device__ __forceinline__ const uint64_t* rank_base(const PullArgs& a, uint32_t
 // seen row, or -- multi-GPU -- a ghost row in the receive buffer), or 0.  The
 // parents of a run are consecutive node ids [p_lo, p_hi] (BFS numbering):
 // their generation bytes are staged into LDS by loads issued together with
-// the nodes' own metadata, so phase 1 costs one memory round trip.
+// the nodes' own metadata, so phase 1 costs one memory round trip.  lvl0:
+// the first node of the run's level -- a parent counts once, at its first
+// child, and the look-back at the node before the run stops at the level's
+// start: ghost references (rank, record index) start again at every level, so
+// the last node of the level above may carry the first node's reference
+// without sharing its parent.
 template <class Ctr>
 __device__ __forceinline__ void pull_resolve(const PullArgs& a, const PullTopic& P, uint32_t nb, uint32_t nk,
                                              uint32_t p_lo, uint32_t p_hi, uint64_t* src, uint8_t* genl,
-                                             uint32_t lane, uint32_t cur, Ctr& c, uint32_t gin,
+                                             uint32_t lane, uint32_t cur, Ctr& c, uint32_t gin, uint32_t lvl0,
                                              uint32_t stage_cap = kPullMaxKids) {
   uint32_t g0 = 0;
   const bool staged = p_lo != kNoneNode && p_hi - p_lo < stage_cap;  // genl holds stage_cap + 8 bytes
@@ -139,7 +144,7 @@ __device__ __forceinline__ void pull_resolve(const PullArgs& a, const PullTopic&
     // the group's own loads -- not a second round trip after them
     const uint32_t q = nb + j0;
     uint32_t pm = kNoneNode, gm = kNoneNode;
-    if (lane == 0 && q > P.nbase) {
+    if (lane == 0 && q > lvl0) {
       pm = a.node_parent[q - 1];
       if (gin != kNoneNode) gm = a.ghost_ref[q - 1];
     }
@@ -424,7 +429,7 @@ __global__ __launch_bounds__(kBlock) void k_pull(PullArgs a, const PullChunk* __
     const uint32_t n1 = ch.node_end - ch.node_begin;
     // LDS ops of a wave are processed in order: the table written in phase 1
     // is visible to the reads that follow
-    pull_resolve(a, P, ch.node_begin, n1, ch.p_lo, ch.p_hi, src, genl, lane, cur, c, ch.gin);
+    pull_resolve(a, P, ch.node_begin, n1, ch.p_lo, ch.p_hi, src, genl, lane, cur, c, ch.gin, ch.lvl0);
     pull_stream<kRecord, kNT>(a, P, ch.node_begin, n1, src, lane, round, c);
     if (ch.e_hi > ch.e_lo) pull_ship(a, P, ch.node_begin, ch.e_lo, ch.e_hi, ch.gout, src, lane);
   }
@@ -625,7 +630,7 @@ __global__ __launch_bounds__(64) void k_pull_pair(PullArgs a, const PullChunk* _
       pf_f[s] = j < nk0 ? a.node_flags[ch.c_lo + j] : 0u;
     }
     WaveCtr ca;
-    pull_resolve(a, P, ch.node_begin, n1, ch.p_lo, ch.p_hi, src, genl, lane, cur, ca, ch.gin, kPairPar);
+    pull_resolve(a, P, ch.node_begin, n1, ch.p_lo, ch.p_hi, src, genl, lane, cur, ca, ch.gin, ch.lvl0, kPairPar);
     for (uint32_t j0 = 0; j0 < n1; j0 += 64) {
       const uint64_t b = __ballot(j0 + lane < n1 && src[j0 + lane] != 0);
       if (lane == 0) reach[j0 >> 6] = b;
@@ -1169,13 +1174,13 @@ __device__ __forceinline__ void chain_level0_direct(const PullArgs& a, const Cha
   P.root = cp->root;
   WaveCtr c;
   if constexpr (!kSlices) {
-    pull_resolve(a, P, node_begin, n0, p_lo, p_hi, src, genl, lane, cur, c, kNoneNode, kChainPar);
+    pull_resolve(a, P, node_begin, n0, p_lo, p_hi, src, genl, lane, cur, c, kNoneNode, P.nbase, kChainPar);
     pull_stream<kRecord, kNT, true>(a, P, node_begin, n0, src, lane, round, c, stage);
   } else {
     // (pull_resolve stamps generations and counts whole rows: slice 0 keeps
     // its node counts, every slice its own words)
     PullCtr pc;
-    pull_resolve(a, P, node_begin, n0, p_lo, p_hi, src, genl, lane, cur, pc, kNoneNode, kChainPar);
+    pull_resolve(a, P, node_begin, n0, p_lo, p_hi, src, genl, lane, cur, pc, kNoneNode, P.nbase, kChainPar);
     const uint32_t nodes = __reduce_add_sync(~0ull, pc.kids), hit = __reduce_add_sync(~0ull, pc.reached);
     const uint32_t par = __reduce_add_sync(~0ull, pc.parents);
     if (C.slice0) {

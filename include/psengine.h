@@ -734,7 +734,16 @@ int ps_overlapped_windows(ps_engine* e, uint64_t* count_out);
  * messages; each owns a hash partition of every topic's tree nodes and ps_run
  * exchanges, each round, the deliveries addressed to other ranks' nodes
  * (stream-ordered all-to-allv over RCCL / xGMI).  Stats and ps_read_* cover
- * the owned nodes; sums over ranks give the job totals.
+ * the owned nodes; sums over ranks give the job totals of deliveries,
+ * duplicates, deliveries_per_round and the seen digest.  (A rank that owns
+ * none of a topic's nodes answers ps_read_delivered for its messages with
+ * zeros.)  The frontier counters are per reader, not per owner: in a level
+ * run frontier_per_round[q] (and frontier_entries) of rank r counts, per
+ * (topic, start group) the round writes, every reached parent of the level
+ * above -- owned by r or read as a ghost record / row of another rank --
+ * that has at least one child, live or not, owned by r.  A parent with
+ * children on k ranks counts once on each, so the ranks' sum exceeds the
+ * one-rank count by k - 1 for every such parent.
  *   PS_PART_PEER     owner(p) = splitmix64(p) mod world (the
  *                    default): every round ships each parent row whose
  *                    children live on other ranks once per such rank
