@@ -42,6 +42,13 @@
 //                         size and subtree messages from its children's, and
 //                         what lies below it into its peer's two sums
 //   k_downstream_top      the narrow levels under a root in one block
+// and, for ps_peer_cut / ps_cut_track (§5.5l), the losses blamed on their cut points:
+//   k_audience_missed     behind k_audience_weights: what a node's row lacks
+//                         into its peer's sum
+//   k_cut_level           k_downstream_level's pass, a full node looking at its
+//                         children: one that lacks messages is a cut point, its
+//                         subtree's words into its peer's three sums
+//   k_cut_top             the narrow levels under a root in one block
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -752,6 +759,131 @@ __global__ __launch_bounds__(kDownBlock) void k_downstream_top(DownArgs g) {
   }
 }
 
+// ---- losses blamed on their cut points (ps_peer_cut, ps_cut_track) -------------
+
+// One wave per strip, one node per lane, behind k_audience_weights: what the
+// node's row lacks of its topic's window messages into missed[its peer].  A
+// strip holds no root; a full node adds nothing and reads no peer.
+__global__ __launch_bounds__(kAudBlock) void k_audience_missed(CutArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.d.n_strips) return;
+  const AudStrip S = g.d.strips[s];
+  uint32_t lo = 0, hi = g.d.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.d.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const DownEntry E = g.d.entries[lo - 1];
+  const uint32_t* __restrict__ k = g.d.k + E.n0;
+  unsigned long long* const missed = reinterpret_cast<unsigned long long*>(g.missed);
+  for (uint32_t i = lane; i < S.n; i += kWave) {
+    const uint32_t u = S.u0 + i;
+    const uint32_t have = k[u];
+    if (have < E.c_t) atomicAdd(missed + g.d.node_peer[E.nbase + u], static_cast<unsigned long long>(E.c_t - have));
+  }
+}
+
+// Child c of a full node lacks messages: the tree is cut at c.  Its subtree's
+// two words (n nodes, k messages held) into the three sums of c's peer.
+__device__ __forceinline__ void cut_point(const CutArgs& g, const DownEntry& E, uint32_t c, uint32_t n, uint64_t k) {
+  const uint32_t peer = g.d.node_peer[E.nbase + c];
+  atomicAdd(reinterpret_cast<unsigned long long*>(g.cuts) + peer, 1ull);
+  if (n > 1) atomicAdd(reinterpret_cast<unsigned long long*>(g.orphaned) + peer, static_cast<unsigned long long>(n - 1));
+  atomicAdd(reinterpret_cast<unsigned long long*>(g.lost) + peer,
+            static_cast<unsigned long long>(static_cast<uint64_t>(E.c_t) * n - k));
+}
+
+// down_nodes' walk over the nodes [lo, hi) of level d < depth, without the
+// peer sums of its own: a node's two words from its children's, and, at a node
+// that is full -- the root counts as full, whatever k holds for it --, every
+// child that is not is a cut point, found here with its subtree's words at
+// hand.  A wide node's lanes each look at their own children.
+__device__ __forceinline__ void cut_nodes(const CutArgs& g, const DownEntry& E, const uint32_t* __restrict__ lv, uint32_t d,
+                                          uint32_t lo, uint32_t hi, uint32_t tid, uint32_t nt) {
+  const uint32_t lane = tid & (kWave - 1);
+  const uint32_t c0 = lv[d + 1], c1 = lv[d + 2];
+  const uint32_t rp0 = g.d.row_ptr[E.nbase + lv[d]];
+  const bool leaf_kids = d + 1 == E.depth;
+  const uint32_t* const k = g.d.k + E.n0;
+  uint32_t* const w_n = g.d.w_n + E.n0;
+  uint64_t* const w_k = g.d.w_k + E.n0;
+  for (uint32_t u0 = lo + (tid & ~(kWave - 1)); u0 < hi; u0 += nt) {  // (wave-uniform)
+    const bool in = u0 + lane < hi;
+    const uint32_t u = min(u0 + lane, hi - 1);
+    const uint32_t r0 = g.d.row_ptr[E.nbase + u], r1 = g.d.row_ptr[E.nbase + u + 1];
+    // (clamped into level d + 1, whatever the CSR says)
+    const uint32_t cb = min(c0 + (r0 - rp0), c1);
+    const uint32_t deg = in ? min(r1 - r0, c1 - cb) : 0u;
+    const bool wide = deg > kWave;
+    const uint32_t ku = k[u];
+    const bool full = d == 0 || ku == E.c_t;
+    uint32_t sn = 0;
+    uint64_t sk = 0;
+    if (!wide) {
+      for (uint32_t j = 0; j < deg; ++j) {
+        const uint32_t kc = k[cb + j];
+        const uint32_t cn = leaf_kids ? 1u : w_n[cb + j];
+        const uint64_t ck = leaf_kids ? kc : w_k[cb + j];
+        sn += cn;
+        sk += ck;
+        if (full && kc < E.c_t) cut_point(g, E, cb + j, cn, ck);
+      }
+    }
+    uint64_t todo = __ballot(wide);
+    while (todo) {
+      const uint32_t j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t b = __shfl(cb, static_cast<int>(j), 64), n = __shfl(deg, static_cast<int>(j), 64);
+      const bool pfull = __shfl(static_cast<int>(full), static_cast<int>(j), 64) != 0;
+      uint32_t pn = 0;
+      uint64_t pk = 0;
+      for (uint32_t i = lane; i < n; i += kWave) {
+        const uint32_t kc = k[b + i];
+        const uint32_t cn = leaf_kids ? 1u : w_n[b + i];
+        const uint64_t ck = leaf_kids ? kc : w_k[b + i];
+        pn += cn;
+        pk += ck;
+        if (pfull && kc < E.c_t) cut_point(g, E, b + i, cn, ck);
+      }
+      pn = wave_sum_u32(pn);
+      pk = dev::wave_sum_u64(pk);
+      if (lane == j) {
+        sn = pn;
+        sk = pk;
+      }
+    }
+    if (in) {
+      w_n[u] = 1 + sn;
+      w_k[u] = ku + sk;
+    }
+  }
+}
+
+// k_downstream_level's launch: one block per work item, stream order the only
+// order between the launches' waves.
+__global__ __launch_bounds__(kDownBlock) void k_cut_level(CutArgs g, uint32_t w0) {
+  const DownWork W = g.d.work[w0 + blockIdx.x];
+  const DownEntry E = g.d.entries[W.entry];
+  if (W.level >= E.depth) return;  // (block-uniform; leaves take no work)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  cut_nodes(g, E, lv, W.level, max(W.lo, lv[W.level]), min(W.hi, lv[W.level + 1]), threadIdx.x, kDownBlock);
+}
+
+// k_downstream_top's: one block per entry walks the levels [0, top) upwards,
+// a barrier between two levels.
+__global__ __launch_bounds__(kDownBlock) void k_cut_top(CutArgs g) {
+  const DownEntry E = g.d.entries[blockIdx.x];
+  if (!E.c_t || g.d.entries[blockIdx.x + 1].strip0 == E.strip0) return;  // (block-uniform)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  for (uint32_t d = min(E.top, E.depth); d-- > 0;) {
+    cut_nodes(g, E, lv, d, lv[d], lv[d + 1], threadIdx.x, kDownBlock);
+    __syncthreads();
+  }
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -1305,6 +1437,25 @@ hipError_t launch_downstream_level(const DownArgs& g, uint32_t w0, uint32_t w1, 
 hipError_t launch_downstream_top(const DownArgs& g, hipStream_t s) {
   if (g.n_strips == 0 || g.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_downstream_top, dim3(g.n), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_audience_missed(const CutArgs& g, hipStream_t s) {
+  if (g.d.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_audience_missed, dim3((g.d.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0) return hipSuccess;
+  hipLaunchKernelGGL(k_cut_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_cut_top(const CutArgs& g, hipStream_t s) {
+  if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cut_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
   return hipGetLastError();
 }
 

@@ -15,18 +15,9 @@
 
 using namespace psamd;
 
+// ---- what the passes over subtrees share (drain_impl.hpp; drain_cut.cpp too) -----
+
 namespace {
-
-using Down = Drain::Downstream;
-
-// The tree topics of a request (a mesh topic of the window's node space takes
-// no part in the pass) and what their level tables come to
-struct Req {
-  std::vector<uint32_t> topic;
-  size_t n_lvl = 0;      // level-table words of the topics with rows to read
-  size_t n_work = 0;     // work items of their level launches
-  uint64_t n_nodes = 0;  // their nodes, roots included: the scratch words
-};
 
 // The levels [0, top) of a level table are k_downstream_top's: from the root
 // down to the first level wider than a block.  The deepest level holds leaves
@@ -38,26 +29,28 @@ uint32_t down_top(const std::vector<uint32_t>& lv) {
   return d;
 }
 
-int down_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
+}  // namespace
+
+int psamd::down_plan(ps_engine* e, const uint32_t* topic, size_t n, const char* who, DownReq* R) {
   for (size_t i = 0; i < n; ++i) {
     const uint32_t t = topic[i];
     if (hops_is_mesh(e, t)) continue;
     R->topic.push_back(t);
     if (!hops_active(e, t)) continue;
     if (!hops_levels_stand(e, t))
-      return e->fail(PS_E_STATE, "downstream: a topic was set anew since the last window: run first");
+      return e->fail(PS_E_STATE, std::string(who) + ": a topic was set anew since the last window: run first");
     const auto& lv = e->topics[t].level_off;
     const uint32_t depth = static_cast<uint32_t>(lv.size()) - 2;
     R->n_lvl += lv.size();
     R->n_nodes += lv.back();
     for (uint32_t d = down_top(lv); d < depth; ++d) R->n_work += ceil_div(lv[d + 1] - lv[d], kDownBlock);
   }
-  if (R->n_work >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one downstream pass");
+  if (R->n_work >= kDrainRowLimit) return e->fail(PS_E_RANGE, std::string("too many rows in one ") + who + " pass");
   return PS_OK;
 }
 
 // where the parts of the pass's input block lie: entries | levels | work | strips
-void down_layout(const Req& R, Down::Shape* K) {
+void psamd::down_layout(const DownReq& R, Down::Shape* K) {
   K->n = R.topic.size();
   K->o_lvl = align256((K->n + 1) * sizeof(DownEntry));
   K->o_work = K->o_lvl + align256(std::max<size_t>(R.n_lvl, 1) * 4);
@@ -67,8 +60,8 @@ void down_layout(const Req& R, Down::Shape* K) {
 // aud_stage's entries [n + 1] as the downstream pass's, into de; the level
 // tables into lv and the work list into wk where they are given (with the
 // launches' bounds in the shape); the shape's counts
-void down_entries(ps_engine* e, const Req& R, const AudEntry* ae, const AudShape& A, DownEntry* de, uint32_t* lv, DownWork* wk,
-                  Down::Shape* K) {
+void psamd::down_entries(ps_engine* e, const DownReq& R, const AudEntry* ae, const AudShape& A, DownEntry* de, uint32_t* lv,
+                         DownWork* wk, Down::Shape* K) {
   const size_t n = R.topic.size();
   uint32_t lvl0 = 0, n0 = 0, launches = 0;
   for (size_t i = 0; i < n; ++i) {
@@ -109,12 +102,11 @@ void down_entries(ps_engine* e, const Req& R, const AudEntry* ae, const AudShape
   }
 }
 
-// classify, the weights, the level launches and the top kernel over the block
-// `din` on `stream`, into below / carried.  ms: classify, weights, levels + top
-// (PSAMD_DRAIN_TIMING)
-int down_pass(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape& K, uint64_t* below, uint64_t* carried,
-              const PhaseTimer& tm, float* ms) {
-  if (K.ns == 0) return PS_OK;  // no row to read: nothing to add
+// The front of a pass over the block `din` (K.ns > 0) on `stream`: its buffers,
+// classify and the weights; *out: the kernels' arguments, the sums left null.
+// ms: classify, weights (PSAMD_DRAIN_TIMING)
+int psamd::down_front(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape& K, const PhaseTimer& tm, float* ms,
+                      DownArgs* out) {
   auto& D = e->drain;
   hipStream_t s = e->stream;
   HIP_TRY(P.d_verdict.ensure(K.n_verdicts), "alloc downstream verdicts");
@@ -148,11 +140,26 @@ int down_pass(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape
   d.w_k = P.d_scratch.as<uint64_t>();
   d.k = reinterpret_cast<uint32_t*>(d.w_k + K.n_nodes);
   d.w_n = d.k + K.n_nodes;
-  d.below = below;
-  d.carried = carried;
   HIP_TRY(tm.begin(), "event");
   HIP_TRY(launch_audience_weights(a, d, s), "k_audience_weights");
   HIP_TRY(tm.end(ms[1]), "event");
+  *out = d;
+  return PS_OK;
+}
+
+namespace {
+
+// classify, the weights, the level launches and the top kernel over the block
+// `din` on `stream`, into below / carried.  ms: classify, weights, levels + top
+// (PSAMD_DRAIN_TIMING)
+int down_pass(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape& K, uint64_t* below, uint64_t* carried,
+              const PhaseTimer& tm, float* ms) {
+  if (K.ns == 0) return PS_OK;  // no row to read: nothing to add
+  hipStream_t s = e->stream;
+  DownArgs d{};
+  if (const int rc = down_front(e, P, din, K, tm, ms, &d)) return rc;
+  d.below = below;
+  d.carried = carried;
   HIP_TRY(tm.begin(), "event");
   for (size_t j = 0; j + 1 < K.launch.size(); ++j)
     HIP_TRY(launch_downstream_level(d, K.launch[j], K.launch[j + 1], s), "k_downstream_level");
@@ -161,13 +168,13 @@ int down_pass(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape
   return PS_OK;
 }
 
+}  // namespace
+
 // every pass enqueued so far is complete: nothing waits for one any more
-void down_settled(Down& H) {
+void psamd::down_settled(Down& H) {
   for (auto& f : H.fence) f.pending = false;
   for (auto& a : H.arena) a.pending = false;
 }
-
-}  // namespace
 
 // ---- the standing pass's run hooks (run.cpp calls them) -------------------------
 
@@ -195,6 +202,24 @@ int psamd::downstream_window(ps_engine* e) {
   auto& D = e->drain;
   auto& H = D.down;
   if (!H.on || !H.open) return PS_OK;
+  Down::Shape K;
+  size_t n = 0;
+  int rc = down_window_stage(e, H, "downstream", &K, &n);
+  if (rc) return rc;
+  const PhaseTimer untimed{D.ev_t, e->stream, false};
+  float none[3] = {0, 0, 0};
+  uint64_t* const acc = H.d_acc.as<uint64_t>();
+  if ((rc = down_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, acc, acc + e->cfg.n_peers, untimed, none))) return rc;
+  return down_window_done(e, H, "downstream", n);
+}
+
+// What a standing pass over subtrees (state H, open) does in front of its
+// kernels: the window's tables, then the input block in H.track.d_in -- whole,
+// or the entry table alone while H.strip_key stands.  *K: its shape; *n_tree:
+// the tree topics among the standing ones.
+int psamd::down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape* Kout, size_t* n_tree) {
+  auto& D = e->drain;
+  const std::string w(who);
   auto& R = H.open->mem;
   if (const int rj = twin_join(e)) return rj;
   hipStream_t s = e->stream;
@@ -202,8 +227,8 @@ int psamd::downstream_window(ps_engine* e) {
   uint8_t* h = nullptr;
   int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
   if (rc) return rc;
-  Req Q;
-  if ((rc = down_plan(e, H.topic.data(), H.topic.size(), &Q))) return rc;
+  DownReq Q;
+  if ((rc = down_plan(e, H.topic.data(), H.topic.size(), who, &Q))) return rc;
   const size_t n = Q.topic.size();
   const uint32_t* const topic = Q.topic.data();
 
@@ -216,49 +241,76 @@ int psamd::downstream_window(ps_engine* e) {
     key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
     key.push_back(topic[i]);
   }
-  Down::Shape K;
+  Down::Shape& K = *Kout;
   down_layout(Q, &K);
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   uint8_t* hs = nullptr;
   if (key == H.strip_key) {
-    HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc downstream staging");
+    HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc subtree pass staging");
     aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);
     down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), nullptr, nullptr, &K);
     if (K.ns != H.kept.ns || K.n_verdicts != H.kept.n_verdicts || K.n_nodes != H.kept.n_nodes || K.o_strips != H.kept.o_strips)
-      return e->fail(PS_E_STATE, "downstream: the kept strips are not the window's");
+      return e->fail(PS_E_STATE, w + ": the kept strips are not the window's");
     K.bytes = H.kept.bytes;
     K.launch = H.kept.launch;
     HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, (n + 1) * sizeof(DownEntry), hipMemcpyHostToDevice, s),
-            "upload downstream entries");
+            "upload subtree pass entries");
   } else {
     H.strip_key.clear();
     size_t o = 0;
     uint64_t strips_max = 0;
     (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
-    if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one downstream window");
-    HIP_TRY(sink_stage(R, K.o_strips + strips_max * sizeof(AudStrip), &hs), "alloc downstream staging");
+    if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one " + w + " window");
+    HIP_TRY(sink_stage(R, K.o_strips + strips_max * sizeof(AudStrip), &hs), "alloc subtree pass staging");
     if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
-      return e->fail(PS_E_STATE, "downstream: more strips than staged");
+      return e->fail(PS_E_STATE, w + ": more strips than staged");
     down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl),
                  reinterpret_cast<DownWork*>(hs + K.o_work), &K);
     K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
-    HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc downstream strips");
-    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload downstream strips");
+    HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc subtree pass strips");
+    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload subtree pass strips");
     H.kept = K;
     H.strip_key = key;
   }
-  const PhaseTimer untimed{D.ev_t, s, false};
-  float none[3] = {0, 0, 0};
-  uint64_t* const acc = H.d_acc.as<uint64_t>();
-  if ((rc = down_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, acc, acc + e->cfg.n_peers, untimed, none))) return rc;
+  *n_tree = n;
+  return PS_OK;
+}
+
+// ... and behind them: the fence of the row set, the run's event, the counts
+int psamd::down_window_done(ps_engine* e, Down& H, const char* who, size_t n_tree) {
+  hipStream_t s = e->stream;
+  int rc;
   // classify and the counted rows read the window's row set: the events are
   // recorded whether or not a row was read
-  if ((rc = pass_fence(e, H.fence, "downstream"))) return rc;
+  if ((rc = pass_fence(e, H.fence, who))) return rc;
   HIP_TRY(hipEventRecord(H.open->ev, s), "event");
   H.open->pending = true;
   H.windows += 1;
-  H.skipped += H.topic.size() - n;  // the mesh topics of this window
+  H.skipped += H.topic.size() - n_tree;  // the mesh topics of this window
+  return PS_OK;
+}
+
+// A blocking call's input block over the named tree topics (none a mesh), cut
+// whole into H.stage; *K: its shape
+int psamd::down_sync_stage(ps_engine* e, Down& H, const uint32_t* topic, size_t n, const char* who, Down::Shape* Kout) {
+  DownReq Q;
+  if (const int rc = down_plan(e, topic, n, who, &Q)) return rc;
+  Down::Shape& K = *Kout;
+  down_layout(Q, &K);
+  size_t o = 0;
+  uint64_t strips_max = 0;
+  (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
+  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  uint8_t* const hs = H.stage.data();
+  std::vector<AudEntry> ae(n + 1);
+  AudShape A;
+  if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
+    return e->fail(PS_E_STATE, std::string(who) + ": more strips than staged");
+  down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl),
+               reinterpret_cast<DownWork*>(hs + K.o_work), &K);
+  K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
   return PS_OK;
 }
 
@@ -283,23 +335,9 @@ int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* 
   float ms[4] = {0, 0, 0, 0};  // classify, weights, levels + top, copy (PSAMD_DRAIN_TIMING)
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
-  Req Q;
-  if ((rc = down_plan(e, topic, n, &Q))) return rc;
   Down::Shape K;
-  down_layout(Q, &K);
-  size_t o = 0;
-  uint64_t strips_max = 0;
-  (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
-  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  if ((rc = down_sync_stage(e, H, topic, n, "downstream", &K))) return rc;
   uint8_t* const hs = H.stage.data();
-  std::vector<AudEntry> ae(n + 1);
-  AudShape A;
-  if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
-    return e->fail(PS_E_STATE, "downstream: more strips than staged");
-  down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl),
-               reinterpret_cast<DownWork*>(hs + K.o_work), &K);
-  K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
   const double host_ms = ms_since(t_host0);
 
   HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc downstream strips");

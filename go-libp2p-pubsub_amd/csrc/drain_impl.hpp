@@ -24,6 +24,11 @@
 //                     messages below its nodes, bottom-up over the same level
 //                     tables behind the same strips and verdicts, with buffers
 //                     of their own
+//   drain_cut.cpp     ps_peer_cut, ps_cut_track / _take and run.cpp's hooks
+//                     (§5.5l): per peer, what its nodes missed and what was lost
+//                     behind its cut points, over the downstream pass's plan
+//                     (down_plan .. down_window_done below), with buffers of
+//                     their own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -39,7 +44,8 @@
 //  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
 //    over each row set) and Load::fence (the last standing load pass over
 //    each), Hops::fence (the last standing hop pass) and Downstream::fence
-//    (the last standing downstream pass) are read by drain_fence (run.cpp).
+//    (the last standing downstream pass) and Cut::fence (the last standing
+//    cut pass) are read by drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics
@@ -245,5 +251,34 @@ bool hops_active(ps_engine* e, uint32_t t);
 bool hops_levels_stand(ps_engine* e, uint32_t t);
 // the topic as it is defined now builds into a mesh
 bool hops_child_lists_mesh(const TopicHost& T);
+
+// ---- drain_downstream.cpp: what the passes over subtrees share (drain_cut.cpp) ------
+
+using Down = Drain::Downstream;  // (Drain::Cut is the same shape)
+
+// The tree topics of a request (a mesh topic of the window's node space takes
+// no part in the pass) and what their level tables come to
+struct DownReq {
+  std::vector<uint32_t> topic;
+  size_t n_lvl = 0;      // level-table words of the topics with rows to read
+  size_t n_work = 0;     // work items of their level launches
+  uint64_t n_nodes = 0;  // their nodes, roots included: the scratch words
+};
+// the plan of a request, the layout of its input block (entries | levels |
+// work | strips) and the block's first three parts; `who` names the pass in messages
+int down_plan(ps_engine* e, const uint32_t* topic, size_t n, const char* who, DownReq* R);
+void down_layout(const DownReq& R, Down::Shape* K);
+void down_entries(ps_engine* e, const DownReq& R, const AudEntry* ae, const AudShape& A, DownEntry* de, uint32_t* lv,
+                  DownWork* wk, Down::Shape* K);
+// a pass's buffers, k_audience_classify and k_audience_weights over the block `din`
+int down_front(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape& K, const PhaseTimer& tm, float* ms,
+               DownArgs* out);
+// a blocking call's block over the named tree topics, whole, into H.stage
+int down_sync_stage(ps_engine* e, Down& H, const uint32_t* topic, size_t n, const char* who, Down::Shape* K);
+// a standing pass's window around its kernels: the block into H.track.d_in
+// (kept while H.strip_key stands); the fence, the run's event and the counts
+int down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape* K, size_t* n_tree);
+int down_window_done(ps_engine* e, Down& H, const char* who, size_t n_tree);
+void down_settled(Down& H);
 
 }  // namespace psamd

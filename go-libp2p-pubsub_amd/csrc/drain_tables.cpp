@@ -507,14 +507,16 @@ void drain_destroy(ps_engine* e) {
   for (auto& f : D.hops.fence)
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.hops.ev_take) (void)hipEventDestroy(D.hops.ev_take);
-  if (D.down.h_out) (void)hipHostFree(D.down.h_out);
-  for (auto& a : D.down.arena) {
-    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
-    if (a.ev) (void)hipEventDestroy(a.ev);
+  for (auto* H : {&D.down, &D.cut}) {
+    if (H->h_out) (void)hipHostFree(H->h_out);
+    for (auto& a : H->arena) {
+      for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
+      if (a.ev) (void)hipEventDestroy(a.ev);
+    }
+    for (auto& f : H->fence)
+      if (f.ev) (void)hipEventDestroy(f.ev);
+    if (H->ev_take) (void)hipEventDestroy(H->ev_take);
   }
-  for (auto& f : D.down.fence)
-    if (f.ev) (void)hipEventDestroy(f.ev);
-  if (D.down.ev_take) (void)hipEventDestroy(D.down.ev_take);
 }
 
 }  // namespace psamd

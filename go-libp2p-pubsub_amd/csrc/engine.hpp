@@ -891,6 +891,18 @@ struct ps_engine {
       PassFence fence[2];
       hipEvent_t ev_take = nullptr;
     } down;
+
+    // ps_peer_cut / ps_cut_track / ps_cut_take (host code:
+    // drain_cut.cpp): per peer, what its nodes missed, and for its cut points
+    // -- nodes that lack messages under a full parent -- their number, the
+    // nodes behind them and the deliveries lost at and behind them:
+    // k_audience_missed behind k_audience_weights, then k_cut_level per BFS
+    // level and k_cut_top over the downstream pass's plan.  The state has the
+    // downstream pass's shape, field for field, with four arrays where that
+    // holds two (missed | cuts | orphaned | lost in d_out and d_acc); it
+    // shares no buffer with it.
+    using Cut = Downstream;
+    Cut cut;
   } drain;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
@@ -1050,6 +1062,11 @@ void hops_abort(ps_engine* e);
 int downstream_open(ps_engine* e);
 int downstream_window(ps_engine* e);
 void downstream_abort(ps_engine* e);
+// drain_cut.cpp, the standing cut pass (ps_cut_track; all no-ops while nothing
+// is tracked): called where the downstream pass's hooks are
+int cut_open(ps_engine* e);
+int cut_window(ps_engine* e);
+void cut_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

@@ -1011,4 +1011,32 @@ hipError_t launch_downstream_level(const DownArgs& g, uint32_t w0, uint32_t w1, 
 // k_downstream_top: one block per entry, behind the last level launch
 hipError_t launch_downstream_top(const DownArgs& g, hipStream_t s);
 
+// ---- losses blamed on their cut points (ps_peer_cut, ps_cut_track) --
+// The same strips, entries, level tables, work list and scratch as the pass
+// above (DownArgs, whose below / carried stay unused), turned into four sums
+// per peer.  With miss(v) = c_t - k(v), the root counting as full: a node v
+// adds miss(v) to missed[its peer]; a non-root node u that lacks messages
+// under a full parent is a cut point and adds 1 to cuts, w_n[u] - 1 to
+// orphaned and c_t * w_n[u] - w_k[u] to lost, each at its peer.
+// k_audience_missed runs over the strips behind k_audience_weights.
+// k_cut_level / k_cut_top are k_downstream_level / k_downstream_top without
+// the peer sums of their own: they build w_n and w_k bottom-up and find the
+// cut points from the parent's side -- a full node walks its children's words
+// anyway --, so that no parent array is needed, no launch covers the deepest
+// level, and node_peer is read for cut points only.  Level 0 counts as full
+// whatever k[root] holds (k_audience_weights stores 0 there).
+struct CutArgs {
+  DownArgs d;
+  uint64_t* missed;    // [n_peers] each, added into
+  uint64_t* cuts;
+  uint64_t* orphaned;
+  uint64_t* lost;
+};
+// k_audience_missed: one wave per strip behind k_audience_weights, a node per lane
+hipError_t launch_audience_missed(const CutArgs& g, hipStream_t s);
+// k_cut_level over work items [w0, w1): one launch of the bottom-up pass
+hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStream_t s);
+// k_cut_top: one block per entry, behind the last level launch
+hipError_t launch_cut_top(const CutArgs& g, hipStream_t s);
+
 }  // namespace psamd

@@ -194,6 +194,9 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   // ... and the standing downstream pass's (ps_downstream_track)
   for (const auto& F : e->drain.down.fence)
     if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending downstream pass");
+  // ... and the standing cut pass's (ps_cut_track)
+  for (const auto& F : e->drain.cut.fence)
+    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending cut pass");
   return PS_OK;
 }
 
@@ -1456,8 +1459,9 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
     int rc = run_window(e, msgs, win, st);
     e->defer_last = false;
     // (the window that was remembered: after a k_flood timeout, its re-run)
-    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e)) && !(rc = hops_window(e)))
-      rc = downstream_window(e);
+    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e)) && !(rc = hops_window(e)) &&
+        !(rc = downstream_window(e)))
+      rc = cut_window(e);
     if (rc) return rc;
   }
   return PS_OK;
@@ -1580,13 +1584,15 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer);
 int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
   int rc = sink_precheck(e);
   if (rc || (rc = sink_open(e))) return rc;
-  if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = downstream_open(e)) && !(rc = run_windows(e, stp, may_defer)))
+  if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = downstream_open(e)) && !(rc = cut_open(e)) &&
+      !(rc = run_windows(e, stp, may_defer)))
     rc = sink_close(e);
   if (rc) {
     sink_abort(e);
     load_abort(e);
     hops_abort(e);
     downstream_abort(e);
+    cut_abort(e);
   }
   return rc;
 }

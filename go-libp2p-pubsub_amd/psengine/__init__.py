@@ -181,6 +181,9 @@ PROTOTYPES = [
     ("ps_peer_downstream", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p]),
     ("ps_downstream_track", C.c_int, [_P, _u32p, C.c_size_t]),
     ("ps_downstream_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_peer_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_cut_track", C.c_int, [_P, _u32p, C.c_size_t]),
+    ("ps_cut_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -835,6 +838,40 @@ class Engine:
         self._check(self._L.ps_downstream_take(self._h, _p(below, C.c_uint64), _p(carried, C.c_uint64), C.byref(nw),
                                                C.byref(nsk)))
         return below, carried, nw.value, nsk.value
+
+    def peer_cut(self, topics) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """What the last window lost over the named distinct tree topics, and
+        where the trees were cut (ps_peer_cut): (missed, cuts, orphaned, lost),
+        uint64 [n_peers] each -- the messages the peer's own nodes lack; its
+        cut points (nodes that lack messages under a full parent); the nodes
+        behind them, live or not; and the deliveries that did not happen at
+        and behind them."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        out = [np.empty(self.n_peers, dtype=np.uint64) for _ in range(4)]
+        self._check(self._L.ps_peer_cut(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out)))
+        return out[0], out[1], out[2], out[3]
+
+    def cut_track(self, topics):
+        """Registers standing tree topics (ps_cut_track): from now on every
+        window of every run adds its losses and cut points over them into
+        totals on the device (cut_take).  No topic clears the tracking;
+        setting or clearing zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_cut_track(self._h, _p(t, C.c_uint32), t.size))
+
+    def cut_take(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, int, int]:
+        """The totals since the last take or track call (ps_cut_take):
+        (missed, cuts, orphaned, lost, n_windows, n_skipped); n_skipped counts
+        the (topic, window) pairs left out because the topic was a mesh there.
+        The totals and both counts start again at 0."""
+        out = [np.empty(self.n_peers, dtype=np.uint64) for _ in range(4)]
+        nw, nsk = C.c_uint64(), C.c_uint64()
+        self._check(self._L.ps_cut_take(self._h, *(_p(a, C.c_uint64) for a in out), C.byref(nw), C.byref(nsk)))
+        return out[0], out[1], out[2], out[3], nw.value, nsk.value
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

@@ -718,6 +718,76 @@ int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n,
 int ps_downstream_track(ps_engine* e, const uint32_t* topic, size_t n);
 int ps_downstream_take(ps_engine* e, uint64_t* below_out, uint64_t* carried_out, /* [n_peers], nullable */
                        uint64_t* n_windows_out, uint64_t* n_skipped_out);
+/* Losses blamed on their cut points: after a live mask, a drop or churn, what
+ * was not delivered and at which peer the tree was cut (one rank; DESIGN.md
+ * 5.5l).  Per window and per named tree topic t with c_t > 0 messages in it,
+ * on the node space that window ran on: every node v carries k(v),
+ * ps_peer_load's k -- the number of t's window messages its row holds; 0 for a
+ * tree node the window did not reach -- and the root counts as full, k(root) =
+ * c_t: it is the source.  miss(v) = c_t - k(v), 0 for the root.  A non-root
+ * node u is a cut point when k(u) < c_t and its parent is full; T(u) is u
+ * together with its strict descendants.  Four sums in peer space:
+ *   missed[p]   += miss(v) for every node v of peer p: what p itself did not get
+ *   cuts[p]     += 1 for every cut point u of p
+ *   orphaned[p] += |T(u)| - 1 for every cut point u of p: the subscribers cut
+ *                  off behind it, live or not, as in ps_peer_downstream's below
+ *   lost[p]     += the sum of miss(v) over v in T(u) for every cut point u of
+ *                  p, that is c_t * |T(u)| - the sum of k(v) over T(u): the
+ *                  deliveries that did not happen because the tree was cut at
+ *                  u, u's own included.
+ * A topic with no message in the window adds nothing; peers outside the node
+ * space add nothing: both as in ps_peer_load, ps_topic_hops and
+ * ps_peer_downstream.
+ *   Four identities follow.  (1) For the named topics, the sum of missed over
+ * the peers is the sum over t of c_t * (n_nodes_t - 1) - deliveries_t.  (2) The
+ * sum of lost equals the sum of missed: a tree node's row is a subset of its
+ * parent's row, so every node with a miss lies in exactly one cut point's
+ * T(u).  (3) In a window where every row is full or empty -- every tree window
+ * of a healthy engine -- a cut point u of peer p, the only one of p in a single
+ * named topic, gives lost[p] = c_t * (1 + orphaned[p]), orphaned[p] = below[p]
+ * and carried[p] = 0, below and carried being ps_peer_downstream's.  (4) Under
+ * an all-live mask all four arrays are zero.
+ *   Mesh topics are refused: a DAG has no subtrees.  A tree topic that shares
+ * a window with a mesh is answered as any other.
+ *   ps_peer_cut answers for the last window of the last run, blocking, with
+ * ps_peer_load's window, stream-ordering and twin-join rules.  The n topics
+ * are distinct; the arrays ([n_peers] each, any may be NULL, not all four) are
+ * written in full: peers in no named topic read 0, and n == 0 gives all zeros.
+ * PS_E_INVAL for a NULL engine, n > 0 without topic, all outputs NULL or a
+ * topic named twice; PS_E_RANGE, nothing written, for a topic out of range;
+ * PS_E_NOTREADY before any run; PS_E_STATE, nothing written, on a multi-rank
+ * engine, when a named topic is a mesh in that window's node space, and for a
+ * topic that was set anew over another kind since the window (its levels are
+ * gone: run first).
+ *   ps_cut_track registers n standing topics (copied; n == 0 clears the
+ * tracking and frees the totals).  PS_E_INVAL / PS_E_RANGE as above, and
+ * PS_E_STATE for a topic whose child lists make a mesh: the previous tracking
+ * stays.  PS_E_STATE with a run in flight and on a multi-rank engine;
+ * ps_dist_init* on an engine that is tracking cut points returns PS_E_STATE.
+ * Setting or clearing zeroes the totals.  Tracking is independent of both
+ * sinks, of ps_load_track, of ps_hops_track and of ps_downstream_track: all
+ * may be set at once.  While it is set, every window of every ps_run /
+ * ps_run_async that runs something enqueues the pass behind itself -- the
+ * window is neither planned nor launched differently -- and the pass adds into
+ * four totals on the device, [n_peers] each, in peer space: they survive
+ * node-space rebuilds, joins, leaves and drops between windows.  A tracked
+ * topic that is a mesh in a window's node space adds nothing for that window;
+ * each such (topic, window) pair is counted.
+ *   ps_cut_take waits for the passes enqueued so far, copies the totals since
+ * the last take or track call (each array may be NULL), zeroes them in front
+ * of whatever runs next, sets *n_windows_out to the windows counted and
+ * *n_skipped_out to the (mesh topic, window) pairs left out, and resets both
+ * counts.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with a run in
+ * flight (complete the runs with ps_wait first); PS_E_INVAL for a NULL engine
+ * or count pointer.  After a failed ps_run / ps_wait the totals are
+ * unspecified until the next take or track call. */
+int ps_peer_cut(ps_engine* e, const uint32_t* topic, size_t n,
+                uint64_t* missed_out, uint64_t* cuts_out,
+                uint64_t* orphaned_out, uint64_t* lost_out);   /* [n_peers] each; any may be NULL, not all four */
+int ps_cut_track(ps_engine* e, const uint32_t* topic, size_t n);
+int ps_cut_take(ps_engine* e, uint64_t* missed_out, uint64_t* cuts_out,
+                uint64_t* orphaned_out, uint64_t* lost_out,     /* [n_peers], nullable */
+                uint64_t* n_windows_out, uint64_t* n_skipped_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -111,6 +111,19 @@ for array; then the pipelined step plain, with downstream tracked
 load tracking, the three alternating in one process, with the overlapped
 windows of each, the totals against steps x the blocking answer.  Writes
 DIR/downstream_bench.json.
+
+--cut: the losses blamed on their cut points (ps_peer_cut) over every topic
+after one step under a live mask with about 1 % of the peers dead (--seed; an
+all-live window has no cut point and exercises nothing), --reps repetitions in
+one process: its device phases (classify, weights, missed, levels + top, copy)
+with ps_peer_downstream's under the same mask in the same process as the
+yardstick, and its wall; the derivation a caller has without it --
+ps_drain_topics + ps_topic_get_parents per topic + numpy depths, cut points
+and a bottom-up sum -- and its wall, the two answers compared array for array;
+then the pipelined step plain, with cuts tracked (ps_cut_track, one ps_cut_take
+per loop) and beside load, hop and downstream tracking, the three alternating
+in one process, the totals against steps x the blocking answer.  Writes
+DIR/cut_bench.json.
 """
 from __future__ import annotations
 
@@ -1254,10 +1267,28 @@ def host_peer_downstream(eng, wl, topics):
     ps_peer_downstream: the audience answer, every topic's parent array, depths
     by numpy as in host_topic_hops, then each level's (1, k) pairs added into
     the parents', the deepest level first."""
-    r = eng.drain_topics(topics)
     n = wl.n_peers
     below = np.zeros(n, dtype=np.uint64)
     carried = np.zeros(n, dtype=np.uint64)
+    for c, par, root, k, depth, levels in host_topic_trees(eng, wl, topics):
+        w_n = (depth >= 0).astype(np.uint64)
+        w_k = k.copy()
+        for at in reversed(levels):
+            np.add.at(w_n, par[at], w_n[at])
+            np.add.at(w_k, par[at], w_k[at])
+        member = depth >= 0
+        below[member] += w_n[member] - np.uint64(1)
+        carried[member] += w_k[member] - k[member]
+    return below, carried
+
+
+def host_topic_trees(eng, wl, topics):
+    """What the host derivations over subtrees start from, per topic with
+    messages: (c, parents, root, k per peer -- the root's and every
+    non-member's 0 --, depth per peer, the peers of levels 1 ..), from the
+    audience answer and ps_topic_get_parents."""
+    r = eng.drain_topics(topics)
+    n = wl.n_peers
     sizes = np.diff(r["list_off"]).astype(np.uint64)
     c_all = np.bincount(wl.msg_topics, minlength=len(wl.topics))
     for i, t in enumerate(topics):
@@ -1289,15 +1320,7 @@ def host_peer_downstream(eng, wl, topics):
             k[r["exc_peer"][lo:hi]] = ke
         k[root] = 0
         k[depth < 0] = 0
-        w_n = (depth >= 0).astype(np.uint64)
-        w_k = k.copy()
-        for at in reversed(levels):
-            np.add.at(w_n, par[at], w_n[at])
-            np.add.at(w_k, par[at], w_k[at])
-        member = depth >= 0
-        below[member] += w_n[member] - np.uint64(1)
-        carried[member] += w_k[member] - k[member]
-    return below, carried
+        yield c, par, root, k, depth, levels
 
 
 def downstream_main(a, wl):
@@ -1402,6 +1425,152 @@ def downstream_main(a, wl):
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "downstream_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def host_peer_cut(eng, wl, topics):
+    """The losses and their cut points as a caller derives them without
+    ps_peer_cut: host_topic_trees' k per peer, miss = c - k for the non-root
+    members, a cut point where a member lacks messages under a full parent, and
+    each level's (1, miss) pairs added into the parents', the deepest first."""
+    n = wl.n_peers
+    out = [np.zeros(n, dtype=np.uint64) for _ in range(4)]
+    for c, par, root, k, depth, levels in host_topic_trees(eng, wl, topics):
+        member = depth > 0
+        miss = np.where(member, np.uint64(c) - k, np.uint64(0))
+        w_n = (depth >= 0).astype(np.uint64)
+        w_m = miss.copy()
+        for at in reversed(levels):
+            np.add.at(w_n, par[at], w_n[at])
+            np.add.at(w_m, par[at], w_m[at])
+        up = np.where(member, par, root).astype(np.int64)
+        cut = member & (miss > 0) & (miss[up] == 0)
+        out[0] += miss
+        out[1] += cut.astype(np.uint64)
+        out[2][cut] += w_n[cut] - np.uint64(1)
+        out[3][cut] += w_m[cut]
+    return tuple(out)
+
+
+def cut_main(a, wl):
+    """--cut (see the module text).  Writes DIR/cut_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": a.steps, "warmup": a.warmup, "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+        WL.build_engine_topics(eng, wl)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        for tag, call, key in (("peer_cut", eng.peer_cut, "cut_phases"),
+                               ("peer_downstream", eng.peer_downstream, "downstream_phases")):
+            rows = []
+            for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+                with StderrCapture() as cap:
+                    got = call(topics)
+                row = phase_line(cap.text, tag)
+                for k in ("strips", "nodes", "row_bytes", "work", "launches"):
+                    m = re.search(rf"\b{k} (\d+)", cap.text)
+                    if m:
+                        row[k] = int(m.group(1))
+                rows.append(row)
+            res[key] = rows[1:]
+            if tag == "peer_cut":
+                blocking = got
+        res.update(deliveries=int(st.deliveries), missed_sum=int(blocking[0].sum()), cut_points=int(blocking[1].sum()),
+                   orphaned_sum=int(blocking[2].sum()), lost_sum=int(blocking[3].sum()),
+                   peers_with_a_cut=int((blocking[1] > 0).sum()), lost_max=int(blocking[3].max()))
+        assert res["lost_sum"] == res["missed_sum"] and res["cut_points"] > 0
+    eng, _ = masked_engine({})
+    with eng:
+        walls = {"cut": [], "host": [], "downstream": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.peer_cut(topics)
+            walls["cut"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            want = host_peer_cut(eng, wl, topics)
+            walls["host"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.peer_downstream(topics)
+            walls["downstream"].append(1e3 * (time.perf_counter() - t0))
+            for g, w, name in zip(got, want, ("missed", "cuts", "orphaned", "lost")):
+                assert np.array_equal(g, w), f"ps_peer_cut {name} differs from the host derivation"
+            for g, w in zip(got, blocking):
+                assert np.array_equal(g, w)
+    res["cut_wall_ms"], res["host_derivation_wall_ms"], res["downstream_wall_ms"] = \
+        (walls[k][1:] for k in ("cut", "host", "downstream"))
+    res["answers_agree"] = True
+    res["host_over_cut_wall"] = float(np.median(res["host_derivation_wall_ms"]) / np.median(res["cut_wall_ms"]))
+    res["cut_over_downstream_wall"] = float(np.median(res["cut_wall_ms"]) / np.median(res["downstream_wall_ms"]))
+    cp, dp = res["cut_phases"], res["downstream_phases"]
+    res["cut_levels_over_downstream_levels"] = float(np.median([p["levels_ms"] for p in cp]) /
+                                                     np.median([p["levels_ms"] for p in dp]))
+
+    # tracking in the pipelined loop: plain, cut, beside load, hops and downstream
+    for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING"):
+        os.environ.pop(k, None)
+    eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    eng.set_live(live)
+    none = np.zeros(0, dtype=np.uint32)
+    modes = {"plain": (False, False), "cut": (True, False), "beside_load_hops_and_downstream": (True, True)}
+
+    def timed(cut, others, steps):
+        eng.cut_track(topics if cut else none)
+        eng.downstream_track(topics if others else none)
+        eng.hops_track(topics if others else none)
+        eng.load_track(topics if others else none)
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        loop_plain(eng, wl, steps)
+        tc = eng.cut_take() if cut else None
+        td = eng.downstream_take() if others else None
+        th = eng.hops_take() if others else None
+        tl = eng.load_take() if others else None
+        return 1e3 * (time.perf_counter() - t0) / steps, eng.overlapped_windows() - o0, tc, td, th, tl
+
+    with eng:
+        eng.publish(wl.msg_topics)
+        eng.run()
+        load0, hops0, down0 = eng.peer_load(topics), eng.topic_hops(topics), eng.peer_downstream(topics)
+        for mode in modes.values():
+            timed(*mode, a.warmup)
+        ms = {k: [] for k in modes}
+        over = {k: [] for k in modes}
+        for _ in range(a.reps):
+            for name, (cut, others) in modes.items():
+                t, o, tc, td, th, tl = timed(cut, others, a.steps)
+                ms[name].append(t)
+                over[name].append(int(o))
+                if cut:
+                    assert tc[4:] == (a.steps, 0)
+                    for g, w in zip(tc[:4], blocking):
+                        assert np.array_equal(g, w * np.uint64(a.steps)), "tracked cut totals differ"
+                if others:
+                    assert td[2:] == (a.steps, 0) and np.array_equal(td[1], down0[1] * np.uint64(a.steps))
+                    assert th[3:] == (a.steps, 0) and np.array_equal(th[2], hops0[2] * np.uint64(a.steps))
+                    assert tl[2] == a.steps and np.array_equal(tl[0], load0[0] * np.uint64(a.steps))
+        for track in (eng.cut_track, eng.downstream_track, eng.hops_track, eng.load_track):
+            track(none)
+    res.update(ms_per_step=ms, overlapped_windows=over, tracked_totals_agree=True,
+               cut_minus_plain_ms=float(np.median(ms["cut"]) - np.median(ms["plain"])),
+               beside_minus_plain_ms=float(np.median(ms["beside_load_hops_and_downstream"]) - np.median(ms["plain"])))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "cut_bench.json"), "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
 
 
@@ -1550,8 +1719,12 @@ def main():
     ap.add_argument("--hops", action="store_true", help="ps_topic_hops against the host derivation; tracking in the pipelined loop")
     ap.add_argument("--downstream", action="store_true",
                     help="ps_peer_downstream against the host derivation; tracking in the pipelined loop")
+    ap.add_argument("--cut", action="store_true",
+                    help="ps_peer_cut against ps_peer_downstream and the host derivation; tracking in the pipelined loop")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.cut:
+        return cut_main(a, wl)
     if a.downstream:
         return downstream_main(a, wl)
     if a.hops:
