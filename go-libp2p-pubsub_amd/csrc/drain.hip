@@ -49,6 +49,13 @@
 //                         children: one that lacks messages is a cut point, its
 //                         subtree's words into its peer's three sums
 //   k_cut_top             the narrow levels under a root in one block
+// and, for ps_peer_report / ps_report_track (§5.5m), those four answers from one pass:
+//   k_report_nodes        behind one k_audience_classify: a node's k once, into
+//                         the sections selected per launch (load's sums, the hop
+//                         partials, the k word, the misses)
+//   k_report_level        the bottom-up pass once: k_cut_level's walk with
+//                         k_downstream_level's two sums
+//   k_report_top          the narrow levels under a root in one block
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -884,6 +891,213 @@ __global__ __launch_bounds__(kDownBlock) void k_cut_top(CutArgs g) {
   }
 }
 
+// ---- the four answers from one pass (ps_peer_report, ps_report_track) ----------
+
+// One wave per strip behind k_audience_classify, a node per lane: a node's k
+// once -- the verdict byte (full: c_t, none: 0), anything else, and under the
+// seam every full row, through load_count_row; no verdict byte where classify
+// counted no exception in the strip -- and from it what each section selected
+// at compile time takes: k_audience_load's two adds (and the root's share from
+// the entry's first strip), k_audience_hops' partial pair per (strip, level),
+// k_audience_weights' word (the root's 0), k_audience_missed's add.  With hops
+// selected a tree strip is walked level by level as k_audience_hops walks it,
+// else in one run; the sums are integers, so the order changes nothing.  An
+// entry that is no tree feeds the load section alone.
+template <bool kLoad, bool kHops, bool kWords, bool kMissed>
+__global__ __launch_bounds__(kAudBlock) void k_report_nodes(DrainArgs a, ReportArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const ReportEntry E = g.entries[lo - 1];
+  const bool tree = E.tree != 0;  // (wave-uniform, as everything read from E and S)
+  if (!kLoad && !tree) return;
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  const bool all_full = !g.count_rows && g.n_exc[s] == 0;
+  const uint32_t end = S.u0 + S.n;
+  unsigned long long* const recv = reinterpret_cast<unsigned long long*>(g.recv);
+  unsigned long long* const sent = reinterpret_cast<unsigned long long*>(g.sent);
+  unsigned long long* const missed = reinterpret_cast<unsigned long long*>(g.missed);
+  uint32_t* const kout = kWords ? g.k + E.n0 : nullptr;
+  // the level of the strip's first node (a strip holds no root: d >= 1)
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  uint32_t d = 0, slot = 0;
+  if (kHops && tree) {
+    lo = 1, hi = E.depth + 1;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (lv[mid] <= S.u0) lo = mid + 1;
+      else hi = mid;
+    }
+    d = lo - 1;
+    slot = E.part0 + (s - E.strip0) + (d - 1);
+  }
+  for (uint32_t u = S.u0; u < end;) {
+    const bool hop = kHops && tree && d >= 1 && d <= E.depth;
+    const uint32_t ue = hop ? min(end, max(lv[d + 1], u + 1)) : end;
+    uint32_t reached = 0;  // (wave-uniform)
+    uint64_t deliv = 0;
+    if (all_full && !kLoad && !kWords) {
+      // every node holds c_t: nothing is missed, the partials follow from the bounds
+      reached = ue - u;
+      deliv = static_cast<uint64_t>(reached) * E.c_t;
+    } else {
+      for (uint32_t i0 = u; i0 < ue; i0 += kWave) {
+        const uint32_t i = min(i0 + lane, ue - 1);
+        const bool in = i0 + lane < ue;
+        uint32_t peer = 0, deg = 0;
+        if (kLoad) {
+          peer = g.node_peer[S.nbase + i];
+          deg = g.row_ptr[S.nbase + i + 1] - g.row_ptr[S.nbase + i];
+        }
+        uint32_t k = in ? E.c_t : 0u;
+        if (!all_full) {
+          const uint32_t v = vin[i - S.u0];
+          const bool full = !gather && v == kDrainRowAny;
+          const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+          k = in && full && !count ? E.c_t : 0u;
+          uint64_t todo = __ballot(count);
+          while (todo) {
+            const uint32_t j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint32_t c = load_count_row(a, T, i0 + j, lane);
+            if (lane == j) k = c;
+          }
+        }
+        if (kLoad && k) {
+          atomicAdd(recv + peer, static_cast<unsigned long long>(k));
+          if (deg) atomicAdd(sent + peer, static_cast<unsigned long long>(k) * deg);
+        }
+        if (kWords && in && tree) kout[i] = k;
+        if (kMissed && in && tree && k < E.c_t) {
+          if (!kLoad) peer = g.node_peer[S.nbase + i];
+          atomicAdd(missed + peer, static_cast<unsigned long long>(E.c_t - k));
+        }
+        if (kHops && hop) {
+          reached += __popcll(__ballot(k != 0));
+          deliv += wave_sum_u32(k);
+        }
+      }
+    }
+    if (kHops && hop) {
+      if (lane == 0) {
+        g.part_reached[slot] = reached;
+        g.part_deliv[slot] = deliv;
+      }
+      ++d, ++slot;
+    }
+    u = ue;
+  }
+  if (E.strip0 == s && lane == 0) {
+    if (kLoad && E.root != kLoadNoRoot && E.c_t) {
+      const uint32_t deg = g.row_ptr[E.root + 1] - g.row_ptr[E.root];
+      if (deg) atomicAdd(sent + g.node_peer[E.root], static_cast<unsigned long long>(E.c_t) * deg);
+    }
+    if (kWords && tree) kout[0] = 0;
+  }
+}
+
+// cut_nodes' walk over the nodes [lo, hi) of level d < depth with down_nodes'
+// two adds: a node's two words from its children's, written once; every child
+// of a full node -- the root counts as full -- that lacks messages is a cut
+// point; and what lies strictly below the node into its peer's below / carried.
+__device__ __forceinline__ void report_nodes(const CutArgs& g, const DownEntry& E, const uint32_t* __restrict__ lv, uint32_t d,
+                                             uint32_t lo, uint32_t hi, uint32_t tid, uint32_t nt) {
+  const uint32_t lane = tid & (kWave - 1);
+  const uint32_t c0 = lv[d + 1], c1 = lv[d + 2];
+  const uint32_t rp0 = g.d.row_ptr[E.nbase + lv[d]];
+  const bool leaf_kids = d + 1 == E.depth;
+  const uint32_t* const k = g.d.k + E.n0;
+  uint32_t* const w_n = g.d.w_n + E.n0;
+  uint64_t* const w_k = g.d.w_k + E.n0;
+  unsigned long long* const below = reinterpret_cast<unsigned long long*>(g.d.below);
+  unsigned long long* const carried = reinterpret_cast<unsigned long long*>(g.d.carried);
+  for (uint32_t u0 = lo + (tid & ~(kWave - 1)); u0 < hi; u0 += nt) {  // (wave-uniform)
+    const bool in = u0 + lane < hi;
+    const uint32_t u = min(u0 + lane, hi - 1);
+    const uint32_t r0 = g.d.row_ptr[E.nbase + u], r1 = g.d.row_ptr[E.nbase + u + 1];
+    // (clamped into level d + 1, whatever the CSR says)
+    const uint32_t cb = min(c0 + (r0 - rp0), c1);
+    const uint32_t deg = in ? min(r1 - r0, c1 - cb) : 0u;
+    const bool wide = deg > kWave;
+    const uint32_t ku = k[u];
+    const bool full = d == 0 || ku == E.c_t;
+    uint32_t sn = 0;
+    uint64_t sk = 0;
+    if (!wide) {
+      for (uint32_t j = 0; j < deg; ++j) {
+        const uint32_t kc = k[cb + j];
+        const uint32_t cn = leaf_kids ? 1u : w_n[cb + j];
+        const uint64_t ck = leaf_kids ? kc : w_k[cb + j];
+        sn += cn;
+        sk += ck;
+        if (full && kc < E.c_t) cut_point(g, E, cb + j, cn, ck);
+      }
+    }
+    uint64_t todo = __ballot(wide);
+    while (todo) {
+      const uint32_t j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t b = __shfl(cb, static_cast<int>(j), 64), n = __shfl(deg, static_cast<int>(j), 64);
+      const bool pfull = __shfl(static_cast<int>(full), static_cast<int>(j), 64) != 0;
+      uint32_t pn = 0;
+      uint64_t pk = 0;
+      for (uint32_t i = lane; i < n; i += kWave) {
+        const uint32_t kc = k[b + i];
+        const uint32_t cn = leaf_kids ? 1u : w_n[b + i];
+        const uint64_t ck = leaf_kids ? kc : w_k[b + i];
+        pn += cn;
+        pk += ck;
+        if (pfull && kc < E.c_t) cut_point(g, E, b + i, cn, ck);
+      }
+      pn = wave_sum_u32(pn);
+      pk = dev::wave_sum_u64(pk);
+      if (lane == j) {
+        sn = pn;
+        sk = pk;
+      }
+    }
+    if (in) {
+      w_n[u] = 1 + sn;
+      w_k[u] = ku + sk;
+      const uint32_t peer = g.d.node_peer[E.nbase + u];
+      if (sn) atomicAdd(below + peer, static_cast<unsigned long long>(sn));
+      if (sk) atomicAdd(carried + peer, static_cast<unsigned long long>(sk));
+    }
+  }
+}
+
+// k_downstream_level's launch: one block per work item, stream order the only
+// order between the launches' waves.
+__global__ __launch_bounds__(kDownBlock) void k_report_level(CutArgs g, uint32_t w0) {
+  const DownWork W = g.d.work[w0 + blockIdx.x];
+  const DownEntry E = g.d.entries[W.entry];
+  if (W.level >= E.depth) return;  // (block-uniform; leaves take no work)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  report_nodes(g, E, lv, W.level, max(W.lo, lv[W.level]), min(W.hi, lv[W.level + 1]), threadIdx.x, kDownBlock);
+}
+
+// k_downstream_top's: one block per entry walks the levels [0, top) upwards,
+// a barrier between two levels.
+__global__ __launch_bounds__(kDownBlock) void k_report_top(CutArgs g) {
+  const DownEntry E = g.d.entries[blockIdx.x];
+  if (!E.c_t || g.d.entries[blockIdx.x + 1].strip0 == E.strip0) return;  // (block-uniform)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  for (uint32_t d = min(E.top, E.depth); d-- > 0;) {
+    report_nodes(g, E, lv, d, lv[d], lv[d + 1], threadIdx.x, kDownBlock);
+    __syncthreads();
+  }
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -1456,6 +1670,39 @@ hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStrea
 hipError_t launch_cut_top(const CutArgs& g, hipStream_t s) {
   if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cut_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+// the sections of g.what as k_report_nodes' template: both subtree sections
+// take the k word, the cut section the misses too
+hipError_t launch_report_nodes(const DrainArgs& a, const ReportArgs& g, hipStream_t s) {
+  if (g.n_strips == 0) return hipSuccess;
+  if (g.what == 0 || (g.what & ~kReportAll)) return hipErrorInvalidValue;
+  using Kernel = void (*)(DrainArgs, ReportArgs);
+  static const Kernel table[2][2][3] = {
+      {{nullptr, k_report_nodes<false, false, true, false>, k_report_nodes<false, false, true, true>},
+       {k_report_nodes<false, true, false, false>, k_report_nodes<false, true, true, false>,
+        k_report_nodes<false, true, true, true>}},
+      {{k_report_nodes<true, false, false, false>, k_report_nodes<true, false, true, false>,
+        k_report_nodes<true, false, true, true>},
+       {k_report_nodes<true, true, false, false>, k_report_nodes<true, true, true, false>,
+        k_report_nodes<true, true, true, true>}}};
+  const uint32_t words = g.what & kReportCut ? 2u : g.what & kReportDown ? 1u : 0u;
+  const Kernel k = table[g.what & kReportLoad ? 1 : 0][g.what & kReportHops ? 1 : 0][words];
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_report_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0) return hipSuccess;
+  hipLaunchKernelGGL(k_report_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_report_top(const CutArgs& g, hipStream_t s) {
+  if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_report_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
   return hipGetLastError();
 }
 

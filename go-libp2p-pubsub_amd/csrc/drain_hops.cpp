@@ -14,20 +14,13 @@
 
 using namespace psamd;
 
-namespace {
-
 using Hops = Drain::Hops;
 
 static_assert(kHopsCols == PS_MAX_ROUNDS, "a column per round of ps_stats");
 
-// The tree topics of a request with their positions in it: a mesh topic of
-// the window's node space takes no part in the pass
-struct Req {
-  std::vector<uint32_t> topic, row;
-  size_t n_lvl = 0;  // level-table words of the topics with rows to read
-};
+// ---- the plan and the entry table of a pass over tree levels (drain_impl.hpp; drain_report.cpp too) --
 
-int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
+int psamd::hops_plan(ps_engine* e, const uint32_t* topic, size_t n, HopsReq* R) {
   for (size_t i = 0; i < n; ++i) {
     const uint32_t t = topic[i];
     if (hops_is_mesh(e, t)) continue;
@@ -40,17 +33,21 @@ int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, Req* R) {
   return PS_OK;
 }
 
+namespace {
+
 // where the parts of the pass's input block lie: entries | levels | strips
-void hops_layout(const Req& R, Hops::Shape* K) {
+void hops_layout(const HopsReq& R, Hops::Shape* K) {
   K->n = R.topic.size();
   K->o_lvl = align256((K->n + 1) * sizeof(HopsEntry));
   K->o_strips = K->o_lvl + align256(std::max<size_t>(R.n_lvl, 1) * 4);
 }
 
+}  // namespace
+
 // aud_stage's entries [n + 1] as the hop pass's, into he; the level tables
 // into lv where it is given; the shape's counts
-void hops_entries(ps_engine* e, const Req& R, const AudEntry* ae, const AudShape& A, HopsEntry* he, uint32_t* lv,
-                  Hops::Shape* K) {
+void psamd::hops_entries(ps_engine* e, const HopsReq& R, const AudEntry* ae, const AudShape& A, HopsEntry* he, uint32_t* lv,
+                         Hops::Shape* K) {
   const size_t n = R.topic.size();
   uint32_t lvl0 = 0;
   uint64_t part0 = 0;
@@ -78,6 +75,8 @@ void hops_entries(ps_engine* e, const Req& R, const AudEntry* ae, const AudShape
   K->row_bytes = A.row_bytes;
   K->n_parts = part0;
 }
+
+namespace {
 
 // classify, then the two hop kernels, over the block `din` on `stream`, into
 // the three [rows][PS_MAX_ROUNDS] arrays.  ms: classify, hops, sum (PSAMD_DRAIN_TIMING)
@@ -216,7 +215,7 @@ int psamd::hops_window(ps_engine* e) {
   uint8_t* h = nullptr;
   int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
   if (rc) return rc;
-  Req Q;
+  HopsReq Q;
   if ((rc = hops_plan(e, H.topic.data(), H.topic.size(), &Q))) return rc;
   const size_t n = Q.topic.size();
   const uint32_t* const topic = Q.topic.data();
@@ -296,7 +295,7 @@ int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes
   float ms[4] = {0, 0, 0, 0};  // classify, hops, sum, copy (PSAMD_DRAIN_TIMING)
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
-  Req Q;
+  HopsReq Q;
   if ((rc = hops_plan(e, topic, n, &Q))) return rc;
   Hops::Shape K;
   hops_layout(Q, &K);

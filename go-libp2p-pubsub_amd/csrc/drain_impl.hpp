@@ -29,6 +29,12 @@
 //                     behind its cut points, over the downstream pass's plan
 //                     (down_plan .. down_window_done below), with buffers of
 //                     their own
+//   drain_report.cpp  ps_peer_report, ps_report_track / _take and run.cpp's
+//                     hooks (§5.5m): the four answers above from one classify,
+//                     one per-node kernel and one bottom-up sweep, over the hop
+//                     pass's and the downstream pass's plans (hops_plan,
+//                     hops_entries, down_plan .. down_entries below), with
+//                     buffers of their own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -45,7 +51,8 @@
 //    over each row set) and Load::fence (the last standing load pass over
 //    each), Hops::fence (the last standing hop pass) and Downstream::fence
 //    (the last standing downstream pass) and Cut::fence (the last standing
-//    cut pass) are read by drain_fence (run.cpp).
+//    cut pass) and Report::fence (the last standing report pass) are read by
+//    drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics
@@ -251,6 +258,18 @@ bool hops_active(ps_engine* e, uint32_t t);
 bool hops_levels_stand(ps_engine* e, uint32_t t);
 // the topic as it is defined now builds into a mesh
 bool hops_child_lists_mesh(const TopicHost& T);
+
+// The tree topics of a request with their positions in it: a mesh topic of
+// the window's node space takes no part in the pass
+struct HopsReq {
+  std::vector<uint32_t> topic, row;
+  size_t n_lvl = 0;  // level-table words of the topics with rows to read
+};
+int hops_plan(ps_engine* e, const uint32_t* topic, size_t n, HopsReq* R);
+// aud_stage's entries [n + 1] as the hop pass's, into he; the level tables
+// into lv where it is given; the shape's counts (the layout stays the caller's)
+void hops_entries(ps_engine* e, const HopsReq& R, const AudEntry* ae, const AudShape& A, HopsEntry* he, uint32_t* lv,
+                  Drain::Hops::Shape* K);
 
 // ---- drain_downstream.cpp: what the passes over subtrees share (drain_cut.cpp) ------
 

@@ -517,6 +517,14 @@ void drain_destroy(ps_engine* e) {
       if (f.ev) (void)hipEventDestroy(f.ev);
     if (H->ev_take) (void)hipEventDestroy(H->ev_take);
   }
+  if (D.report.h_out) (void)hipHostFree(D.report.h_out);
+  for (auto& a : D.report.arena) {
+    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
+    if (a.ev) (void)hipEventDestroy(a.ev);
+  }
+  for (auto& f : D.report.fence)
+    if (f.ev) (void)hipEventDestroy(f.ev);
+  if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
 }
 
 }  // namespace psamd

@@ -903,6 +903,60 @@ struct ps_engine {
     // shares no buffer with it.
     using Cut = Downstream;
     Cut cut;
+
+    // ps_peer_report / ps_report_track / ps_report_take (host
+    // code: drain_report.cpp): the four answers above from one pass --
+    // k_report_nodes behind one k_audience_classify, k_audience_hops_sum, and
+    // one bottom-up sweep (k_report_level / k_report_top where both subtree
+    // sections are selected, else that section's own level kernels).  Shaped
+    // as the others: the blocking call and the standing pass each own their
+    // buffers, and nothing here is another family's.
+    struct Report {
+      // one pass's device buffers: the input block (report entries | hop
+      // entries | downstream entries | levels | work | strips), the verdict
+      // bytes and strip counts of classify, the hop partials, the scratch
+      // k | w_n | w_k
+      struct Pass {
+        psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_part_r, d_part_d, d_scratch;
+      };
+      // where the block's parts lie and what the grids and buffers are sized by
+      struct Shape {
+        size_t n = 0, n_tree = 0;  // entries: all of them, the tree topics in front
+        size_t o_hops = 0, o_down = 0, o_lvl = 0, o_work = 0, o_strips = 0, bytes = 0;
+        uint32_t ns = 0, max_cols = 0;
+        uint64_t n_verdicts = 0, n_parts = 0, n_nodes = 0, row_bytes = 0;
+        std::vector<uint32_t> launch;
+      };
+      // where the eleven arrays lie in an output block of 64-bit words, in
+      // ps_report's order: recv sent nodes reached deliv below carried missed
+      // cuts orphaned lost; off[11]: the block's words
+      struct Out {
+        size_t off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+      };
+      // ps_peer_report: its pass, the cleared output block, its pinned copy
+      Pass sync;
+      psamd::DevBuf d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+      // ps_report_track: the standing topics and sections, the totals since the
+      // last take or track call (the output block's layout over the standing topics)
+      bool on = false;
+      uint32_t what = 0;
+      std::vector<uint32_t> topic;
+      Pass track;
+      psamd::DevBuf d_acc;
+      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out of the tree sections
+      // the levels, work list and strips on the device while what they are cut from stays
+      std::vector<uint64_t> strip_key;
+      Shape kept;
+      // pinned staging per run and the last pass per row set (PassArena, PassFence)
+      PassArena arena[2];
+      uint64_t runs = 0;
+      PassArena* open = nullptr;  // the run being enqueued
+      PassFence fence[2];
+      hipEvent_t ev_take = nullptr;
+    } report;
   } drain;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
@@ -1067,6 +1121,11 @@ void downstream_abort(ps_engine* e);
 int cut_open(ps_engine* e);
 int cut_window(ps_engine* e);
 void cut_abort(ps_engine* e);
+// drain_report.cpp, the standing report pass (ps_report_track; all no-ops while
+// nothing is tracked): called where the cut pass's hooks are
+int report_open(ps_engine* e);
+int report_window(ps_engine* e);
+void report_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

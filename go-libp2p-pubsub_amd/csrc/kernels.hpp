@@ -1039,4 +1039,56 @@ hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStrea
 // k_cut_top: one block per entry, behind the last level launch
 hipError_t launch_cut_top(const CutArgs& g, hipStream_t s);
 
+// ---- the four answers from one pass (ps_peer_report, ps_report_track) --
+// What the four families above compute, each behind a classify of its own,
+// behind one: k_report_nodes works a node's k out once and feeds every section
+// selected in `what` (PS_REPORT_*) from it -- recv / sent as k_audience_load,
+// the (strip, level) partials as k_audience_hops into HopsArgs' slots (the
+// unchanged k_audience_hops_sum sums them), the k word as k_audience_weights,
+// missed as k_audience_missed.  Its entry table covers every strip: the tree
+// entries first, in the order of HopsArgs::entries and DownArgs::entries (one
+// index serves all three tables), then the entries that feed the load section
+// alone (meshes; every topic where nothing else is selected).
+// k_report_level / k_report_top are the one bottom-up sweep where both subtree
+// sections are selected: cut_nodes' walk with down_nodes' two adds.  With one
+// of them selected the pass launches that section's own level kernels.
+constexpr uint32_t kReportLoad = 1u, kReportHops = 2u, kReportDown = 4u, kReportCut = 8u, kReportAll = 15u;
+struct ReportEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window
+  uint32_t root;    // the root's node (node space), kLoadNoRoot: none on this rank
+  uint32_t tree;    // 1: a tree topic, the fields below stand; 0: the entry feeds the load section alone
+  uint32_t lvl0;    // HopsEntry::lvl0
+  uint32_t depth;   // HopsEntry::depth
+  uint32_t part0;   // HopsEntry::part0
+  uint32_t n0;      // DownEntry::n0
+  uint32_t pad[3];
+};
+struct ReportArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const ReportEntry* entries;  // [n + 1]
+  uint32_t n;
+  uint32_t what;             // PS_REPORT_* bits: the template the launch picks
+  const uint32_t* levels;
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint64_t* n_exc;     // AudArgs::n_exc: 0 = every node of the strip is full
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  const uint32_t* node_peer;
+  const uint32_t* row_ptr;
+  uint64_t* recv;            // [n_peers] each, added into (load)
+  uint64_t* sent;
+  uint32_t* part_reached;    // HopsArgs' slots (hops)
+  uint64_t* part_deliv;
+  uint32_t* k;               // DownArgs::k (downstream, cut)
+  uint64_t* missed;          // [n_peers], added into (cut)
+};
+// k_report_nodes: one wave per strip behind k_audience_classify, a node per lane
+hipError_t launch_report_nodes(const DrainArgs& a, const ReportArgs& g, hipStream_t s);
+// k_report_level over work items [w0, w1), k_report_top: the bottom-up pass
+// with all six sums of CutArgs (d.below and d.carried too)
+hipError_t launch_report_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStream_t s);
+hipError_t launch_report_top(const CutArgs& g, hipStream_t s);
+
 }  // namespace psamd

@@ -87,6 +87,17 @@ class DistConfig(C.Structure):
                 ("split_depth", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Report(C.Structure):
+    """ps_report (include/psengine.h): eleven nullable output pointers."""
+    _fields_ = [(k, C.POINTER(C.c_uint64)) for k in
+                ("recv", "sent", "nodes", "reached", "deliv", "below", "carried", "missed", "cuts", "orphaned", "lost")]
+
+
+REPORT_LOAD, REPORT_HOPS, REPORT_DOWNSTREAM, REPORT_CUT, REPORT_ALL = 0x1, 0x2, 0x4, 0x8, 0xF
+# the arrays of each section, in ps_report's order
+REPORT_SECTIONS = ((REPORT_LOAD, ("recv", "sent")), (REPORT_HOPS, ("nodes", "reached", "deliv")),
+                   (REPORT_DOWNSTREAM, ("below", "carried")), (REPORT_CUT, ("missed", "cuts", "orphaned", "lost")))
+
 DIST_F_COPY = 0x1  # loopback: copy the records into the receive buffer (the RCCL data path)
 DIST_F_INPLACE = 0x2  # loopback: ghost-fed nodes read the owner's rows in place (no records)
 XCHG_NONE, XCHG_ZERO_COPY, XCHG_COPY, XCHG_IN_PLACE = 0, 1, 2, 3  # ps_stats.xchg_path
@@ -184,6 +195,9 @@ PROTOTYPES = [
     ("ps_peer_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
     ("ps_cut_track", C.c_int, [_P, _u32p, C.c_size_t]),
     ("ps_cut_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_peer_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
+    ("ps_report_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32]),
+    ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -872,6 +886,54 @@ class Engine:
         nw, nsk = C.c_uint64(), C.c_uint64()
         self._check(self._L.ps_cut_take(self._h, *(_p(a, C.c_uint64) for a in out), C.byref(nw), C.byref(nsk)))
         return out[0], out[1], out[2], out[3], nw.value, nsk.value
+
+    def _report_arrays(self, n_topics: int, what: int) -> tuple[dict, Report]:
+        """The selected sections' arrays (hop arrays [n_topics, MAX_ROUNDS],
+        the others [n_peers]) and the ps_report that points at them."""
+        arrays, rep = {}, Report()
+        for sec, names in REPORT_SECTIONS:
+            if not what & sec:
+                continue
+            for k in names:
+                shape = (n_topics, MAX_ROUNDS) if sec == REPORT_HOPS else (self.n_peers,)
+                arrays[k] = np.zeros(shape, dtype=np.uint64)
+                setattr(rep, k, _p(arrays[k], C.c_uint64))
+        return arrays, rep
+
+    def peer_report(self, topics, what: int = REPORT_ALL) -> dict:
+        """The last window's load, hops, downstream and cut answers over the
+        named distinct topics from one pass (ps_peer_report): a dict of the
+        arrays of the sections selected in `what` (REPORT_*), each what that
+        section's own call returns (peer_load, topic_hops, peer_downstream,
+        peer_cut)."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        arrays, rep = self._report_arrays(t.size, what)
+        self._check(self._L.ps_peer_report(self._h, _p(t, C.c_uint32), t.size, what, C.byref(rep), C.sizeof(Report)))
+        return arrays
+
+    def report_track(self, topics, what: int = REPORT_ALL):
+        """Registers standing topics and sections (ps_report_track): from now on
+        every window of every run adds the selected sections over them into
+        totals on the device (report_take), one pass a window.  No topic clears
+        the tracking; setting or clearing zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_report_track(self._h, _p(t, C.c_uint32), t.size, what))
+        self._report = (int(t.size), int(what)) if t.size else None
+
+    def report_take(self) -> tuple[dict, int, int]:
+        """The totals since the last take or track call (ps_report_take):
+        (dict of the tracked sections' arrays, n_windows, n_skipped); n_skipped
+        counts the (topic, window) pairs left out of the tree sections because
+        the topic was a mesh there.  The totals and both counts start again at 0."""
+        n, what = getattr(self, "_report", None) or (0, REPORT_ALL)
+        arrays, rep = self._report_arrays(n, what)
+        nw, nsk = C.c_uint64(), C.c_uint64()
+        self._check(self._L.ps_report_take(self._h, C.byref(rep), C.sizeof(Report), C.byref(nw), C.byref(nsk)))
+        return arrays, nw.value, nsk.value
 
     def seen_digest(self) -> int:
         d = C.c_uint64()

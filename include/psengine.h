@@ -788,6 +788,65 @@ int ps_cut_track(ps_engine* e, const uint32_t* topic, size_t n);
 int ps_cut_take(ps_engine* e, uint64_t* missed_out, uint64_t* cuts_out,
                 uint64_t* orphaned_out, uint64_t* lost_out,     /* [n_peers], nullable */
                 uint64_t* n_windows_out, uint64_t* n_skipped_out);
+
+/* The four answers above from one pass: per-peer load, deliveries by hop, the
+ * audience behind each peer and the losses blamed on their cut points, for an
+ * operator who wants all of them every window (one rank).
+ * `what` selects sections (PS_REPORT_*); a section's arrays are defined by the
+ * comment of the call named beside it below, and this is the defining
+ * property: on the same engine, the same window and the same distinct topics,
+ * every array of a selected section is bit for bit what that call writes.  The
+ * report runs one classify pass, one per-node kernel and one bottom-up sweep
+ * where the four calls run four, four and two.
+ *   ps_report is filled by the caller: eleven output pointers.  A pointer of
+ * a section that is not selected is not touched; a NULL pointer inside a
+ * selected section is skipped.  out_size is sizeof(ps_report) as the caller
+ * compiled it (the struct is not among those ps_abi_check covers): a mismatch
+ * is PS_E_INVAL.
+ *   ps_peer_report answers for the last window of the last run, blocking, with
+ * ps_peer_load's window, stream-ordering and twin-join rules.  PS_E_INVAL for
+ * a NULL engine or out, a wrong out_size, what == 0 or bits outside
+ * PS_REPORT_ALL, n > 0 without topic, a topic named twice, or a selected
+ * section whose pointers are all NULL; PS_E_RANGE, nothing written, for a
+ * topic out of range; PS_E_NOTREADY before any run; PS_E_STATE, nothing
+ * written, on a multi-rank engine, and -- when what selects any section other
+ * than PS_REPORT_LOAD -- when a named topic is a mesh in that window's node
+ * space or was set anew over another kind since the window.  what ==
+ * PS_REPORT_LOAD answers meshes, as ps_peer_load does.  n == 0 is valid: the
+ * peer-space arrays read zero and the hop arrays are not written.
+ *   ps_report_track / ps_report_take follow ps_cut_track / ps_cut_take rule
+ * for rule, independent of both sinks and of the four trackers above: all may
+ * be set at once.  ps_report_track returns PS_E_STATE for a topic whose child
+ * lists make a mesh unless what == PS_REPORT_LOAD.  While it is set, every
+ * window of every ps_run / ps_run_async that runs something enqueues the one
+ * pass behind itself -- the window is neither planned nor launched
+ * differently -- into totals on the device: peer space for the eight per-peer
+ * arrays, [n][PS_MAX_ROUNDS] by request position for the three hop arrays.  A
+ * tracked topic that is a mesh in a window's node space adds its load section
+ * if that is selected and nothing to the others, and is counted once in
+ * n_skipped for that (topic, window) when a section other than load is
+ * selected.  Per section the totals are what that section's own tracker would
+ * have accumulated.  ps_report_take copies the selected sections' totals,
+ * zeroes them in front of whatever runs next and returns and resets the two
+ * counts; PS_E_INVAL also for a NULL out or a wrong out_size. */
+#define PS_REPORT_LOAD       0x1u   /* recv, sent                        (ps_peer_load)       */
+#define PS_REPORT_HOPS       0x2u   /* nodes, reached, deliv             (ps_topic_hops)      */
+#define PS_REPORT_DOWNSTREAM 0x4u   /* below, carried                    (ps_peer_downstream) */
+#define PS_REPORT_CUT        0x8u   /* missed, cuts, orphaned, lost      (ps_peer_cut)        */
+#define PS_REPORT_ALL        0xFu
+
+typedef struct ps_report {          /* caller-filled: eleven nullable output pointers */
+  uint64_t *recv, *sent;                       /* [n_peers]                          */
+  uint64_t *nodes, *reached, *deliv;           /* [n * PS_MAX_ROUNDS], row i = topic[i] */
+  uint64_t *below, *carried;                   /* [n_peers]                          */
+  uint64_t *missed, *cuts, *orphaned, *lost;   /* [n_peers]                          */
+} ps_report;
+
+int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
+                   const ps_report* out, size_t out_size);
+int ps_report_track(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what);
+int ps_report_take(ps_engine* e, const ps_report* out, size_t out_size,
+                   uint64_t* n_windows_out, uint64_t* n_skipped_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

@@ -124,6 +124,18 @@ then the pipelined step plain, with cuts tracked (ps_cut_track, one ps_cut_take
 per loop) and beside load, hop and downstream tracking, the three alternating
 in one process, the totals against steps x the blocking answer.  Writes
 DIR/cut_bench.json.
+
+--report: the four answers from one pass (ps_peer_report, all sections) over
+every topic after one step under --cut's live mask, --reps repetitions
+alternating in one process with the sequence ps_peer_load + ps_topic_hops +
+ps_peer_downstream + ps_peer_cut: the device phases of each call
+(PSAMD_DRAIN_TIMING) and the walls, the answers compared array for array; then
+the pipelined step plain, with the report tracked (ps_report_track, all
+sections, one ps_report_take per loop) and with the four trackers together,
+the three alternating in one process, with the overlapped windows of each, the
+totals against steps x the blocking answer.  Writes DIR/report_bench.json.
+--report-once: one step and one ps_peer_report, nothing else (for a kernel
+trace of one pass).
 """
 from __future__ import annotations
 
@@ -1574,6 +1586,156 @@ def cut_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+REPORT_CALLS = (("peer_load", "peer_load", ("recv", "sent")), ("topic_hops", "topic_hops", ("nodes", "reached", "deliv")),
+                ("peer_downstream", "peer_downstream", ("below", "carried")),
+                ("peer_cut", "peer_cut", ("missed", "cuts", "orphaned", "lost")))
+
+
+def four_calls(eng, topics):
+    out = {}
+    for _, method, names in REPORT_CALLS:
+        out.update(zip(names, getattr(eng, method)(topics)))
+    return out
+
+
+def report_main(a, wl):
+    """--report, --report-once (see the module text).  Writes DIR/report_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": a.steps, "warmup": a.warmup, "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+        WL.build_engine_topics(eng, wl)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    if a.report_once:
+        eng, st = masked_engine({})
+        with eng:
+            got = eng.peer_report(topics)
+            print(json.dumps({"deliveries": int(st.deliveries), "recv_sum": int(got["recv"].sum()),
+                              "cut_points": int(got["cuts"].sum())}))
+        return
+
+    # the device phases, the report and the four calls alternating
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        phases = {"peer_report": []}
+        phases.update({tag: [] for tag, _, _ in REPORT_CALLS})
+        for _ in range(a.reps + 1):  # (the first calls build the window's tables and allocate)
+            with StderrCapture() as cap:
+                got = eng.peer_report(topics)
+            row = phase_line(cap.text, "peer_report")
+            for k in ("strips", "nodes", "partials", "work", "launches"):
+                m = re.search(rf"\b{k} (\d+)", cap.text)
+                if m:
+                    row[k] = int(m.group(1))
+            phases["peer_report"].append(row)
+            for tag, method, names in REPORT_CALLS:
+                with StderrCapture() as cap:
+                    want = getattr(eng, method)(topics)
+                phases[tag].append(phase_line(cap.text, tag))
+                for k, w in zip(names, want):
+                    assert np.array_equal(got[k], w), f"ps_peer_report {k} differs from ps_{tag}"
+        res["phases"] = {k: v[1:] for k, v in phases.items()}
+
+        def device_ms(rows):
+            return float(np.median([sum(v for k, v in r.items() if k.endswith("_ms") and k != "host_strips_ms") for r in rows]))
+
+        res["report_device_ms"] = device_ms(res["phases"]["peer_report"])
+        res["four_calls_device_ms"] = float(sum(device_ms(res["phases"][tag]) for tag, _, _ in REPORT_CALLS))
+        res.update(deliveries=int(st.deliveries), recv_sum=int(got["recv"].sum()), cut_points=int(got["cuts"].sum()),
+                   lost_sum=int(got["lost"].sum()), missed_sum=int(got["missed"].sum()))
+        assert res["recv_sum"] == res["deliveries"] and res["lost_sum"] == res["missed_sum"] and res["cut_points"] > 0
+    # the walls, untimed
+    eng, _ = masked_engine({})
+    with eng:
+        walls = {"report": [], "four_calls": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.peer_report(topics)
+            walls["report"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            blocking = four_calls(eng, topics)
+            walls["four_calls"].append(1e3 * (time.perf_counter() - t0))
+            for k in got:
+                assert np.array_equal(got[k], blocking[k]), k
+    res["report_wall_ms"], res["four_calls_wall_ms"] = walls["report"][1:], walls["four_calls"][1:]
+    res["answers_agree"] = True
+    res["four_calls_over_report_wall"] = float(np.median(res["four_calls_wall_ms"]) / np.median(res["report_wall_ms"]))
+
+    # tracking in the pipelined loop: plain, the report, the four trackers
+    eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+    WL.build_engine_topics(eng, wl)
+    eng.set_live(live)
+    none = np.zeros(0, dtype=np.uint32)
+    modes = ("plain", "report", "four_trackers")
+    trackers = (eng.load_track, eng.hops_track, eng.downstream_track, eng.cut_track)
+    takes = (("load", eng.load_take, ("recv", "sent")), ("hops", eng.hops_take, ("nodes", "reached", "deliv")),
+             ("downstream", eng.downstream_take, ("below", "carried")), ("cut", eng.cut_take, ("missed", "cuts", "orphaned", "lost")))
+
+    def timed(mode, steps):
+        eng.report_track(topics if mode == "report" else none)
+        for track in trackers:
+            track(topics if mode == "four_trackers" else none)
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        loop_plain(eng, wl, steps)
+        totals, windows = {}, []
+        if mode == "report":
+            totals, nw, nsk = eng.report_take()
+            windows = [nw]
+            assert nsk == 0
+        elif mode == "four_trackers":
+            for _, take, names in takes:
+                r = take()
+                totals.update(zip(names, r))
+                windows.append(r[len(names)])
+        return 1e3 * (time.perf_counter() - t0) / steps, eng.overlapped_windows() - o0, totals, windows
+
+    with eng:
+        for mode in modes:
+            timed(mode, a.warmup)
+        ms = {k: [] for k in modes}
+        over = {k: [] for k in modes}
+        for _ in range(a.reps):
+            for mode in modes:
+                t, o, totals, windows = timed(mode, a.steps)
+                ms[mode].append(t)
+                over[mode].append(int(o))
+                assert all(w == a.steps for w in windows), (mode, windows)
+                for k, g in totals.items():
+                    assert np.array_equal(g, blocking[k] * np.uint64(a.steps)), f"{mode}: tracked {k} totals differ"
+                assert mode == "plain" or o > 0, f"{mode}: no overlapped window"
+        eng.report_track(none)
+        for track in trackers:
+            track(none)
+    four = ms["four_trackers"]
+    res.update(ms_per_step=ms, overlapped_windows=over, tracked_totals_agree=True,
+               report_minus_plain_ms=float(np.median(ms["report"]) - np.median(ms["plain"])),
+               four_trackers_minus_plain_ms=float(np.median(four) - np.median(ms["plain"])),
+               four_trackers_spread_ms=float(max(four) - min(four)),
+               four_trackers_minus_report_ms=float(np.median(four) - np.median(ms["report"])))
+    res["report_below_four_trackers_by_more_than_their_spread"] = bool(
+        res["four_trackers_minus_report_ms"] > res["four_trackers_spread_ms"])
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "report_bench.json"), "w") as f:  # (a line per key, a line per phase row)
+            rows = [f" {json.dumps(k)}: {json.dumps(v)}" for k, v in res.items() if k != "phases"]
+            rows.append(' "phases": {\n' + ",\n".join(
+                f"  {json.dumps(k)}: [\n   " + ",\n   ".join(json.dumps(r) for r in v) + "]" for k, v in res["phases"].items()) + "}")
+            f.write("{\n" + ",\n".join(rows) + "\n}\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -1721,8 +1883,13 @@ def main():
                     help="ps_peer_downstream against the host derivation; tracking in the pipelined loop")
     ap.add_argument("--cut", action="store_true",
                     help="ps_peer_cut against ps_peer_downstream and the host derivation; tracking in the pipelined loop")
+    ap.add_argument("--report", action="store_true",
+                    help="ps_peer_report against the four calls in sequence; report tracking against the four trackers")
+    ap.add_argument("--report-once", action="store_true", help="one step and one ps_peer_report (for a kernel trace)")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
+    if a.report or a.report_once:
+        return report_main(a, wl)
     if a.cut:
         return cut_main(a, wl)
     if a.downstream:
