@@ -56,6 +56,16 @@
 //   k_report_level        the bottom-up pass once: k_cut_level's walk with
 //                         k_downstream_level's two sums
 //   k_report_top          the narrow levels under a root in one block
+// and, for ps_dist_report (§5.5n), a rank's share of load, hops and downstream on
+// a sharded engine's numbering (one rank's too):
+//   k_dist_nodes          k_report_nodes where node 0 need not be a root and a
+//                         level may be empty; the roots' share of `sent`
+//   k_dist_hops_sum       k_audience_hops_sum over such a level table
+//   k_dist_sweep_level    one launch per level, bottom-up: a node's accumulator
+//                         into its peer's two sums, and pushed to its parent --
+//                         the parent's accumulator, or a record for its owner
+//   k_dist_apply          behind a level's exchange: the records received into
+//                         the parents' accumulators
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -1098,6 +1108,248 @@ __global__ __launch_bounds__(kDownBlock) void k_report_top(CutArgs g) {
   }
 }
 
+// ---- a rank's share of the report (ps_dist_report) -------------------------------
+
+// k_report_nodes for a rank's own numbering (kernels.hpp, DistArgs): the same k
+// per node and the same two load adds; a partial pair per (strip, level) in
+// k_audience_hops' slots -- part0 + (s - strip0) + (d - 1): levels a strip
+// does not meet, empty ones among them, leave gaps and no two pairs share a
+// slot --; the k word at the node's own place, none for a root.  The waves
+// behind the strips' take an entry each and add its root's share of `sent`: a
+// root's owner may own no other node of the topic, and then no strip of it.
+template <bool kLoad, bool kHops, bool kWords>
+__global__ __launch_bounds__(kAudBlock) void k_dist_nodes(DrainArgs a, DistArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  unsigned long long* const sent = reinterpret_cast<unsigned long long*>(g.sent);
+  if (s >= g.n_strips) {
+    if (!kLoad || s - g.n_strips >= g.n || lane != 0) return;
+    const DistEntry E = g.entries[s - g.n_strips];
+    if (E.root == kLoadNoRoot || !E.c_t) return;
+    const uint32_t deg = g.row_ptr[E.root + 1] - g.row_ptr[E.root];
+    if (deg) atomicAdd(sent + g.node_peer[E.root], static_cast<unsigned long long>(E.c_t) * deg);
+    return;
+  }
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const DistEntry E = g.entries[lo - 1];
+  const bool tree = E.tree != 0;  // (wave-uniform, as everything read from E and S)
+  if (!kLoad && !tree) return;
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  const bool all_full = !g.count_rows && g.n_exc[s] == 0;
+  const uint32_t end = S.u0 + S.n;
+  unsigned long long* const recv = reinterpret_cast<unsigned long long*>(g.recv);
+  uint32_t* const kout = kWords ? g.k + E.n0 : nullptr;
+  // the level of the strip's first node: the last one that starts at or before
+  // it (an empty level starts where the next one does)
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  uint32_t d = 0;
+  if (kHops && tree) {
+    lo = 0, hi = E.depth + 1;
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (lv[mid] <= S.u0) lo = mid + 1;
+      else hi = mid;
+    }
+    d = lo ? lo - 1 : 0;
+  }
+  for (uint32_t u = S.u0; u < end;) {
+    bool hop = false;
+    uint32_t ue = end;
+    if (kHops && tree) {
+      while (d <= E.depth && lv[d + 1] <= u) ++d;
+      hop = d >= 1 && d <= E.depth;  // (a strip holds no root)
+      if (hop) ue = min(end, lv[d + 1]);
+    }
+    uint32_t reached = 0;  // (wave-uniform)
+    uint64_t deliv = 0;
+    if (all_full && !kLoad && !kWords) {
+      // every node holds c_t: the sums follow from the bounds
+      reached = ue - u;
+      deliv = static_cast<uint64_t>(reached) * E.c_t;
+    } else {
+      for (uint32_t i0 = u; i0 < ue; i0 += kWave) {
+        const uint32_t i = min(i0 + lane, ue - 1);
+        const bool in = i0 + lane < ue;
+        uint32_t peer = 0, deg = 0;
+        if (kLoad) {
+          peer = g.node_peer[S.nbase + i];
+          deg = g.row_ptr[S.nbase + i + 1] - g.row_ptr[S.nbase + i];
+        }
+        uint32_t k = in ? E.c_t : 0u;
+        if (!all_full) {
+          const uint32_t v = vin[i - S.u0];
+          const bool full = !gather && v == kDrainRowAny;
+          const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+          k = in && full && !count ? E.c_t : 0u;
+          uint64_t todo = __ballot(count);
+          while (todo) {
+            const uint32_t j = __builtin_ctzll(todo);
+            todo &= todo - 1;
+            const uint32_t c = load_count_row(a, T, i0 + j, lane);
+            if (lane == j) k = c;
+          }
+        }
+        if (kLoad && k) {
+          atomicAdd(recv + peer, static_cast<unsigned long long>(k));
+          if (deg) atomicAdd(sent + peer, static_cast<unsigned long long>(k) * deg);
+        }
+        if (kWords && in && tree && i < E.nn) kout[i] = k;
+        if (kHops && hop) {
+          reached += __popcll(__ballot(k != 0));
+          deliv += wave_sum_u32(k);
+        }
+      }
+    }
+    if (kHops && hop && lane == 0) {
+      const uint32_t slot = min(E.part0 + (s - E.strip0) + (d - 1), g.n_parts - 1);
+      g.part_reached[slot] = reached;
+      g.part_deliv[slot] = deliv;
+    }
+    u = ue;
+  }
+}
+
+// k_audience_hops_sum for a rank's own level table: one block per (entry,
+// column) adds the partials of the strips that meet the column's levels -- a
+// level's first to its last node; an empty level has none -- and the level's
+// size into the entry's row: one writer per word, plain loads and stores.
+__global__ __launch_bounds__(kHopsSumBlock) void k_dist_hops_sum(DistArgs g) {
+  __shared__ uint64_t part[2][kHopsSumBlock / kWave];
+  const uint32_t h = blockIdx.y + 1;
+  const DistEntry E = g.entries[blockIdx.x];
+  if (!E.tree || !E.c_t || h > min(E.depth, kHopsCols - 1) || g.entries[blockIdx.x + 1].strip0 == E.strip0) return;
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  const uint32_t d_hi = h == kHopsCols - 1 ? E.depth : h;
+  const uint32_t u0 = lv[1];  // (the entry's strips start at its first node that is no root)
+  uint64_t r = 0, dl = 0;
+  for (uint32_t d = h; d <= d_hi; ++d) {
+    if (lv[d + 1] <= lv[d]) continue;  // (block-uniform)
+    const uint32_t sa = (lv[d] - u0) / E.per, sb = (lv[d + 1] - 1 - u0) / E.per;  // (relative to strip0)
+    const uint32_t p0 = E.part0 + (d - 1);
+    for (uint32_t s0 = sa + threadIdx.x; s0 <= sb; s0 += kHopsSumBlock) {
+      const uint32_t slot = min(p0 + s0, g.n_parts - 1);
+      r += g.part_reached[slot];
+      dl += g.part_deliv[slot];
+    }
+  }
+  r = dev::wave_sum_u64(r);
+  dl = dev::wave_sum_u64(dl);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    part[0][threadIdx.x / kWave] = r;
+    part[1][threadIdx.x / kWave] = dl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    r = dl = 0;
+    for (uint32_t w = 0; w < kHopsSumBlock / kWave; ++w) {
+      r += part[0][w];
+      dl += part[1][w];
+    }
+    const size_t at = static_cast<size_t>(blockIdx.x) * kHopsCols + h;
+    g.nodes[at] += lv[d_hi + 1] - lv[h];
+    g.reached[at] += r;
+    g.deliv[at] += dl;
+  }
+}
+
+// One add of (vn, vk) into the pair of words at (pn, pk), the active lanes of
+// a wave a push each.  Where every active lane of the wave pushes to one pair
+// -- siblings of one wide parent lie side by side -- the wave sums first and
+// one lane adds.
+__device__ __forceinline__ void dist_push(unsigned long long* pn, unsigned long long* pk, uint64_t vn, uint64_t vk,
+                                          bool on) {
+  const uint64_t act = __ballot(on);
+  if (!act) return;
+  const uint32_t first = __builtin_ctzll(act);
+  const uint64_t key = reinterpret_cast<uint64_t>(pn);
+  const uint64_t key0 = static_cast<uint64_t>(__shfl(static_cast<uint32_t>(key >> 32), static_cast<int>(first), 64)) << 32 |
+                        __shfl(static_cast<uint32_t>(key), static_cast<int>(first), 64);
+  if (__popcll(act) > 1 && __ballot(on && key != key0) == 0) {
+    const uint64_t sn = dev::wave_sum_u64(on ? vn : 0ull), sk = dev::wave_sum_u64(on ? vk : 0ull);
+    if ((threadIdx.x & (kWave - 1)) == first) {
+      if (sn) atomicAdd(pn, static_cast<unsigned long long>(sn));
+      if (sk) atomicAdd(pk, static_cast<unsigned long long>(sk));
+    }
+    return;
+  }
+  if (on) {
+    if (vn) atomicAdd(pn, static_cast<unsigned long long>(vn));
+    if (vk) atomicAdd(pk, static_cast<unsigned long long>(vk));
+  }
+}
+
+// One block per work item of this launch, a thread per node of level `level`
+// (kernels.hpp, DistArgs).  What the node's accumulator holds was added by the
+// launches of the levels below, on this rank and -- through the exchanges and
+// k_dist_apply between them -- on the others: stream order and the
+// transport's are the only order.
+__global__ __launch_bounds__(kDownBlock) void k_dist_sweep_level(DistArgs g, uint32_t level, uint32_t w0) {
+  const DistWork W = g.work[w0 + blockIdx.x];
+  const DistEntry E = g.entries[W.entry];
+  const uint32_t* __restrict__ lv = g.levels + E.lvl0;
+  if (!E.tree || !E.c_t || level > E.depth || !E.nn) return;  // (block-uniform)
+  const uint32_t lo = max(W.lo, lv[level]), hi = min(min(W.hi, lv[level + 1]), E.nn);
+  const uint32_t u = lo + threadIdx.x;
+  const bool in = u < hi;
+  const uint32_t uc = in ? u : E.nn - 1;  // (clamped into the entry's words)
+  unsigned long long* const acc_n = reinterpret_cast<unsigned long long*>(g.acc_n) + E.n0;
+  unsigned long long* const acc_k = reinterpret_cast<unsigned long long*>(g.acc_k) + E.n0;
+  unsigned long long* const below = reinterpret_cast<unsigned long long*>(g.below);
+  unsigned long long* const carried = reinterpret_cast<unsigned long long*>(g.carried);
+  const uint64_t an = in ? acc_n[uc] : 0ull, ak = in ? acc_k[uc] : 0ull;
+  if (in) {
+    const uint32_t peer = g.node_peer[E.nbase + uc];
+    if (an) atomicAdd(below + peer, static_cast<unsigned long long>(an));
+    if (ak) atomicAdd(carried + peer, static_cast<unsigned long long>(ak));
+  }
+  if (level == 0) return;  // (block-uniform: a root pushes nothing)
+  const uint64_t wn = 1 + an, wk = g.k[E.n0 + uc] + ak;
+  const uint32_t par = g.node_parent[E.nbase + uc];
+  unsigned long long *pn = nullptr, *pk = nullptr;
+  bool on = false;
+  if (in && par != kNoneNode) {
+    const uint32_t p = min(par - E.nbase, E.nn - 1);  // (par >= nbase: the parent is a node of this topic)
+    on = par >= E.nbase;
+    pn = acc_n + p;
+    pk = acc_k + p;
+  } else if (in && g.gslot) {
+    const uint32_t gs = g.gslot[E.nbase + uc];
+    const uint32_t owner = gs >> kRemoteRankShift;
+    if (gs != kNoneNode && owner < g.world && g.n_send) {
+      const uint32_t rec = min(g.send_base[E.sb0 + level * g.world + owner] + (gs & kRemoteIdMask), g.n_send - 1);
+      on = true;
+      pn = reinterpret_cast<unsigned long long*>(&g.send[rec].n);
+      pk = reinterpret_cast<unsigned long long*>(&g.send[rec].k);
+    }
+  }
+  dist_push(pn, pk, wn, wk, on);
+}
+
+// One block per apply item, a thread per received record: into the
+// accumulator of the parent the record belongs to.  Two ranks may hold
+// children of one parent: atomics here too.
+__global__ __launch_bounds__(kDownBlock) void k_dist_apply(DistArgs g, uint32_t a0) {
+  const DistApply A = g.apply[a0 + blockIdx.x];
+  const DistEntry E = g.entries[A.entry];
+  if (threadIdx.x >= A.n || !E.nn) return;
+  const uint32_t r = min(A.rec0 + threadIdx.x, g.n_recv - 1), pl = min(A.pl0 + threadIdx.x, g.n_plist - 1);
+  const DistRec R = g.rcv[r];
+  const uint32_t par = g.plist[pl];
+  if (par < E.nbase) return;
+  const uint32_t p = min(par - E.nbase, E.nn - 1);
+  if (R.n) atomicAdd(reinterpret_cast<unsigned long long*>(g.acc_n) + E.n0 + p, static_cast<unsigned long long>(R.n));
+  if (R.k) atomicAdd(reinterpret_cast<unsigned long long*>(g.acc_k) + E.n0 + p, static_cast<unsigned long long>(R.k));
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -1703,6 +1955,41 @@ hipError_t launch_report_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipSt
 hipError_t launch_report_top(const CutArgs& g, hipStream_t s) {
   if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_report_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+// the sections of g.what as k_dist_nodes' template; a wave per strip and one
+// per entry behind them (the roots' share of `sent`) where load is selected
+hipError_t launch_dist_nodes(const DrainArgs& a, const DistArgs& g, hipStream_t s) {
+  if (g.what == 0 || (g.what & ~(kReportLoad | kReportHops | kReportDown))) return hipErrorInvalidValue;
+  const uint32_t waves = g.n_strips + (g.what & kReportLoad ? g.n : 0u);
+  if (waves == 0) return hipSuccess;
+  using Kernel = void (*)(DrainArgs, DistArgs);
+  static const Kernel table[2][2][2] = {
+      {{nullptr, k_dist_nodes<false, false, true>}, {k_dist_nodes<false, true, false>, k_dist_nodes<false, true, true>}},
+      {{k_dist_nodes<true, false, false>, k_dist_nodes<true, false, true>},
+       {k_dist_nodes<true, true, false>, k_dist_nodes<true, true, true>}}};
+  const Kernel k = table[g.what & kReportLoad ? 1 : 0][g.what & kReportHops ? 1 : 0][g.what & kReportDown ? 1 : 0];
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k, dim3((waves + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_hops_sum(const DistArgs& g, uint32_t max_cols, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0 || max_cols == 0 || g.n_parts == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_hops_sum, dim3(g.n, max_cols), dim3(kHopsSumBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_sweep_level(const DistArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_sweep_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, level, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_apply(const DistArgs& g, uint32_t a0, uint32_t a1, hipStream_t s) {
+  if (a1 <= a0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_apply, dim3(a1 - a0), dim3(kDownBlock), 0, s, g, a0);
   return hipGetLastError();
 }
 

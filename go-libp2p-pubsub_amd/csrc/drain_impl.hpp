@@ -35,6 +35,12 @@
 //                     pass's and the downstream pass's plans (hops_plan,
 //                     hops_entries, down_plan .. down_entries below), with
 //                     buffers of their own
+//   drain_dist.cpp    ps_dist_report (§5.5n): a rank's share of the load, hop and
+//                     downstream sections on an engine of any rank count --
+//                     the audience pass's strips and classify, kernels of its
+//                     own for a sharded rank's numbering, and a bottom-up sweep
+//                     that crosses ranks through Transport::exchange; blocking
+//                     only, with buffers of its own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:

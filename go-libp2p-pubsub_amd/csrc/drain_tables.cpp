@@ -525,6 +525,7 @@ void drain_destroy(ps_engine* e) {
   for (auto& f : D.report.fence)
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
+  if (D.dist.h_out) (void)hipHostFree(D.dist.h_out);
 }
 
 }  // namespace psamd

@@ -957,7 +957,35 @@ struct ps_engine {
       PassFence fence[2];
       hipEvent_t ev_take = nullptr;
     } report;
+
+    // ps_dist_report (host code: drain_dist.cpp): a rank's
+    // share of the load, hop and downstream sections -- k_dist_nodes behind
+    // one k_audience_classify, k_dist_hops_sum, then k_dist_sweep_level per level with the
+    // transport's exchange and k_dist_apply where a level's edges cross ranks.
+    // Blocking only; buffers of its own.
+    struct Dist {
+      // the input block (entries | levels | send bases | work | apply | strips),
+      // classify's verdicts and counts, the hop partials, the per-node words
+      // k | acc_n | acc_k, the sweep's send and receive records, the cleared
+      // output block
+      psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_part_r, d_part_d, d_scratch, d_send, d_recv, d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+    } dist;
   } drain;
+
+  // The slot tables of ps_dist_report's cross-rank sweep (graph.cpp
+  // build_dist_slots), built on the first report after a node-space build
+  struct DistSlots {
+    uint64_t epoch = ~0ull;       // graph_epoch the tables stand for
+    std::vector<uint32_t> gslot;  // per node: a remote parent's owner << 27 | its record index there; kNone: none
+    std::vector<uint32_t> plist;  // per ghost record this rank receives as the parents' owner: the parent's node
+    // per topic, by (children's level L, children's rank b): the first word
+    // of plist, TopicHost::gcnt[(L * world + rank) * world + b] of them
+    std::vector<std::vector<uint32_t>> pl_off;
+    psamd::DevBuf d_gslot, d_plist;
+  } dist_slots;
 
   // per-window uploads (topic table, seeds, reduce descriptors) go through
   // pinned staging: a copy from pageable memory blocks the host until the
@@ -1077,6 +1105,7 @@ void partition_topic(const std::vector<uint32_t>& order, const std::vector<uint3
                      const std::vector<uint32_t>& level, int32_t world, uint32_t part, uint32_t split_depth,
                      std::vector<int32_t>& owner);
 int build_graph(ps_engine* e);  // host node space (any rank count); no device calls
+int build_dist_slots(ps_engine* e, ps_engine::DistSlots* S);  // ps_dist_report's slot tables (host only)
 void build_flags(ps_engine* e);
 int ensure_mirrors(ps_engine* e);
 int upload_graph(ps_engine* e);

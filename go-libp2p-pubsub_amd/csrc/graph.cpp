@@ -357,6 +357,90 @@ int build_graph(ps_engine* e) {
   return PS_OK;
 }
 
+// The slot tables of ps_dist_report's cross-rank sweep (drain_dist.cpp;
+// DESIGN.md §5.5n), from build_graph's walk over the topics as they stand --
+// the caller makes sure no topic changed since the node space was built.  A
+// ghost-fed node's record at its parent's owner a is the one build_graph
+// numbers kk[b] = gc[a * world + b]++, whichever data path the flood takes
+// (the in-place rows address the parent's row instead, so ghost_ref does not
+// always hold it).  Built on the first report after a node-space build, never
+// by the build itself: ps_run does not pay for it.
+int build_dist_slots(ps_engine* e, ps_engine::DistSlots* S) {
+  const uint32_t n = e->cfg.n_peers;
+  const int32_t W = std::max(e->world, 1), me = e->rank;
+  const uint32_t ntop = static_cast<uint32_t>(e->topics.size());
+  S->gslot.clear();
+  S->plist.clear();
+  S->pl_off.assign(ntop, {});
+  std::vector<uint32_t> local(n, kNone), loc, gs_of, mine, kk(W), gc;
+  std::vector<std::vector<uint32_t>> cur(W), nxt_local(W), nxt_ghost(static_cast<size_t>(W) * W), pl(W);
+  TopicBfs B;
+  for (uint32_t t = 0; t < ntop; ++t) {
+    const TopicHost& T = e->topics[t];
+    if (!T.exists) continue;
+    if (const int rc = topic_bfs(e, T, local, B)) return rc;
+    const uint32_t N = static_cast<uint32_t>(B.order.size()), depth = B.level.back();
+    const auto& owner = B.owner;
+    bool same = depth == T.depth && T.gcnt.size() == (W > 1 ? static_cast<size_t>(depth + 2) * W * W : 0);
+    loc.assign(N, 0);
+    gs_of.assign(N, kNone);
+    mine.clear();
+    std::vector<uint32_t> next_id(W, 0);
+    for (auto& v : cur) v.clear();
+    cur[owner[0]].push_back(0);
+    loc[0] = next_id[owner[0]]++;
+    if (owner[0] == me) mine.push_back(0);
+    S->pl_off[t].assign(static_cast<size_t>(depth + 2) * W, static_cast<uint32_t>(S->plist.size()));
+    for (uint32_t d = 0; d < depth && same; ++d) {
+      for (auto& v : nxt_local) v.clear();
+      for (auto& v : nxt_ghost) v.clear();
+      for (auto& v : pl) v.clear();
+      gc.assign(static_cast<size_t>(W) * W, 0);
+      for (int32_t a = 0; a < W; ++a)
+        for (uint32_t u : cur[a]) {
+          const uint32_t p = B.order[u];
+          uint32_t mask = 0;
+          for (uint32_t k = B.rp[p]; k < B.rp[p + 1]; ++k) {
+            const uint32_t v = local[B.cl[k]];
+            if (B.bfs_parent[v] != u) continue;
+            const int32_t b = owner[v];
+            if (b == a) {
+              nxt_local[a].push_back(v);
+              continue;
+            }
+            if (!(mask >> b & 1u)) {
+              mask |= 1u << b;
+              kk[b] = gc[a * W + b]++;
+              if (a == me) pl[b].push_back(T.nbase + loc[u]);
+            }
+            if (b == me) gs_of[v] = static_cast<uint32_t>(a) << kRemoteRankShift | kk[b];
+            nxt_ghost[static_cast<size_t>(b) * W + a].push_back(v);
+          }
+        }
+      for (int32_t r = 0; r < W; ++r) {
+        auto& c = cur[r];
+        c.swap(nxt_local[r]);
+        for (int32_t a = 0; a < W; ++a) {
+          const auto& g = nxt_ghost[static_cast<size_t>(r) * W + a];
+          c.insert(c.end(), g.begin(), g.end());
+        }
+        for (uint32_t v : c) loc[v] = next_id[r]++;
+        if (r == me) mine.insert(mine.end(), c.begin(), c.end());
+      }
+      for (int32_t b = 0; b < W; ++b) {
+        S->pl_off[t][static_cast<size_t>(d + 1) * W + b] = static_cast<uint32_t>(S->plist.size());
+        S->plist.insert(S->plist.end(), pl[b].begin(), pl[b].end());
+      }
+      for (size_t i = 0; W > 1 && i < gc.size(); ++i) same &= gc[i] == T.gcnt[static_cast<size_t>(d + 1) * W * W + i];
+    }
+    for (uint32_t p : B.order) local[p] = kNone;
+    if (!same || mine.size() != T.n_nodes) return e->fail(PS_E_STATE, "a topic changed since the node space was built: run first");
+    for (uint32_t u : mine) S->gslot.push_back(gs_of[u]);
+  }
+  if (S->gslot.size() != e->n_nodes) return e->fail(PS_E_STATE, "the topics changed since the node space was built: run first");
+  return PS_OK;
+}
+
 void build_flags(ps_engine* e) {
   e->node_flags.assign(e->n_nodes, 0);
   for (uint32_t u = 0; u < e->n_nodes; ++u) {

@@ -1091,4 +1091,109 @@ hipError_t launch_report_nodes(const DrainArgs& a, const ReportArgs& g, hipStrea
 hipError_t launch_report_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStream_t s);
 hipError_t launch_report_top(const CutArgs& g, hipStream_t s);
 
+// ---- a rank's share of the report (ps_dist_report) ------------
+// Load, hops and downstream for the nodes one rank owns, on whatever node
+// numbering the window ran on: one rank's BFS order, or a sharded rank's --
+// level by level, a level's locally fed nodes ahead of its ghost-fed ones, a
+// level possibly empty, node 0 the root only on the root's owner.  The entry
+// table follows the request (entry i is topic[i], row i of the hop arrays;
+// entry n closes it); a tree entry carries the rank's own level table as
+// HopsEntry does and its first word n0 of the three per-node arrays k, acc_n
+// and acc_k, which the host clears ahead of the pass.
+//   k_dist_nodes        one wave per strip behind k_audience_classify, a node
+//                       per lane: k once, into recv / sent, into a partial
+//                       pair per (strip, level) in HopsArgs' slots and into
+//                       the k word.  Nothing is written for a root by position:
+//                       a root's words stay as cleared.
+//   k_dist_hops_sum     k_audience_hops_sum over a level table whose levels
+//                       may be empty: one block per (entry, column).
+//   k_dist_sweep_level  one launch per absolute level L, the deepest first,
+//                       level 0 last: node u adds its accumulator (acc_n,
+//                       acc_k) -- what lies strictly below it -- to below /
+//                       carried of its peer and pushes (1 + acc_n, k + acc_k)
+//                       to its parent: into the parent's accumulator where this
+//                       rank owns it (node_parent), else into the record
+//                       send[base[sb0 + L * world + a] + j] of the parent's
+//                       owner a and record index j (gslot[u] = a << 27 | j);
+//                       a root pushes nothing.
+//   k_dist_apply        behind a level's exchange: a received record into the
+//                       accumulator of the parent it names (plist).
+// Stream order and the transport's own ordering are the only order between
+// the launches; every add is a relaxed device-scope 64-bit atomic, a zero add
+// skipped.  Every table-derived index is clamped into its entry's words.
+struct DistEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window
+  uint32_t root;    // the root's node (node space), kLoadNoRoot: none on this rank
+  uint32_t tree;    // 1: a tree topic, the fields below stand; 0: the entry feeds the load section alone
+  uint32_t lvl0;    // the topic's level table in DistArgs::levels: depth + 2 words
+  uint32_t depth;   // its deepest level
+  uint32_t nbase;   // the topic's first node in node space
+  uint32_t nn;      // its nodes on this rank
+  uint32_t n0;      // the entry's first word of k / acc_n / acc_k
+  uint32_t sb0;     // the entry's first word of DistArgs::send_base: (depth + 1) * world words
+  uint32_t per;     // nodes of every strip of the entry but the last (HopsEntry::per)
+  uint32_t part0;   // the entry's first partial slot: it owns strips + depth of them (HopsEntry::part0)
+  uint32_t pad;
+};
+static_assert(sizeof(DistEntry) == 56, "DistEntry is uploaded as laid out here");
+struct DistRec {
+  uint64_t n, k;  // nodes and window messages of the subtrees pushed so far
+};
+struct DistWork {
+  uint32_t entry;
+  uint32_t lo, hi;  // topic-relative nodes of the launch's level, at most kDownBlock
+};
+struct DistApply {
+  uint32_t entry;
+  uint32_t rec0;   // the item's first received record
+  uint32_t pl0;    // ... and its first word of DistArgs::plist
+  uint32_t n;      // records, at most kDownBlock
+};
+struct DistArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const DistEntry* entries;  // [n + 1]
+  uint32_t n;
+  uint32_t what;             // PS_REPORT_* bits within PS_REPORT_DIST
+  uint32_t world;
+  const uint32_t* levels;
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint64_t* n_exc;     // AudArgs::n_exc: 0 = every node of the strip is full
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  const uint32_t* node_peer;
+  const uint32_t* node_parent;
+  const uint32_t* row_ptr;
+  uint64_t* recv;            // [n_peers] each, added into (load)
+  uint64_t* sent;
+  uint32_t* part_reached;    // per (strip, level) slot (hops)
+  uint64_t* part_deliv;
+  uint32_t n_parts;
+  uint64_t* nodes;           // [n][kHopsCols] each, added into (hops)
+  uint64_t* reached;
+  uint64_t* deliv;
+  uint32_t* k;               // per-node words (downstream)
+  uint64_t* acc_n;
+  uint64_t* acc_k;
+  uint64_t* below;           // [n_peers] each, added into (downstream)
+  uint64_t* carried;
+  const DistWork* work;      // launch by launch
+  const uint32_t* gslot;     // per node of the node space: owner << 27 | record index of a remote parent, kNone
+  const uint32_t* send_base; // per (entry, level, owner): the first record of the entry's run in that region
+  DistRec* send;             // the sweep's send records
+  uint32_t n_send;
+  const DistApply* apply;    // exchange by exchange
+  const uint32_t* plist;     // per ghost record this rank receives: the parent's node
+  const DistRec* rcv;        // the sweep's received records
+  uint32_t n_recv, n_plist;
+};
+hipError_t launch_dist_nodes(const DrainArgs& a, const DistArgs& g, hipStream_t s);
+// k_dist_hops_sum over columns 1 .. max_cols (the deepest entry's, kHopsCols - 1 at most)
+hipError_t launch_dist_hops_sum(const DistArgs& g, uint32_t max_cols, hipStream_t s);
+// k_dist_sweep_level over work items [w0, w1): the nodes of level `level`
+hipError_t launch_dist_sweep_level(const DistArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s);
+// k_dist_apply over apply items [a0, a1): one exchange's records
+hipError_t launch_dist_apply(const DistArgs& g, uint32_t a0, uint32_t a1, hipStream_t s);
+
 }  // namespace psamd

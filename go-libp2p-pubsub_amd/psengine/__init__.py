@@ -94,6 +94,7 @@ class Report(C.Structure):
 
 
 REPORT_LOAD, REPORT_HOPS, REPORT_DOWNSTREAM, REPORT_CUT, REPORT_ALL = 0x1, 0x2, 0x4, 0x8, 0xF
+REPORT_DIST = 0x7  # LOAD | HOPS | DOWNSTREAM: the sections ps_dist_report answers
 # the arrays of each section, in ps_report's order
 REPORT_SECTIONS = ((REPORT_LOAD, ("recv", "sent")), (REPORT_HOPS, ("nodes", "reached", "deliv")),
                    (REPORT_DOWNSTREAM, ("below", "carried")), (REPORT_CUT, ("missed", "cuts", "orphaned", "lost")))
@@ -198,6 +199,7 @@ PROTOTYPES = [
     ("ps_peer_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_report_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32]),
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
+    ("ps_dist_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -911,6 +913,20 @@ class Engine:
             raise ValueError("topics must be a 1-d array")
         arrays, rep = self._report_arrays(t.size, what)
         self._check(self._L.ps_peer_report(self._h, _p(t, C.c_uint32), t.size, what, C.byref(rep), C.sizeof(Report)))
+        return arrays
+
+    def dist_report(self, topics, what: int = REPORT_DIST) -> dict:
+        """This rank's share of peer_report's load, hop and downstream sections
+        over the named distinct topics (ps_dist_report), on an engine of any
+        rank count: a dict of the arrays of the sections selected in `what`
+        (within REPORT_DIST).  The ranks' arrays add up to a one-rank engine's
+        peer_report.  With REPORT_DOWNSTREAM on a multi-rank engine the call is
+        collective: every rank makes it, with the same topics and `what`."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        arrays, rep = self._report_arrays(t.size, what)
+        self._check(self._L.ps_dist_report(self._h, _p(t, C.c_uint32), t.size, what, C.byref(rep), C.sizeof(Report)))
         return arrays
 
     def report_track(self, topics, what: int = REPORT_ALL):

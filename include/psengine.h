@@ -847,6 +847,48 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
 int ps_report_track(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what);
 int ps_report_take(ps_engine* e, const ps_report* out, size_t out_size,
                    uint64_t* n_windows_out, uint64_t* n_skipped_out);
+
+/* This rank's share of ps_peer_report's load, hop and downstream sections, on
+ * an engine of any rank count: the analytic read a sharded
+ * engine answers.  The same ps_report struct; only the selected sections'
+ * pointers are touched; the last window of the last run; blocking.
+ *   A rank's share is what the nodes it owns contribute, on the node space the
+ * window ran on.  For every named topic t with c_t > 0 window messages and
+ * every node u of t this rank owns, with peer p and k(u) the window messages
+ * u's row holds (c_t for a full row, 0 for a node the window did not reach):
+ *   load        recv[p] += k(u) for a non-root u; sent[p] += k(u) * deg(u),
+ *               deg counting every child, local or remote, live or not; on the
+ *               root's owner sent[root] += c_t * deg(root);
+ *   hops        for a non-root u at BFS level d, in row i = the topic's place
+ *               in the request, column min(d, PS_MAX_ROUNDS - 1): nodes += 1,
+ *               reached += (k(u) > 0), deliv += k(u);
+ *   downstream  for every owned u, the root included, over its strict
+ *               descendants on whatever rank they live: below[p] += their
+ *               number, carried[p] += the sum of their k.
+ * Summed over the ranks every array is, bit for bit, what ps_peer_report
+ * writes on a one-rank engine for the same trees, live mask, publishes and
+ * request; on a one-rank engine the call equals ps_peer_report itself (it runs
+ * its own kernels, with nothing to exchange).
+ *   With PS_REPORT_DOWNSTREAM selected on a multi-rank engine the call is
+ * COLLECTIVE, as ps_run is: every rank calls it with the same topics in the
+ * same order and the same `what`, after the same run; the sums cross ranks
+ * through the transport's exchange, level by level.  PS_REPORT_LOAD and
+ * PS_REPORT_HOPS alone exchange nothing: any rank may ask alone.
+ *   PS_E_INVAL for a NULL engine or out, a wrong out_size, what == 0 or a bit
+ * outside PS_REPORT_DIST (PS_REPORT_CUT is not answered across ranks), n > 0
+ * without topic, a topic named twice, or a selected section whose pointers are
+ * all NULL; PS_E_RANGE, nothing written, for a topic out of range;
+ * PS_E_NOTREADY before any run; PS_E_STATE with a run in flight on a
+ * multi-rank engine, for a topic set anew since the window, and -- unless what
+ * == PS_REPORT_LOAD -- for a mesh topic (one-rank engines only: a multi-rank
+ * engine holds none).  A failed exchange returns the transport's error
+ * (PS_E_DEVICE) with the outputs unspecified; a rank that does not arrive
+ * makes the others' exchange time out, as in ps_run.  n == 0 is valid: the
+ * peer-space arrays read zero, the hop arrays are not written, nothing is
+ * exchanged. */
+#define PS_REPORT_DIST 0x7u   /* LOAD | HOPS | DOWNSTREAM: the sections ps_dist_report answers */
+int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
+                   const ps_report* out, size_t out_size);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a
