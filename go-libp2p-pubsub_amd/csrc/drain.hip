@@ -66,6 +66,13 @@
 //                         the parent's accumulator, or a record for its owner
 //   k_dist_apply          behind a level's exchange: the records received into
 //                         the parents' accumulators
+// and, for ps_dist_cut (§5.5o), a rank's share of the cut, decided at the child:
+//   k_dist_cut_nodes      k_dist_nodes' k word, and what the node lacks into
+//                         `missed`
+//   k_dist_cut_fill       the k of the parents this rank owns into the words
+//                         their children's ranks receive ahead of the sweep
+//   k_dist_cut_level      k_dist_sweep_level's push; a node that lacks messages
+//                         under a full parent adds its subtree's losses
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -1350,6 +1357,119 @@ __global__ __launch_bounds__(kDownBlock) void k_dist_apply(DistArgs g, uint32_t 
   if (R.k) atomicAdd(reinterpret_cast<unsigned long long*>(g.acc_k) + E.n0 + p, static_cast<unsigned long long>(R.k));
 }
 
+// ---- a rank's share of the cut (ps_dist_cut) --------------------------------------
+
+// k_dist_nodes<false, false, true> (kernels.hpp, DistCutArgs): the same k per
+// node into the k word, none for a root, and what the node lacks of the
+// window's messages into missed of its peer.
+__global__ __launch_bounds__(kAudBlock) void k_dist_cut_nodes(DrainArgs a, DistCutArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.d.n_strips) return;
+  const AudStrip S = g.d.strips[s];
+  uint32_t lo = 0, hi = g.d.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.d.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const DistEntry E = g.d.entries[lo - 1];
+  if (!E.tree) return;  // (wave-uniform, as everything read from E and S)
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.d.verdict + S.v0;
+  const bool all_full = !g.d.count_rows && g.d.n_exc[s] == 0;
+  const uint32_t end = S.u0 + S.n;
+  unsigned long long* const missed = reinterpret_cast<unsigned long long*>(g.missed);
+  uint32_t* const kout = g.d.k + E.n0;
+  for (uint32_t i0 = S.u0; i0 < end; i0 += kWave) {
+    const uint32_t i = min(i0 + lane, end - 1);
+    const bool in = i0 + lane < end;
+    uint32_t k = in ? E.c_t : 0u;
+    if (!all_full) {
+      const uint32_t v = vin[i - S.u0];
+      const bool full = !gather && v == kDrainRowAny;
+      const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.d.count_rows)));
+      k = in && full && !count ? E.c_t : 0u;
+      uint64_t todo = __ballot(count);
+      while (todo) {
+        const uint32_t j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint32_t c = load_count_row(a, T, i0 + j, lane);
+        if (lane == j) k = c;
+      }
+    }
+    if (in && i < E.nn) {
+      kout[i] = k;
+      if (k < E.c_t) atomicAdd(missed + g.d.node_peer[S.nbase + i], static_cast<unsigned long long>(E.c_t - k));
+    }
+  }
+}
+
+// One block per fill item, a thread per plist record this rank holds as the
+// parents' owner: the parent's k into the word its children's rank reads it
+// from.  A root's k word stays 0: it counts as full.
+__global__ __launch_bounds__(kDownBlock) void k_dist_cut_fill(DistCutArgs g) {
+  const DistApply A = g.fill[blockIdx.x];
+  const DistEntry E = g.d.entries[A.entry];
+  if (threadIdx.x >= A.n || !E.nn || !g.n_down_send || !g.d.n_plist) return;
+  const uint32_t w = min(A.rec0 + threadIdx.x, g.n_down_send - 1), pl = min(A.pl0 + threadIdx.x, g.d.n_plist - 1);
+  const uint32_t par = g.d.plist[pl];
+  if (par < E.nbase) return;
+  const uint32_t p = min(par - E.nbase, E.nn - 1);
+  g.down_send[w] = par == E.root ? E.c_t : g.d.k[E.n0 + p];
+}
+
+// k_dist_sweep_level's launch (kernels.hpp, DistCutArgs): the same accumulator
+// and the same push; where the node lacks messages under a full parent, its
+// subtree is what the cut lost.  The parent's k is a word this rank wrote
+// (k_dist_cut_nodes) or received ahead of the sweep (the downward exchange).
+__global__ __launch_bounds__(kDownBlock) void k_dist_cut_level(DistCutArgs g, uint32_t level, uint32_t w0) {
+  const DistWork W = g.d.work[w0 + blockIdx.x];
+  const DistEntry E = g.d.entries[W.entry];
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  if (!E.tree || !E.c_t || level == 0 || level > E.depth || !E.nn) return;  // (block-uniform: a root adds and pushes nothing)
+  const uint32_t lo = max(W.lo, lv[level]), hi = min(min(W.hi, lv[level + 1]), E.nn);
+  const uint32_t u = lo + threadIdx.x;
+  const bool in = u < hi;
+  const uint32_t uc = in ? u : E.nn - 1;  // (clamped into the entry's words)
+  unsigned long long* const acc_n = reinterpret_cast<unsigned long long*>(g.d.acc_n) + E.n0;
+  unsigned long long* const acc_k = reinterpret_cast<unsigned long long*>(g.d.acc_k) + E.n0;
+  const uint64_t an = in ? acc_n[uc] : 0ull, ak = in ? acc_k[uc] : 0ull;
+  const uint32_t k = g.d.k[E.n0 + uc];
+  const uint32_t par = g.d.node_parent[E.nbase + uc];
+  unsigned long long *pn = nullptr, *pk = nullptr;
+  bool on = false;
+  uint32_t kp = 0;  // the parent's k
+  if (in && par != kNoneNode) {
+    const uint32_t p = min(par - E.nbase, E.nn - 1);  // (par >= nbase: the parent is a node of this topic)
+    on = par >= E.nbase;
+    pn = acc_n + p;
+    pk = acc_k + p;
+    kp = par == E.root ? E.c_t : g.d.k[E.n0 + p];
+  } else if (in && g.d.gslot) {
+    const uint32_t gs = g.d.gslot[E.nbase + uc];
+    const uint32_t owner = gs >> kRemoteRankShift;
+    if (gs != kNoneNode && owner < g.d.world && g.d.n_send && g.n_down_recv) {
+      const uint32_t at = E.sb0 + level * g.d.world + owner, j = gs & kRemoteIdMask;
+      const uint32_t rec = min(g.d.send_base[at] + j, g.d.n_send - 1);
+      on = true;
+      pn = reinterpret_cast<unsigned long long*>(&g.d.send[rec].n);
+      pk = reinterpret_cast<unsigned long long*>(&g.d.send[rec].k);
+      kp = g.down_recv[min(g.down_base[at] + j, g.n_down_recv - 1)];
+    }
+  }
+  if (on && k < E.c_t && kp == E.c_t) {
+    const uint32_t peer = g.d.node_peer[E.nbase + uc];
+    atomicAdd(reinterpret_cast<unsigned long long*>(g.cuts) + peer, 1ull);
+    if (an) atomicAdd(reinterpret_cast<unsigned long long*>(g.orphaned) + peer, static_cast<unsigned long long>(an));
+    atomicAdd(reinterpret_cast<unsigned long long*>(g.lost) + peer,
+              static_cast<unsigned long long>(static_cast<uint64_t>(E.c_t) * (1 + an) - (k + ak)));
+  }
+  dist_push(pn, pk, 1 + an, k + ak, on);
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -1990,6 +2110,25 @@ hipError_t launch_dist_sweep_level(const DistArgs& g, uint32_t level, uint32_t w
 hipError_t launch_dist_apply(const DistArgs& g, uint32_t a0, uint32_t a1, hipStream_t s) {
   if (a1 <= a0) return hipSuccess;
   hipLaunchKernelGGL(k_dist_apply, dim3(a1 - a0), dim3(kDownBlock), 0, s, g, a0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_cut_nodes(const DrainArgs& a, const DistCutArgs& g, hipStream_t s) {
+  if (g.d.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_dist_cut_nodes, dim3((g.d.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream_t s) {
+  if (n_fill == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_cut_fill, dim3(n_fill), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0 || level == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_cut_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, level, w0);
   return hipGetLastError();
 }
 

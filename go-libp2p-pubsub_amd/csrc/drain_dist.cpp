@@ -13,6 +13,12 @@
 // lies follows from the replicated topology (TopicHost::gcnt) and the request
 // alone, so the ranks make the same exchanges in the same order with no
 // handshake.  Blocking; buffers of its own.
+//   ps_dist_cut answers ps_peer_cut the same way, through the
+// same front, plan and sweep (dist_stage .. dist_sweep): k_dist_cut_nodes
+// writes the k word and the misses, k_dist_cut_fill and one exchange in the
+// opposite direction bring every remote parent's k to its children's ranks
+// ahead of the sweep, and k_dist_cut_level decides at the child -- k < c_t under
+// a parent with k == c_t -- and pushes as the sweep does.
 #include "drain_impl.hpp"
 
 using namespace psamd;
@@ -66,6 +72,16 @@ struct Plan {
   uint64_t n_words = 0;          // per-node words: k, acc_n, acc_k each
   uint64_t n_send = 0, n_recv = 0;
   size_t o_lvl = 0, o_base = 0, o_work = 0, o_apply = 0, o_strips = 0;
+  // ps_dist_cut alone (dist_cut_plan): the downward exchange ahead of the
+  // sweep -- its fill items, the received runs' first words per (entry, level,
+  // owner) as send_base, its regions in bytes per rank -- behind the strips
+  bool cut = false;
+  std::vector<DistApply> fill;
+  std::vector<uint32_t> down_base;
+  Xchg down;
+  bool down_on = false;              // some named tree topic has a cross-rank edge
+  uint64_t n_dsend = 0, n_drecv = 0;  // words
+  size_t o_fill = 0, o_dbase = 0;
 };
 
 // the rank's own level table of a tree topic stands for the last window's
@@ -182,6 +198,54 @@ int dist_plan(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what, cons
   return PS_OK;
 }
 
+// ps_dist_cut's downward exchange over a sweep's plan: the sweep's regions
+// with the two ranks swapped, a 32-bit word where the sweep has a record, all
+// levels in one exchange.  The region me -> q holds, level by level and entry
+// by entry, the gcnt[(L * world + me) * world + q] parents' words of plist; the
+// one received from a is found through down_base as the sweep's send regions
+// are through send_base.  A region is padded to whole 16-byte units.
+int dist_cut_plan(ps_engine* e, size_t n, Plan* P) {
+  const uint32_t W = static_cast<uint32_t>(std::max(e->world, 1)), me = static_cast<uint32_t>(e->rank);
+  P->cut = true;
+  P->down_base.assign(P->send_base.size(), 0);
+  if (W == 1) return PS_OK;
+  Xchg& X = P->down;
+  X.s_off.assign(W, 0), X.s_len.assign(W, 0), X.r_off.assign(W, 0), X.r_len.assign(W, 0);
+  uint64_t crossing = 0;
+  for (uint32_t q = 0; q < W; ++q) {
+    X.s_off[q] = P->n_dsend * 4;
+    X.r_off[q] = P->n_drecv * 4;
+    for (uint32_t L = 1; L <= P->max_depth; ++L)
+      for (size_t i = 0; i < n; ++i) {
+        const DistEntry& E = P->entries[i];
+        const TopicHost& T = e->topics[E.topic];
+        if (!E.tree || L > E.depth || T.gcnt.size() < static_cast<size_t>(E.depth + 2) * W * W) continue;
+        const uint32_t* gc = &T.gcnt[static_cast<size_t>(L) * W * W];
+        // the words this rank's parents send to their children at q, and those
+        // q's parents send to this rank's children of level L
+        const uint32_t out_n = q == me ? 0 : gc[me * W + q], in_n = q == me ? 0 : gc[q * W + me];
+        const uint32_t pl0 = e->dist_slots.pl_off[E.topic][static_cast<size_t>(L) * W + q];
+        for (uint32_t j = 0; j < out_n; j += kDownBlock)
+          P->fill.push_back(DistApply{static_cast<uint32_t>(i), static_cast<uint32_t>(P->n_dsend) + j, pl0 + j,
+                                      std::min(kDownBlock, out_n - j)});
+        P->n_dsend += out_n;
+        P->down_base[E.sb0 + L * W + q] = static_cast<uint32_t>(P->n_drecv);
+        P->n_drecv += in_n;
+        if (q == 0)
+          for (uint32_t a = 0; a < W; ++a)
+            for (uint32_t b = 0; b < W; ++b)
+              if (a != b) crossing += gc[a * W + b];
+      }
+    P->n_dsend = (P->n_dsend + 3) & ~3ull;
+    P->n_drecv = (P->n_drecv + 3) & ~3ull;
+    X.s_len[q] = P->n_dsend * 4 - X.s_off[q];
+    X.r_len[q] = P->n_drecv * 4 - X.r_off[q];
+  }
+  P->down_on = crossing != 0;
+  if (P->n_dsend >= kDrainRowLimit || P->n_drecv >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many records in one dist cut");
+  return PS_OK;
+}
+
 // the slot tables of the node space the last window ran on, on the device
 int dist_slots_ready(ps_engine* e) {
   auto& S = e->dist_slots;
@@ -201,6 +265,150 @@ int dist_slots_ready(ps_engine* e) {
 template <class T>
 void put(uint8_t* at, const std::vector<T>& v) {
   if (!v.empty()) std::memcpy(at, v.data(), v.size() * sizeof(T));
+}
+
+// ---- what ps_dist_report and ps_dist_cut share ---------------------------------------
+
+// The strips' shape (the plan reads the entries' first strips), the plan, then
+// the input block in Dist::stage; cut: ps_dist_cut's downward exchange too
+int dist_stage(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what, bool cut, Plan* Pp, Drain::AudShape* Ap,
+               size_t* in_bytes) {
+  auto& H = e->drain.dist;
+  Plan& P = *Pp;
+  Drain::AudShape& A = *Ap;
+  size_t o = 0;
+  uint64_t strips_max = 0;
+  (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
+  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
+  std::vector<AudEntry> ae(n + 1);
+  (void)aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);  // (the shape and the entries' first strips alone)
+  if (const int rc = dist_plan(e, topic, n, what, ae.data(), &P)) return rc;
+  if (cut)
+    if (const int rc = dist_cut_plan(e, n, &P)) return rc;
+  P.o_lvl = align256((n + 1) * sizeof(DistEntry));
+  P.o_base = P.o_lvl + align256(std::max<size_t>(P.levels.size(), 1) * 4);
+  P.o_work = P.o_base + align256(std::max<size_t>(P.send_base.size(), 1) * 4);
+  P.o_apply = P.o_work + align256(std::max<size_t>(P.work.size(), 1) * sizeof(DistWork));
+  P.o_strips = P.o_apply + align256(std::max<size_t>(P.apply.size(), 1) * sizeof(DistApply));
+  P.o_fill = P.o_strips + (cut ? align256(std::max<size_t>(A.ns, 1) * sizeof(AudStrip)) : std::max<size_t>(A.ns, 1) * sizeof(AudStrip));
+  P.o_dbase = P.o_fill + (cut ? align256(std::max<size_t>(P.fill.size(), 1) * sizeof(DistApply)) : 0);
+  *in_bytes = P.o_dbase + (cut ? std::max<size_t>(P.down_base.size(), 1) * 4 : 0);
+  H.stage.resize(*in_bytes);
+  uint8_t* const hs = H.stage.data();
+  if (A.ns && !aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + P.o_strips), A.ns, &A))
+    return e->fail(PS_E_STATE, "dist report: more strips than staged");
+  put(hs, P.entries);
+  put(hs + P.o_lvl, P.levels);
+  put(hs + P.o_base, P.send_base);
+  put(hs + P.o_work, P.work);
+  put(hs + P.o_apply, P.apply);
+  put(hs + P.o_fill, P.fill);
+  put(hs + P.o_dbase, P.down_base);
+  return PS_OK;
+}
+
+// The buffers both passes work in, and what they add into cleared once up
+// front: no send region is rewritten while a peer may read it
+int dist_buffers(ps_engine* e, const Plan& P, const Drain::AudShape& A, size_t in_bytes, bool hops) {
+  auto& H = e->drain.dist;
+  hipStream_t s = e->stream;
+  const size_t scratch_bytes = static_cast<size_t>(P.n_words) * 20;
+  HIP_TRY(H.d_in.ensure(in_bytes), "alloc dist report input");
+  HIP_TRY(H.d_verdict.ensure(A.n_verdicts), "alloc dist report verdicts");
+  HIP_TRY(H.d_exc.ensure((static_cast<size_t>(A.ns) + 1) * 8), "alloc dist report counts");
+  HIP_TRY(H.d_full.ensure(static_cast<size_t>(A.ns) * 4), "alloc dist report counts");
+  if (hops) {
+    const size_t n_parts = std::max<size_t>(P.n_parts, 1);
+    HIP_TRY(H.d_part_r.ensure(n_parts * 4), "alloc dist report partials");
+    HIP_TRY(H.d_part_d.ensure(n_parts * 8), "alloc dist report partials");
+  }
+  HIP_TRY(H.d_scratch.ensure(scratch_bytes), "alloc dist report words");
+  HIP_TRY(H.d_send.ensure(P.n_send * sizeof(DistRec)), "alloc dist report records");
+  HIP_TRY(H.d_recv.ensure(P.n_recv * sizeof(DistRec)), "alloc dist report records");
+  if (scratch_bytes) HIP_TRY(hipMemsetAsync(H.d_scratch.p, 0, scratch_bytes, s), "clear dist report words");
+  if (P.n_send) HIP_TRY(hipMemsetAsync(H.d_send.p, 0, P.n_send * sizeof(DistRec), s), "clear dist report records");
+  return PS_OK;
+}
+
+// The front of both passes: the block's upload, one k_audience_classify over
+// the strips (ms0: its time), and the pass's arguments but for its sums
+int dist_front(ps_engine* e, const Plan& P, const Drain::AudShape& A, size_t in_bytes, size_t n, uint32_t what, const DrainArgs& a,
+               const PhaseTimer& tm, float& ms0, DistArgs* rp) {
+  auto& D = e->drain;
+  auto& H = D.dist;
+  hipStream_t s = e->stream;
+  HIP_TRY(hipMemcpyAsync(H.d_in.p, H.stage.data(), in_bytes, hipMemcpyHostToDevice, s), "upload dist report input");
+  const uint8_t* const din = H.d_in.as<uint8_t>();
+  AudArgs g{};
+  g.strips = reinterpret_cast<const AudStrip*>(din + P.o_strips);
+  g.n_strips = A.ns;
+  g.share = D.env.share;
+  g.verdict = H.d_verdict.as<uint8_t>();
+  g.n_exc = H.d_exc.as<uint64_t>();
+  g.n_full = H.d_full.as<uint32_t>();
+  if (A.ns) {
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
+    HIP_TRY(tm.end(ms0), "event");
+  }
+  const bool ranks = (what & kReportDown) && e->world > 1;
+  DistArgs& r = *rp;
+  r = DistArgs{};
+  r.strips = g.strips;
+  r.n_strips = A.ns;
+  r.entries = reinterpret_cast<const DistEntry*>(din);
+  r.n = static_cast<uint32_t>(n);
+  r.what = what;
+  r.world = static_cast<uint32_t>(std::max(e->world, 1));
+  r.levels = reinterpret_cast<const uint32_t*>(din + P.o_lvl);
+  r.verdict = g.verdict;
+  r.n_exc = g.n_exc;
+  r.count_rows = D.env.load_rows;
+  r.node_peer = e->d_node_peer.as<uint32_t>();
+  r.node_parent = e->d_node_parent.as<uint32_t>();
+  r.row_ptr = e->d_row_ptr.as<uint32_t>();
+  r.part_reached = H.d_part_r.as<uint32_t>();
+  r.part_deliv = H.d_part_d.as<uint64_t>();
+  r.n_parts = static_cast<uint32_t>(std::max<size_t>(P.n_parts, 1));
+  r.acc_n = H.d_scratch.as<uint64_t>();
+  r.acc_k = r.acc_n + P.n_words;
+  r.k = reinterpret_cast<uint32_t*>(r.acc_k + P.n_words);
+  r.work = reinterpret_cast<const DistWork*>(din + P.o_work);
+  r.gslot = ranks ? e->dist_slots.d_gslot.as<uint32_t>() : nullptr;
+  r.send_base = reinterpret_cast<const uint32_t*>(din + P.o_base);
+  r.send = H.d_send.as<DistRec>();
+  r.n_send = static_cast<uint32_t>(P.n_send);
+  r.apply = reinterpret_cast<const DistApply*>(din + P.o_apply);
+  r.plist = e->dist_slots.d_plist.as<uint32_t>();
+  r.rcv = H.d_recv.as<DistRec>();
+  r.n_recv = static_cast<uint32_t>(P.n_recv);
+  r.n_plist = static_cast<uint32_t>(e->dist_slots.plist.size());
+  return PS_OK;
+}
+
+// The sweep: level(L, w0, w1) launches the pass's kernel over a level's work
+// items, the deepest level first; behind a level whose edges cross ranks, its
+// exchange and k_dist_apply.  Adds the exchanges made and the bytes shipped.
+template <class Level>
+int dist_sweep(ps_engine* e, const Plan& P, const DistArgs& r, Level&& level, const char* kernel, uint64_t* exchanges,
+               uint64_t* bytes_sent) {
+  auto& H = e->drain.dist;
+  hipStream_t s = e->stream;
+  size_t x = 0;
+  for (size_t j = 0; j + 1 < P.launch.size(); ++j) {
+    const uint32_t L = P.max_depth - static_cast<uint32_t>(j);
+    HIP_TRY(level(L, P.launch[j], P.launch[j + 1]), kernel);
+    if (x == P.xchg.size() || P.xchg[x].level != L) continue;
+    const Xchg& X = P.xchg[x++];
+    std::string xerr;
+    const hipError_t xe = e->transport->exchange(H.d_send.as<uint8_t>(), X.s_off, X.s_len, H.d_recv.as<uint8_t>(), X.r_off,
+                                                 X.r_len, s, &xerr);
+    if (xe != hipSuccess) return e->fail(PS_E_DEVICE, xerr);
+    *exchanges += 1;
+    for (const uint64_t b : X.s_len) *bytes_sent += b;
+    HIP_TRY(launch_dist_apply(r, X.a0, X.a1, s), "k_dist_apply");
+  }
+  return PS_OK;
 }
 
 }  // namespace
@@ -232,31 +440,10 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   float ms[5] = {0, 0, 0, 0, 0};  // classify, nodes, hop sums, sweep, copy (PSAMD_DRAIN_TIMING)
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
-  // the strips' shape first (the plan reads the entries' first strips), then the block
-  size_t o = 0;
-  uint64_t strips_max = 0;
-  (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
-  if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  std::vector<AudEntry> ae(n + 1);
-  AudShape A;
-  (void)aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);  // (the shape and the entries' first strips alone)
   Plan P;
-  if ((rc = dist_plan(e, topic, n, what, ae.data(), &P))) return rc;
-  P.o_lvl = align256((n + 1) * sizeof(DistEntry));
-  P.o_base = P.o_lvl + align256(std::max<size_t>(P.levels.size(), 1) * 4);
-  P.o_work = P.o_base + align256(std::max<size_t>(P.send_base.size(), 1) * 4);
-  P.o_apply = P.o_work + align256(std::max<size_t>(P.work.size(), 1) * sizeof(DistWork));
-  P.o_strips = P.o_apply + align256(std::max<size_t>(P.apply.size(), 1) * sizeof(DistApply));
-  const size_t in_bytes = P.o_strips + std::max<size_t>(A.ns, 1) * sizeof(AudStrip);
-  H.stage.resize(in_bytes);
-  uint8_t* const hs = H.stage.data();
-  if (A.ns && !aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + P.o_strips), A.ns, &A))
-    return e->fail(PS_E_STATE, "dist report: more strips than staged");
-  put(hs, P.entries);
-  put(hs + P.o_lvl, P.levels);
-  put(hs + P.o_base, P.send_base);
-  put(hs + P.o_work, P.work);
-  put(hs + P.o_apply, P.apply);
+  AudShape A;
+  size_t in_bytes = 0;
+  if ((rc = dist_stage(e, topic, n, what, false, &P, &A, &in_bytes))) return rc;
   const double host_ms = ms_since(t_host0);
 
   // the output block: the seven arrays in ps_report's order
@@ -264,81 +451,22 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   size_t off[8] = {0};
   for (size_t i = 0; i < 7; ++i) off[i + 1] = off[i] + (kArraySection[i] == kReportHops ? n * kHopsCols : np);
   const size_t out_bytes = off[7] * 8;
-  const size_t scratch_bytes = static_cast<size_t>(P.n_words) * 20;
-  HIP_TRY(H.d_in.ensure(in_bytes), "alloc dist report input");
   HIP_TRY(H.d_out.ensure(out_bytes), "alloc dist report sums");
-  HIP_TRY(H.d_verdict.ensure(A.n_verdicts), "alloc dist report verdicts");
-  HIP_TRY(H.d_exc.ensure((static_cast<size_t>(A.ns) + 1) * 8), "alloc dist report counts");
-  HIP_TRY(H.d_full.ensure(static_cast<size_t>(A.ns) * 4), "alloc dist report counts");
-  const size_t n_parts = std::max<size_t>(P.n_parts, 1);
-  if (what & kReportHops) {
-    HIP_TRY(H.d_part_r.ensure(n_parts * 4), "alloc dist report partials");
-    HIP_TRY(H.d_part_d.ensure(n_parts * 8), "alloc dist report partials");
-  }
-  HIP_TRY(H.d_scratch.ensure(scratch_bytes), "alloc dist report words");
-  HIP_TRY(H.d_send.ensure(P.n_send * sizeof(DistRec)), "alloc dist report records");
-  HIP_TRY(H.d_recv.ensure(P.n_recv * sizeof(DistRec)), "alloc dist report records");
   HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes), "alloc dist report view");
+  if ((rc = dist_buffers(e, P, A, in_bytes, what & kReportHops))) return rc;
   uint64_t* const out = H.d_out.as<uint64_t>();
-  // everything the pass adds into, cleared once up front: no send region is
-  // rewritten while a peer may read it
   HIP_TRY(hipMemsetAsync(out, 0, std::max<size_t>(out_bytes, 8), s), "clear dist report sums");
-  if (scratch_bytes) HIP_TRY(hipMemsetAsync(H.d_scratch.p, 0, scratch_bytes, s), "clear dist report words");
-  if (P.n_send) HIP_TRY(hipMemsetAsync(H.d_send.p, 0, P.n_send * sizeof(DistRec), s), "clear dist report records");
-  HIP_TRY(hipMemcpyAsync(H.d_in.p, hs, in_bytes, hipMemcpyHostToDevice, s), "upload dist report input");
 
-  const uint8_t* const din = H.d_in.as<uint8_t>();
   const DrainArgs a = drain_args(e, D.tab);
-  AudArgs g{};
-  g.strips = reinterpret_cast<const AudStrip*>(din + P.o_strips);
-  g.n_strips = A.ns;
-  g.share = D.env.share;
-  g.verdict = H.d_verdict.as<uint8_t>();
-  g.n_exc = H.d_exc.as<uint64_t>();
-  g.n_full = H.d_full.as<uint32_t>();
-  if (A.ns) {
-    HIP_TRY(tm.begin(), "event");
-    HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
-    HIP_TRY(tm.end(ms[0]), "event");
-  }
-
   DistArgs r{};
-  r.strips = g.strips;
-  r.n_strips = A.ns;
-  r.entries = reinterpret_cast<const DistEntry*>(din);
-  r.n = static_cast<uint32_t>(n);
-  r.what = what;
-  r.world = static_cast<uint32_t>(std::max(e->world, 1));
-  r.levels = reinterpret_cast<const uint32_t*>(din + P.o_lvl);
-  r.verdict = g.verdict;
-  r.n_exc = g.n_exc;
-  r.count_rows = D.env.load_rows;
-  r.node_peer = e->d_node_peer.as<uint32_t>();
-  r.node_parent = e->d_node_parent.as<uint32_t>();
-  r.row_ptr = e->d_row_ptr.as<uint32_t>();
+  if ((rc = dist_front(e, P, A, in_bytes, n, what, a, tm, ms[0], &r))) return rc;
   r.recv = out + off[0];
   r.sent = out + off[1];
-  r.part_reached = H.d_part_r.as<uint32_t>();
-  r.part_deliv = H.d_part_d.as<uint64_t>();
-  r.n_parts = static_cast<uint32_t>(n_parts);
   r.nodes = out + off[2];
   r.reached = out + off[3];
   r.deliv = out + off[4];
   r.below = out + off[5];
   r.carried = out + off[6];
-  r.acc_n = H.d_scratch.as<uint64_t>();
-  r.acc_k = r.acc_n + P.n_words;
-  r.k = reinterpret_cast<uint32_t*>(r.acc_k + P.n_words);
-  r.work = reinterpret_cast<const DistWork*>(din + P.o_work);
-  r.gslot = sweep && ranks ? e->dist_slots.d_gslot.as<uint32_t>() : nullptr;
-  r.send_base = reinterpret_cast<const uint32_t*>(din + P.o_base);
-  r.send = H.d_send.as<DistRec>();
-  r.n_send = static_cast<uint32_t>(P.n_send);
-  r.apply = reinterpret_cast<const DistApply*>(din + P.o_apply);
-  r.plist = e->dist_slots.d_plist.as<uint32_t>();
-  r.rcv = H.d_recv.as<DistRec>();
-  r.n_recv = static_cast<uint32_t>(P.n_recv);
-  r.n_plist = static_cast<uint32_t>(e->dist_slots.plist.size());
   HIP_TRY(tm.begin(), "event");
   HIP_TRY(launch_dist_nodes(a, r, s), "k_dist_nodes");
   HIP_TRY(tm.end(ms[1]), "event");
@@ -353,20 +481,8 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   const uint64_t slot_bytes = (P.n_send + P.n_recv) * sizeof(DistRec);
   if (sweep) {
     HIP_TRY(tm.begin(), "event");
-    size_t x = 0;
-    for (size_t j = 0; j + 1 < P.launch.size(); ++j) {
-      const uint32_t L = P.max_depth - static_cast<uint32_t>(j);
-      HIP_TRY(launch_dist_sweep_level(r, L, P.launch[j], P.launch[j + 1], s), "k_dist_sweep_level");
-      if (x == P.xchg.size() || P.xchg[x].level != L) continue;
-      const Xchg& X = P.xchg[x++];
-      std::string xerr;
-      const hipError_t xe = e->transport->exchange(H.d_send.as<uint8_t>(), X.s_off, X.s_len, H.d_recv.as<uint8_t>(), X.r_off,
-                                                   X.r_len, s, &xerr);
-      if (xe != hipSuccess) return e->fail(PS_E_DEVICE, xerr);
-      exchanges += 1;
-      for (const uint64_t b : X.s_len) bytes_sent += b;
-      HIP_TRY(launch_dist_apply(r, X.a0, X.a1, s), "k_dist_apply");
-    }
+    const auto level = [&](uint32_t L, uint32_t w0, uint32_t w1) { return launch_dist_sweep_level(r, L, w0, w1, s); };
+    if ((rc = dist_sweep(e, P, r, level, "k_dist_sweep_level", &exchanges, &bytes_sent))) return rc;
     HIP_TRY(tm.end(ms[3]), "event");
   }
 
@@ -392,6 +508,108 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
                  "psamd dist_report: rank %d topics %zu what %u strips %u nodes %llu work %zu launches %zu exchanges %llu "
                  "sent_bytes %llu slot_bytes %llu classify_ms %.4f nodes_ms %.4f sum_ms %.4f sweep_ms %.4f copy_ms %.4f host_plan_ms %.4f\n",
                  e->rank, n, what, A.ns, static_cast<unsigned long long>(P.n_words), P.work.size(),
+                 P.launch.empty() ? size_t(0) : P.launch.size() - 1, static_cast<unsigned long long>(exchanges),
+                 static_cast<unsigned long long>(bytes_sent), static_cast<unsigned long long>(slot_bytes), ms[0], ms[1], ms[2],
+                 ms[3], ms[4], host_ms);
+  return PS_OK;
+}
+
+// ---- ps_dist_cut ----------------------------------------------------
+
+int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_out, uint64_t* cuts_out,
+                uint64_t* orphaned_out, uint64_t* lost_out) {
+  uint64_t* const outs[4] = {missed_out, cuts_out, orphaned_out, lost_out};
+  if (!e || (n && !topic) || (!missed_out && !cuts_out && !orphaned_out && !lost_out)) return PS_E_INVAL;
+  if (const int rc = drain_enter(e, {nullptr, "no completed run", nullptr, false})) return rc;
+  if (e->world > 1 && e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
+  if (const int rj = twin_join(e)) return rj;
+  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_dist_cut: a mesh topic has no subtrees");
+  const bool ranks = e->world > 1;
+  if (ranks && (e->graph_dirty || !e->transport))
+    return e->fail(PS_E_STATE, "ps_dist_cut: the topics changed since the last run: run first");
+  auto& D = e->drain;
+  auto& H = D.dist;
+  const auto t_host0 = hclock::now();
+  int rc = drain_ready(e);
+  if (!rc) rc = drain_tables(e);
+  if (!rc && ranks) rc = dist_slots_ready(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  float ms[5] = {0, 0, 0, 0, 0};  // classify, nodes, fill + downward exchange, sweep, copy (PSAMD_DRAIN_TIMING)
+  const PhaseTimer tm{D.ev_t, s, D.env.timing};
+
+  Plan P;
+  AudShape A;
+  size_t in_bytes = 0;
+  if ((rc = dist_stage(e, topic, n, kReportDown, true, &P, &A, &in_bytes))) return rc;
+  const double host_ms = ms_since(t_host0);
+
+  // the output block: missed | cuts | orphaned | lost
+  const size_t np = e->cfg.n_peers, out_bytes = 4 * np * 8;
+  HIP_TRY(H.d_out.ensure(out_bytes), "alloc dist cut sums");
+  HIP_TRY(H.d_dsend.ensure(P.n_dsend * 4), "alloc dist cut words");
+  HIP_TRY(H.d_drecv.ensure(P.n_drecv * 4), "alloc dist cut words");
+  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes), "alloc dist cut view");
+  if ((rc = dist_buffers(e, P, A, in_bytes, false))) return rc;
+  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(hipMemsetAsync(out, 0, std::max<size_t>(out_bytes, 8), s), "clear dist cut sums");
+  if (P.n_dsend) HIP_TRY(hipMemsetAsync(H.d_dsend.p, 0, P.n_dsend * 4, s), "clear dist cut words");
+
+  const DrainArgs a = drain_args(e, D.tab);
+  DistCutArgs g{};
+  if ((rc = dist_front(e, P, A, in_bytes, n, kReportDown, a, tm, ms[0], &g.d))) return rc;
+  const uint8_t* const din = H.d_in.as<uint8_t>();
+  g.missed = out;
+  g.cuts = out + np;
+  g.orphaned = out + 2 * np;
+  g.lost = out + 3 * np;
+  g.fill = reinterpret_cast<const DistApply*>(din + P.o_fill);
+  g.down_send = H.d_dsend.as<uint32_t>();
+  g.down_recv = H.d_drecv.as<uint32_t>();
+  g.down_base = reinterpret_cast<const uint32_t*>(din + P.o_dbase);
+  g.n_down_send = static_cast<uint32_t>(P.n_dsend);
+  g.n_down_recv = static_cast<uint32_t>(P.n_drecv);
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_dist_cut_nodes(a, g, s), "k_dist_cut_nodes");
+  HIP_TRY(tm.end(ms[1]), "event");
+
+  // the parents' k to the children's ranks: one exchange, all levels, ahead of the sweep
+  uint64_t exchanges = 0, bytes_sent = 0;
+  const uint64_t slot_bytes = (P.n_send + P.n_recv) * sizeof(DistRec) + (P.n_dsend + P.n_drecv) * 4;
+  if (P.down_on) {
+    HIP_TRY(tm.begin(), "event");
+    HIP_TRY(launch_dist_cut_fill(g, static_cast<uint32_t>(P.fill.size()), s), "k_dist_cut_fill");
+    std::string xerr;
+    const Xchg& X = P.down;
+    const hipError_t xe = e->transport->exchange(H.d_dsend.as<uint8_t>(), X.s_off, X.s_len, H.d_drecv.as<uint8_t>(), X.r_off,
+                                                 X.r_len, s, &xerr);
+    if (xe != hipSuccess) return e->fail(PS_E_DEVICE, xerr);
+    exchanges += 1;
+    for (const uint64_t b : X.s_len) bytes_sent += b;
+    HIP_TRY(tm.end(ms[2]), "event");
+  }
+  HIP_TRY(tm.begin(), "event");
+  const auto level = [&](uint32_t L, uint32_t w0, uint32_t w1) { return launch_dist_cut_level(g, L, w0, w1, s); };
+  if ((rc = dist_sweep(e, P, g.d, level, "k_dist_cut_level", &exchanges, &bytes_sent))) return rc;
+  HIP_TRY(tm.end(ms[3]), "event");
+
+  // one copy: from the first array asked for to the last
+  size_t lo = 0, hi = 4;
+  while (!outs[lo]) ++lo;
+  while (!outs[hi - 1]) --hi;
+  HIP_TRY(tm.begin(), "event");
+  if (np) HIP_TRY(hipMemcpyAsync(H.h_out + lo * np * 8, out + lo * np, (hi - lo) * np * 8, hipMemcpyDeviceToHost, s), "read dist cut sums");
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  HIP_TRY(tm.end(ms[4]), "event");
+  for (size_t i = lo; i < hi; ++i)
+    if (outs[i] && np) std::memcpy(outs[i], H.h_out + i * np * 8, np * 8);
+  if (D.env.timing)
+    std::fprintf(stderr,
+                 "psamd dist_cut: rank %d topics %zu strips %u nodes %llu work %zu launches %zu exchanges %llu "
+                 "sent_bytes %llu slot_bytes %llu classify_ms %.4f nodes_ms %.4f down_ms %.4f sweep_ms %.4f copy_ms %.4f host_plan_ms %.4f\n",
+                 e->rank, n, A.ns, static_cast<unsigned long long>(P.n_words), P.work.size(),
                  P.launch.empty() ? size_t(0) : P.launch.size() - 1, static_cast<unsigned long long>(exchanges),
                  static_cast<unsigned long long>(bytes_sent), static_cast<unsigned long long>(slot_bytes), ms[0], ms[1], ms[2],
                  ms[3], ms[4], host_ms);

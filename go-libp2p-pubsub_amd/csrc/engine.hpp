@@ -969,6 +969,9 @@ struct ps_engine {
       // k | acc_n | acc_k, the sweep's send and receive records, the cleared
       // output block
       psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_part_r, d_part_d, d_scratch, d_send, d_recv, d_out;
+      // ps_dist_cut (§5.5o) works in the same buffers -- both calls block -- and
+      // in the words of its downward exchange: the parents' k sent and received
+      psamd::DevBuf d_dsend, d_drecv;
       std::vector<uint8_t> stage;  // (the upload is waited for in the call)
       uint8_t* h_out = nullptr;
       size_t out_cap = 0;

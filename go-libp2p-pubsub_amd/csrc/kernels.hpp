@@ -1196,4 +1196,42 @@ hipError_t launch_dist_sweep_level(const DistArgs& g, uint32_t level, uint32_t w
 // k_dist_apply over apply items [a0, a1): one exchange's records
 hipError_t launch_dist_apply(const DistArgs& g, uint32_t a0, uint32_t a1, hipStream_t s);
 
+// ---- a rank's share of the cut (ps_dist_cut) ------------------
+// ps_peer_cut's four sums for the nodes one rank owns, decided from the
+// child's side: u is a cut point iff k(u) < c_t and its parent's k == c_t (a
+// root counts as c_t).  DistArgs' tables, words and sweep (d) carry it; a
+// remote parent's k arrives ahead of the sweep in one downward exchange whose
+// regions mirror the sweep's with the two ranks swapped: a word per (remote
+// parent, child rank) pair, the pair's record index (gslot / plist) its place.
+//   k_dist_cut_nodes  k_dist_nodes<false, false, true> plus c_t - k into
+//                     missed of the node's peer.
+//   k_dist_cut_fill   one block per fill item, a thread per plist record this
+//                     rank holds as the parents' owner: the parent's k (c_t for
+//                     the entry's root) into down_send[rec0 + j].
+//   k_dist_cut_level  k_dist_sweep_level's launch: node u of level L >= 1
+//                     with (acc_n, acc_k), its k and its parent's -- the k word
+//                     of a local parent, else down_recv[down_base[sb0 + L *
+//                     world + a] + j] -- adds 1, acc_n and c_t * (1 + acc_n) -
+//                     (k + acc_k) into cuts, orphaned and lost of its peer
+//                     where it is a cut point, then pushes as the sweep does.
+//                     below and carried are not written.
+// k_dist_apply is the sweep's.  Order, atomics and clamping as above.
+struct DistCutArgs {
+  DistArgs d;                 // recv .. carried unused
+  uint64_t* missed;           // [n_peers] each, added into
+  uint64_t* cuts;
+  uint64_t* orphaned;
+  uint64_t* lost;
+  const DistApply* fill;      // fill items: rec0 the first word of down_send, pl0 of plist, n words
+  uint32_t* down_send;        // the parents' k, region by region
+  const uint32_t* down_recv;  // ... as received
+  const uint32_t* down_base;  // per (entry, level, owner) as send_base: the first word of the run in down_recv
+  uint32_t n_down_send, n_down_recv;
+};
+hipError_t launch_dist_cut_nodes(const DrainArgs& a, const DistCutArgs& g, hipStream_t s);
+// k_dist_cut_fill over fill items [0, n_fill)
+hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream_t s);
+// k_dist_cut_level over work items [w0, w1): the nodes of level `level` (>= 1)
+hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s);
+
 }  // namespace psamd

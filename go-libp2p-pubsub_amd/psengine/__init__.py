@@ -200,6 +200,7 @@ PROTOTYPES = [
     ("ps_report_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32]),
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
     ("ps_dist_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
+    ("ps_dist_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -928,6 +929,21 @@ class Engine:
         arrays, rep = self._report_arrays(t.size, what)
         self._check(self._L.ps_dist_report(self._h, _p(t, C.c_uint32), t.size, what, C.byref(rep), C.sizeof(Report)))
         return arrays
+
+    def dist_cut(self, topics) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """This rank's share of peer_cut over the named distinct tree topics
+        (ps_dist_cut), on an engine of any rank count: (missed, cuts,
+        orphaned, lost), uint64 [n_peers] each, for the nodes this rank owns --
+        the subtree behind a cut point counted on whatever rank it lies.  The
+        ranks' arrays add up to a one-rank engine's peer_cut.  On a multi-rank
+        engine the call is collective whenever topics are named: every rank
+        makes it, with the same topics in the same order."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        out = [np.empty(self.n_peers, dtype=np.uint64) for _ in range(4)]
+        self._check(self._L.ps_dist_cut(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out)))
+        return out[0], out[1], out[2], out[3]
 
     def report_track(self, topics, what: int = REPORT_ALL):
         """Registers standing topics and sections (ps_report_track): from now on

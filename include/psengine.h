@@ -889,6 +889,42 @@ int ps_report_take(ps_engine* e, const ps_report* out, size_t out_size,
 #define PS_REPORT_DIST 0x7u   /* LOAD | HOPS | DOWNSTREAM: the sections ps_dist_report answers */
 int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
                    const ps_report* out, size_t out_size);
+
+/* This rank's share of ps_peer_cut, on an engine of any rank count (DESIGN.md
+ * 5.5o): what was not delivered and at which peer each tree was cut, where
+ * the subtree behind a cut point may lie on several ranks.  The last window of
+ * the last run; blocking.
+ *   For every named tree topic t with c_t > 0 window messages and every node u
+ * of t this rank owns, with peer p and k(u) as in ps_dist_report (the root
+ * counts as full, k(root) = c_t):
+ *   missed[p] += c_t - k(u) for a non-root u;
+ *   where u is a non-root with k(u) < c_t whose parent, on whatever rank, is
+ *   full -- a cut point --, over T(u) = u and its strict descendants on
+ *   whatever rank they live:
+ *     cuts[p] += 1, orphaned[p] += |T(u)| - 1,
+ *     lost[p] += c_t * |T(u)| - (the sum of k over T(u)).
+ * The decision is made from the k values, seen from the child: a rank lacks
+ * only the fullness of a remote parent, and one word per (remote parent, child
+ * rank) pair brings it ahead of the bottom-up sweep.  Summed over the ranks
+ * every array is, bit for bit, what ps_peer_cut writes on a one-rank engine for
+ * the same trees, live mask, publishes and request; each rank's arrays are that
+ * answer's per-node values masked to the nodes it owns; on a one-rank engine the
+ * call equals ps_peer_cut itself (it runs its own kernels, with nothing to
+ * exchange).  An idle topic and peers outside the node space add nothing.
+ *   On a multi-rank engine the call is COLLECTIVE whenever n > 0, as ps_run
+ * is: every rank calls it with the same topics in the same order, after the
+ * same run.  Which of the four pointers are NULL does not change the pass and
+ * may differ between the ranks.
+ *   PS_E_INVAL for a NULL engine, n > 0 without topic, all four outputs NULL
+ * or a topic named twice; PS_E_RANGE, nothing written, for a topic out of
+ * range; PS_E_NOTREADY before any run; PS_E_STATE with a run in flight on a
+ * multi-rank engine, for a topic set anew since the window or topics changed
+ * since the run, and for a mesh topic (one-rank engines only).  A failed
+ * exchange returns the transport's error (PS_E_DEVICE) with the outputs
+ * unspecified.  n == 0 is valid: all zeros, nothing exchanged. */
+int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n,
+                uint64_t* missed_out, uint64_t* cuts_out,
+                uint64_t* orphaned_out, uint64_t* lost_out);  /* [n_peers] each; any may be NULL, not all four */
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

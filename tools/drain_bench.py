@@ -146,6 +146,16 @@ ranks on a cfg4-shaped run under the peer hash (one GPU: the ranks are threads
 of this process): the collective call's wall per rank, its exchanges, the bytes
 a rank ships in them and the bytes of its send and receive records, the ranks'
 sum compared with the one-rank answer.  Writes DIR/dist_report_bench.json.
+
+--dist-cut: a rank's share of the cut (ps_dist_cut).  One rank: over every
+topic after one step under --cut's live mask, --reps repetitions alternating in
+one process with ps_peer_cut -- the yardstick --: the device phases of both
+(PSAMD_DRAIN_TIMING) and the walls, the answers compared array for array.  Then
+2 and 4 loopback ranks on --dist-report's cfg4-shaped run, alternating with
+ps_dist_report(PS_REPORT_DOWNSTREAM) -- the yardstick there --: the wall per
+rank, the exchanges, the bytes a rank ships in them and the bytes of its
+records and words, the ranks' sum compared with the one-rank answer on every
+call.  Writes DIR/dist_cut_bench.json.
 """
 from __future__ import annotations
 
@@ -1900,6 +1910,174 @@ def dist_report_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def dist_cut_main(a, wl):
+    """--dist-cut (see the module text).  Writes DIR/dist_cut_bench.json."""
+    import threading
+
+    names = ("missed", "cuts", "orphaned", "lost")
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+        WL.build_engine_topics(eng, wl)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    def counts(text, row, keys):
+        for k in keys:
+            m = re.search(rf"\b{k} (\d+)", text)
+            if m:
+                row[k] = int(m.group(1))
+        return row
+
+    # 1. one rank: the device phases, the two calls alternating
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        phases = {"peer_cut": [], "dist_cut": []}
+        for _ in range(a.reps + 1):  # (the first calls build the window's tables and allocate)
+            with StderrCapture() as cap:
+                want = eng.peer_cut(topics)
+            phases["peer_cut"].append(counts(cap.text, phase_line(cap.text, "peer_cut"), ("strips", "nodes", "work", "launches")))
+            with StderrCapture() as cap:
+                got = eng.dist_cut(topics)
+            phases["dist_cut"].append(counts(cap.text, phase_line(cap.text, "dist_cut"), ("strips", "nodes", "work", "launches")))
+            for k, g, w in zip(names, got, want):
+                assert np.array_equal(g, w), f"ps_dist_cut {k} differs from ps_peer_cut"
+        res["phases"] = {k: v[1:] for k, v in phases.items()}
+
+        def device_ms(rows):
+            return float(np.median([sum(v for k, v in r.items() if k.endswith("_ms") and not k.startswith("host_")) for r in rows]))
+
+        res["peer_cut_device_ms"] = device_ms(res["phases"]["peer_cut"])
+        res["dist_cut_device_ms"] = device_ms(res["phases"]["dist_cut"])
+        res["peer_cut_levels_ms"] = float(np.median([r["levels_ms"] for r in res["phases"]["peer_cut"]]))
+        res["dist_cut_sweep_ms"] = float(np.median([r["sweep_ms"] for r in res["phases"]["dist_cut"]]))
+        res["dist_minus_peer_cut_device_ms"] = res["dist_cut_device_ms"] - res["peer_cut_device_ms"]
+        res.update(deliveries=int(st.deliveries), cut_points=int(got[1].sum()), missed_sum=int(got[0].sum()))
+        assert int(got[3].sum()) == res["missed_sum"] and res["cut_points"] > 0
+    eng, _ = masked_engine({})
+    with eng:
+        walls = {"peer_cut": [], "dist_cut": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            want = eng.peer_cut(topics)
+            walls["peer_cut"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            got = eng.dist_cut(topics)
+            walls["dist_cut"].append(1e3 * (time.perf_counter() - t0))
+            for k, g, w in zip(names, got, want):
+                assert np.array_equal(g, w), k
+    res["peer_cut_wall_ms"], res["dist_cut_wall_ms"] = walls["peer_cut"][1:], walls["dist_cut"][1:]
+    res["dist_over_peer_cut_wall"] = float(np.median(res["dist_cut_wall_ms"]) / np.median(res["peer_cut_wall_ms"]))
+    res["answers_agree"] = True
+
+    # 2. loopback ranks, cfg4-shaped, the peer hash; the yardstick there: ps_dist_report(PS_REPORT_DOWNSTREAM)
+    w4 = WL.cfg4(200_000, 300)
+    live4 = (np.random.default_rng(a.seed).random(w4.n_peers) >= 0.03).astype(np.uint8)
+    live4[0] = 1
+    with PE.Engine(w4.n_peers, 1, seed=w4.seed) as one:
+        WL.build_engine_topics(one, w4)
+        one.set_live(live4)
+        one.publish(w4.msg_topics)
+        one.run()
+        whole = one.peer_cut([0])
+        whole_down = one.peer_report([0], PE.REPORT_DOWNSTREAM)
+    res["ranks"] = {"workload": "cfg4-shaped: 200000 peers, 300 messages, one topic", "partition": "peer hash",
+                    "cut_points": int(whole[1].sum()), "worlds": {}}
+
+    def threads(fn, world):
+        out, errs = [None] * world, []
+
+        def go(r):
+            try:
+                out[r] = fn(r)
+            except Exception as ex:  # noqa: BLE001
+                errs.append((r, ex))
+
+        th = [threading.Thread(target=go, args=(r,)) for r in range(world)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join(timeout=300)
+        assert not any(t.is_alive() for t in th) and not errs, errs
+        return out
+
+    def ranks_up(world, timed):
+        os.environ.pop("PSAMD_DRAIN_TIMING", None)
+        if timed:
+            os.environ["PSAMD_DRAIN_TIMING"] = "1"
+        lb = PE.Loopback(world)
+        engines = [PE.Engine(w4.n_peers, 1, seed=w4.seed) for _ in range(world)]
+        os.environ.pop("PSAMD_DRAIN_TIMING", None)
+        for r, e in enumerate(engines):
+            e.dist_init_loopback(lb, r)
+            WL.build_engine_topics(e, w4)
+            e.set_live(live4)
+            e.publish(w4.msg_topics)
+        threads(lambda r: engines[r].run(), world)
+        return lb, engines
+
+    calls = {"dist_cut": lambda e: e.dist_cut([0]), "dist_report": lambda e: e.dist_report([0], PE.REPORT_DOWNSTREAM)}
+    for world in (2, 4):
+        # the pass's shape and device phases from engines under PSAMD_DRAIN_TIMING, the walls from plain ones
+        lb, engines = ranks_up(world, True)
+        shape = {}
+        for tag, call in calls.items():
+            for _ in range(2):  # (the first call builds the slot tables and allocates)
+                with StderrCapture() as cap:
+                    threads(lambda r: call(engines[r]), world)
+            shape[tag] = []
+            for r in range(world):
+                m = re.search(rf"psamd {tag}: rank {r} .*", cap.text)
+                assert m, cap.text
+                row = {k: float(v) for k, v in re.findall(r"(\w+_ms) ([0-9.]+)", m.group(0))}
+                shape[tag].append(counts(m.group(0), row, ("strips", "nodes", "launches", "exchanges", "sent_bytes", "slot_bytes")))
+        for e in engines:
+            e.close()
+        lb.close()
+        lb, engines = ranks_up(world, False)
+        walls = {tag: [] for tag in calls}
+        for _ in range(a.reps + 1):
+            for tag, call in calls.items():  # (alternating)
+
+                def timed_call(r):
+                    t0 = time.perf_counter()
+                    got = call(engines[r])
+                    return 1e3 * (time.perf_counter() - t0), got
+
+                out = threads(timed_call, world)
+                if tag == "dist_cut":
+                    for i, k in enumerate(names):
+                        assert np.array_equal(sum(o[1][i] for o in out), whole[i]), f"{world} ranks: the sum of {k} differs from one rank's"
+                else:
+                    for k in whole_down:
+                        assert np.array_equal(sum(o[1][k] for o in out), whole_down[k]), f"{world} ranks: the sum of {k} differs"
+                walls[tag].append([o[0] for o in out])
+        med = {tag: float(np.median(np.array(w[1:]))) for tag, w in walls.items()}
+        res["ranks"]["worlds"][str(world)] = {
+            "per_rank": shape, "first_call_wall_ms": {tag: w[0] for tag, w in walls.items()},
+            "wall_ms": {tag: w[1:] for tag, w in walls.items()}, "median_wall_ms": med,
+            "dist_cut_over_dist_report_wall": med["dist_cut"] / med["dist_report"]}
+        for e in engines:
+            e.close()
+        lb.close()
+    res["ranks"]["sums_agree"] = True
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "dist_cut_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -2052,10 +2230,14 @@ def main():
     ap.add_argument("--report-once", action="store_true", help="one step and one ps_peer_report (for a kernel trace)")
     ap.add_argument("--dist-report", action="store_true",
                     help="ps_dist_report against ps_peer_report on one rank; the collective call on 2 and 4 loopback ranks")
+    ap.add_argument("--dist-cut", action="store_true",
+                    help="ps_dist_cut against ps_peer_cut on one rank; against ps_dist_report's downstream on 2 and 4 loopback ranks")
     a = ap.parse_args()
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
     if a.dist_report:
         return dist_report_main(a, wl)
+    if a.dist_cut:
+        return dist_cut_main(a, wl)
     if a.report or a.report_once:
         return report_main(a, wl)
     if a.cut:
