@@ -73,6 +73,15 @@
 //                         their children's ranks receive ahead of the sweep
 //   k_dist_cut_level      k_dist_sweep_level's push; a node that lacks messages
 //                         under a full parent adds its subtree's losses
+// and, for ps_topic_spread (§5.5p), hops and duplicate copies of meshes and trees:
+//   k_spread_nodes        behind k_audience_classify: a node's k into its word
+//                         and its peer's recv; holders and a tree's unreached per entry
+//   k_spread_unreached    a mesh's unreached nodes, each peer once
+//   k_spread_level        one launch per BFS level over the child lists, top-down,
+//                         from a frontier queue into the other: copies per peer,
+//                         a hop per forwarder
+//   k_spread_sum          the hop words into reached / deliv per (entry, column)
+//   k_spread_dup          copies - recv per peer
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -1470,6 +1479,283 @@ __global__ __launch_bounds__(kDownBlock) void k_dist_cut_level(DistCutArgs g, ui
   dist_push(pn, pk, 1 + an, k + ak, on);
 }
 
+// ---- hops and duplicate copies, meshes too (ps_topic_spread) ---------------------
+
+constexpr uint32_t kSpreadBlock = 256;
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, static_cast<uint32_t>(__shfl_xor(v, m, 64)));
+  return v;
+}
+
+// One wave per strip, one node per lane: k_audience_weights' k into the node's
+// word, and into recv of its peer; the strip's nodes with k > 0 and, for a
+// tree, those with k == 0 into the entry's two counts, an add per wave each.
+__global__ __launch_bounds__(kAudBlock) void k_spread_nodes(DrainArgs a, SpreadArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const uint32_t ei = lo - 1;
+  const SpreadEntry E = g.entries[ei];
+  if (!E.c_t || S.n == 0 || S.u0 + S.n > E.nn) return;  // (the strip lies within the entry's words)
+  const DrainTopic T = a.topics[S.topic];
+  const bool gather = T.flags & kDrainGather;
+  const uint8_t* __restrict__ vin = g.verdict + S.v0;
+  uint32_t* __restrict__ kout = g.k + E.n0;
+  const bool all_full = !g.count_rows && g.n_exc[s] == 0;
+  uint32_t n_zero = 0, n_held = 0;  // (wave-uniform)
+  for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+    const uint32_t i = i0 + lane;
+    const bool in = i < S.n;
+    uint32_t k = E.c_t;
+    if (!all_full) {
+      const uint32_t v = vin[min(i, S.n - 1)];
+      const bool full = !gather && v == kDrainRowAny;
+      const bool count = in && (gather || ((v & kDrainRowAny) && (!full || g.count_rows)));
+      k = full && !count ? E.c_t : 0u;
+      uint64_t todo = __ballot(count);
+      while (todo) {
+        const uint32_t j = __builtin_ctzll(todo);
+        todo &= todo - 1;
+        const uint32_t c = load_count_row(a, T, S.u0 + i0 + j, lane);
+        if (lane == j) k = c;
+      }
+    }
+    if (in) {
+      kout[S.u0 + i] = k;
+      const uint32_t peer = g.node_peer[E.nbase + S.u0 + i];
+      if (k && peer < g.n_peers) atomicAdd(reinterpret_cast<unsigned long long*>(g.recv) + peer, static_cast<unsigned long long>(k));
+    }
+    const uint32_t held = __popcll(__ballot(in && k != 0));
+    n_held += held;
+    n_zero += min(S.n - i0, kWave) - held;
+  }
+  if (lane == 0) {
+    // (a tree's nodes are its peers; a mesh's are counted by k_spread_unreached)
+    if (n_zero && !E.mesh)
+      atomicAdd(reinterpret_cast<unsigned long long*>(g.unreached) + ei, static_cast<unsigned long long>(n_zero));
+    if (n_held) atomicAdd(reinterpret_cast<unsigned long long*>(g.holders) + ei, static_cast<unsigned long long>(n_held));
+  }
+}
+
+// the child entry that names node v of entry E: 1 where v is a non-root node
+// without messages and this entry is the one that marks its hop word
+__device__ __forceinline__ uint32_t spread_name(const SpreadArgs& g, const SpreadEntry& E, uint32_t v) {
+  const uint32_t r = v - E.nbase;
+  if (r == 0 || r >= E.nn || g.k[E.n0 + r] != 0) return 0;
+  uint32_t* const h = g.hop + E.n0 + r;
+  return *h == kSpreadNone && atomicCAS(h, kSpreadNone, kSpreadNamed) == kSpreadNone ? 1u : 0u;
+}
+
+// One wave per strip of a mesh entry, one node per lane, the wave of the
+// entry's first strip the root too: the node's child entries one by one, or
+// by the whole wave where it has more than g.wide; a non-root target without
+// messages is counted once, by the entry that marks its hop word (kernels.hpp).
+__global__ __launch_bounds__(kAudBlock) void k_spread_unreached(SpreadArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.n_strips) return;
+  const AudStrip S = g.strips[s];
+  uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (g.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return;
+  const uint32_t ei = lo - 1;
+  const SpreadEntry E = g.entries[ei];
+  if (!E.c_t || !E.mesh || S.n == 0 || S.u0 + S.n > E.nn) return;
+  const uint32_t n_items = S.n + (E.strip0 == s ? 1u : 0u);  // (item S.n: the root)
+  uint32_t cnt = 0;
+  for (uint32_t i0 = 0; i0 < n_items; i0 += kWave) {  // (wave-uniform)
+    const uint32_t i = i0 + lane;
+    uint32_t r0 = 0, deg = 0;
+    if (i < n_items) {
+      const uint32_t u = i < S.n ? S.u0 + i : 0u;
+      r0 = min(g.row_ptr[E.nbase + u], g.n_edges);
+      const uint32_t r1 = min(g.row_ptr[E.nbase + u + 1], g.n_edges);
+      deg = r1 > r0 ? r1 - r0 : 0u;
+    }
+    const uint32_t dn = deg <= g.wide ? deg : 0u;
+    for (uint32_t j = 0; j < dn; ++j) cnt += spread_name(g, E, g.col[r0 + j]);
+    uint64_t todo = __ballot(deg > g.wide);
+    while (todo) {  // (a node of many entries: lanes across them)
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t w0 = __shfl(r0, src, 64), w1 = w0 + __shfl(deg, src, 64);
+      for (uint32_t j = w0 + lane; j < w1; j += kWave) cnt += spread_name(g, E, g.col[j]);
+    }
+  }
+  cnt = wave_sum_u32(cnt);
+  if (lane == 0 && cnt) atomicAdd(reinterpret_cast<unsigned long long*>(g.unreached) + ei, static_cast<unsigned long long>(cnt));
+}
+
+// The child entry of a frontier item of entry E that names node v: where the
+// target forwards (the root, or a node whose row holds messages), the item's
+// kq into copies of the target's peer; true: this entry is the one that gave
+// the (non-root) target *vr its hop `next`, so it joins the next frontier.
+__device__ __forceinline__ bool spread_edge(const SpreadArgs& g, const SpreadEntry& E, uint32_t v, uint32_t kq,
+                                            uint32_t next, uint32_t* vr) {
+  const uint32_t r = v - E.nbase;  // (a node of another topic, or no node at all: past nn either way)
+  *vr = r;
+  if (r >= E.nn) return false;
+  if (r != 0 && g.k[E.n0 + r] == 0) return false;
+  const uint32_t peer = g.node_peer[E.nbase + r];
+  if (peer < g.n_peers) atomicAdd(reinterpret_cast<unsigned long long*>(g.copies) + peer, static_cast<unsigned long long>(kq));
+  if (r == 0) return false;
+  uint32_t* const h = g.hop + E.n0 + r;
+  // (a stale kSpreadNone costs a compare-and-swap that fails; the word never returns to it)
+  return *h == kSpreadNone && atomicCAS(h, kSpreadNone, next) == kSpreadNone;
+}
+
+// the lanes with `push` append (ei, vr) to the next queue: one add per wave
+__device__ __forceinline__ void spread_append(const SpreadArgs& g, SpreadItem* __restrict__ qout, uint32_t* n_out, bool push,
+                                              uint32_t ei, uint32_t vr, uint32_t lane) {
+  const uint64_t b = __ballot(push);
+  if (!b) return;  // (wave-uniform)
+  const uint32_t leader = __builtin_ctzll(b);
+  uint32_t base = 0;
+  if (lane == leader) base = atomicAdd(n_out, static_cast<uint32_t>(__popcll(b)));
+  base = __shfl(base, static_cast<int>(leader), 64);
+  const uint32_t at = base + __popcll(b & ((1ull << lane) - 1));
+  if (push && at < g.q_cap) qout[at] = SpreadItem{ei, vr};
+}
+
+// Launch L of the BFS (kernels.hpp): the waves stride over the frontier, a
+// lane per item; items of at most g.wide child entries walk them lane by lane,
+// in step up to the wave's longest, the others are walked one after the other
+// by the whole wave.
+__global__ __launch_bounds__(kSpreadBlock) void k_spread_level(SpreadArgs g, uint32_t L) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kSpreadBlock / kWave) + threadIdx.x / kWave);
+  const uint32_t n_waves = gridDim.x * (kSpreadBlock / kWave);
+  if (blockIdx.x == 0 && threadIdx.x == 0) g.cnt[(L + 2) % 3] = 0;
+  const uint32_t n_in = min(g.cnt[L % 3], g.q_cap);
+  const SpreadItem* __restrict__ qin = g.queue + static_cast<size_t>(L & 1) * g.q_cap;
+  SpreadItem* __restrict__ qout = g.queue + static_cast<size_t>((L + 1) & 1) * g.q_cap;
+  uint32_t* const n_out = g.cnt + (L + 1) % 3;
+  for (uint64_t i0 = static_cast<uint64_t>(wave) * kWave; i0 < n_in; i0 += static_cast<uint64_t>(n_waves) * kWave) {  // (wave-uniform)
+    const bool in = i0 + lane < n_in;
+    const SpreadItem q = qin[min(static_cast<uint32_t>(i0) + lane, n_in - 1)];
+    const uint32_t ei = min(q.entry, g.n - 1);
+    const SpreadEntry E = g.entries[ei];
+    const bool ok = in && q.entry < g.n && E.c_t && q.node < E.nn;
+    uint32_t kq = 0, r0 = 0, deg = 0;
+    if (ok) {
+      kq = q.node == 0 ? E.c_t : g.k[E.n0 + q.node];
+      r0 = min(g.row_ptr[E.nbase + q.node], g.n_edges);
+      const uint32_t r1 = min(g.row_ptr[E.nbase + q.node + 1], g.n_edges);
+      deg = kq && r1 > r0 ? r1 - r0 : 0u;
+    }
+    const uint32_t dn = deg <= g.wide ? deg : 0u;
+    const uint32_t d_max = wave_max_u32(dn);
+    for (uint32_t j = 0; j < d_max; ++j) {
+      uint32_t vr = 0;
+      bool push = false;
+      if (j < dn) push = spread_edge(g, E, g.col[r0 + j], kq, L + 1, &vr);
+      spread_append(g, qout, n_out, push, ei, vr, lane);
+    }
+    uint64_t todo = __ballot(deg > g.wide);
+    while (todo) {
+      const int src = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t we = __shfl(ei, src, 64), wk = __shfl(kq, src, 64);
+      const uint32_t w0 = __shfl(r0, src, 64), w1 = w0 + __shfl(deg, src, 64);
+      const SpreadEntry W = g.entries[we];
+      for (uint32_t j0 = w0; j0 < w1; j0 += kWave) {
+        uint32_t vr = 0;
+        bool push = false;
+        if (j0 + lane < w1) push = spread_edge(g, W, g.col[j0 + lane], wk, L + 1, &vr);
+        spread_append(g, qout, n_out, push, we, vr, lane);
+      }
+    }
+  }
+}
+
+// One wave per strip: the strip's nodes with k > 0 and a hop, 64 at a time,
+// column by column of those the 64 hold -- the nodes of the column and their k
+// summed over the wave, one lane adding the pair to the wave's LDS row -- and
+// the row's pairs that are not zero into the entry's rows.
+__global__ __launch_bounds__(kAudBlock) void k_spread_sum(SpreadArgs g) {
+  __shared__ uint32_t hr[kAudBlock / kWave][kHopsCols];
+  __shared__ uint64_t hd[kAudBlock / kWave][kHopsCols];
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t w = threadIdx.x / kWave;
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + w);
+  for (uint32_t c = lane; c < kHopsCols; c += kWave) {
+    hr[w][c] = 0;
+    hd[w][c] = 0;
+  }
+  __syncthreads();
+  uint32_t ei = 0, n_vis = 0;
+  bool valid = s < g.n_strips;
+  AudStrip S{};
+  SpreadEntry E{};
+  if (valid) {
+    S = g.strips[s];
+    uint32_t lo = 0, hi = g.n;  // the last entry whose first strip is <= s: the one that holds it
+    while (lo < hi) {
+      const uint32_t mid = lo + (hi - lo) / 2;
+      if (g.entries[mid].strip0 <= s) lo = mid + 1;
+      else hi = mid;
+    }
+    valid = lo != 0;
+    ei = valid ? lo - 1 : 0;
+    E = g.entries[ei];
+    valid = valid && E.c_t && S.n && S.u0 + S.n <= E.nn;
+  }
+  if (valid) {
+    for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+      const uint32_t i = i0 + lane;
+      const uint32_t at = E.n0 + S.u0 + min(i, S.n - 1);
+      const uint32_t k = i < S.n ? g.k[at] : 0u;
+      const uint32_t h = g.hop[at];
+      const bool vis = k != 0 && h != kSpreadNone;
+      const uint32_t c = min(h, kHopsCols - 1);
+      uint64_t todo = __ballot(vis);
+      n_vis += __popcll(todo);
+      while (todo) {
+        const int src = __builtin_ctzll(todo);
+        const uint32_t cc = __shfl(c, src, 64);
+        const bool mine = vis && c == cc;
+        const uint64_t m = __ballot(mine);
+        todo &= ~m;
+        const uint64_t kc = dev::wave_sum_u64(mine ? k : 0u);
+        if (lane == 0) {
+          hr[w][cc] += __popcll(m);
+          hd[w][cc] += kc;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (!valid) return;
+  unsigned long long* const reached = reinterpret_cast<unsigned long long*>(g.reached) + static_cast<size_t>(ei) * kHopsCols;
+  unsigned long long* const deliv = reinterpret_cast<unsigned long long*>(g.deliv) + static_cast<size_t>(ei) * kHopsCols;
+  for (uint32_t c = lane; c < kHopsCols; c += kWave)
+    if (hr[w][c]) {
+      atomicAdd(reached + c, static_cast<unsigned long long>(hr[w][c]));
+      atomicAdd(deliv + c, static_cast<unsigned long long>(hd[w][c]));
+    }
+  if (lane == 0 && n_vis) atomicAdd(reinterpret_cast<unsigned long long*>(g.visited) + ei, static_cast<unsigned long long>(n_vis));
+}
+
+// a thread per peer: what it was sent beyond what it received
+__global__ __launch_bounds__(kSpreadBlock) void k_spread_dup(SpreadArgs g) {
+  const uint32_t p = blockIdx.x * kSpreadBlock + threadIdx.x;
+  if (p < g.n_peers) g.dup[p] = g.copies[p] - g.recv[p];
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -2129,6 +2415,39 @@ hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream
 hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s) {
   if (w1 <= w0 || level == 0) return hipSuccess;
   hipLaunchKernelGGL(k_dist_cut_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, level, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_nodes(const DrainArgs& a, const SpreadArgs& g, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_spread_nodes, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, a, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_unreached(const SpreadArgs& g, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_spread_unreached, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_level(const SpreadArgs& g, uint32_t level, uint32_t blocks, hipStream_t s) {
+  if (g.n == 0 || g.q_cap == 0 || blocks == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_spread_level, dim3(blocks), dim3(kSpreadBlock), 0, s, g, level);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_sum(const SpreadArgs& g, hipStream_t s) {
+  if (g.n_strips == 0 || g.n == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_spread_sum, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_dup(const SpreadArgs& g, hipStream_t s) {
+  if (g.n_peers == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_spread_dup, dim3((g.n_peers + kSpreadBlock - 1) / kSpreadBlock), dim3(kSpreadBlock), 0, s, g);
   return hipGetLastError();
 }
 

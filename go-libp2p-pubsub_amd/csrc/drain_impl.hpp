@@ -41,6 +41,10 @@
 //                     own for a sharded rank's numbering, and a bottom-up sweep
 //                     that crosses ranks through Transport::exchange; blocking
 //                     only, with buffers of its own
+//   drain_spread.cpp  ps_topic_spread (§5.5p): hops and duplicate copies for meshes
+//                     and trees alike -- the audience pass's strips and classify,
+//                     then a frontier BFS over the node space's child lists, one
+//                     launch per level; blocking only, with buffers of its own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:

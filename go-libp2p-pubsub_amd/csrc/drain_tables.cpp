@@ -526,6 +526,7 @@ void drain_destroy(ps_engine* e) {
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
   if (D.dist.h_out) (void)hipHostFree(D.dist.h_out);
+  if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);
 }
 
 }  // namespace psamd

@@ -604,6 +604,9 @@ struct ps_engine {
       bool share = true;
       // ps_peer_load, ps_load_track: a full row is counted from its words like a partial one (A/B: PSAMD_LOAD_COUNT=rows)
       bool load_rows = false;
+      // ps_topic_spread: a frontier node with more child entries than this is walked by its wave, lanes across
+      // entries; up to it by its lane alone (A/B: PSAMD_SPREAD_WIDE, 0: every node by the wave)
+      uint32_t spread_wide = 16;
     } env;
 
     hipStream_t copy_stream = nullptr;        // results leave on it, beside whatever `stream` runs next
@@ -976,6 +979,23 @@ struct ps_engine {
       uint8_t* h_out = nullptr;
       size_t out_cap = 0;
     } dist;
+
+    // ps_topic_spread (host code: drain_spread.cpp): hops and
+    // duplicate copies of meshes and trees -- k_spread_nodes behind one
+    // k_audience_classify, one k_spread_level launch per BFS level over the
+    // child lists, k_spread_sum and k_spread_dup.  Blocking only; buffers of
+    // its own.
+    struct Spread {
+      // the input block (entries | strips), classify's verdicts and counts,
+      // the per-node words k | hop, the three frontier counts with the two
+      // queues behind them, the cleared output block
+      psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_scratch, d_queue, d_out;
+      std::vector<uint8_t> stage, seed;  // (the uploads are waited for in the call)
+      // the pinned copy of the output block; behind it the frontier count the
+      // host reads between batches of level launches
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+    } spread;
   } drain;
 
   // The slot tables of ps_dist_report's cross-rank sweep (graph.cpp

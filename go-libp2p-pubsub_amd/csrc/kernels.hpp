@@ -1234,4 +1234,93 @@ hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream
 // k_dist_cut_level over work items [w0, w1): the nodes of level `level` (>= 1)
 hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s);
 
+// ---- hops and duplicate copies, meshes too (ps_topic_spread) ----
+// A frontier BFS over the CSR child lists, from the rows the window left: the
+// forwarders F of a topic are its root and every non-root node whose row holds
+// k > 0 of its c_t window messages; a forwarder's hop is its BFS distance from
+// the root within F, and a visited forwarder q sends k'(q) (c_t for the root)
+// along every child entry whose target is in F.  The entry table follows the
+// request (entry i is topic[i], row i of the per-topic outputs; entry n closes
+// it); an entry owns nn words of the two per-node arrays from n0, the root's
+// first: k, and the hop word (kSpreadNone: not visited).
+//   k_spread_nodes  one wave per strip behind k_audience_classify, a node per
+//                   lane: k into its word and into recv of the node's peer;
+//                   per entry the nodes with k > 0 and, for a tree, those
+//                   with k == 0.
+//   k_spread_unreached  a mesh's nodes with k == 0, each peer once: where a
+//                   parent lists a peer twice the node space keeps a node for
+//                   either entry, and every child entry names the later one.
+//                   One wave per strip, a node per lane (an entry's first
+//                   strip: its root too) walks its child entries; a named
+//                   node with k == 0 is counted by the entry that turns its
+//                   hop word from kSpreadNone into kSpreadNamed -- a word the
+//                   BFS never reads, so the launch may run beside the levels.
+//   k_spread_level  launch L: the frontier queue [L & 1], cnt[L % 3] items
+//                   (the host seeds queue 0 with the roots), a lane per item;
+//                   an item's child entries one by one where it has at most
+//                   `wide` of them, else by the whole wave, lanes across
+//                   entries.  A target in F adds the item's k' to copies of
+//                   its peer; a non-root target whose hop word one
+//                   compare-and-swap turns from kSpreadNone into L + 1 is
+//                   appended to queue [(L + 1) & 1], once whatever names it.
+//                   The launch clears cnt[(L + 2) % 3], which no launch before
+//                   L + 1 adds to.  The grid is the host's; its waves stride
+//                   over the items.
+//   k_spread_sum    one wave per strip: the hop words of the nodes with k > 0
+//                   into a (reached, deliv) pair per column in LDS, the pairs
+//                   that are not zero added to the entry's rows; the visited
+//                   nodes per entry.
+//   k_spread_dup    a thread per peer: dup = copies - recv (modulo 2^64).
+// Stream order is the only order between the launches; every add is a relaxed
+// device-scope atomic on integers, so the sums do not depend on the order;
+// every index that comes from a table is checked against its array.
+constexpr uint32_t kSpreadNone = 0xFFFFFFFFu;
+constexpr uint32_t kSpreadNamed = 0xFFFFFFFEu;  // the hop word of a node without messages that a child entry names
+struct SpreadEntry {
+  uint32_t topic;
+  uint32_t strip0;  // the entry's first strip (entry n: n_strips)
+  uint32_t c_t;     // the topic's messages in the window (0: the entry takes no part)
+  uint32_t nbase;   // the topic's first node (its root) in node space
+  uint32_t nn;      // its nodes, the root included
+  uint32_t n0;      // the entry's first word of k / hop
+  uint32_t mesh;    // 1: a mesh in the window's node space (k_spread_unreached counts its unreached nodes)
+  uint32_t pad;
+};
+struct SpreadItem {
+  uint32_t entry, node;  // a frontier node, topic-relative
+};
+struct SpreadArgs {
+  const AudStrip* strips;
+  uint32_t n_strips;
+  const SpreadEntry* entries;  // [n + 1]
+  uint32_t n;
+  const uint8_t* verdict;    // AudArgs::verdict after k_audience_classify
+  const uint64_t* n_exc;     // AudArgs::n_exc: 0 = every node of the strip is full
+  uint32_t count_rows;       // 1: a full row is counted from its words too (the PSAMD_LOAD_COUNT seam)
+  uint32_t wide;             // child entries from which an item is walked by the wave
+  const uint32_t* node_peer;
+  const uint32_t* row_ptr;
+  const uint32_t* col;
+  uint32_t n_edges, n_peers;
+  uint32_t* k;               // per-node words
+  uint32_t* hop;
+  SpreadItem* queue;         // [2][q_cap]
+  uint32_t q_cap;
+  uint32_t* cnt;             // [3] items of the queues, by launch % 3
+  uint64_t* reached;         // [n][kHopsCols] each, added into
+  uint64_t* deliv;
+  uint64_t* unreached;       // [n] each, added into
+  uint64_t* holders;         // nodes with k > 0
+  uint64_t* visited;
+  uint64_t* recv;            // [n_peers] each; recv and copies added into, dup written
+  uint64_t* copies;
+  uint64_t* dup;
+};
+hipError_t launch_spread_nodes(const DrainArgs& a, const SpreadArgs& g, hipStream_t s);
+hipError_t launch_spread_unreached(const SpreadArgs& g, hipStream_t s);
+// k_spread_level for level `level` on `blocks` blocks
+hipError_t launch_spread_level(const SpreadArgs& g, uint32_t level, uint32_t blocks, hipStream_t s);
+hipError_t launch_spread_sum(const SpreadArgs& g, hipStream_t s);
+hipError_t launch_spread_dup(const SpreadArgs& g, hipStream_t s);
+
 }  // namespace psamd

@@ -201,6 +201,7 @@ PROTOTYPES = [
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
     ("ps_dist_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_dist_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_topic_spread", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -944,6 +945,24 @@ class Engine:
         out = [np.empty(self.n_peers, dtype=np.uint64) for _ in range(4)]
         self._check(self._L.ps_dist_cut(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out)))
         return out[0], out[1], out[2], out[3]
+
+    def topic_spread(self, topics) -> dict:
+        """Hops and duplicate copies of the last window for the named distinct
+        topics, meshes and trees alike (ps_topic_spread): a dict of reached and
+        deliv, uint64 [n, MAX_ROUNDS], row i for topics[i] -- per hop the
+        forwarders the window reached and the messages they hold; unreached and
+        stranded, uint64 [n] -- the non-root nodes whose rows hold nothing, and
+        those that hold messages no forwarder's child entry leads to; copies
+        and dup, uint64 [n_peers] -- the copies sent to each peer and those
+        beyond what it received."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        out = {"reached": np.zeros((t.size, MAX_ROUNDS), dtype=np.uint64), "deliv": np.zeros((t.size, MAX_ROUNDS), dtype=np.uint64),
+               "unreached": np.zeros(t.size, dtype=np.uint64), "stranded": np.zeros(t.size, dtype=np.uint64),
+               "copies": np.empty(self.n_peers, dtype=np.uint64), "dup": np.empty(self.n_peers, dtype=np.uint64)}
+        self._check(self._L.ps_topic_spread(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out.values())))
+        return out
 
     def report_track(self, topics, what: int = REPORT_ALL):
         """Registers standing topics and sections (ps_report_track): from now on

@@ -925,6 +925,54 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
 int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n,
                 uint64_t* missed_out, uint64_t* cuts_out,
                 uint64_t* orphaned_out, uint64_t* lost_out);  /* [n_peers] each; any may be NULL, not all four */
+
+/* Hops and duplicate copies, for mesh topics and tree topics alike (one rank;
+ * DESIGN.md 5.5p): how deep a topic's messages travelled, and what the edges
+ * beyond a tree cost, at which peers.  Per named topic t with c_t > 0 messages
+ * in the window, on the node space that window ran on, with k(u) ps_peer_load's
+ * k -- the number of t's window messages the row of node u holds (the
+ * PSAMD_LOAD_COUNT=rows seam applies):
+ *   Forwarders.  F is the root plus every non-root node with k(u) > 0;
+ * k'(root) = c_t and k'(u) = k(u) otherwise.
+ *   Hop.  h(root) = 0; for any other u in F, h(u) = 1 + min h(q) over the
+ * child entries (q -> u) with q in F: the BFS distance from the root within F,
+ * read from the rows and not from the live mask.  The flood is
+ * level-synchronous and its seen test lets the first arrival win, so this is
+ * the hop every message reached u at.
+ *   Per topic row.  Column min(h(u), PS_MAX_ROUNDS - 1) gets reached += 1 and
+ * deliv += k(u) for every non-root u in F that the BFS visits.  Column 0
+ * stays 0; the last column collects the deeper hops, as in ps_topic_hops.
+ *   unreached[i] counts the non-root nodes with k == 0, a peer once: where a
+ * mesh parent lists a peer twice the node space holds a node for either
+ * entry, and only the one the child entries name counts.  stranded[i] counts
+ * the non-root nodes with k > 0 that the BFS never visits -- 0 on a healthy
+ * engine, reported and not assumed.
+ *   Per peer.  Every child entry (q -> u) with q in F, q visited and u in F
+ * adds k'(q) to copies[peer(u)]: every forwarder sends each message once along
+ * every child entry whose target received it.  Entries count with their
+ * multiplicity; self-loops and entries naming the root are included -- the
+ * root is no recipient, so everything sent to it is a duplicate.
+ *   dup[p] = copies[p] - recv[p], recv ps_peer_load's for the same topics:
+ * exact while every row is full or empty; computed modulo 2^64.
+ * A topic with no message in the window adds nothing; peers outside the node
+ * space add nothing.  On a tree reached / deliv equal ps_topic_hops' rows,
+ * copies equals recv and dup is 0.
+ *   ps_topic_spread answers for the last window of the last run, blocking, with
+ * ps_peer_load's window, stream-ordering and twin-join rules.  The n topics
+ * are distinct; row i of reached / deliv ([n * PS_MAX_ROUNDS]) and word i of
+ * unreached / stranded ([n]) belong to topic[i]; copies / dup are [n_peers].
+ * Any of the six may be NULL, not all; the arrays given are written in full.
+ * n == 0 is valid: the peer arrays read zero and the others are not written.
+ * PS_E_INVAL for a NULL engine, n > 0 without topic, all six outputs NULL or a
+ * topic named twice; PS_E_RANGE, nothing written, for a topic out of range;
+ * PS_E_NOTREADY before any run; PS_E_STATE on a multi-rank engine and for a
+ * tree topic that was set anew over another kind since the window.
+ *   There is no tracker and no asynchronous form: a window's depth is not
+ * known to the host before ps_wait, and the pass launches once per hop. */
+int ps_topic_spread(ps_engine* e, const uint32_t* topic, size_t n,
+                    uint64_t* reached_out, uint64_t* deliv_out,      /* [n * PS_MAX_ROUNDS], row i = topic[i] */
+                    uint64_t* unreached_out, uint64_t* stranded_out, /* [n] */
+                    uint64_t* copies_out, uint64_t* dup_out);        /* [n_peers] */
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

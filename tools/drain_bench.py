@@ -156,6 +156,19 @@ ps_dist_report(PS_REPORT_DOWNSTREAM) -- the yardstick there --: the wall per
 rank, the exchanges, the bytes a rank ships in them and the bytes of its
 records and words, the ranks' sum compared with the one-rank answer on every
 call.  Writes DIR/dist_cut_bench.json.
+
+--spread: hops and duplicate copies of a mesh (ps_topic_spread).  The tool
+builds its own mesh -- --spread-peers peers (default 2^20), random out-degree
+0..6, 3 % dead, one topic, 1,024 messages -- and a second shape with one hub of
+--spread-hub children below the root.  Per shape: the device phases of the
+call (PSAMD_DRAIN_TIMING: classify, nodes, levels with their launch count, sum,
+copy) beside ps_peer_load's on the same window -- the yardstick: the same
+front, comparable work per node -- with a frontier node walked by its wave
+from 0, 16 (the default), 64 and never (PSAMD_AB=1 PSAMD_SPREAD_WIDE); then the
+walls of ps_topic_spread, ps_peer_load and the same answer derived on the host
+(ps_peer_load's recv, the child lists, a frontier BFS in numpy), --reps
+repetitions alternating in one process, the answers compared array for array.
+Writes DIR/spread_bench.json.
 """
 from __future__ import annotations
 
@@ -2202,6 +2215,142 @@ def shared_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def spread_graph(n, hub, seed):
+    """(row_ptr, col, root, live): out-degree uniform in 0..6, children uniform
+    over the peers but the root; the root has six; 3 % dead.  hub > 0: peer 1, a
+    child of the root, lists `hub` distinct peers instead."""
+    rng = np.random.default_rng(seed)
+    deg = rng.integers(0, 7, size=n)
+    deg[0] = 6
+    if hub:
+        deg[1] = hub
+    rp = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(deg, out=rp[1:])
+    col = rng.integers(1, n, size=int(rp[-1]))
+    if hub:
+        col[rp[0]] = 1
+        col[rp[1]:rp[2]] = rng.choice(np.arange(2, n), size=hub, replace=False)
+    live = (rng.random(n) >= 0.03).astype(np.uint8)
+    live[:2] = 1
+    return rp.astype(np.uint32), col.astype(np.uint32), 0, live
+
+
+def host_topic_spread(eng, rp, cl, root, c):
+    """The answer as a caller derives it without ps_topic_spread: who holds
+    the messages from ps_peer_load, then a frontier BFS over the child lists in
+    numpy (the rows of this workload are full or empty: k is c or 0)."""
+    recv, _ = eng.peer_load([0])
+    n = recv.size
+    rp = rp.astype(np.int64)
+    in_f = recv > 0
+    in_f[root] = True
+    member = np.zeros(n, dtype=bool)  # named by a child entry of a member: the node space
+    level = np.full(n, -1, dtype=np.int64)
+    level[root] = 0
+    copies = np.zeros(n, dtype=np.int64)
+    cur, h = np.array([root], dtype=np.int64), 0
+    while cur.size:
+        h += 1
+        lo, ln = rp[cur], rp[cur + 1] - rp[cur]
+        idx = np.repeat(lo - np.concatenate([[0], np.cumsum(ln)[:-1]]), ln) + np.arange(int(ln.sum()))
+        tgt = cl[idx].astype(np.int64)
+        tgt = tgt[in_f[tgt]]
+        copies += np.bincount(tgt, minlength=n) * c
+        new = np.unique(tgt[level[tgt] < 0])
+        level[new] = h
+        cur = new
+    # the node space: everything the root reaches over all child lists
+    member[root] = True
+    cur = np.array([root], dtype=np.int64)
+    while cur.size:
+        lo, ln = rp[cur], rp[cur + 1] - rp[cur]
+        idx = np.repeat(lo - np.concatenate([[0], np.cumsum(ln)[:-1]]), ln) + np.arange(int(ln.sum()))
+        new = np.unique(cl[idx].astype(np.int64))
+        new = new[~member[new]]
+        member[new] = True
+        cur = new
+    vis = level > 0
+    cols = np.minimum(level[vis], PE.MAX_ROUNDS - 1)
+    reached = np.bincount(cols, minlength=PE.MAX_ROUNDS).astype(np.uint64)
+    out = {"reached": reached[None, :], "deliv": (reached * np.uint64(c))[None, :],
+           "unreached": np.array([int(member.sum()) - 1 - int((recv > 0).sum())], dtype=np.uint64),
+           "stranded": np.array([int(((recv > 0) & (level < 0)).sum())], dtype=np.uint64),
+           "copies": copies.astype(np.uint64), "dup": (copies - recv.astype(np.int64)).astype(np.uint64)}
+    return out
+
+
+def spread_main(a):
+    """--spread (see above).  Writes DIR/spread_bench.json."""
+    c = 1024
+    res = {"n_peers": a.spread_peers, "n_msgs": c, "reps": a.reps, "hub": a.spread_hub, "shapes": {}}
+
+    def engine(env, g):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_SPREAD_WIDE"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(a.spread_peers, 1)
+        eng.set_children(0, g[2], g[0], g[1])
+        eng.set_live(g[3])
+        eng.publish(np.zeros(c))
+        return eng, eng.run()
+
+    for shape, hub in (("random", 0), ("hub", a.spread_hub)):
+        g = spread_graph(a.spread_peers, hub, a.seed)
+        row = {"edges": int(g[1].size), "wide": {}}
+        for wide in (16, 0, 64, 1 << 20):
+            env = {"PSAMD_DRAIN_TIMING": "1"}
+            if wide != 16:
+                env.update(PSAMD_AB="1", PSAMD_SPREAD_WIDE=str(wide))
+            eng, st = engine(env, g)
+            with eng:
+                rows = []
+                for _ in range(a.reps + 1):  # (the first call builds the window's tables and allocates)
+                    with StderrCapture() as cap:
+                        got = eng.topic_spread([0])
+                    r = phase_line(cap.text, "topic_spread")
+                    for k in ("strips", "nodes", "row_bytes", "level_launches"):
+                        r[k] = int(re.search(rf"\b{k} (\d+)", cap.text).group(1))
+                    rows.append(r)
+                row["wide"][str(wide)] = rows[1:]
+                if wide == 16:
+                    lrows = []
+                    for _ in range(a.reps + 1):
+                        with StderrCapture() as cap:
+                            eng.peer_load([0])
+                        lrows.append(phase_line(cap.text, "peer_load"))
+                    row["load_phases"] = lrows[1:]
+                    assert int(got["deliv"].sum()) == st.deliveries and int(got["dup"].astype(np.int64).sum()) == st.duplicates
+                    row.update(deliveries=int(st.deliveries), duplicates=int(st.duplicates), rounds=int(st.rounds),
+                               run_ms=float(st.run_ms), reached=int(got["reached"].sum()), unreached=int(got["unreached"][0]),
+                               stranded=int(got["stranded"][0]), depth=int(np.nonzero(got["reached"][0])[0].max()),
+                               dup_peers=int((got["dup"] > 0).sum()), dup_max=int(got["dup"].max()))
+        eng, _ = engine({}, g)
+        with eng:
+            walls = {"spread": [], "load": [], "host": []}
+            for _ in range(a.reps + 1):
+                t0 = time.perf_counter()
+                got = eng.topic_spread([0])
+                walls["spread"].append(1e3 * (time.perf_counter() - t0))
+                t0 = time.perf_counter()
+                eng.peer_load([0])
+                walls["load"].append(1e3 * (time.perf_counter() - t0))
+                t0 = time.perf_counter()
+                want = host_topic_spread(eng, g[0], g[1], g[2], c)
+                walls["host"].append(1e3 * (time.perf_counter() - t0))
+                for k in want:
+                    assert np.array_equal(got[k], want[k]), f"ps_topic_spread {k} differs from the host derivation"
+        row["spread_wall_ms"], row["load_wall_ms"], row["host_derivation_wall_ms"] = (walls[k][1:] for k in ("spread", "load", "host"))
+        row["answers_agree"] = True
+        row["host_over_spread_wall"] = float(np.median(row["host_derivation_wall_ms"]) / np.median(row["spread_wall_ms"]))
+        row["spread_over_load_wall"] = float(np.median(row["spread_wall_ms"]) / np.median(row["load_wall_ms"]))
+        res["shapes"][shape] = row
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "spread_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WL.CONFIGS))
@@ -2232,7 +2381,12 @@ def main():
                     help="ps_dist_report against ps_peer_report on one rank; the collective call on 2 and 4 loopback ranks")
     ap.add_argument("--dist-cut", action="store_true",
                     help="ps_dist_cut against ps_peer_cut on one rank; against ps_dist_report's downstream on 2 and 4 loopback ranks")
+    ap.add_argument("--spread", action="store_true", help="ps_topic_spread on a mesh of its own against ps_peer_load and the host derivation")
+    ap.add_argument("--spread-peers", type=int, default=1 << 20)
+    ap.add_argument("--spread-hub", type=int, default=4096)
     a = ap.parse_args()
+    if a.spread:
+        return spread_main(a)
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
     if a.dist_report:
         return dist_report_main(a, wl)
