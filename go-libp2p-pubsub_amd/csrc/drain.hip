@@ -49,6 +49,13 @@
 //                         children: one that lacks messages is a cut point, its
 //                         subtree's words into its peer's three sums
 //   k_cut_top             the narrow levels under a root in one block
+// and, for ps_topic_blame / ps_blame (§5.5q), each missed subscriber and its cut point:
+//   k_blame_top           the narrow levels under a root in one block, downwards:
+//                         a node hands its children their cut point and its level
+//   k_blame_level         one launch per BFS level, top-down, behind it
+//   k_blame_count / _emit the nodes that lack messages, strip by strip, into
+//                         records in node order
+//   k_blame_gather        a (topic, node) query's four facts from the words
 // and, for ps_peer_report / ps_report_track (§5.5m), those four answers from one pass:
 //   k_report_nodes        behind one k_audience_classify: a node's k once, into
 //                         the sections selected per launch (load's sums, the hop
@@ -915,6 +922,189 @@ __global__ __launch_bounds__(kDownBlock) void k_cut_top(CutArgs g) {
     cut_nodes(g, E, lv, d, lv[d], lv[d + 1], threadIdx.x, kDownBlock);
     __syncthreads();
   }
+}
+
+// ---- each missed subscriber and its cut point (ps_topic_blame, ps_blame) --------
+
+// cut_nodes' visit of the nodes [lo, hi) of level d < depth, downwards: every
+// child of level d + 1 gets its two words from its one parent -- none where
+// the child is full; itself and d + 1 where the parent is full (level 0
+// counts as full, whatever k holds for it); else the parent's own two, which
+// the level above left.  One writer per word: plain stores.
+__device__ __forceinline__ void blame_nodes(const BlameArgs& g, const DownEntry& E, const uint32_t* __restrict__ lv, uint32_t d,
+                                            uint32_t lo, uint32_t hi, uint32_t tid, uint32_t nt) {
+  const uint32_t lane = tid & (kWave - 1);
+  const uint32_t c0 = lv[d + 1], c1 = lv[d + 2];
+  const uint32_t rp0 = g.d.row_ptr[E.nbase + lv[d]];
+  const uint32_t* const k = g.d.k + E.n0;
+  uint32_t* const cut_node = g.cut_node + E.n0;
+  uint32_t* const cut_level = g.cut_level + E.n0;
+  for (uint32_t u0 = lo + (tid & ~(kWave - 1)); u0 < hi; u0 += nt) {  // (wave-uniform)
+    const bool in = u0 + lane < hi;
+    const uint32_t u = min(u0 + lane, hi - 1);
+    const uint32_t r0 = g.d.row_ptr[E.nbase + u], r1 = g.d.row_ptr[E.nbase + u + 1];
+    // (clamped into level d + 1, whatever the CSR says)
+    const uint32_t cb = min(c0 + (r0 - rp0), c1);
+    const uint32_t deg = in ? min(r1 - r0, c1 - cb) : 0u;
+    const bool wide = deg > kWave;
+    const bool full = d == 0 || k[u] == E.c_t;
+    // what a child that lacks messages inherits under a node that does too
+    const uint32_t pn = full ? 0u : cut_node[u], pl = full ? d + 1 : cut_level[u];
+    if (!wide) {
+      for (uint32_t j = 0; j < deg; ++j) {
+        const uint32_t c = cb + j;
+        const bool cfull = k[c] == E.c_t;
+        cut_node[c] = cfull ? kBlameNone : full ? c : pn;
+        cut_level[c] = cfull ? kBlameNone : pl;
+      }
+    }
+    uint64_t todo = __ballot(wide);
+    while (todo) {
+      const uint32_t j = __builtin_ctzll(todo);
+      todo &= todo - 1;
+      const uint32_t b = __shfl(cb, static_cast<int>(j), 64), n = __shfl(deg, static_cast<int>(j), 64);
+      const bool pfull = __shfl(static_cast<int>(full), static_cast<int>(j), 64) != 0;
+      const uint32_t qn = __shfl(pn, static_cast<int>(j), 64), ql = __shfl(pl, static_cast<int>(j), 64);
+      for (uint32_t i = lane; i < n; i += kWave) {
+        const uint32_t c = b + i;
+        const bool cfull = k[c] == E.c_t;
+        cut_node[c] = cfull ? kBlameNone : pfull ? c : qn;
+        cut_level[c] = cfull ? kBlameNone : ql;
+      }
+    }
+  }
+}
+
+// One block per entry, first: the levels [0, top), none wider than the block,
+// walked downwards; the barrier between two levels orders the block's own
+// stores and loads.  It leaves the words of the levels 1 .. top.
+__global__ __launch_bounds__(kDownBlock) void k_blame_top(BlameArgs g) {
+  const DownEntry E = g.d.entries[blockIdx.x];
+  if (!E.c_t || g.d.entries[blockIdx.x + 1].strip0 == E.strip0) return;  // (block-uniform)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  const uint32_t top = min(E.top, E.depth);
+  for (uint32_t d = 0; d < top; ++d) {
+    blame_nodes(g, E, lv, d, lv[d], lv[d + 1], threadIdx.x, kDownBlock);
+    __syncthreads();
+  }
+}
+
+// One block per work item of this launch: a run of nodes of a level >= top,
+// whose own words the launch before wrote (level top's: k_blame_top).  Stream
+// order is the only order between the launches' waves.
+__global__ __launch_bounds__(kDownBlock) void k_blame_level(BlameArgs g, uint32_t w0) {
+  const DownWork W = g.d.work[w0 + blockIdx.x];
+  const DownEntry E = g.d.entries[W.entry];
+  if (W.level >= E.depth) return;  // (block-uniform; leaves have no children)
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  blame_nodes(g, E, lv, W.level, max(W.lo, lv[W.level]), min(W.hi, lv[W.level + 1]), threadIdx.x, kDownBlock);
+}
+
+// the last level d in [0, depth] with lv[d] <= u (lv[0] = 0)
+__device__ __forceinline__ uint32_t blame_level_of(const uint32_t* __restrict__ lv, uint32_t depth, uint32_t u) {
+  uint32_t lo = 0, hi = depth + 1;
+  while (hi - lo > 1) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (lv[mid] <= u) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// the entry that holds strip s: the last one whose first strip is <= s (false: none)
+__device__ __forceinline__ bool blame_entry_of(const DownArgs& d, uint32_t s, DownEntry* E) {
+  uint32_t lo = 0, hi = d.n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (d.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return false;
+  *E = d.entries[lo - 1];
+  return true;
+}
+
+// One wave per strip, one node per lane: the strip's nodes that lack messages.
+// The wave behind the last strip writes the closing 0.
+__global__ __launch_bounds__(kAudBlock) void k_blame_count(BlameArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s > g.d.n_strips) return;
+  uint32_t c = 0;
+  DownEntry E;
+  if (s < g.d.n_strips && blame_entry_of(g.d, s, &E)) {
+    const AudStrip S = g.d.strips[s];
+    const uint32_t* __restrict__ k = g.d.k + E.n0;
+    for (uint32_t i = lane; i < S.n; i += kWave) c += k[S.u0 + i] < E.c_t;
+  }
+  c = wave_sum_u32(c);
+  if (lane == 0) g.n_rec[s] = c;
+}
+
+// One wave per strip: the nodes that lack messages, in node order (ballot and
+// lane prefix), from the strip's offset on.  The first n + 1 threads of the
+// grid leave the entries' record offsets.
+__global__ __launch_bounds__(kAudBlock) void k_blame_emit(BlameArgs g) {
+  const uint32_t tid = blockIdx.x * kAudBlock + threadIdx.x;
+  if (tid <= g.d.n) g.rec_off[tid] = g.off[min(g.d.entries[tid].strip0, g.d.n_strips)];
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.d.n_strips || g.n_rec[s] == 0) return;
+  DownEntry E;
+  if (!blame_entry_of(g.d, s, &E)) return;
+  const AudStrip S = g.d.strips[s];
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  const uint32_t nn = lv[E.depth + 1];
+  const uint32_t* __restrict__ k = g.d.k + E.n0;
+  const uint32_t* __restrict__ cut_node = g.cut_node + E.n0;
+  const uint32_t* __restrict__ cut_level = g.cut_level + E.n0;
+  uint64_t at = g.off[s];
+  for (uint32_t i0 = 0; i0 < S.n; i0 += kWave) {
+    const uint32_t i = i0 + lane;
+    const uint32_t u = S.u0 + min(i, S.n - 1);
+    const uint32_t have = k[u];
+    const bool rec = i < S.n && have < E.c_t;
+    const uint64_t b = __ballot(rec);
+    const uint64_t to = at + __popcll(b & ((1ull << lane) - 1));
+    if (rec && to < g.cap) {
+      const uint32_t cn = cut_node[u];
+      if (g.rec_peer) g.rec_peer[to] = g.d.node_peer[E.nbase + u];
+      if (g.rec_cut_peer) g.rec_cut_peer[to] = cn < nn ? g.d.node_peer[E.nbase + cn] : kBlameNone;
+      if (g.rec_hop) g.rec_hop[to] = blame_level_of(lv, E.depth, u);
+      if (g.rec_cut_hop) g.rec_cut_hop[to] = cut_level[u];
+      if (g.rec_missed) g.rec_missed[to] = E.c_t - have;
+    }
+    at += __popcll(b);
+  }
+}
+
+// One thread per query.  A peer without a node of the topic: none, none, none,
+// 0.  The root, a full row and every node of a topic idle in the window: none,
+// its level, none, 0 -- the latter without a read of the sweep's words.
+__global__ __launch_bounds__(kAudBlock) void k_blame_gather(BlameArgs g, BlameGather q) {
+  const uint32_t i = blockIdx.x * kAudBlock + threadIdx.x;
+  if (i >= q.n) return;
+  const DrainQuery Q = q.queries[i];
+  uint32_t cut_peer = kBlameNone, hop = kBlameNone, cut_hop = kBlameNone, missed = 0;
+  if (Q.node != kBlameNone) {
+    const BlameTopic T = q.topics[Q.topic];
+    hop = blame_level_of(q.levels + T.lvl0, T.depth, Q.node);
+    if (T.entry != kBlameNone && Q.node != 0) {
+      const DownEntry E = g.d.entries[T.entry];
+      const uint32_t nn = g.d.levels[E.lvl0 + E.depth + 1];
+      const uint32_t have = Q.node < nn ? g.d.k[E.n0 + Q.node] : E.c_t;
+      if (have < E.c_t) {
+        const uint32_t cn = g.cut_node[E.n0 + Q.node];
+        missed = E.c_t - have;
+        cut_hop = g.cut_level[E.n0 + Q.node];
+        cut_peer = cn < nn ? g.d.node_peer[E.nbase + cn] : kBlameNone;
+      }
+    }
+  }
+  if (q.cut_peer) q.cut_peer[i] = cut_peer;
+  if (q.hop) q.hop[i] = hop;
+  if (q.cut_hop) q.cut_hop[i] = cut_hop;
+  if (q.missed) q.missed[i] = missed;
 }
 
 // ---- the four answers from one pass (ps_peer_report, ps_report_track) ----------
@@ -2328,6 +2518,39 @@ hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStrea
 hipError_t launch_cut_top(const CutArgs& g, hipStream_t s) {
   if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_cut_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_blame_top(const BlameArgs& g, hipStream_t s) {
+  if (g.d.n_strips == 0 || g.d.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_blame_top, dim3(g.d.n), dim3(kDownBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_blame_level(const BlameArgs& g, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0) return hipSuccess;
+  hipLaunchKernelGGL(k_blame_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_blame_count(const BlameArgs& g, hipStream_t s) {
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_blame_count, dim3((g.d.n_strips + 1 + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+// (the grid covers the strips, a wave each, and the n + 1 record offsets, a thread each)
+hipError_t launch_blame_emit(const BlameArgs& g, hipStream_t s) {
+  const uint32_t per = kAudBlock / kWave;
+  const uint32_t by_strip = (g.d.n_strips + per - 1) / per, by_entry = (g.d.n + 1 + kAudBlock - 1) / kAudBlock;
+  const uint32_t blocks = by_strip > by_entry ? by_strip : by_entry;
+  hipLaunchKernelGGL(k_blame_emit, dim3(blocks), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_blame_gather(const BlameArgs& g, const BlameGather& q, hipStream_t s) {
+  if (q.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_blame_gather, dim3((q.n + kAudBlock - 1) / kAudBlock), dim3(kAudBlock), 0, s, g, q);
   return hipGetLastError();
 }
 

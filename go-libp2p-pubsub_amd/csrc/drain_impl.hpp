@@ -45,6 +45,12 @@
 //                     and trees alike -- the audience pass's strips and classify,
 //                     then a frontier BFS over the node space's child lists, one
 //                     launch per level; blocking only, with buffers of its own
+//   drain_blame.cpp   ps_topic_blame, ps_blame (§5.5q): each node that lacks
+//                     messages with the cut point it hangs behind -- the
+//                     downstream pass's plan and front (down_sync_stage,
+//                     down_front below), then a top-down sweep over the same
+//                     levels, records by count / scan / emit or a gather for
+//                     explicit queries; blocking only, with buffers of its own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:

@@ -527,6 +527,8 @@ void drain_destroy(ps_engine* e) {
   if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
   if (D.dist.h_out) (void)hipHostFree(D.dist.h_out);
   if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);
+  for (uint8_t* h : {D.blame.h_off, D.blame.h_rec, D.blame.h_out})
+    if (h) (void)hipHostFree(h);
 }
 
 }  // namespace psamd

@@ -996,6 +996,30 @@ struct ps_engine {
       uint8_t* h_out = nullptr;
       size_t out_cap = 0;
     } spread;
+
+    // ps_topic_blame / ps_blame (host code: drain_blame.cpp):
+    // each missed subscriber with its cut point -- k_blame_top and one
+    // k_blame_level launch per BFS level, top-down, behind the downstream
+    // pass's front (k_audience_classify, k_audience_weights) over its plan;
+    // then k_blame_count, the scan and k_blame_emit into records, or
+    // k_blame_gather for explicit queries.  Blocking only; buffers of its own.
+    struct Blame {
+      // the front's buffers (plan.sync) and the staged input block
+      // (plan.stage), as down_sync_stage and down_front take them: nothing
+      // else of the downstream pass's shape is used
+      Downstream plan;
+      // the sweep's words cut_node | cut_level, a word per node each; the
+      // strips' record counts, their exclusive sum and its temporary; the
+      // entries' record offsets; the record arrays the call was asked for
+      psamd::DevBuf d_cut, d_cnt, d_off, d_scan, d_rec_off, d_rec;
+      // ps_blame: queries | topic table | levels in one block, the four outputs
+      psamd::DevBuf d_q, d_out;
+      std::vector<uint8_t> qstage;  // (the upload is waited for in the call)
+      // pinned: rec_off, the record arrays lent until the next ps_topic_blame,
+      // and ps_blame's outputs
+      uint8_t *h_off = nullptr, *h_rec = nullptr, *h_out = nullptr;
+      size_t off_cap = 0, rec_cap = 0, out_cap = 0;
+    } blame;
   } drain;
 
   // The slot tables of ps_dist_report's cross-rank sweep (graph.cpp

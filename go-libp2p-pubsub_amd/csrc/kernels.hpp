@@ -1039,6 +1039,80 @@ hipError_t launch_cut_level(const CutArgs& g, uint32_t w0, uint32_t w1, hipStrea
 // k_cut_top: one block per entry, behind the last level launch
 hipError_t launch_cut_top(const CutArgs& g, hipStream_t s);
 
+// ---- each missed subscriber and its cut point (ps_topic_blame, ps_blame) --
+// The pass above asks what hangs behind a cut point; this one asks, for every
+// node that lacks messages, which cut point it hangs behind.  The same strips,
+// entries, level tables and work list (DownArgs; w_n, w_k, below and carried
+// stay unused) and k from k_audience_weights, walked the other way: with
+// cut(u) = u where u's parent is full (level 0 counts as full) and
+// cut(parent(u)) else, for every non-root node u with k(u) < c_t, two scratch
+// words of the pass's own per node, an entry's from n0 as k's:
+//   cut_node[u]   cut(u), topic-relative; kBlameNone where k(u) == c_t
+//   cut_level[u]  the BFS level of cut(u); kBlameNone where k(u) == c_t
+//   k_blame_top     one block per entry walks the levels [0, top) downwards, a
+//                   barrier between two levels: a node of level d visits its
+//                   CSR child range in level d + 1 (cut_nodes' range
+//                   arithmetic and clamping; a lane a node, a node with more
+//                   than a wave's worth of children spread over the wave) and
+//                   writes each child's two words -- (child, d + 1) where the
+//                   node is full, else the node's own two.
+//   k_blame_level   the same visit over work items [w0, w1); the launches run
+//                   in the reverse of the bottom-up order, behind k_blame_top,
+//                   so a level's own words were written by the launch before
+//                   (level `top`'s by k_blame_top).  Every word has one
+//                   writer: no atomics, plain stores; stream order is the
+//                   only order between the launches.
+//   k_blame_count   one wave per strip: its nodes with k < c_t into n_rec
+//                   (n_rec[n_strips] = 0); drain_scan turns them into off.
+//   k_blame_emit    one wave per strip: those nodes in node order from record
+//                   off[strip] on, below cap -- the node's peer, the peer of
+//                   cut(u), the node's level (its topic's level table, binary
+//                   search), cut_level and c_t - k; an array that is null is
+//                   not written.  rec_off[i] = off[entries[i].strip0] for i in
+//                   [0, n]: the records of entry i, rec_off[n] the total.
+//   k_blame_gather  one thread per DrainQuery {topic, node} (node: topic-
+//                   relative, the root 0, kBlameNone: the peer holds no node of
+//                   the topic) through a table per topic id: the topic's entry
+//                   (kBlameNone: idle in the window -- the sweep's scratch is
+//                   not read) and its level table among `levels`.
+constexpr uint32_t kBlameNone = 0xFFFFFFFFu;  // PS_NONE
+struct BlameTopic {
+  uint32_t entry;  // the topic's entry among DownArgs::entries; kBlameNone: none, or idle in the window
+  uint32_t lvl0;   // its level table in BlameGather::levels: depth + 2 words
+  uint32_t depth;
+  uint32_t pad;
+};
+struct BlameArgs {
+  DownArgs d;
+  uint32_t* cut_node;
+  uint32_t* cut_level;
+  uint64_t* n_rec;       // [n_strips + 1]
+  const uint64_t* off;   // [n_strips + 1] the exclusive sum of n_rec
+  uint64_t* rec_off;     // [n + 1]
+  uint32_t* rec_peer;    // [cap] each; null: not asked for
+  uint32_t* rec_cut_peer;
+  uint32_t* rec_hop;
+  uint32_t* rec_cut_hop;
+  uint32_t* rec_missed;
+  uint64_t cap;
+};
+struct BlameGather {
+  const DrainQuery* queries;  // [n]
+  uint32_t n;
+  const BlameTopic* topics;   // by topic id
+  const uint32_t* levels;
+  uint32_t* cut_peer;         // [n] each, written in full
+  uint32_t* hop;
+  uint32_t* cut_hop;
+  uint32_t* missed;
+};
+// k_blame_top, then k_blame_level over work items [w0, w1)
+hipError_t launch_blame_top(const BlameArgs& g, hipStream_t s);
+hipError_t launch_blame_level(const BlameArgs& g, uint32_t w0, uint32_t w1, hipStream_t s);
+hipError_t launch_blame_count(const BlameArgs& g, hipStream_t s);
+hipError_t launch_blame_emit(const BlameArgs& g, hipStream_t s);
+hipError_t launch_blame_gather(const BlameArgs& g, const BlameGather& q, hipStream_t s);
+
 // ---- the four answers from one pass (ps_peer_report, ps_report_track) --
 // What the four families above compute, each behind a classify of its own,
 // behind one: k_report_nodes works a node's k out once and feeds every section

@@ -196,6 +196,9 @@ PROTOTYPES = [
     ("ps_peer_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
     ("ps_cut_track", C.c_int, [_P, _u32p, C.c_size_t]),
     ("ps_cut_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_topic_blame", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p),
+                                 C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u32p), _u64p]),
+    ("ps_blame", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u32p, _u32p, _u32p, _u32p]),
     ("ps_peer_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_report_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32]),
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
@@ -890,6 +893,38 @@ class Engine:
         nw, nsk = C.c_uint64(), C.c_uint64()
         self._check(self._L.ps_cut_take(self._h, *(_p(a, C.c_uint64) for a in out), C.byref(nw), C.byref(nsk)))
         return out[0], out[1], out[2], out[3], nw.value, nsk.value
+
+    def topic_blame(self, topics) -> dict:
+        """Every non-root node of the named distinct tree topics that lacks
+        messages of the last window, with the cut point to blame
+        (ps_topic_blame): a dict of numpy copies -- rec_off[n + 1], and per
+        record, in node order, peer, cut_peer (the peer of the nearest node on
+        the way up that lacks messages under a full parent), hop and cut_hop
+        (their BFS levels) and missed.  Topic i's records are
+        [rec_off[i], rec_off[i + 1])."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        off = _u64p()
+        ptrs = [_u32p() for _ in range(5)]
+        total = C.c_uint64()
+        self._check(self._L.ps_topic_blame(self._h, _p(t, C.c_uint32), t.size, C.byref(off), *(C.byref(p) for p in ptrs),
+                                           C.byref(total)))
+        out = {"rec_off": _view(off, t.size + 1, np.uint64).copy()}
+        for k, p in zip(("peer", "cut_peer", "hop", "cut_hop", "missed"), ptrs):
+            out[k] = _view(p, total.value, np.uint32).copy()
+        return out
+
+    def blame(self, topics, peers) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """topic_blame's facts for explicit (topic, peer) queries, repeats and
+        any order allowed (ps_blame): (cut_peer, hop, cut_hop, missed), uint32
+        [n] each.  The root, a peer with a full row and any node of a topic
+        idle in the window: cut_peer = cut_hop = NONE, missed 0, hop its level;
+        a peer outside the topic's node space: NONE, NONE, NONE, 0."""
+        t, p, tp, pp = _queries(topics, peers)
+        out = [np.empty(t.size, dtype=np.uint32) for _ in range(4)]
+        self._check(self._L.ps_blame(self._h, tp, pp, t.size, *(_p(a, C.c_uint32) for a in out)))
+        return out[0], out[1], out[2], out[3]
 
     def _report_arrays(self, n_topics: int, what: int) -> tuple[dict, Report]:
         """The selected sections' arrays (hop arrays [n_topics, MAX_ROUNDS],

@@ -788,6 +788,61 @@ int ps_cut_track(ps_engine* e, const uint32_t* topic, size_t n);
 int ps_cut_take(ps_engine* e, uint64_t* missed_out, uint64_t* cuts_out,
                 uint64_t* orphaned_out, uint64_t* lost_out,     /* [n_peers], nullable */
                 uint64_t* n_windows_out, uint64_t* n_skipped_out);
+/* Each missed subscriber and its cut point: "subscriber X did not get the
+ * window's messages: where was its path cut, and how far up?" (one rank, tree
+ * topics, the last window of the last run, blocking).
+ * ps_drain_topics lists who missed, ps_peer_cut sums per cut point; these two
+ * calls join a missed subscriber to the peer to blame.  Per named tree topic t
+ * with c_t > 0 window messages, on the node space that window ran on: k(u) is
+ * ps_peer_cut's k and the root counts as full; miss(u) = c_t - k(u), 0 for
+ * the root; a cut point is a non-root node with k < c_t whose parent is full
+ * -- ps_peer_cut's definition, word for word.  For a non-root node u with
+ * miss(u) > 0, cut(u) is the nearest cut point on the path from u up to the
+ * root, u itself included: u if its parent is full, and else cut(parent(u)).
+ * This is well defined without assuming that a row is a subset of its
+ * parent's: the walk ends at the root's child at the latest.  hop(u) is u's
+ * BFS level, cut_hop(u) the level of cut(u): exact uint32_t values, with no
+ * clamp at PS_MAX_ROUNDS.
+ *   ps_topic_blame: the records of topic[i] are rec_off[i] .. rec_off[i+1],
+ * total = rec_off[n]; one record per non-root node with miss > 0, in
+ * ascending node (breadth-first) order -- for a tree topic entry for entry the
+ * order and the set of ps_drain_topics' exceptions for the same request.  A
+ * record holds the node's peer, the peer of cut(u), hop(u), cut_hop(u) and
+ * miss(u).  A topic with no message in the window has no records.  The arrays
+ * are lent from pinned memory the engine owns, as ps_drain_topics lends its
+ * own, valid until the next ps_topic_blame or ps_destroy.  Any of the five
+ * record pointers may be NULL: that array is neither copied nor lent.
+ * rec_off_out and total_out are required.  PS_E_INVAL for a NULL engine,
+ * rec_off_out or total_out NULL, n > 0 without topic, or a topic named twice;
+ * PS_E_RANGE, nothing written, for a topic out of range; PS_E_NOTREADY before
+ * any run; PS_E_STATE, nothing written, on a multi-rank engine, when a named
+ * topic is a mesh in that window's node space, and for a topic that was set
+ * anew over another kind since the window.  n == 0 is valid: rec_off = {0},
+ * total 0.  Window, stream-ordering and twin-join rules as ps_peer_load's.
+ *   ps_blame gives the same facts for n explicit (topic, peer) queries, which
+ * may repeat and come in any order; the topics need not be distinct.  A query
+ * whose peer is the root or holds a full row gets cut_peer = cut_hop =
+ * PS_NONE, missed = 0 and hop = its level; so does every query of a topic
+ * with no message in the window.  A peer outside the topic's node space
+ * (unattached or orphan) gets PS_NONE in cut_peer, hop and cut_hop, and missed
+ * = 0.  Any of the four outputs may be NULL, not all four; those given are
+ * written in full.  Errors as ps_topic_blame's (repeats are no error), with
+ * PS_E_RANGE, nothing written, for a topic or peer out of range and
+ * PS_E_STATE if any queried topic is a mesh.
+ *   There is no tracker and no _begin / _end form: a run's records are
+ * variable-size per window, and the sink machinery for that is its own piece
+ * of work. */
+int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n,
+                   const uint64_t** rec_off_out,      /* [n + 1]          */
+                   const uint32_t** rec_peer_out,     /* [total] each     */
+                   const uint32_t** rec_cut_peer_out,
+                   const uint32_t** rec_hop_out,
+                   const uint32_t** rec_cut_hop_out,
+                   const uint32_t** rec_missed_out,
+                   uint64_t* total_out);
+int ps_blame(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n,
+             uint32_t* cut_peer_out, uint32_t* hop_out,
+             uint32_t* cut_hop_out, uint32_t* missed_out);   /* [n] each */
 
 /* The four answers above from one pass: per-peer load, deliveries by hop, the
  * audience behind each peer and the losses blamed on their cut points, for an

@@ -125,6 +125,17 @@ per loop) and beside load, hop and downstream tracking, the three alternating
 in one process, the totals against steps x the blocking answer.  Writes
 DIR/cut_bench.json.
 
+--blame: each missed subscriber and its cut point (ps_topic_blame) over every
+topic after one step under --cut's live mask, --reps repetitions alternating in
+one process with its two yardsticks: (a) ps_peer_cut on the same window -- the
+device phases of both (PSAMD_DRAIN_TIMING; ps_topic_blame's: classify, weights,
+sweep, count + scan, emit, copy) and the walls --, and (b) the derivation a
+caller has without it -- ps_drain_topics + ps_topic_get_parents per topic + a
+numpy walk from the root down -- and its wall, the two answers compared record
+for record on every repetition; the records, the bytes copied, and one ps_blame
+over the records' own (topic, peer) pairs against them.  Writes
+DIR/blame_bench.json.
+
 --report: the four answers from one pass (ps_peer_report, all sections) over
 every topic after one step under --cut's live mask, --reps repetitions
 alternating in one process with the sequence ps_peer_load + ps_topic_hops +
@@ -1327,11 +1338,13 @@ def host_peer_downstream(eng, wl, topics):
     return below, carried
 
 
-def host_topic_trees(eng, wl, topics):
+def host_topic_trees(eng, wl, topics, with_exc=False):
     """What the host derivations over subtrees start from, per topic with
     messages: (c, parents, root, k per peer -- the root's and every
     non-member's 0 --, depth per peer, the peers of levels 1 ..), from the
-    audience answer and ps_topic_get_parents."""
+    audience answer and ps_topic_get_parents.  with_exc: the topic's position
+    in the request and the peers of its exceptions, in the audience answer's
+    order, behind them."""
     r = eng.drain_topics(topics)
     n = wl.n_peers
     sizes = np.diff(r["list_off"]).astype(np.uint64)
@@ -1365,7 +1378,10 @@ def host_topic_trees(eng, wl, topics):
             k[r["exc_peer"][lo:hi]] = ke
         k[root] = 0
         k[depth < 0] = 0
-        yield c, par, root, k, depth, levels
+        if with_exc:
+            yield c, par, root, k, depth, levels, i, r["exc_peer"][lo:hi]
+        else:
+            yield c, par, root, k, depth, levels
 
 
 def downstream_main(a, wl):
@@ -1616,6 +1632,113 @@ def cut_main(a, wl):
     if a.out:
         os.makedirs(a.out, exist_ok=True)
         with open(os.path.join(a.out, "cut_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
+def host_topic_blame(eng, wl, topics):
+    """Each missed subscriber and its cut point as a caller derives them
+    without ps_topic_blame: host_topic_trees' k per peer and levels, the cut
+    point and its level handed down level by level from the root, and the
+    records in the order of the audience answer's exceptions."""
+    n = wl.n_peers
+    recs = [[np.empty(0, dtype=np.uint32)] for _ in range(5)]
+    off = np.zeros(len(topics) + 1, dtype=np.uint64)
+    for c, par, root, k, depth, levels, i, exc in host_topic_trees(eng, wl, topics, with_exc=True):
+        miss = np.where(depth > 0, np.uint64(c) - k, np.uint64(0)).astype(np.int64)
+        cut_peer = np.full(n, -1, dtype=np.int64)
+        cut_hop = np.full(n, -1, dtype=np.int64)
+        for d, at in enumerate(levels, 1):
+            up = par[at].astype(np.int64)
+            lacks, full_parent = miss[at] > 0, miss[up] == 0
+            cut_peer[at] = np.where(lacks, np.where(full_parent, at, cut_peer[up]), -1)
+            cut_hop[at] = np.where(lacks, np.where(full_parent, d, cut_hop[up]), -1)
+        q = exc[miss[exc] > 0].astype(np.int64)
+        off[i + 1] = q.size
+        for out, x in zip(recs, (q, cut_peer[q], depth[q], cut_hop[q], miss[q])):
+            out.append(x.astype(np.uint32))
+    return {"rec_off": np.cumsum(off, dtype=np.uint64), **{k: np.concatenate(x) for k, x in zip(BLAME_KEYS, recs)}}
+
+
+BLAME_KEYS = ("peer", "cut_peer", "hop", "cut_hop", "missed")
+
+
+def blame_main(a, wl):
+    """--blame (see the module text).  Writes DIR/blame_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+        WL.build_engine_topics(eng, wl)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    # the device phases, alternating with yardstick (a): ps_peer_cut's on the same window
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        rows = {"topic_blame": [], "peer_cut": []}
+        for _ in range(a.reps + 1):  # (the first calls build the window's tables and allocate)
+            for tag, call in (("topic_blame", eng.topic_blame), ("peer_cut", eng.peer_cut)):
+                with StderrCapture() as cap:
+                    got = call(topics)
+                row = phase_line(cap.text, tag)
+                for k in ("strips", "nodes", "row_bytes", "work", "launches", "records", "copied_bytes"):
+                    m = re.search(rf"\b{k} (\d+)", cap.text)
+                    if m:
+                        row[k] = int(m.group(1))
+                rows[tag].append(row)
+                if tag == "topic_blame":
+                    blocking = got
+        res["blame_phases"], res["cut_phases"] = rows["topic_blame"][1:], rows["peer_cut"][1:]
+        total = int(blocking["rec_off"][-1])
+        res.update(deliveries=int(st.deliveries), records=total, copied_bytes=(nt + 1) * 8 + 5 * 4 * total,
+                   cut_points=int((blocking["peer"] == blocking["cut_peer"]).sum()),
+                   missed_sum=int(blocking["missed"].astype(np.uint64).sum()),
+                   deepest_record=int(blocking["hop"].max()) if total else 0,
+                   farthest_cut=int((blocking["hop"] - blocking["cut_hop"]).max()) if total else 0)
+        assert total > 0
+    # the walls, alternating with both yardsticks: (a) ps_peer_cut, (b) the host derivation
+    eng, _ = masked_engine({})
+    with eng:
+        walls = {"blame": [], "host": [], "cut": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            got = eng.topic_blame(topics)
+            walls["blame"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            want = host_topic_blame(eng, wl, topics)
+            walls["host"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            eng.peer_cut(topics)
+            walls["cut"].append(1e3 * (time.perf_counter() - t0))
+            for k in ("rec_off",) + BLAME_KEYS:
+                assert np.array_equal(got[k], want[k]), f"ps_topic_blame {k} differs from the host derivation"
+                assert np.array_equal(got[k], blocking[k]), k
+        # ps_blame over the records' own (topic, peer) pairs: ps_topic_blame expanded
+        qt = np.repeat(topics, np.diff(got["rec_off"]).astype(np.int64))
+        t0 = time.perf_counter()
+        q = eng.blame(qt, got["peer"])
+        res["blame_queries"], res["blame_queries_wall_ms"] = int(qt.size), 1e3 * (time.perf_counter() - t0)
+        for g, k in zip(q, ("cut_peer", "hop", "cut_hop", "missed")):
+            assert np.array_equal(g, got[k]), f"ps_blame {k} differs from ps_topic_blame"
+    res["blame_wall_ms"], res["host_derivation_wall_ms"], res["cut_wall_ms"] = (walls[k][1:] for k in ("blame", "host", "cut"))
+    res["answers_agree"] = True
+    res["host_over_blame_wall"] = float(np.median(res["host_derivation_wall_ms"]) / np.median(res["blame_wall_ms"]))
+    res["blame_over_cut_wall"] = float(np.median(res["blame_wall_ms"]) / np.median(res["cut_wall_ms"]))
+    bp, cp = res["blame_phases"], res["cut_phases"]
+    res["blame_sweep_over_cut_levels"] = float(np.median([p["sweep_ms"] for p in bp]) / np.median([p["levels_ms"] for p in cp]))
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "blame_bench.json"), "w") as f:
             f.write(json.dumps(res, indent=1) + "\n")
 
 
@@ -2374,6 +2497,7 @@ def main():
                     help="ps_peer_downstream against the host derivation; tracking in the pipelined loop")
     ap.add_argument("--cut", action="store_true",
                     help="ps_peer_cut against ps_peer_downstream and the host derivation; tracking in the pipelined loop")
+    ap.add_argument("--blame", action="store_true", help="ps_topic_blame against ps_peer_cut and the host derivation")
     ap.add_argument("--report", action="store_true",
                     help="ps_peer_report against the four calls in sequence; report tracking against the four trackers")
     ap.add_argument("--report-once", action="store_true", help="one step and one ps_peer_report (for a kernel trace)")
@@ -2394,6 +2518,8 @@ def main():
         return dist_cut_main(a, wl)
     if a.report or a.report_once:
         return report_main(a, wl)
+    if a.blame:
+        return blame_main(a, wl)
     if a.cut:
         return cut_main(a, wl)
     if a.downstream:
