@@ -1669,6 +1669,123 @@ __global__ __launch_bounds__(kDownBlock) void k_dist_cut_level(DistCutArgs g, ui
   dist_push(pn, pk, 1 + an, k + ak, on);
 }
 
+// ---- a rank's share of the blame (ps_dist_blame) -----------------------------------
+
+// One block per fill item of the level about to run, a thread per plist record
+// this rank holds as the parents' owner: the parent's pair into the 8 bytes
+// its children's rank reads it from.  A full parent and the entry's root --
+// whose words nothing writes -- read as (none, none).
+__global__ __launch_bounds__(kDownBlock) void k_dist_blame_fill(DistBlameArgs g, uint32_t f0) {
+  const DistApply A = g.fill[f0 + blockIdx.x];
+  const DistEntry E = g.d.entries[A.entry];
+  if (threadIdx.x >= A.n || !E.nn || !g.n_down_send || !g.d.n_plist) return;
+  const uint32_t w = min(A.rec0 + threadIdx.x, g.n_down_send - 1), pl = min(A.pl0 + threadIdx.x, g.d.n_plist - 1);
+  const uint32_t par = g.d.plist[pl];
+  if (par < E.nbase) return;
+  const uint32_t p = E.n0 + min(par - E.nbase, E.nn - 1);
+  const bool full = par == E.root || g.d.k[p] >= E.c_t;
+  g.down_send[w] = full ? make_uint2(kBlameNone, kBlameNone) : make_uint2(g.cut_peer[p], g.cut_hop[p]);
+}
+
+// k_dist_sweep_level's launch, walked the other way (kernels.hpp,
+// DistBlameArgs): a thread per node of level `level` >= 1.  The parent's pair
+// is two words the launch of the level above wrote on this rank, or 8 bytes
+// that level's owner filled and this level's exchange brought.
+__global__ __launch_bounds__(kDownBlock) void k_dist_blame_level(DistBlameArgs g, uint32_t level, uint32_t w0) {
+  const DistWork W = g.d.work[w0 + blockIdx.x];
+  const DistEntry E = g.d.entries[W.entry];
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  if (!E.tree || !E.c_t || level == 0 || level > E.depth || !E.nn) return;  // (block-uniform: a root has no record)
+  const uint32_t lo = max(W.lo, lv[level]), hi = min(min(W.hi, lv[level + 1]), E.nn);
+  const uint32_t u = lo + threadIdx.x;
+  if (u >= hi) return;
+  uint2 cut = make_uint2(kBlameNone, kBlameNone);
+  if (g.d.k[E.n0 + u] < E.c_t) {
+    uint2 up = cut;  // the parent's pair; none: it is full
+    const uint32_t par = g.d.node_parent[E.nbase + u];
+    if (par != kNoneNode) {
+      if (par >= E.nbase && par != E.root) {
+        const uint32_t p = E.n0 + min(par - E.nbase, E.nn - 1);
+        if (g.d.k[p] < E.c_t) up = make_uint2(g.cut_peer[p], g.cut_hop[p]);
+      }
+    } else if (g.d.gslot) {
+      const uint32_t gs = g.d.gslot[E.nbase + u];
+      const uint32_t owner = gs >> kRemoteRankShift;
+      if (gs != kNoneNode && owner < g.d.world && g.n_down_recv)
+        up = g.down_recv[min(g.down_base[E.sb0 + level * g.d.world + owner] + (gs & kRemoteIdMask), g.n_down_recv - 1)];
+    }
+    cut = up.x == kBlameNone ? make_uint2(g.d.node_peer[E.nbase + u], level) : up;
+  }
+  g.cut_peer[E.n0 + u] = cut.x;
+  g.cut_hop[E.n0 + u] = cut.y;
+}
+
+// the entry that holds strip s: the last one whose first strip is <= s (false: none)
+__device__ __forceinline__ bool dist_entry_of(const DistArgs& d, uint32_t s, DistEntry* E) {
+  uint32_t lo = 0, hi = d.n;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (d.entries[mid].strip0 <= s) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == 0) return false;
+  *E = d.entries[lo - 1];
+  return true;
+}
+
+// k_blame_count over a rank's strips: one wave per strip, one node per lane.
+// The wave behind the last strip writes the closing 0.
+__global__ __launch_bounds__(kAudBlock) void k_dist_blame_count(DistBlameArgs g) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s > g.d.n_strips) return;
+  uint32_t c = 0;
+  DistEntry E;
+  if (s < g.d.n_strips && dist_entry_of(g.d, s, &E) && E.tree) {
+    const AudStrip S = g.d.strips[s];
+    const uint32_t* __restrict__ k = g.d.k + E.n0;
+    const uint32_t end = min(S.u0 + S.n, E.nn);
+    for (uint32_t u = S.u0 + lane; u < end; u += kWave) c += k[u] < E.c_t;
+  }
+  c = wave_sum_u32(c);
+  if (lane == 0) g.n_rec[s] = c;
+}
+
+// k_blame_emit over a rank's strips: the nodes that lack messages, in the
+// rank's own node order (ballot and lane prefix), from the strip's offset on.
+// The first n + 1 threads of the grid leave the entries' record offsets.
+__global__ __launch_bounds__(kAudBlock) void k_dist_blame_emit(DistBlameArgs g) {
+  const uint32_t tid = blockIdx.x * kAudBlock + threadIdx.x;
+  if (tid <= g.d.n) g.rec_off[tid] = g.off[min(g.d.entries[tid].strip0, g.d.n_strips)];
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.d.n_strips || g.n_rec[s] == 0) return;
+  DistEntry E;
+  if (!dist_entry_of(g.d, s, &E) || !E.tree || !E.nn) return;
+  const AudStrip S = g.d.strips[s];
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  const uint32_t* __restrict__ k = g.d.k + E.n0;
+  const uint32_t* __restrict__ cut_peer = g.cut_peer + E.n0;
+  const uint32_t* __restrict__ cut_hop = g.cut_hop + E.n0;
+  const uint32_t end = min(S.u0 + S.n, E.nn);
+  uint64_t at = g.off[s];
+  for (uint32_t u0 = S.u0; u0 < end; u0 += kWave) {
+    const uint32_t u = min(u0 + lane, end - 1);
+    const uint32_t have = k[u];
+    const bool rec = u0 + lane < end && have < E.c_t;
+    const uint64_t b = __ballot(rec);
+    const uint64_t to = at + __popcll(b & ((1ull << lane) - 1));
+    if (rec && to < g.cap) {
+      if (g.rec_peer) g.rec_peer[to] = g.d.node_peer[E.nbase + u];
+      if (g.rec_cut_peer) g.rec_cut_peer[to] = cut_peer[u];
+      if (g.rec_hop) g.rec_hop[to] = blame_level_of(lv, E.depth, u);
+      if (g.rec_cut_hop) g.rec_cut_hop[to] = cut_hop[u];
+      if (g.rec_missed) g.rec_missed[to] = E.c_t - have;
+    }
+    at += __popcll(b);
+  }
+}
+
 // ---- hops and duplicate copies, meshes too (ps_topic_spread) ---------------------
 
 constexpr uint32_t kSpreadBlock = 256;
@@ -2638,6 +2755,33 @@ hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream
 hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s) {
   if (w1 <= w0 || level == 0) return hipSuccess;
   hipLaunchKernelGGL(k_dist_cut_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, level, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_blame_fill(const DistBlameArgs& g, uint32_t f0, uint32_t f1, hipStream_t s) {
+  if (f1 <= f0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_blame_fill, dim3(f1 - f0), dim3(kDownBlock), 0, s, g, f0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_blame_level(const DistBlameArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s) {
+  if (w1 <= w0 || level == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dist_blame_level, dim3(w1 - w0), dim3(kDownBlock), 0, s, g, level, w0);
+  return hipGetLastError();
+}
+
+hipError_t launch_dist_blame_count(const DistBlameArgs& g, hipStream_t s) {
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_dist_blame_count, dim3((g.d.n_strips + 1 + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+// (the grid covers the strips, a wave each, and the n + 1 record offsets, a thread each)
+hipError_t launch_dist_blame_emit(const DistBlameArgs& g, hipStream_t s) {
+  const uint32_t per = kAudBlock / kWave;
+  const uint32_t by_strip = (g.d.n_strips + per - 1) / per, by_entry = (g.d.n + 1 + kAudBlock - 1) / kAudBlock;
+  const uint32_t blocks = by_strip > by_entry ? by_strip : by_entry;
+  hipLaunchKernelGGL(k_dist_blame_emit, dim3(blocks), dim3(kAudBlock), 0, s, g);
   return hipGetLastError();
 }
 

@@ -19,6 +19,13 @@
 // opposite direction bring every remote parent's k to its children's ranks
 // ahead of the sweep, and k_dist_cut_level decides at the child -- k < c_t under
 // a parent with k == c_t -- and pushes as the sweep does.
+//   ps_dist_blame answers ps_topic_blame for the nodes this
+// rank owns, through the same front and plan: k_dist_nodes leaves the k word,
+// then the sweep's work list is walked from level 1 down -- ahead of a level
+// whose edges from the level above cross ranks, k_dist_blame_fill and one
+// exchange bring the remote parents' (cut peer, cut hop) pairs, and
+// k_dist_blame_level decides at the child.  k_dist_blame_count, the scan and
+// k_dist_blame_emit turn the words into records, lent from pinned memory.
 #include "drain_impl.hpp"
 
 using namespace psamd;
@@ -82,7 +89,14 @@ struct Plan {
   bool down_on = false;              // some named tree topic has a cross-rank edge
   uint64_t n_dsend = 0, n_drecv = 0;  // words
   size_t o_fill = 0, o_dbase = 0;
+  // ps_dist_blame alone (dist_blame_plan): a downward exchange per level that
+  // has a cross-rank edge, by ascending level, a0 .. a1 its fill items;
+  // n_dsend, n_drecv and down_base count 8-byte pairs
+  std::vector<Xchg> downs;
 };
+
+// which downward exchange a pass stages behind the sweep's tables
+enum class DownKind { none, cut, blame };
 
 // the rank's own level table of a tree topic stands for the last window's
 // nodes: level 0 the root where this rank owns it, no level running backwards
@@ -246,6 +260,60 @@ int dist_cut_plan(ps_engine* e, size_t n, Plan* P) {
   return PS_OK;
 }
 
+// ps_dist_blame's downward exchanges over a sweep's plan: dist_cut_plan's
+// layout -- the sweep's regions with the two ranks swapped, found through
+// down_base per (entry, level, owner) -- with an 8-byte pair where the cut has
+// a word, and an exchange per level: a level's pairs exist only once the level
+// above has run.  Level L's region me -> q holds, entry by entry, the
+// gcnt[(L * world + me) * world + q] parents' pairs of plist, padded to whole
+// 16-byte units.  Whether a level exchanges follows from gcnt alone, whatever
+// c_t is: every rank makes the same exchanges in the same order.
+int dist_blame_plan(ps_engine* e, size_t n, Plan* P) {
+  const uint32_t W = static_cast<uint32_t>(std::max(e->world, 1)), me = static_cast<uint32_t>(e->rank);
+  P->cut = true;
+  P->down_base.assign(P->send_base.size(), 0);
+  if (W == 1) return PS_OK;
+  for (uint32_t L = 1; L <= P->max_depth; ++L) {
+    Xchg X;
+    X.level = L;
+    X.s_off.assign(W, 0), X.s_len.assign(W, 0), X.r_off.assign(W, 0), X.r_len.assign(W, 0);
+    X.a0 = static_cast<uint32_t>(P->fill.size());
+    uint64_t crossing = 0;
+    for (uint32_t q = 0; q < W; ++q) {
+      X.s_off[q] = P->n_dsend * 8;
+      X.r_off[q] = P->n_drecv * 8;
+      for (size_t i = 0; i < n; ++i) {
+        const DistEntry& E = P->entries[i];
+        const TopicHost& T = e->topics[E.topic];
+        if (!E.tree || L > E.depth || T.gcnt.size() < static_cast<size_t>(E.depth + 2) * W * W) continue;
+        const uint32_t* gc = &T.gcnt[static_cast<size_t>(L) * W * W];
+        // the pairs this rank's parents send to their children at q, and those
+        // q's parents send to this rank's children of level L
+        const uint32_t out_n = q == me ? 0 : gc[me * W + q], in_n = q == me ? 0 : gc[q * W + me];
+        const uint32_t pl0 = e->dist_slots.pl_off[E.topic][static_cast<size_t>(L) * W + q];
+        for (uint32_t j = 0; j < out_n; j += kDownBlock)
+          P->fill.push_back(DistApply{static_cast<uint32_t>(i), static_cast<uint32_t>(P->n_dsend) + j, pl0 + j,
+                                      std::min(kDownBlock, out_n - j)});
+        P->n_dsend += out_n;
+        P->down_base[E.sb0 + L * W + q] = static_cast<uint32_t>(P->n_drecv);
+        P->n_drecv += in_n;
+        if (q == 0)
+          for (uint32_t a = 0; a < W; ++a)
+            for (uint32_t b = 0; b < W; ++b)
+              if (a != b) crossing += gc[a * W + b];
+      }
+      P->n_dsend = (P->n_dsend + 1) & ~1ull;
+      P->n_drecv = (P->n_drecv + 1) & ~1ull;
+      X.s_len[q] = P->n_dsend * 8 - X.s_off[q];
+      X.r_len[q] = P->n_drecv * 8 - X.r_off[q];
+    }
+    X.a1 = static_cast<uint32_t>(P->fill.size());
+    if (crossing) P->downs.push_back(std::move(X));
+  }
+  if (P->n_dsend >= kDrainRowLimit || P->n_drecv >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many records in one dist blame");
+  return PS_OK;
+}
+
 // the slot tables of the node space the last window ran on, on the device
 int dist_slots_ready(ps_engine* e) {
   auto& S = e->dist_slots;
@@ -267,12 +335,14 @@ void put(uint8_t* at, const std::vector<T>& v) {
   if (!v.empty()) std::memcpy(at, v.data(), v.size() * sizeof(T));
 }
 
-// ---- what ps_dist_report and ps_dist_cut share ---------------------------------------
+// ---- what ps_dist_report, ps_dist_cut and ps_dist_blame share -------------------------
 
 // The strips' shape (the plan reads the entries' first strips), the plan, then
-// the input block in Dist::stage; cut: ps_dist_cut's downward exchange too
-int dist_stage(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what, bool cut, Plan* Pp, Drain::AudShape* Ap,
+// the input block in Dist::stage; down: ps_dist_cut's or ps_dist_blame's
+// downward exchange too
+int dist_stage(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what, DownKind down, Plan* Pp, Drain::AudShape* Ap,
                size_t* in_bytes) {
+  const bool cut = down != DownKind::none;
   auto& H = e->drain.dist;
   Plan& P = *Pp;
   Drain::AudShape& A = *Ap;
@@ -284,7 +354,7 @@ int dist_stage(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what, boo
   (void)aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);  // (the shape and the entries' first strips alone)
   if (const int rc = dist_plan(e, topic, n, what, ae.data(), &P)) return rc;
   if (cut)
-    if (const int rc = dist_cut_plan(e, n, &P)) return rc;
+    if (const int rc = down == DownKind::blame ? dist_blame_plan(e, n, &P) : dist_cut_plan(e, n, &P)) return rc;
   P.o_lvl = align256((n + 1) * sizeof(DistEntry));
   P.o_base = P.o_lvl + align256(std::max<size_t>(P.levels.size(), 1) * 4);
   P.o_work = P.o_base + align256(std::max<size_t>(P.send_base.size(), 1) * 4);
@@ -443,7 +513,7 @@ int ps_dist_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   Plan P;
   AudShape A;
   size_t in_bytes = 0;
-  if ((rc = dist_stage(e, topic, n, what, false, &P, &A, &in_bytes))) return rc;
+  if ((rc = dist_stage(e, topic, n, what, DownKind::none, &P, &A, &in_bytes))) return rc;
   const double host_ms = ms_since(t_host0);
 
   // the output block: the seven arrays in ps_report's order
@@ -543,7 +613,7 @@ int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_
   Plan P;
   AudShape A;
   size_t in_bytes = 0;
-  if ((rc = dist_stage(e, topic, n, kReportDown, true, &P, &A, &in_bytes))) return rc;
+  if ((rc = dist_stage(e, topic, n, kReportDown, DownKind::cut, &P, &A, &in_bytes))) return rc;
   const double host_ms = ms_since(t_host0);
 
   // the output block: missed | cuts | orphaned | lost
@@ -613,6 +683,149 @@ int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_
                  P.launch.empty() ? size_t(0) : P.launch.size() - 1, static_cast<unsigned long long>(exchanges),
                  static_cast<unsigned long long>(bytes_sent), static_cast<unsigned long long>(slot_bytes), ms[0], ms[1], ms[2],
                  ms[3], ms[4], host_ms);
+  return PS_OK;
+}
+
+// ---- ps_dist_blame --------------------------------------------------
+
+int ps_dist_blame(ps_engine* e, const uint32_t* topic, size_t n, const uint64_t** rec_off_out, const uint32_t** rec_peer_out,
+                  const uint32_t** rec_cut_peer_out, const uint32_t** rec_hop_out, const uint32_t** rec_cut_hop_out,
+                  const uint32_t** rec_missed_out, uint64_t* total_out) {
+  const uint32_t** const outs[5] = {rec_peer_out, rec_cut_peer_out, rec_hop_out, rec_cut_hop_out, rec_missed_out};
+  if (!e || (n && !topic) || !rec_off_out || !total_out) return PS_E_INVAL;
+  if (const int rc = drain_enter(e, {nullptr, "no completed run", nullptr, false})) return rc;
+  if (e->world > 1 && e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
+  if (const int rj = twin_join(e)) return rj;
+  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  for (size_t i = 0; i < n; ++i)
+    if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_dist_blame: a mesh topic has no cut points");
+  const bool ranks = e->world > 1;
+  if (ranks && (e->graph_dirty || !e->transport))
+    return e->fail(PS_E_STATE, "ps_dist_blame: the topics changed since the last run: run first");
+  auto& D = e->drain;
+  auto& H = D.dist;
+  const auto t_host0 = hclock::now();
+  int rc = drain_ready(e);
+  if (!rc) rc = drain_tables(e);
+  if (!rc && ranks) rc = dist_slots_ready(e);
+  if (rc) return rc;
+  hipStream_t s = e->stream;
+  float ms[6] = {0, 0, 0, 0, 0, 0};  // classify, nodes, fills + exchanges + sweep, count + scan, emit, copy (PSAMD_DRAIN_TIMING)
+  const PhaseTimer tm{D.ev_t, s, D.env.timing};
+
+  Plan P;
+  AudShape A;
+  size_t in_bytes = 0;
+  if ((rc = dist_stage(e, topic, n, kReportDown, DownKind::blame, &P, &A, &in_bytes))) return rc;
+  const double host_ms = ms_since(t_host0);
+
+  // the record arrays on the device hold every non-root node of the rank's
+  // strips, so nothing waits between the scan and the emit; the pinned view is
+  // sized by the total, behind the one wait for it
+  size_t asked = 0;
+  for (auto* o : outs) asked += o != nullptr;
+  const uint64_t cap = A.n_verdicts;
+  const size_t d_stride = align256(cap * 4), n_off = static_cast<size_t>(A.ns) + 1;
+  HIP_TRY(pinned_ensure(&H.h_off, nullptr, &H.off_cap, (n + 1) * 8), "alloc dist blame offsets");
+  uint64_t* const h_off = reinterpret_cast<uint64_t*>(H.h_off);
+  HIP_TRY(H.d_dsend.ensure(P.n_dsend * 8), "alloc dist blame pairs");
+  HIP_TRY(H.d_drecv.ensure(P.n_drecv * 8), "alloc dist blame pairs");
+  HIP_TRY(H.d_cut.ensure(std::max<size_t>(P.n_words, 1) * 8), "alloc dist blame words");
+  HIP_TRY(H.d_cnt.ensure(n_off * 8), "alloc dist blame counts");
+  HIP_TRY(H.d_off.ensure(n_off * 8), "alloc dist blame offsets");
+  HIP_TRY(H.d_rec_off.ensure((n + 1) * 8), "alloc dist blame offsets");
+  HIP_TRY(H.d_rec.ensure(std::max<size_t>(std::max<size_t>(asked, 1) * d_stride, 1)), "alloc dist blame records");
+  size_t scan_bytes = 0;
+  HIP_TRY(drain_scan(nullptr, &scan_bytes, H.d_cnt.as<uint64_t>(), H.d_off.as<uint64_t>(), A.ns + 1, s), "size dist blame scan");
+  HIP_TRY(H.d_scan.ensure(scan_bytes), "alloc dist blame scan");
+  if ((rc = dist_buffers(e, P, A, in_bytes, false))) return rc;
+  // (no send region is rewritten within the call: a level has regions of its own)
+  if (P.n_dsend) HIP_TRY(hipMemsetAsync(H.d_dsend.p, 0, P.n_dsend * 8, s), "clear dist blame pairs");
+
+  const DrainArgs a = drain_args(e, D.tab);
+  DistBlameArgs g{};
+  if ((rc = dist_front(e, P, A, in_bytes, n, kReportDown, a, tm, ms[0], &g.d))) return rc;
+  const uint8_t* const din = H.d_in.as<uint8_t>();
+  g.cut_peer = H.d_cut.as<uint32_t>();
+  g.cut_hop = g.cut_peer + std::max<size_t>(P.n_words, 1);
+  g.fill = reinterpret_cast<const DistApply*>(din + P.o_fill);
+  g.down_send = H.d_dsend.as<uint2>();
+  g.down_recv = H.d_drecv.as<uint2>();
+  g.down_base = reinterpret_cast<const uint32_t*>(din + P.o_dbase);
+  g.n_down_send = static_cast<uint32_t>(P.n_dsend);
+  g.n_down_recv = static_cast<uint32_t>(P.n_drecv);
+  g.n_rec = H.d_cnt.as<uint64_t>();
+  g.off = H.d_off.as<uint64_t>();
+  g.rec_off = H.d_rec_off.as<uint64_t>();
+  g.cap = cap;
+  uint32_t** const recs[5] = {&g.rec_peer, &g.rec_cut_peer, &g.rec_hop, &g.rec_cut_hop, &g.rec_missed};
+  for (size_t i = 0, j = 0; i < 5; ++i)
+    if (outs[i]) *recs[i] = reinterpret_cast<uint32_t*>(H.d_rec.as<uint8_t>() + j++ * d_stride);
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_dist_nodes(a, g.d, s), "k_dist_nodes");  // (the k word alone: k_dist_nodes<false, false, true>)
+  HIP_TRY(tm.end(ms[1]), "event");
+
+  // top-down: ahead of level L's launch its parents' pairs to the children's
+  // ranks, where some edge into the level crosses ranks
+  uint64_t exchanges = 0, bytes_sent = 0;
+  const uint64_t slot_bytes = (P.n_dsend + P.n_drecv) * 8;
+  HIP_TRY(tm.begin(), "event");
+  size_t x = 0;
+  for (uint32_t L = 1; L <= P.max_depth; ++L) {
+    if (x < P.downs.size() && P.downs[x].level == L) {
+      const Xchg& X = P.downs[x++];
+      HIP_TRY(launch_dist_blame_fill(g, X.a0, X.a1, s), "k_dist_blame_fill");
+      std::string xerr;
+      const hipError_t xe = e->transport->exchange(H.d_dsend.as<uint8_t>(), X.s_off, X.s_len, H.d_drecv.as<uint8_t>(), X.r_off,
+                                                   X.r_len, s, &xerr);
+      if (xe != hipSuccess) return e->fail(PS_E_DEVICE, xerr);
+      exchanges += 1;
+      for (const uint64_t b : X.s_len) bytes_sent += b;
+    }
+    // (the sweep's work list holds the deepest level first)
+    const size_t j = P.max_depth - L;
+    if (j + 1 < P.launch.size()) HIP_TRY(launch_dist_blame_level(g, L, P.launch[j], P.launch[j + 1], s), "k_dist_blame_level");
+  }
+  HIP_TRY(tm.end(ms[2]), "event");
+
+  // the records; the one wait before the copies is local, and behind every
+  // exchange of the call
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_dist_blame_count(g, s), "k_dist_blame_count");
+  scan_bytes = H.d_scan.bytes;
+  HIP_TRY(drain_scan(H.d_scan.p, &scan_bytes, g.n_rec, H.d_off.as<uint64_t>(), A.ns + 1, s), "dist blame scan");
+  HIP_TRY(tm.end(ms[3]), "event");
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(launch_dist_blame_emit(g, s), "k_dist_blame_emit");
+  HIP_TRY(tm.end(ms[4]), "event");
+  HIP_TRY(tm.begin(), "event");
+  HIP_TRY(hipMemcpyAsync(h_off, g.rec_off, (n + 1) * 8, hipMemcpyDeviceToHost, s), "read dist blame offsets");
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  const uint64_t total = h_off[n];
+  if (total > cap) return e->fail(PS_E_STATE, "ps_dist_blame: more records than nodes");
+  const size_t h_stride = align256(total * 4);
+  HIP_TRY(pinned_ensure(&H.h_rec, nullptr, &H.rec_cap, std::max<size_t>(asked * h_stride, 1)), "alloc dist blame view");
+  // one copy per array asked for
+  for (size_t i = 0, j = 0; i < 5 && total; ++i)
+    if (outs[i]) {
+      HIP_TRY(hipMemcpyAsync(H.h_rec + j * h_stride, *recs[i], total * 4, hipMemcpyDeviceToHost, s), "read dist blame records");
+      ++j;
+    }
+  HIP_TRY(hipStreamSynchronize(s), "sync");
+  HIP_TRY(tm.end(ms[5]), "event");
+  *rec_off_out = h_off;
+  for (size_t i = 0, j = 0; i < 5; ++i)
+    if (outs[i]) *outs[i] = reinterpret_cast<const uint32_t*>(H.h_rec + j++ * h_stride);
+  *total_out = total;
+  if (D.env.timing)
+    std::fprintf(stderr,
+                 "psamd dist_blame: rank %d topics %zu strips %u nodes %llu work %zu launches %u exchanges %llu sent_bytes %llu "
+                 "slot_bytes %llu records %llu copied_bytes %llu classify_ms %.4f nodes_ms %.4f sweep_ms %.4f count_scan_ms %.4f "
+                 "emit_ms %.4f copy_ms %.4f host_plan_ms %.4f\n",
+                 e->rank, n, A.ns, static_cast<unsigned long long>(P.n_words), P.work.size(), P.max_depth,
+                 static_cast<unsigned long long>(exchanges), static_cast<unsigned long long>(bytes_sent),
+                 static_cast<unsigned long long>(slot_bytes), static_cast<unsigned long long>(total),
+                 static_cast<unsigned long long>((n + 1) * 8 + asked * total * 4), ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], host_ms);
   return PS_OK;
 }
 

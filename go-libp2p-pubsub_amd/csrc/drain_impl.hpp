@@ -40,8 +40,10 @@
 //                     the audience pass's strips and classify, kernels of its
 //                     own for a sharded rank's numbering, and a bottom-up sweep
 //                     that crosses ranks through Transport::exchange; blocking
-//                     only, with buffers of its own
-//   drain_spread.cpp  ps_topic_spread (§5.5p): hops and duplicate copies for meshes
+//                     only, with buffers of its own; ps_dist_cut (§5.5o) and
+//                     ps_dist_blame (§5.5r) through the same front and plan,
+//                     each with a downward exchange of its own
+//   drain_spread.cpp ps_topic_spread (§5.5p): hops and duplicate copies for meshes
 //                     and trees alike -- the audience pass's strips and classify,
 //                     then a frontier BFS over the node space's child lists, one
 //                     launch per level; blocking only, with buffers of its own

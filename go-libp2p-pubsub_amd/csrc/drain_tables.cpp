@@ -525,7 +525,8 @@ void drain_destroy(ps_engine* e) {
   for (auto& f : D.report.fence)
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
-  if (D.dist.h_out) (void)hipHostFree(D.dist.h_out);
+  for (uint8_t* h : {D.dist.h_out, D.dist.h_off, D.dist.h_rec})
+    if (h) (void)hipHostFree(h);
   if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);
   for (uint8_t* h : {D.blame.h_off, D.blame.h_rec, D.blame.h_out})
     if (h) (void)hipHostFree(h);

@@ -978,6 +978,14 @@ struct ps_engine {
       std::vector<uint8_t> stage;  // (the upload is waited for in the call)
       uint8_t* h_out = nullptr;
       size_t out_cap = 0;
+      // ps_dist_blame (§5.5r) too, with 8-byte pairs in d_dsend / d_drecv: the
+      // sweep's words cut_peer | cut_hop, a word per owned node each; the
+      // strips' record counts, their exclusive sum and its temporary; the
+      // entries' record offsets; the record arrays the call was asked for
+      psamd::DevBuf d_cut, d_cnt, d_off, d_scan, d_rec_off, d_rec;
+      // pinned: rec_off and the record arrays lent until the next ps_dist_blame
+      uint8_t *h_off = nullptr, *h_rec = nullptr;
+      size_t off_cap = 0, rec_cap = 0;
     } dist;
 
     // ps_topic_spread (host code: drain_spread.cpp): hops and

@@ -1308,6 +1308,64 @@ hipError_t launch_dist_cut_fill(const DistCutArgs& g, uint32_t n_fill, hipStream
 // k_dist_cut_level over work items [w0, w1): the nodes of level `level` (>= 1)
 hipError_t launch_dist_cut_level(const DistCutArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s);
 
+// ---- a rank's share of the blame (ps_dist_blame) ---------------
+// ps_topic_blame's records for the non-root nodes one rank owns, where cut(u)
+// and every node on the way up to it may live on any rank.  DistArgs' tables
+// and k word (d; k_dist_nodes<false, false, true> leaves k) carry it; two words
+// of the pass's own per owned node, an entry's from n0 as k's:
+//   cut_peer[u]  the peer of cut(u) -- a peer id, since a remote cut point has
+//                no node on this rank; kBlameNone where k(u) >= c_t
+//   cut_hop[u]   the BFS level of cut(u); kBlameNone where k(u) >= c_t
+// The sweep runs top-down and is decided at the child, from its parent's pair
+// alone: none (the parent is full, or the entry's root) makes u its own cut
+// point, anything else is inherited.  A remote parent's pair arrives in a
+// downward exchange per level -- a pair exists only once the level above has
+// run -- whose regions mirror the sweep's upward ones with the two ranks
+// swapped: 8 bytes per (remote parent, child rank) pair, the pair's record
+// index (gslot / plist) its place.
+//   k_dist_blame_fill   one block per fill item of level L, a thread per plist
+//                       record this rank holds as the parents' owner: the
+//                       parent's pair, (none, none) where it is full or the
+//                       entry's root, into down_send[rec0 + j].
+//   k_dist_blame_level  one block per work item of level L >= 1, a thread per
+//                       node: none where k(u) >= c_t; else the parent's pair
+//                       -- the two words of a local parent, or down_recv[
+//                       down_base[sb0 + L * world + a] + j] -- or (peer(u), L)
+//                       where that pair is none.  One writer per word: plain
+//                       stores, no atomics.
+//   k_dist_blame_count  k_blame_count over the rank's strips and DistEntry.
+//   k_dist_blame_emit   k_blame_emit: the records in node order (ballot and
+//                       lane prefix); rec_hop from the rank's own level table,
+//                       whose levels may be empty.
+// Stream order and the transport's own ordering are the only order between the
+// launches.  Every table-derived index is clamped into its entry's words or its
+// region.
+struct DistBlameArgs {
+  DistArgs d;                 // recv .. carried, acc_n, acc_k, send, rcv unused
+  uint32_t* cut_peer;         // per-node words, beside d.k
+  uint32_t* cut_hop;
+  const DistApply* fill;      // fill items, level by level: rec0 the first pair of down_send, pl0 of plist, n pairs
+  uint2* down_send;           // the parents' pairs, level by level, region by region
+  const uint2* down_recv;     // ... as received
+  const uint32_t* down_base;  // per (entry, level, owner) as send_base: the first pair of the run in down_recv
+  uint32_t n_down_send, n_down_recv;
+  uint64_t* n_rec;            // [n_strips + 1]
+  const uint64_t* off;        // [n_strips + 1] the exclusive sum of n_rec
+  uint64_t* rec_off;          // [n + 1]
+  uint32_t* rec_peer;         // [cap] each; null: not asked for
+  uint32_t* rec_cut_peer;
+  uint32_t* rec_hop;
+  uint32_t* rec_cut_hop;
+  uint32_t* rec_missed;
+  uint64_t cap;
+};
+// k_dist_blame_fill over fill items [f0, f1): one level's
+hipError_t launch_dist_blame_fill(const DistBlameArgs& g, uint32_t f0, uint32_t f1, hipStream_t s);
+// k_dist_blame_level over work items [w0, w1): the nodes of level `level` (>= 1)
+hipError_t launch_dist_blame_level(const DistBlameArgs& g, uint32_t level, uint32_t w0, uint32_t w1, hipStream_t s);
+hipError_t launch_dist_blame_count(const DistBlameArgs& g, hipStream_t s);
+hipError_t launch_dist_blame_emit(const DistBlameArgs& g, hipStream_t s);
+
 // ---- hops and duplicate copies, meshes too (ps_topic_spread) ----
 // A frontier BFS over the CSR child lists, from the rows the window left: the
 // forwarders F of a topic are its root and every non-root node whose row holds

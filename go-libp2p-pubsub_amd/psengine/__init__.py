@@ -204,6 +204,8 @@ PROTOTYPES = [
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
     ("ps_dist_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_dist_cut", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_dist_blame", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p),
+                                C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u32p), _u64p]),
     ("ps_topic_spread", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
@@ -980,6 +982,28 @@ class Engine:
         out = [np.empty(self.n_peers, dtype=np.uint64) for _ in range(4)]
         self._check(self._L.ps_dist_cut(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out)))
         return out[0], out[1], out[2], out[3]
+
+    def dist_blame(self, topics) -> dict:
+        """This rank's share of topic_blame over the named distinct tree topics
+        (ps_dist_blame), on an engine of any rank count: topic_blame's dict --
+        rec_off[n + 1], and per record peer, cut_peer, hop, cut_hop and missed
+        -- for the missed non-root nodes this rank owns, in its own node
+        order; the cut point may lie on any rank.  Keyed by (request position,
+        peer) the ranks' records together are a one-rank engine's topic_blame.
+        On a multi-rank engine the call is collective whenever topics are
+        named: every rank makes it, with the same topics in the same order."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        off = _u64p()
+        ptrs = [_u32p() for _ in range(5)]
+        total = C.c_uint64()
+        self._check(self._L.ps_dist_blame(self._h, _p(t, C.c_uint32), t.size, C.byref(off), *(C.byref(p) for p in ptrs),
+                                          C.byref(total)))
+        out = {"rec_off": _view(off, t.size + 1, np.uint64).copy()}
+        for k, p in zip(("peer", "cut_peer", "hop", "cut_hop", "missed"), ptrs):
+            out[k] = _view(p, total.value, np.uint32).copy()
+        return out
 
     def topic_spread(self, topics) -> dict:
         """Hops and duplicate copies of the last window for the named distinct

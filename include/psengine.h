@@ -981,6 +981,54 @@ int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n,
                 uint64_t* missed_out, uint64_t* cuts_out,
                 uint64_t* orphaned_out, uint64_t* lost_out);  /* [n_peers] each; any may be NULL, not all four */
 
+/* This rank's share of ps_topic_blame, on an engine of any rank count
+ * (DESIGN.md 5.5r): each missed subscriber this rank owns and the peer where
+ * its path was cut, where the cut point and every node on the way up to it may
+ * live on any rank.  The last window of the last run; blocking.
+ *   One record per non-root node u this rank owns (ps_partition_owner of its
+ * peer) with miss(u) > 0, for every named tree topic with c_t > 0 window
+ * messages.  k, miss, cut point and cut(u) are ps_topic_blame's, word for
+ * word: k(u) the window messages u's row holds, miss(u) = c_t - k(u), a cut
+ * point a non-root node with k < c_t under a full parent, cut(u) the nearest
+ * cut point on the way from u up to the root, u included; the root counts as
+ * full.  A record holds u's peer, the peer of cut(u), hop(u), cut_hop(u) --
+ * exact BFS levels, with no clamp at PS_MAX_ROUNDS -- and miss(u).  The records
+ * of topic[i] are rec_off[i] .. rec_off[i+1], total = rec_off[n], in the
+ * rank's own ascending node order: within a topic rec_hop never decreases.
+ *   Keyed by (request position, peer) the ranks' records together are, field
+ * for field, the records ps_topic_blame gives on a one-rank engine for the
+ * same trees, live mask, publishes and request; a rank returns exactly the
+ * records whose node it owns; on a one-rank engine the call equals
+ * ps_topic_blame entry for entry, order included (it runs its own kernels,
+ * with nothing to exchange).
+ *   The arrays are lent from pinned memory the engine owns, valid until the
+ * next ps_dist_blame or ps_destroy; the view is separate from ps_topic_blame's.
+ * Any of the five record pointers may be NULL: that array is neither written,
+ * copied nor lent.  rec_off_out and total_out are required.
+ *   On a multi-rank engine the call is COLLECTIVE whenever n > 0, as
+ * ps_dist_cut is: every rank calls it with the same topics in the same order,
+ * after the same run.  Which record pointers are NULL does not change the pass
+ * and may differ between the ranks.
+ *   PS_E_INVAL for a NULL engine, rec_off_out or total_out NULL, n > 0 without
+ * topic, or a topic named twice; PS_E_RANGE, nothing written, for a topic out
+ * of range; PS_E_NOTREADY before any run; PS_E_STATE with a run in flight on a
+ * multi-rank engine, for a topic set anew since the window or topics changed
+ * since the run, and for a mesh topic (one-rank engines only).  A failed
+ * exchange returns the transport's error (PS_E_DEVICE) with the outputs
+ * unspecified.  n == 0 is valid: rec_off = {0}, total 0, nothing exchanged.
+ *   ps_topic_blame and ps_blame keep refusing multi-rank engines.  There is no
+ * sharded form of ps_blame, no tracker and no _begin / _end form: a query's
+ * peer may be owned by another rank than the one that asks, and a run's records
+ * are variable-size per window -- each its own piece of work. */
+int ps_dist_blame(ps_engine* e, const uint32_t* topic, size_t n,
+                  const uint64_t** rec_off_out,      /* [n + 1]          */
+                  const uint32_t** rec_peer_out,     /* [total] each     */
+                  const uint32_t** rec_cut_peer_out,
+                  const uint32_t** rec_hop_out,
+                  const uint32_t** rec_cut_hop_out,
+                  const uint32_t** rec_missed_out,
+                  uint64_t* total_out);
+
 /* Hops and duplicate copies, for mesh topics and tree topics alike (one rank;
  * DESIGN.md 5.5p): how deep a topic's messages travelled, and what the edges
  * beyond a tree cost, at which peers.  Per named topic t with c_t > 0 messages

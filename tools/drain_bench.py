@@ -168,6 +168,16 @@ rank, the exchanges, the bytes a rank ships in them and the bytes of its
 records and words, the ranks' sum compared with the one-rank answer on every
 call.  Writes DIR/dist_cut_bench.json.
 
+--dist-blame: a rank's share of the blame (ps_dist_blame).  One rank: over
+every topic after one step under --cut's live mask, --reps repetitions
+alternating in one process with ps_topic_blame -- the yardstick --: the device
+phases of both (PSAMD_DRAIN_TIMING) and the walls, the answers compared entry
+for entry.  Then 2 and 4 loopback ranks on --dist-report's cfg4-shaped run,
+alternating with ps_dist_cut -- the yardstick there --: the wall per rank, the
+exchanges, the bytes a rank ships in them and the bytes of its pairs, the
+records and the bytes copied; the ranks' union, keyed by peer, compared with
+the one-rank ps_topic_blame on every call.  Writes DIR/dist_blame_bench.json.
+
 --spread: hops and duplicate copies of a mesh (ps_topic_spread).  The tool
 builds its own mesh -- --spread-peers peers (default 2^20), random out-degree
 0..6, 3 % dead, one topic, 1,024 messages -- and a second shape with one hub of
@@ -2214,6 +2224,182 @@ def dist_cut_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def dist_blame_main(a, wl):
+    """--dist-blame (see the module text).  Writes DIR/dist_blame_bench.json."""
+    import threading
+
+    keys = ("peer", "cut_peer", "hop", "cut_hop", "missed")
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        for k in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_DRAIN_EMIT"):
+            os.environ.pop(k, None)
+        os.environ.update(env)
+        eng = PE.Engine(wl.n_peers, nt, seed=wl.seed)
+        WL.build_engine_topics(eng, wl)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    def counts(text, row, keys):
+        for k in keys:
+            m = re.search(rf"\b{k} (\d+)", text)
+            if m:
+                row[k] = int(m.group(1))
+        return row
+
+    def device_ms(rows):
+        return float(np.median([sum(v for k, v in r.items() if k.endswith("_ms") and not k.startswith("host_")) for r in rows]))
+
+    # 1. one rank: the device phases, the two calls alternating
+    shape_keys = ("strips", "nodes", "work", "launches", "records", "copied_bytes")
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        phases = {"topic_blame": [], "dist_blame": []}
+        for _ in range(a.reps + 1):  # (the first calls build the window's tables and allocate)
+            with StderrCapture() as cap:
+                want = eng.topic_blame(topics)
+            phases["topic_blame"].append(counts(cap.text, phase_line(cap.text, "topic_blame"), shape_keys))
+            with StderrCapture() as cap:
+                got = eng.dist_blame(topics)
+            phases["dist_blame"].append(counts(cap.text, phase_line(cap.text, "dist_blame"), shape_keys))
+            for k in ("rec_off",) + keys:
+                assert np.array_equal(got[k], want[k]), f"ps_dist_blame {k} differs from ps_topic_blame"
+        res["phases"] = {k: v[1:] for k, v in phases.items()}
+        res["topic_blame_device_ms"] = device_ms(res["phases"]["topic_blame"])
+        res["dist_blame_device_ms"] = device_ms(res["phases"]["dist_blame"])
+        res["topic_blame_sweep_ms"] = float(np.median([r["sweep_ms"] for r in res["phases"]["topic_blame"]]))
+        res["dist_blame_sweep_ms"] = float(np.median([r["sweep_ms"] for r in res["phases"]["dist_blame"]]))
+        res["dist_over_topic_blame_device"] = res["dist_blame_device_ms"] / res["topic_blame_device_ms"]
+        res.update(deliveries=int(st.deliveries), records=int(got["peer"].size),
+                   cut_points=int((got["peer"] == got["cut_peer"]).sum()))
+        assert res["records"] > res["cut_points"] > 0
+    eng, _ = masked_engine({})
+    with eng:
+        walls = {"topic_blame": [], "dist_blame": []}
+        for _ in range(a.reps + 1):
+            t0 = time.perf_counter()
+            want = eng.topic_blame(topics)
+            walls["topic_blame"].append(1e3 * (time.perf_counter() - t0))
+            t0 = time.perf_counter()
+            got = eng.dist_blame(topics)
+            walls["dist_blame"].append(1e3 * (time.perf_counter() - t0))
+            for k in ("rec_off",) + keys:
+                assert np.array_equal(got[k], want[k]), k
+    res["topic_blame_wall_ms"], res["dist_blame_wall_ms"] = walls["topic_blame"][1:], walls["dist_blame"][1:]
+    res["dist_over_topic_blame_wall"] = float(np.median(res["dist_blame_wall_ms"]) / np.median(res["topic_blame_wall_ms"]))
+    res["answers_agree"] = True
+
+    # 2. loopback ranks, cfg4-shaped, the peer hash; the yardstick there: ps_dist_cut
+    w4 = WL.cfg4(200_000, 300)
+    live4 = (np.random.default_rng(a.seed).random(w4.n_peers) >= 0.03).astype(np.uint8)
+    live4[0] = 1
+    with PE.Engine(w4.n_peers, 1, seed=w4.seed) as one:
+        WL.build_engine_topics(one, w4)
+        one.set_live(live4)
+        one.publish(w4.msg_topics)
+        one.run()
+        whole = one.topic_blame([0])
+        whole_cut = one.peer_cut([0])
+    by_peer = np.argsort(whole["peer"], kind="stable")
+    whole_keyed = {k: whole[k][by_peer] for k in keys}
+    res["ranks"] = {"workload": "cfg4-shaped: 200000 peers, 300 messages, one topic", "partition": "peer hash",
+                    "records": int(whole["peer"].size), "cut_points": int((whole["peer"] == whole["cut_peer"]).sum()),
+                    "worlds": {}}
+
+    def threads(fn, world):
+        out, errs = [None] * world, []
+
+        def go(r):
+            try:
+                out[r] = fn(r)
+            except Exception as ex:  # noqa: BLE001
+                errs.append((r, ex))
+
+        th = [threading.Thread(target=go, args=(r,)) for r in range(world)]
+        for t in th:
+            t.start()
+        for t in th:
+            t.join(timeout=300)
+        assert not any(t.is_alive() for t in th) and not errs, errs
+        return out
+
+    def ranks_up(world, timed):
+        os.environ.pop("PSAMD_DRAIN_TIMING", None)
+        if timed:
+            os.environ["PSAMD_DRAIN_TIMING"] = "1"
+        lb = PE.Loopback(world)
+        engines = [PE.Engine(w4.n_peers, 1, seed=w4.seed) for _ in range(world)]
+        os.environ.pop("PSAMD_DRAIN_TIMING", None)
+        for r, e in enumerate(engines):
+            e.dist_init_loopback(lb, r)
+            WL.build_engine_topics(e, w4)
+            e.set_live(live4)
+            e.publish(w4.msg_topics)
+        threads(lambda r: engines[r].run(), world)
+        return lb, engines
+
+    calls = {"dist_blame": lambda e: e.dist_blame([0]), "dist_cut": lambda e: e.dist_cut([0])}
+    for world in (2, 4):
+        # the pass's shape and device phases from engines under PSAMD_DRAIN_TIMING, the walls from plain ones
+        lb, engines = ranks_up(world, True)
+        shape = {}
+        for tag, call in calls.items():
+            for _ in range(2):  # (the first call builds the slot tables and allocates)
+                with StderrCapture() as cap:
+                    threads(lambda r: call(engines[r]), world)
+            shape[tag] = []
+            for r in range(world):
+                m = re.search(rf"psamd {tag}: rank {r} .*", cap.text)
+                assert m, cap.text
+                row = {k: float(v) for k, v in re.findall(r"(\w+_ms) ([0-9.]+)", m.group(0))}
+                shape[tag].append(counts(m.group(0), row, ("strips", "nodes", "launches", "exchanges", "sent_bytes", "slot_bytes",
+                                                           "records", "copied_bytes")))
+        for e in engines:
+            e.close()
+        lb.close()
+        lb, engines = ranks_up(world, False)
+        walls = {tag: [] for tag in calls}
+        for _ in range(a.reps + 1):
+            for tag, call in calls.items():  # (alternating)
+
+                def timed_call(r):
+                    t0 = time.perf_counter()
+                    got = call(engines[r])
+                    return 1e3 * (time.perf_counter() - t0), got
+
+                out = threads(timed_call, world)
+                if tag == "dist_blame":  # the union, keyed by peer, against the one-rank answer
+                    peer = np.concatenate([o[1]["peer"] for o in out])
+                    at = np.argsort(peer, kind="stable")
+                    for k in keys:
+                        got = np.concatenate([o[1][k] for o in out])[at]
+                        assert np.array_equal(got, whole_keyed[k]), f"{world} ranks: the union's {k} differs from one rank's"
+                else:
+                    for i in range(4):
+                        assert np.array_equal(sum(o[1][i] for o in out), whole_cut[i]), f"{world} ranks: the cut's sum differs"
+                walls[tag].append([o[0] for o in out])
+        med = {tag: float(np.median(np.array(w[1:]))) for tag, w in walls.items()}
+        res["ranks"]["worlds"][str(world)] = {
+            "per_rank": shape, "first_call_wall_ms": {tag: w[0] for tag, w in walls.items()},
+            "wall_ms": {tag: w[1:] for tag, w in walls.items()}, "median_wall_ms": med,
+            "dist_blame_over_dist_cut_wall": med["dist_blame"] / med["dist_cut"]}
+        for e in engines:
+            e.close()
+        lb.close()
+    res["ranks"]["unions_agree"] = True
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "dist_blame_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def raw_shared(eng, qt, qp, lists, off, ids):
     n_lists, total = C.c_uint32(), C.c_uint64()
     u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
@@ -2505,6 +2691,8 @@ def main():
                     help="ps_dist_report against ps_peer_report on one rank; the collective call on 2 and 4 loopback ranks")
     ap.add_argument("--dist-cut", action="store_true",
                     help="ps_dist_cut against ps_peer_cut on one rank; against ps_dist_report's downstream on 2 and 4 loopback ranks")
+    ap.add_argument("--dist-blame", action="store_true",
+                    help="ps_dist_blame against ps_topic_blame on one rank; against ps_dist_cut on 2 and 4 loopback ranks")
     ap.add_argument("--spread", action="store_true", help="ps_topic_spread on a mesh of its own against ps_peer_load and the host derivation")
     ap.add_argument("--spread-peers", type=int, default=1 << 20)
     ap.add_argument("--spread-hub", type=int, default=4096)
@@ -2516,6 +2704,8 @@ def main():
         return dist_report_main(a, wl)
     if a.dist_cut:
         return dist_cut_main(a, wl)
+    if a.dist_blame:
+        return dist_blame_main(a, wl)
     if a.report or a.report_once:
         return report_main(a, wl)
     if a.blame:
