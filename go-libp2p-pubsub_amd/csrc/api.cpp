@@ -48,6 +48,8 @@ int dist_common(ps_engine* e, const ps_dist_config* dc) {
     return e->fail(PS_E_STATE, "cut points are tracked (one rank only): clear them with ps_cut_track first");
   if (e->drain.report.on)
     return e->fail(PS_E_STATE, "a report is tracked (one rank only): clear it with ps_report_track first");
+  if (e->drain.blame_trk.pass.on)
+    return e->fail(PS_E_STATE, "blame is tracked (one rank only): clear it with ps_blame_track first");
   // (every check above passed: the mode changes together with rank and world)
   e->inplace = dc->world > 1 && (dc->flags & PS_DIST_F_INPLACE) != 0;
   e->rank = dc->rank;

@@ -56,6 +56,10 @@
 //   k_blame_count / _emit the nodes that lack messages, strip by strip, into
 //                         records in node order
 //   k_blame_gather        a (topic, node) query's four facts from the words
+//   k_blame_track_commit  ps_blame_track (§5.5s): a window's row of offsets at
+//                         the run's cursor on the device, and the cursor moved on
+//   k_blame_track_emit    k_blame_emit's records from the window's base on,
+//                         below the cap in effect
 // and, for ps_peer_report / ps_report_track (§5.5m), those four answers from one pass:
 //   k_report_nodes        behind one k_audience_classify: a node's k once, into
 //                         the sections selected per launch (load's sums, the hop
@@ -1073,6 +1077,69 @@ __global__ __launch_bounds__(kAudBlock) void k_blame_emit(BlameArgs g) {
       if (g.rec_hop) g.rec_hop[to] = blame_level_of(lv, E.depth, u);
       if (g.rec_cut_hop) g.rec_cut_hop[to] = cut_level[u];
       if (g.rec_missed) g.rec_missed[to] = E.c_t - have;
+    }
+    at += __popcll(b);
+  }
+}
+
+// ps_blame_track's window w behind the scan, a thread per request position:
+// the window's row of the run's rec_off from the cursor the window before
+// left (cur[w & 1]: the window's base, which k_blame_track_emit reads there
+// too), and, by the grid's first thread, the cursor of the window behind
+// (cur[(w + 1) & 1]).  One writer per word: plain loads and stores.
+__global__ __launch_bounds__(kAudBlock) void k_blame_track_commit(BlameArgs g, BlameTrack t) {
+  const uint32_t i = blockIdx.x * kAudBlock + threadIdx.x;
+  const BlameCursor C = t.cur[t.w & 1];
+  const uint32_t ns = g.d.n_strips;
+  if (i < t.n_req) {
+    // the records in front of the entry behind position i: an idle or a
+    // skipped position repeats its predecessor
+    const uint64_t o = ns ? g.off[min(g.d.entries[min(t.ent[i], g.d.n)].strip0, ns)] : 0;
+    t.rec_off[t.w * t.n_req + 1 + i] = C.total + o;
+  }
+  if (i != 0) return;
+  if (t.w == 0) t.rec_off[0] = 0;
+  const uint64_t total = C.total + (ns ? g.off[ns] : 0);
+  BlameCursor N;
+  N.total = total;
+  N.over = C.over || total > t.cap;
+  // (no overflow so far: everything below C.total is stored, and C.total <= cap)
+  N.stored = C.over ? C.stored : total < t.cap ? total : t.cap;
+  N.pad = 0;
+  t.cur[(t.w + 1) & 1] = N;
+}
+
+// k_blame_emit's strips into the run's record arrays: from the window's base
+// on, below the cap in effect, and nothing once a window before overflowed.
+__global__ __launch_bounds__(kAudBlock) void k_blame_track_emit(BlameArgs g, BlameTrack t) {
+  const uint32_t lane = threadIdx.x & (kWave - 1);
+  const uint32_t s = __builtin_amdgcn_readfirstlane(blockIdx.x * (kAudBlock / kWave) + threadIdx.x / kWave);
+  if (s >= g.d.n_strips || g.n_rec[s] == 0) return;
+  const BlameCursor C = t.cur[t.w & 1];
+  if (C.over) return;
+  DownEntry E;
+  if (!blame_entry_of(g.d, s, &E)) return;
+  const AudStrip S = g.d.strips[s];
+  const uint32_t* __restrict__ lv = g.d.levels + E.lvl0;
+  const uint32_t nn = lv[E.depth + 1];
+  const uint32_t* __restrict__ k = g.d.k + E.n0;
+  const uint32_t* __restrict__ cut_node = g.cut_node + E.n0;
+  const uint32_t* __restrict__ cut_level = g.cut_level + E.n0;
+  uint64_t at = C.total + g.off[s];
+  for (uint32_t i0 = 0; i0 < S.n && at < t.cap; i0 += kWave) {  // (wave-uniform)
+    const uint32_t i = i0 + lane;
+    const uint32_t u = S.u0 + min(i, S.n - 1);
+    const uint32_t have = k[u];
+    const bool rec = i < S.n && have < E.c_t;
+    const uint64_t b = __ballot(rec);
+    const uint64_t to = at + __popcll(b & ((1ull << lane) - 1));
+    if (rec && to < t.cap) {
+      const uint32_t cn = cut_node[u];
+      g.rec_peer[to] = g.d.node_peer[E.nbase + u];
+      g.rec_cut_peer[to] = cn < nn ? g.d.node_peer[E.nbase + cn] : kBlameNone;
+      g.rec_hop[to] = blame_level_of(lv, E.depth, u);
+      g.rec_cut_hop[to] = cut_level[u];
+      g.rec_missed[to] = E.c_t - have;
     }
     at += __popcll(b);
   }
@@ -2662,6 +2729,20 @@ hipError_t launch_blame_emit(const BlameArgs& g, hipStream_t s) {
   const uint32_t by_strip = (g.d.n_strips + per - 1) / per, by_entry = (g.d.n + 1 + kAudBlock - 1) / kAudBlock;
   const uint32_t blocks = by_strip > by_entry ? by_strip : by_entry;
   hipLaunchKernelGGL(k_blame_emit, dim3(blocks), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+// (a thread per request position, one block at least: the cursor moves on by a window whatever it holds)
+hipError_t launch_blame_track_commit(const BlameArgs& g, const BlameTrack& t, hipStream_t s) {
+  const uint32_t blocks = t.n_req ? (t.n_req + kAudBlock - 1) / kAudBlock : 1;
+  hipLaunchKernelGGL(k_blame_track_commit, dim3(blocks), dim3(kAudBlock), 0, s, g, t);
+  return hipGetLastError();
+}
+
+hipError_t launch_blame_track_emit(const BlameArgs& g, const BlameTrack& t, hipStream_t s) {
+  if (g.d.n_strips == 0) return hipSuccess;
+  const uint32_t per = kAudBlock / kWave;
+  hipLaunchKernelGGL(k_blame_track_emit, dim3((g.d.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g, t);
   return hipGetLastError();
 }
 

@@ -53,6 +53,11 @@
 //                     down_front below), then a top-down sweep over the same
 //                     levels, records by count / scan / emit or a gather for
 //                     explicit queries; blocking only, with buffers of its own
+//   drain_blame_track.cpp  ps_blame_track / ps_blame_take and run.cpp's hooks
+//                     (§5.5s): that pass behind every window of a run, its
+//                     records appended at a cursor on the device, over the
+//                     downstream pass's window staging (down_window_stage,
+//                     down_window_done below), with buffers of its own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -69,7 +74,8 @@
 //    over each row set) and Load::fence (the last standing load pass over
 //    each), Hops::fence (the last standing hop pass) and Downstream::fence
 //    (the last standing downstream pass) and Cut::fence (the last standing
-//    cut pass) and Report::fence (the last standing report pass) are read by
+//    cut pass), Report::fence (the last standing report pass) and
+//    BlameTrack::pass.fence (the last standing blame pass) are read by
 //    drain_fence (run.cpp).
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.

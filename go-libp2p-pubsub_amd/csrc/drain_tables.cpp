@@ -507,7 +507,7 @@ void drain_destroy(ps_engine* e) {
   for (auto& f : D.hops.fence)
     if (f.ev) (void)hipEventDestroy(f.ev);
   if (D.hops.ev_take) (void)hipEventDestroy(D.hops.ev_take);
-  for (auto* H : {&D.down, &D.cut}) {
+  for (auto* H : {&D.down, &D.cut, &D.blame_trk.pass}) {
     if (H->h_out) (void)hipHostFree(H->h_out);
     for (auto& a : H->arena) {
       for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
@@ -528,7 +528,9 @@ void drain_destroy(ps_engine* e) {
   for (uint8_t* h : {D.dist.h_out, D.dist.h_off, D.dist.h_rec})
     if (h) (void)hipHostFree(h);
   if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);
-  for (uint8_t* h : {D.blame.h_off, D.blame.h_rec, D.blame.h_out})
+  for (hipEvent_t ev : D.blame_trk.ev_t)
+    if (ev) (void)hipEventDestroy(ev);
+  for (uint8_t* h : {D.blame.h_off, D.blame.h_rec, D.blame.h_out, D.blame_trk.h_cur, D.blame_trk.h_off, D.blame_trk.h_rec})
     if (h) (void)hipHostFree(h);
 }
 

@@ -1028,6 +1028,30 @@ struct ps_engine {
       uint8_t *h_off = nullptr, *h_rec = nullptr, *h_out = nullptr;
       size_t off_cap = 0, rec_cap = 0, out_cap = 0;
     } blame;
+
+    // ps_blame_track / ps_blame_take (host code:
+    // drain_blame_track.cpp): the blame pass behind every window of a run, its
+    // records appended at a cursor on the device -- k_blame_track_commit and
+    // k_blame_track_emit behind the blocking call's front, sweep, count and
+    // scan.  Nothing here is the blocking call's or another tracker's.
+    struct BlameTrack {
+      // the standing topics, the pass's buffers (pass.track), the kept strips,
+      // the arenas, the fences and the counts, as the other subtree trackers
+      // keep theirs; sync, d_out, d_acc, stage and h_out stay unused
+      Downstream pass;
+      size_t rec_cap = 0;  // the caller's (zero: the engine's, summed as the windows come)
+      uint64_t cap = 0;    // the cap in effect as far as the last window
+      // the sweep's words, the strips' record counts, their exclusive sum and
+      // its temporary; request position -> the entry behind it; the two
+      // cursors (BlameCursor[2]); the run's rec_off and the five record
+      // arrays, grown with their contents kept
+      psamd::DevBuf d_cut, d_cnt, d_off, d_scan, d_map, d_cur, d_rec_off, d_rec[5];
+      // pinned: the cursor read at a take, rec_off and the record arrays lent
+      // until the next ps_blame_take or ps_blame_track
+      uint8_t *h_cur = nullptr, *h_off = nullptr, *h_rec = nullptr;
+      size_t cur_cap = 0, off_cap = 0, view_cap = 0;
+      hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around a window's phases
+    } blame_trk;
   } drain;
 
   // The slot tables of ps_dist_report's cross-rank sweep (graph.cpp
@@ -1210,6 +1234,11 @@ void cut_abort(ps_engine* e);
 int report_open(ps_engine* e);
 int report_window(ps_engine* e);
 void report_abort(ps_engine* e);
+// drain_blame_track.cpp, the standing blame pass (ps_blame_track; all no-ops
+// while nothing is tracked): called where the report pass's hooks are
+int blame_open(ps_engine* e);
+int blame_window(ps_engine* e);
+void blame_abort(ps_engine* e);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

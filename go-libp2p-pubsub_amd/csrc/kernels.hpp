@@ -1113,6 +1113,47 @@ hipError_t launch_blame_count(const BlameArgs& g, hipStream_t s);
 hipError_t launch_blame_emit(const BlameArgs& g, hipStream_t s);
 hipError_t launch_blame_gather(const BlameArgs& g, const BlameGather& q, hipStream_t s);
 
+// ---- blame records behind every window (ps_blame_track, ps_blame_take) --
+// The pass above behind every window of a run, its records appended where a
+// cursor on the device stands: the front, the sweep, k_blame_count and the scan
+// as they are, then
+//   k_blame_track_commit  a thread per request position i of window w (the
+//                   host counts the windows): rec_off[w * n_req + 1 + i] =
+//                   base + off[entries[ent[i]].strip0], with base the records
+//                   of the windows before, cur[w & 1].total, and ent[i] the
+//                   tree topics among the positions [0, i] -- the entry behind
+//                   position i, so that an idle position and one skipped as a
+//                   mesh repeat their predecessor.  n_strips == 0: a window
+//                   without a row to read, every offset the base; entries and
+//                   off are not read.  The grid's first thread writes
+//                   rec_off[0] = 0 in window 0 and the cursor of the window
+//                   behind, cur[(w + 1) & 1]: total + the window's records;
+//                   over once total passes `cap`; stored = min(total, cap)
+//                   until a window has overflowed, then as it stands.  The two
+//                   cursors alternate so that every word has one writer and
+//                   no thread reads a word this launch writes.
+//   k_blame_track_emit    k_blame_emit's strips (ballot, lane prefix, node
+//                   order, the level by binary search) from record base +
+//                   off[strip] on, below `cap`; nothing where cur[w & 1].over
+//                   is set: a window before overflowed.  All five arrays.
+struct BlameCursor {
+  uint64_t total;   // records of the windows so far, stored or not
+  uint64_t stored;  // of them kept: the arrays hold exactly the first `stored`
+  uint64_t over;    // 1: a window passed the cap in effect; nothing is stored behind it
+  uint64_t pad;
+};
+struct BlameTrack {
+  BlameCursor* cur;     // [2]
+  const uint32_t* ent;  // [n_req]
+  uint64_t* rec_off;    // [(w + 1) * n_req + 1]
+  uint64_t w;
+  uint64_t cap;         // the cap in effect: the record arrays hold that many
+  uint32_t n_req;
+};
+// (BlameArgs: d, cut_node, cut_level, n_rec, off and the five arrays; rec_off and cap stay unused)
+hipError_t launch_blame_track_commit(const BlameArgs& g, const BlameTrack& t, hipStream_t s);
+hipError_t launch_blame_track_emit(const BlameArgs& g, const BlameTrack& t, hipStream_t s);
+
 // ---- the four answers from one pass (ps_peer_report, ps_report_track) --
 // What the four families above compute, each behind a classify of its own,
 // behind one: k_report_nodes works a node's k out once and feeds every section

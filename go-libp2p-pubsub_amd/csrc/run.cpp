@@ -200,6 +200,9 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   // ... and the standing report pass's (ps_report_track)
   for (const auto& F : e->drain.report.fence)
     if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending report pass");
+  // ... and the standing blame pass's (ps_blame_track)
+  for (const auto& F : e->drain.blame_trk.pass.fence)
+    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending blame pass");
   return PS_OK;
 }
 
@@ -1463,8 +1466,8 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
     e->defer_last = false;
     // (the window that was remembered: after a k_flood timeout, its re-run)
     if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e)) && !(rc = hops_window(e)) &&
-        !(rc = downstream_window(e)) && !(rc = cut_window(e)))
-      rc = report_window(e);
+        !(rc = downstream_window(e)) && !(rc = cut_window(e)) && !(rc = report_window(e)))
+      rc = blame_window(e);
     if (rc) return rc;
   }
   return PS_OK;
@@ -1588,7 +1591,7 @@ int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
   int rc = sink_precheck(e);
   if (rc || (rc = sink_open(e))) return rc;
   if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = downstream_open(e)) && !(rc = cut_open(e)) &&
-      !(rc = report_open(e)) && !(rc = run_windows(e, stp, may_defer)))
+      !(rc = report_open(e)) && !(rc = blame_open(e)) && !(rc = run_windows(e, stp, may_defer)))
     rc = sink_close(e);
   if (rc) {
     sink_abort(e);
@@ -1597,6 +1600,7 @@ int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
     downstream_abort(e);
     cut_abort(e);
     report_abort(e);
+    blame_abort(e);
   }
   return rc;
 }

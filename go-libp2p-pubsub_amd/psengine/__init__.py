@@ -199,6 +199,9 @@ PROTOTYPES = [
     ("ps_topic_blame", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p),
                                  C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u32p), _u64p]),
     ("ps_blame", C.c_int, [_P, _u32p, _u32p, C.c_size_t, _u32p, _u32p, _u32p, _u32p]),
+    ("ps_blame_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_size_t]),
+    ("ps_blame_take", C.c_int, [_P, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u32p),
+                                C.POINTER(_u32p), C.POINTER(_u32p), _u64p, _u64p, _u64p, _u64p]),
     ("ps_peer_report", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32, C.POINTER(Report), C.c_size_t]),
     ("ps_report_track", C.c_int, [_P, _u32p, C.c_size_t, C.c_uint32]),
     ("ps_report_take", C.c_int, [_P, C.POINTER(Report), C.c_size_t, _u64p, _u64p]),
@@ -927,6 +930,44 @@ class Engine:
         out = [np.empty(t.size, dtype=np.uint32) for _ in range(4)]
         self._check(self._L.ps_blame(self._h, tp, pp, t.size, *(_p(a, C.c_uint32) for a in out)))
         return out[0], out[1], out[2], out[3]
+
+    def blame_track(self, topics, rec_cap: int = 0):
+        """Registers standing tree topics (ps_blame_track): from now on every
+        window of every run appends topic_blame's records over them on the
+        device (blame_take).  No topic clears the tracking; setting or clearing
+        discards what was not taken.  rec_cap: the records kept between two
+        takes at most; 0: the engine's own cap, summed as the windows come."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_blame_track(self._h, _p(t, C.c_uint32), t.size, rec_cap))
+        self._blame_n = t.size
+
+    def blame_take(self) -> dict:
+        """Everything since the last take or track call (ps_blame_take): a
+        dict of numpy copies -- rec_off[n_windows * n + 1], cumulative, window
+        w's records of request position i at [rec_off[w * n + i],
+        rec_off[w * n + i + 1]); peer, cut_peer, hop, cut_hop and missed, the
+        first `stored` records each; n_windows, n_skipped, total and stored.
+        When the records exceeded the cap the EngineError (PS_E_RANGE) carries
+        that dict as `partial`: rec_off and the counts exact, the arrays the
+        prefix that was kept."""
+        off = _u64p()
+        ptrs = [_u32p() for _ in range(5)]
+        nw, nsk, total, stored = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        rc = self._L.ps_blame_take(self._h, C.byref(off), *(C.byref(p) for p in ptrs), C.byref(nw), C.byref(nsk),
+                                   C.byref(total), C.byref(stored))
+        if rc != -7 or not off:
+            self._check(rc)
+        out = {"rec_off": _view(off, nw.value * getattr(self, "_blame_n", 0) + 1, np.uint64).copy()}
+        for k, p in zip(("peer", "cut_peer", "hop", "cut_hop", "missed"), ptrs):
+            out[k] = _view(p, stored.value, np.uint32).copy()
+        out.update(n_windows=nw.value, n_skipped=nsk.value, total=total.value, stored=stored.value)
+        if rc:
+            err = EngineError(rc, self._L.ps_last_error(self._h).decode())
+            err.partial = out
+            raise err
+        return out
 
     def _report_arrays(self, n_topics: int, what: int) -> tuple[dict, Report]:
         """The selected sections' arrays (hop arrays [n_topics, MAX_ROUNDS],

@@ -829,9 +829,11 @@ int ps_cut_take(ps_engine* e, uint64_t* missed_out, uint64_t* cuts_out,
  * written in full.  Errors as ps_topic_blame's (repeats are no error), with
  * PS_E_RANGE, nothing written, for a topic or peer out of range and
  * PS_E_STATE if any queried topic is a mesh.
- *   There is no tracker and no _begin / _end form: a run's records are
- * variable-size per window, and the sink machinery for that is its own piece
- * of work. */
+ *   ps_blame_track / ps_blame_take below give ps_topic_blame's records behind
+ * every window of every run.  What remains missing is said of ps_blame's
+ * explicit queries: There is no tracker and no _begin / _end form of them.
+ * ps_topic_blame has no _begin / _end form either, and its tracker is for one
+ * rank only. */
 int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n,
                    const uint64_t** rec_off_out,      /* [n + 1]          */
                    const uint32_t** rec_peer_out,     /* [total] each     */
@@ -843,6 +845,63 @@ int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n,
 int ps_blame(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n,
              uint32_t* cut_peer_out, uint32_t* hop_out,
              uint32_t* cut_hop_out, uint32_t* missed_out);   /* [n] each */
+/* ps_topic_blame's records behind every window, not the last one alone (one
+ * rank).  ps_blame_track registers n standing tree topics
+ * (distinct; the list is copied), as ps_cut_track registers its own: n == 0
+ * clears the tracking and frees its buffers; PS_E_INVAL for a NULL engine,
+ * n > 0 without topic or a topic named twice, PS_E_RANGE for a topic out of
+ * range or rec_cap above 2^30, PS_E_STATE for a topic whose child lists make a
+ * mesh, PS_E_NOMEM when the record arrays cannot be allocated -- the previous
+ * tracking stays on each of these --, and PS_E_STATE with a run in flight and
+ * on a multi-rank engine (ps_dist_init* on an engine that tracks returns
+ * PS_E_STATE).  Setting or clearing discards what was not taken.  The tracking
+ * is independent of both sinks and of the five other trackers; all may be set
+ * at once.  From then on every window of every ps_run / ps_run_async that runs
+ * something enqueues the blame pass behind itself -- the window is neither
+ * planned nor launched differently -- and the pass appends its records on the
+ * device, at a cursor that lives on the device: no host wait.
+ *   For window w and request position i the records are rec_off[w*n + i] ..
+ * rec_off[w*n + i + 1]; w counts the windows since the last take or track
+ * call, across runs, in enqueue order; windows that run nothing do not count.
+ * They are, field for field and in the same ascending node order, what
+ * ps_topic_blame would have returned for topic[i] right after that window, on
+ * the node space that window ran on: k, miss, cut point, cut(u), hop and
+ * cut_hop are the ones defined above, word for word.  rec_off is one
+ * cumulative array: rec_off[0] == 0, total = rec_off[n_windows * n].  A topic
+ * idle in a window has an empty slice in that window's row; so has a tracked
+ * topic that is a mesh in the window's node space, and each such (topic,
+ * window) pair is counted once in n_skipped, as ps_cut_track counts it.
+ *   rec_cap > 0: at most that many records are kept between two takes, in five
+ * arrays (20 B a record) allocated by ps_blame_track.  rec_cap == 0: the
+ * engine's own cap -- per window the non-root nodes of the tracked tree topics
+ * that have window messages, 65536 at most, summed as the windows come; the
+ * arrays grow with their contents kept.  Overflow is sticky and leaves a
+ * prefix: records are stored densely in order, none at or past the cap in
+ * effect, and from the first window that overflows no later record is stored;
+ * stored is the number kept, and the arrays hold exactly the first `stored` of
+ * the `total` records.  rec_off, n_windows, n_skipped and total are exact
+ * whatever the cap; ps_blame_take then returns PS_E_RANGE with every output
+ * set.  total == cap is no overflow.
+ *   ps_blame_take waits for the passes enqueued so far and lends rec_off and
+ * the arrays asked for from pinned memory the engine owns (a NULL record
+ * pointer: that array is neither copied nor lent), valid until the next
+ * ps_blame_take, ps_blame_track or ps_destroy; the view is separate from
+ * ps_topic_blame's.  It resets the cursor in front of whatever runs next, and
+ * the counts.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with a run in
+ * flight; PS_E_INVAL for a NULL engine, rec_off_out or count pointer.  A take
+ * with no window since the last one gives rec_off = {0} and zeros.  After a
+ * failed ps_run / ps_wait the content is unspecified until the next take or
+ * track call. */
+int ps_blame_track(ps_engine* e, const uint32_t* topic, size_t n, size_t rec_cap);
+int ps_blame_take(ps_engine* e,
+                  const uint64_t** rec_off_out,      /* [n_windows * n + 1], cumulative */
+                  const uint32_t** rec_peer_out,     /* [stored] each; any may be NULL  */
+                  const uint32_t** rec_cut_peer_out,
+                  const uint32_t** rec_hop_out,
+                  const uint32_t** rec_cut_hop_out,
+                  const uint32_t** rec_missed_out,
+                  uint64_t* n_windows_out, uint64_t* n_skipped_out,
+                  uint64_t* total_out, uint64_t* stored_out);
 
 /* The four answers above from one pass: per-peer load, deliveries by hop, the
  * audience behind each peer and the losses blamed on their cut points, for an
@@ -1016,10 +1075,12 @@ int ps_dist_cut(ps_engine* e, const uint32_t* topic, size_t n,
  * since the run, and for a mesh topic (one-rank engines only).  A failed
  * exchange returns the transport's error (PS_E_DEVICE) with the outputs
  * unspecified.  n == 0 is valid: rec_off = {0}, total 0, nothing exchanged.
- *   ps_topic_blame and ps_blame keep refusing multi-rank engines.  There is no
- * sharded form of ps_blame, no tracker and no _begin / _end form: a query's
- * peer may be owned by another rank than the one that asks, and a run's records
- * are variable-size per window -- each its own piece of work. */
+ *   ps_topic_blame and ps_blame keep refusing multi-rank engines, and so does
+ * ps_blame_track.  What remains missing on a sharded engine: there is no
+ * sharded form of ps_blame, no tracker and no _begin / _end form -- a query's
+ * peer may be owned by another rank than the one that asks, and a sharded
+ * tracker needs collective exchanges inside the run: each its own piece of
+ * work. */
 int ps_dist_blame(ps_engine* e, const uint32_t* topic, size_t n,
                   const uint64_t** rec_off_out,      /* [n + 1]          */
                   const uint32_t** rec_peer_out,     /* [total] each     */

@@ -136,6 +136,18 @@ for record on every repetition; the records, the bytes copied, and one ps_blame
 over the records' own (topic, peer) pairs against them.  Writes
 DIR/blame_bench.json.
 
+--blame-track: the blame records behind every window (ps_blame_track /
+ps_blame_take) over every topic under --cut's live mask, rec_cap set to the
+records of --take-every steps.  The tracked step -- ps_run_async / ps_wait,
+pipelined, one take every --take-every steps -- against the loop it replaces,
+ps_run + ps_topic_blame every step, and against the untracked pipelined step,
+the three alternating in one process: wall per step, the overlapped windows,
+and the records of every take compared with the blocking call's, entry for
+entry.  The device phases of one tracked window and of one ps_topic_blame
+(PSAMD_DRAIN_TIMING: the tracked window's classify, weights, sweep, count +
+scan, commit + emit; the take's wall with its copies) alternate in a second
+engine.  Writes DIR/blame_track_bench.json.
+
 --report: the four answers from one pass (ps_peer_report, all sections) over
 every topic after one step under --cut's live mask, --reps repetitions
 alternating in one process with the sequence ps_peer_load + ps_topic_hops +
@@ -1752,6 +1764,130 @@ def blame_main(a, wl):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+def blame_track_main(a, wl):
+    """--blame-track (see the module text).  Writes DIR/blame_track_bench.json."""
+    nt = len(wl.topics)
+    topics = np.arange(nt, dtype=np.uint32)
+    none = np.zeros(0, dtype=np.uint32)
+    live = (np.random.default_rng(a.seed).random(wl.n_peers) >= 0.01).astype(np.uint8)
+    live[[ts.root for ts in wl.topics]] = 1
+    k = max(1, min(a.take_every, a.steps))
+    steps = a.steps // k * k
+    res = {"workload": wl.name, "scale": a.scale, "n_peers": wl.n_peers, "n_msgs": wl.n_msgs, "topics": nt, "reps": a.reps,
+           "steps": steps, "warmup": a.warmup, "take_every": k, "mask_seed": a.seed, "dead_peers": int((live == 0).sum())}
+
+    def masked_engine(env):
+        eng = fresh_engine(wl, env)
+        eng.set_live(live)
+        eng.publish(wl.msg_topics)
+        return eng, eng.run()
+
+    def agree(t, blocking, windows):
+        assert (t["n_windows"], t["n_skipped"], t["stored"]) == (windows, 0, t["total"]), "the tracker's counts"
+        assert t["total"] == windows * blocking["peer"].size
+        off = blocking["rec_off"].astype(np.int64)
+        want = np.concatenate([[0], (off[1:][None, :] + off[-1] * np.arange(windows)[:, None]).ravel()])
+        assert np.array_equal(t["rec_off"].astype(np.int64), want), "tracked rec_off differs"
+        for key in BLAME_KEYS:
+            assert np.array_equal(t[key], np.tile(blocking[key], windows)), f"tracked {key} differs from ps_topic_blame"
+
+    # the device phases: one tracked window and one blocking call, alternating
+    eng, st = masked_engine({"PSAMD_DRAIN_TIMING": "1"})
+    with eng:
+        assert st.windows == 1
+        blocking = eng.topic_blame(topics)
+        total = int(blocking["rec_off"][-1])
+        assert total > 0
+        rows = {"blame_track": [], "topic_blame": [], "blame_take": []}
+        eng.blame_track(topics, total)
+        for _ in range(a.reps + 1):  # (the first pass allocates)
+            eng.publish(wl.msg_topics)
+            with StderrCapture() as cap:
+                eng.run()
+            row = phase_line(cap.text, "blame_track")
+            for key in ("strips", "nodes", "row_bytes", "work", "launches"):
+                m = re.search(rf"psamd blame_track: .*\b{key} (\d+)", cap.text)
+                if m:
+                    row[key] = int(m.group(1))
+            rows["blame_track"].append(row)
+            with StderrCapture() as cap:
+                t = eng.blame_take()
+            agree(t, blocking, 1)
+            row = phase_line(cap.text, "blame_take")
+            row["copied_bytes"] = int(re.search(r"copied_bytes (\d+)", cap.text).group(1))
+            rows["blame_take"].append(row)
+            with StderrCapture() as cap:
+                got = eng.topic_blame(topics)
+            rows["topic_blame"].append(phase_line(cap.text, "topic_blame"))
+            for key in ("rec_off",) + BLAME_KEYS:
+                assert np.array_equal(got[key], blocking[key]), key
+        eng.blame_track(none)
+        res.update(records=total, deliveries=int(st.deliveries), tracked_phases=rows["blame_track"][1:],
+                   take_phases=rows["blame_take"][1:], blocking_phases=rows["topic_blame"][1:])
+        dev = lambda rs, skip=(): float(np.median([sum(v for q, v in r.items() if q.endswith("_ms") and q not in skip) for r in rs]))
+        res["tracked_window_device_ms"] = dev(res["tracked_phases"], ("host_ms",))
+        res["blocking_call_device_ms"] = dev(res["blocking_phases"], ("host_strips_ms", "copy_ms"))
+        res["blocking_call_copy_ms"] = float(np.median([r["copy_ms"] for r in res["blocking_phases"]]))
+
+    # the walls: the tracked pipelined step, the loop it replaces, the untracked pipelined step
+    eng, _ = masked_engine({})
+
+    def tracked(n):
+        eng.blame_track(topics, total * k)
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        takes = []
+        for _ in range(n // k):
+            loop_plain(eng, wl, k)
+            takes.append(eng.blame_take())
+        ms = 1e3 * (time.perf_counter() - t0) / n
+        over = eng.overlapped_windows() - o0
+        for t in takes:  # (outside the timed part)
+            agree(t, blocking, k)
+        eng.blame_track(none)
+        return ms, over
+
+    def blocking_loop(n):
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            eng.publish(wl.msg_topics)
+            eng.run()
+            got = eng.topic_blame(topics)
+        ms = 1e3 * (time.perf_counter() - t0) / n
+        for key in ("rec_off",) + BLAME_KEYS:
+            assert np.array_equal(got[key], blocking[key]), key
+        return ms, eng.overlapped_windows() - o0
+
+    def plain(n):
+        o0 = eng.overlapped_windows()
+        t0 = time.perf_counter()
+        for _ in range(n // k):
+            loop_plain(eng, wl, k)
+        return 1e3 * (time.perf_counter() - t0) / n, eng.overlapped_windows() - o0
+
+    modes = {"tracked": tracked, "run_plus_topic_blame": blocking_loop, "plain": plain}
+    with eng:
+        for f in modes.values():
+            f(max(a.warmup // k, 1) * k)
+        ms = {name: [] for name in modes}
+        over = {name: [] for name in modes}
+        for _ in range(a.reps):
+            for name, f in modes.items():
+                t, o = f(steps)
+                ms[name].append(t)
+                over[name].append(int(o))
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    res.update(ms_per_step=ms, overlapped_windows=over, records_agree=True, rec_cap=total * k,
+               tracked_minus_plain_ms=med["tracked"] - med["plain"],
+               blocking_loop_over_tracked=med["run_plus_topic_blame"] / med["tracked"])
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "blame_track_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 REPORT_CALLS = (("peer_load", "peer_load", ("recv", "sent")), ("topic_hops", "topic_hops", ("nodes", "reached", "deliv")),
                 ("peer_downstream", "peer_downstream", ("below", "carried")),
                 ("peer_cut", "peer_cut", ("missed", "cuts", "orphaned", "lost")))
@@ -2684,6 +2820,9 @@ def main():
     ap.add_argument("--cut", action="store_true",
                     help="ps_peer_cut against ps_peer_downstream and the host derivation; tracking in the pipelined loop")
     ap.add_argument("--blame", action="store_true", help="ps_topic_blame against ps_peer_cut and the host derivation")
+    ap.add_argument("--blame-track", action="store_true",
+                    help="ps_blame_track in the pipelined loop against ps_run + ps_topic_blame every step")
+    ap.add_argument("--take-every", type=int, default=10, help="--blame-track: steps between two ps_blame_take")
     ap.add_argument("--report", action="store_true",
                     help="ps_peer_report against the four calls in sequence; report tracking against the four trackers")
     ap.add_argument("--report-once", action="store_true", help="one step and one ps_peer_report (for a kernel trace)")
@@ -2708,6 +2847,8 @@ def main():
         return dist_blame_main(a, wl)
     if a.report or a.report_once:
         return report_main(a, wl)
+    if a.blame_track:
+        return blame_track_main(a, wl)
     if a.blame:
         return blame_main(a, wl)
     if a.cut:
