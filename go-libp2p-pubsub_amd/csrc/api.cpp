@@ -38,18 +38,10 @@ int dist_common(ps_engine* e, const ps_dist_config* dc) {
     return e->fail(PS_E_INVAL, "PS_DIST_F_INPLACE reads rows in place: not with PS_DIST_F_COPY");
   if (!e->pending.empty()) return e->fail(PS_E_STATE, "messages pending");
   if (e->drain.sink.on) return e->fail(PS_E_STATE, "a sink is set (one rank only): clear it with ps_sink_set first");
-  if (e->drain.load.on)
-    return e->fail(PS_E_STATE, "per-peer load is tracked (one rank only): clear it with ps_load_track first");
-  if (e->drain.hops.on)
-    return e->fail(PS_E_STATE, "hops are tracked (one rank only): clear them with ps_hops_track first");
-  if (e->drain.down.on)
-    return e->fail(PS_E_STATE, "the downstream audience is tracked (one rank only): clear it with ps_downstream_track first");
-  if (e->drain.cut.on)
-    return e->fail(PS_E_STATE, "cut points are tracked (one rank only): clear them with ps_cut_track first");
-  if (e->drain.report.on)
-    return e->fail(PS_E_STATE, "a report is tracked (one rank only): clear it with ps_report_track first");
-  if (e->drain.blame_trk.pass.on)
-    return e->fail(PS_E_STATE, "blame is tracked (one rank only): clear it with ps_blame_track first");
+  for (const auto* S : e->drain.standing())
+    if (S->on)
+      return e->fail(PS_E_STATE,
+                     std::string(S->name) + " is tracked (one rank only): clear it with ps_" + S->name + "_track first");
   // (every check above passed: the mode changes together with rank and world)
   e->inplace = dc->world > 1 && (dc->flags & PS_DIST_F_INPLACE) != 0;
   e->rank = dc->rank;

@@ -27,7 +27,7 @@ static_assert(kBlameNone == PS_NONE, "the kernels' none is the ABI's");
 int blame_sweep(ps_engine* e, Blame& H, const uint8_t* din, const Down::Shape& K, const PhaseTimer& tm, float* ms,
                 BlameArgs* g) {
   hipStream_t s = e->stream;
-  if (const int rc = down_front(e, H.plan.sync, din, K, tm, ms, &g->d)) return rc;
+  if (const int rc = down_front(e, H.front, din, K, tm, ms, &g->d)) return rc;
   HIP_TRY(H.d_cut.ensure(K.n_nodes * 8), "alloc blame words");
   g->cut_node = H.d_cut.as<uint32_t>();
   g->cut_level = g->cut_node + K.n_nodes;
@@ -80,7 +80,7 @@ int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n, const uint64_t
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
   Down::Shape K;
-  if ((rc = down_sync_stage(e, H.plan, topic, n, "blame", &K))) return rc;
+  if ((rc = down_sync_stage(e, H.stage, topic, n, "blame", &K))) return rc;
   const double host_ms = ms_since(t_host0);
 
   size_t asked = 0;
@@ -100,7 +100,7 @@ int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n, const uint64_t
     const uint64_t cap = K.n_verdicts;
     const size_t d_stride = align256(cap * 4);
     const size_t n_off = static_cast<size_t>(K.ns) + 1;
-    HIP_TRY(H.plan.sync.d_in.ensure(K.bytes), "alloc blame strips");
+    HIP_TRY(H.front.d_in.ensure(K.bytes), "alloc blame strips");
     HIP_TRY(H.d_cnt.ensure(n_off * 8), "alloc blame counts");
     HIP_TRY(H.d_off.ensure(n_off * 8), "alloc blame offsets");
     HIP_TRY(H.d_rec_off.ensure((n + 1) * 8), "alloc blame offsets");
@@ -108,9 +108,9 @@ int ps_topic_blame(ps_engine* e, const uint32_t* topic, size_t n, const uint64_t
     size_t scan_bytes = 0;
     HIP_TRY(drain_scan(nullptr, &scan_bytes, H.d_cnt.as<uint64_t>(), H.d_off.as<uint64_t>(), K.ns + 1, s), "size blame scan");
     HIP_TRY(H.d_scan.ensure(scan_bytes), "alloc blame scan");
-    HIP_TRY(hipMemcpyAsync(H.plan.sync.d_in.p, H.plan.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload blame strips");
+    HIP_TRY(hipMemcpyAsync(H.front.d_in.p, H.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload blame strips");
     BlameArgs g{};
-    if ((rc = blame_sweep(e, H, H.plan.sync.d_in.as<uint8_t>(), K, tm, ms, &g))) return rc;
+    if ((rc = blame_sweep(e, H, H.front.d_in.as<uint8_t>(), K, tm, ms, &g))) return rc;
     g.n_rec = H.d_cnt.as<uint64_t>();
     g.off = H.d_off.as<uint64_t>();
     g.rec_off = H.d_rec_off.as<uint64_t>();
@@ -189,8 +189,8 @@ int ps_blame(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
   Down::Shape K;
-  if ((rc = down_sync_stage(e, H.plan, dt.data(), dt.size(), "blame", &K))) return rc;
-  const DownEntry* const de = reinterpret_cast<const DownEntry*>(H.plan.stage.data());
+  if ((rc = down_sync_stage(e, H.stage, dt.data(), dt.size(), "blame", &K))) return rc;
+  const DownEntry* const de = reinterpret_cast<const DownEntry*>(H.stage.data());
 
   // the gather's block: queries | the table by topic id | the level tables
   size_t n_lvl = 0;
@@ -240,9 +240,9 @@ int ps_blame(ps_engine* e, const uint32_t* topic, const uint32_t* peer, size_t n
   HIP_TRY(hipMemcpyAsync(H.d_q.p, H.qstage.data(), q_bytes, hipMemcpyHostToDevice, s), "upload blame queries");
   BlameArgs g{};
   if (K.ns) {
-    HIP_TRY(H.plan.sync.d_in.ensure(K.bytes), "alloc blame strips");
-    HIP_TRY(hipMemcpyAsync(H.plan.sync.d_in.p, H.plan.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload blame strips");
-    if ((rc = blame_sweep(e, H, H.plan.sync.d_in.as<uint8_t>(), K, tm, ms, &g))) return rc;
+    HIP_TRY(H.front.d_in.ensure(K.bytes), "alloc blame strips");
+    HIP_TRY(hipMemcpyAsync(H.front.d_in.p, H.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload blame strips");
+    if ((rc = blame_sweep(e, H, H.front.d_in.as<uint8_t>(), K, tm, ms, &g))) return rc;
   }
   BlameGather G{};
   G.queries = H.d_q.as<DrainQuery>();

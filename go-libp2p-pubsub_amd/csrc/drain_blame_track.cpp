@@ -33,28 +33,14 @@ int blame_grow(ps_engine* e, DevBuf& buf, size_t need, hipStream_t s) {
 }
 
 void blame_release(Track& T) {
-  auto& P = T.pass.track;
-  for (DevBuf* b : {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_scratch, &T.d_cut, &T.d_cnt, &T.d_off, &T.d_scan, &T.d_map,
-                    &T.d_cur, &T.d_rec_off, &T.d_rec[0], &T.d_rec[1], &T.d_rec[2], &T.d_rec[3], &T.d_rec[4]})
-    b->release();
+  auto& P = T.track;
+  release_all({&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_scratch, &T.d_cut, &T.d_cnt, &T.d_off, &T.d_scan, &T.d_map,
+               &T.d_cur, &T.d_rec_off, &T.d_rec[0], &T.d_rec[1], &T.d_rec[2], &T.d_rec[3], &T.d_rec[4]});
 }
 
 }  // namespace
 
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::blame_open(ps_engine* e) {
-  auto& H = e->drain.blame_trk.pass;
-  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
-}
-
-void psamd::blame_abort(ps_engine* e) {
-  auto& H = e->drain.blame_trk.pass;
-  if (!H.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  H.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, its records appended: the block as cut_window
 // stages its own, the map from request position to the entry behind it, the
@@ -63,12 +49,12 @@ void psamd::blame_abort(ps_engine* e) {
 int psamd::blame_window(ps_engine* e) {
   auto& D = e->drain;
   auto& T = D.blame_trk;
-  auto& H = T.pass;
+  auto& H = T.st;
   if (!H.on || !H.open) return PS_OK;
   const auto t_host0 = hclock::now();
   Down::Shape K;
   size_t n_tree = 0;
-  int rc = down_window_stage(e, H, "blame", &K, &n_tree);
+  int rc = down_window_stage(e, H, T.track, T.kept, &K, &n_tree);
   if (rc) return rc;
   hipStream_t s = e->stream;
   const size_t n = H.topic.size();
@@ -120,7 +106,7 @@ int psamd::blame_window(ps_engine* e) {
     size_t scan_bytes = 0;
     HIP_TRY(drain_scan(nullptr, &scan_bytes, T.d_cnt.as<uint64_t>(), T.d_off.as<uint64_t>(), K.ns + 1, s), "size blame scan");
     HIP_TRY(T.d_scan.ensure(scan_bytes), "alloc blame scan");
-    if ((rc = down_front(e, H.track, H.track.d_in.as<uint8_t>(), K, tm, ms, &g.d))) return rc;
+    if ((rc = down_front(e, T.track, T.track.d_in.as<uint8_t>(), K, tm, ms, &g.d))) return rc;
     g.cut_node = T.d_cut.as<uint32_t>();
     g.cut_level = g.cut_node + K.n_nodes;
     g.n_rec = T.d_cnt.as<uint64_t>();
@@ -154,7 +140,7 @@ int psamd::blame_window(ps_engine* e) {
                  static_cast<unsigned long long>(K.row_bytes), K.launch.empty() ? 0u : K.launch.back(),
                  K.ns ? K.launch.size() + 6 : size_t(1), static_cast<unsigned long long>(T.cap), ms[0], ms[1], ms[2], ms[3],
                  ms[4], host_ms);
-  return down_window_done(e, H, "blame", n_tree);
+  return standing_window_done(e, H, n - n_tree);  // the mesh topics of this window
 }
 
 extern "C" {
@@ -163,17 +149,14 @@ extern "C" {
 
 int ps_blame_track(ps_engine* e, const uint32_t* topic, size_t n, size_t rec_cap) {
   if (!e || (n && !topic)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_blame_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  auto& T = e->drain.blame_trk;
+  auto& H = T.st;
+  if (const int rc = standing_track_check(e, H, topic, n)) return rc;
   if (n && rec_cap > (size_t(1) << 30)) return e->fail(PS_E_RANGE, "ps_blame_track: rec_cap above 2^30");
   for (size_t i = 0; i < n; ++i)
     if (hops_child_lists_mesh(e->topics[topic[i]])) return e->fail(PS_E_STATE, "ps_blame_track: a mesh topic has no cut points");
-  auto& T = e->drain.blame_trk;
-  auto& H = T.pass;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
   // whatever still appends records ends first
-  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
+  if (const int rc = standing_quiesce(e, H)) return rc;
   // the new tracking's buffers before the old one's go: a failed allocation
   // leaves the previous tracking as it stands
   DevBuf rec[5], map, cur, rec_off;
@@ -188,12 +171,7 @@ int ps_blame_track(ps_engine* e, const uint32_t* topic, size_t n, size_t rec_cap
       return e->fail(PS_E_NOMEM, std::string("ps_blame_track: ") + hipGetErrorString(rc));
     }
   }
-  down_settled(H);
-  H.open = nullptr;
-  H.strip_key.clear();
-  H.windows = H.skipped = 0;
-  H.topic.assign(topic, topic + n);
-  H.on = n > 0;
+  standing_retrack(H, topic, n);
   T.rec_cap = n ? rec_cap : 0;
   T.cap = T.rec_cap;
   blame_release(T);
@@ -213,10 +191,8 @@ int ps_blame_take(ps_engine* e, const uint64_t** rec_off_out, const uint32_t** r
   if (!e || !rec_off_out || !n_windows_out || !n_skipped_out || !total_out || !stored_out) return PS_E_INVAL;
   auto& D = e->drain;
   auto& T = D.blame_trk;
-  auto& H = T.pass;
-  if (!H.on) return e->fail(PS_E_NOTREADY, "no blame is tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  auto& H = T.st;
+  if (const int rc = standing_take_enter(e, H)) return rc;
   const auto t0 = hclock::now();
   const size_t n = H.topic.size();
   const uint64_t W = H.windows;
@@ -225,7 +201,7 @@ int ps_blame_take(ps_engine* e, const uint64_t** rec_off_out, const uint32_t** r
   for (auto* o : outs) asked += o != nullptr;
   HIP_TRY(pinned_ensure(&T.h_off, nullptr, &T.off_cap, n_off * 8), "alloc blame offsets");
   HIP_TRY(pinned_ensure(&T.h_cur, nullptr, &T.cur_cap, sizeof(BlameCursor)), "alloc blame cursor");
-  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "blame event");
+  if (const int rc = standing_take_event(e, H)) return rc;
   uint64_t* const h_off = reinterpret_cast<uint64_t*>(T.h_off);
   BlameCursor C{};
   size_t h_stride = 0;
@@ -260,7 +236,7 @@ int ps_blame_take(ps_engine* e, const uint64_t** rec_off_out, const uint32_t** r
     HIP_TRY(hipEventRecord(H.ev_take, s), "event");
     HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the blame records");
   }
-  down_settled(H);
+  standing_settled(H);
   *rec_off_out = h_off;
   for (size_t i = 0, j = 0; i < 5; ++i)
     if (outs[i]) *outs[i] = reinterpret_cast<const uint32_t*>(T.h_rec + j++ * h_stride);

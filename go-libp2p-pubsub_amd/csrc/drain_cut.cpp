@@ -7,7 +7,7 @@
 // whose pass run.cpp's hooks enqueue behind every window of a run, into totals
 // that ps_cut_take copies and clears.  The plan, the input block and the front
 // of the pass (k_audience_classify, k_audience_weights) are the downstream
-// pass's (drain_downstream.cpp: down_plan .. down_window_done); behind them
+// pass's (drain_downstream.cpp: down_plan .. down_window_stage); behind them
 // k_audience_missed over the strips, one k_cut_level launch per level over the
 // same work list, and k_cut_top.  Stream order is the only order between the
 // launches.  Buffers of their own.
@@ -46,35 +46,22 @@ int cut_pass(ps_engine* e, Cut::Pass& P, const uint8_t* din, const Cut::Shape& K
 
 }  // namespace
 
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::cut_open(ps_engine* e) {
-  auto& H = e->drain.cut;
-  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
-}
-
-void psamd::cut_abort(ps_engine* e) {
-  auto& H = e->drain.cut;
-  if (!H.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  H.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, added to the totals, as downstream_window adds
 // its own: all on `stream`, nothing waits.
 int psamd::cut_window(ps_engine* e) {
   auto& D = e->drain;
   auto& H = D.cut;
-  if (!H.on || !H.open) return PS_OK;
+  if (!H.st.on || !H.st.open) return PS_OK;
   Cut::Shape K;
   size_t n = 0;
-  int rc = down_window_stage(e, H, "cut", &K, &n);
+  int rc = down_window_stage(e, H.st, H.track, H.kept, &K, &n);
   if (rc) return rc;
   const PhaseTimer untimed{D.ev_t, e->stream, false};
   float none[4] = {0, 0, 0, 0};
   if ((rc = cut_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, H.d_acc.as<uint64_t>(), untimed, none))) return rc;
-  return down_window_done(e, H, "cut", n);
+  return standing_window_done(e, H.st, H.st.topic.size() - n);  // the mesh topics of this window
 }
 
 extern "C" {
@@ -91,6 +78,7 @@ int ps_peer_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_
     if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_peer_cut: a mesh topic has no subtrees");
   auto& D = e->drain;
   auto& H = D.cut;
+  auto& Ans = H.ans;
   const auto t_host0 = hclock::now();
   int rc = drain_ready(e);
   if (!rc) rc = drain_tables(e);
@@ -101,26 +89,26 @@ int ps_peer_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
   Cut::Shape K;
-  if ((rc = down_sync_stage(e, H, topic, n, "cut", &K))) return rc;
+  if ((rc = down_sync_stage(e, Ans.stage, topic, n, "cut", &K))) return rc;
   const double host_ms = ms_since(t_host0);
 
   HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc cut strips");
-  HIP_TRY(H.d_out.ensure(4 * np * 8), "alloc cut sums");
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, 4 * np * 8), "alloc cut view");
-  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(Ans.d_out.ensure(4 * np * 8), "alloc cut sums");
+  HIP_TRY(pinned_ensure(&Ans.h_out, nullptr, &Ans.out_cap, 4 * np * 8), "alloc cut view");
+  uint64_t* const out = Ans.d_out.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(out, 0, 4 * np * 8, s), "clear cut sums");
-  if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, H.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload cut strips");
+  if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, Ans.stage.data(), K.bytes, hipMemcpyHostToDevice, s), "upload cut strips");
   if ((rc = cut_pass(e, H.sync, H.sync.d_in.as<uint8_t>(), K, out, tm, ms))) return rc;
   // one copy: from the first array asked for to the last
   size_t lo = 0, hi = 4;
   while (!outs[lo]) ++lo;
   while (!outs[hi - 1]) --hi;
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(hipMemcpyAsync(H.h_out + lo * np * 8, out + lo * np, (hi - lo) * np * 8, hipMemcpyDeviceToHost, s), "read cut sums");
+  HIP_TRY(hipMemcpyAsync(Ans.h_out + lo * np * 8, out + lo * np, (hi - lo) * np * 8, hipMemcpyDeviceToHost, s), "read cut sums");
   HIP_TRY(hipStreamSynchronize(s), "sync");
   HIP_TRY(tm.end(ms[4]), "event");
   for (size_t i = lo; i < hi; ++i)
-    if (outs[i]) std::memcpy(outs[i], H.h_out + i * np * 8, np * 8);
+    if (outs[i]) std::memcpy(outs[i], Ans.h_out + i * np * 8, np * 8);
   if (D.env.timing)
     std::fprintf(stderr,
                  "psamd peer_cut: topics %zu strips %u nodes %llu row_bytes %llu work %u launches %zu classify_ms %.4f "
@@ -135,60 +123,30 @@ int ps_peer_cut(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* missed_
 
 int ps_cut_track(ps_engine* e, const uint32_t* topic, size_t n) {
   if (!e || (n && !topic)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_cut_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  auto& H = e->drain.cut;
+  if (const int rc = standing_track_check(e, H.st, topic, n)) return rc;
   for (size_t i = 0; i < n; ++i)
     if (hops_child_lists_mesh(e->topics[topic[i]])) return e->fail(PS_E_STATE, "ps_cut_track: a mesh topic has no subtrees");
-  auto& H = e->drain.cut;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  // whatever still adds into the totals ends first
-  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  down_settled(H);
-  H.open = nullptr;
-  H.strip_key.clear();
-  H.windows = H.skipped = 0;
-  H.topic.assign(topic, topic + n);
-  H.on = n > 0;
-  if (!H.on) {
-    H.d_acc.release();
-    H.track.d_in.release();
-    H.track.d_verdict.release();
-    H.track.d_exc.release();
-    H.track.d_full.release();
-    H.track.d_scratch.release();
-    return PS_OK;
-  }
-  const size_t bytes = 4 * static_cast<size_t>(e->cfg.n_peers) * 8;
-  HIP_TRY(H.d_acc.ensure(bytes), "alloc cut totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, e->stream), "clear cut totals");
-  return PS_OK;
+  if (const int rc = standing_quiesce(e, H.st)) return rc;
+  standing_retrack(H.st, topic, n);
+  auto& P = H.track;
+  return standing_totals(e, H.st, H.d_acc, 4 * static_cast<size_t>(e->cfg.n_peers) * 8,
+                         {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_scratch});
 }
 
 int ps_cut_take(ps_engine* e, uint64_t* missed_out, uint64_t* cuts_out, uint64_t* orphaned_out, uint64_t* lost_out,
                 uint64_t* n_windows_out, uint64_t* n_skipped_out) {
   if (!e || !n_windows_out || !n_skipped_out) return PS_E_INVAL;
   auto& H = e->drain.cut;
-  if (!H.on) return e->fail(PS_E_NOTREADY, "no cut is tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  auto& S = H.st;
   const size_t np = e->cfg.n_peers;
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, 4 * np * 8), "alloc cut view");
-  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "cut event");
-  // every pass ran on `stream`: the copy behind them, the clearing behind the
-  // copy and in front of whatever runs next, one wait
-  hipStream_t s = e->stream;
-  HIP_TRY(hipMemcpyAsync(H.h_out, H.d_acc.p, 4 * np * 8, hipMemcpyDeviceToHost, s), "read cut totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, 4 * np * 8, s), "clear cut totals");
-  HIP_TRY(hipEventRecord(H.ev_take, s), "event");
-  HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the cut totals");
-  down_settled(H);
+  if (const int rc = standing_take_totals(e, S, H.d_acc, H.ans, 4 * np * 8)) return rc;
   uint64_t* const outs[4] = {missed_out, cuts_out, orphaned_out, lost_out};
   for (size_t i = 0; i < 4; ++i)
-    if (outs[i]) std::memcpy(outs[i], H.h_out + i * np * 8, np * 8);
-  *n_windows_out = H.windows;
-  *n_skipped_out = H.skipped;
-  H.windows = H.skipped = 0;
+    if (outs[i]) std::memcpy(outs[i], H.ans.h_out + i * np * 8, np * 8);
+  *n_windows_out = S.windows;
+  *n_skipped_out = S.skipped;
+  S.windows = S.skipped = 0;
   return PS_OK;
 }
 

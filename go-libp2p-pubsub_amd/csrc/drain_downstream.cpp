@@ -170,26 +170,7 @@ int down_pass(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape
 
 }  // namespace
 
-// every pass enqueued so far is complete: nothing waits for one any more
-void psamd::down_settled(Down& H) {
-  for (auto& f : H.fence) f.pending = false;
-  for (auto& a : H.arena) a.pending = false;
-}
-
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::downstream_open(ps_engine* e) {
-  auto& H = e->drain.down;
-  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
-}
-
-void psamd::downstream_abort(ps_engine* e) {
-  auto& H = e->drain.down;
-  if (!H.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  H.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, added to the totals: its tables (built here
 // where nobody has), the entry table -- per window: it carries the window's
@@ -201,44 +182,39 @@ void psamd::downstream_abort(ps_engine* e) {
 int psamd::downstream_window(ps_engine* e) {
   auto& D = e->drain;
   auto& H = D.down;
-  if (!H.on || !H.open) return PS_OK;
+  if (!H.st.on || !H.st.open) return PS_OK;
   Down::Shape K;
   size_t n = 0;
-  int rc = down_window_stage(e, H, "downstream", &K, &n);
+  int rc = down_window_stage(e, H.st, H.track, H.kept, &K, &n);
   if (rc) return rc;
   const PhaseTimer untimed{D.ev_t, e->stream, false};
   float none[3] = {0, 0, 0};
   uint64_t* const acc = H.d_acc.as<uint64_t>();
   if ((rc = down_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, acc, acc + e->cfg.n_peers, untimed, none))) return rc;
-  return down_window_done(e, H, "downstream", n);
+  return standing_window_done(e, H.st, H.st.topic.size() - n);  // the mesh topics of this window
 }
 
-// What a standing pass over subtrees (state H, open) does in front of its
-// kernels: the window's tables, then the input block in H.track.d_in -- whole,
-// or the entry table alone while H.strip_key stands.  *K: its shape; *n_tree:
-// the tree topics among the standing ones.
-int psamd::down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape* Kout, size_t* n_tree) {
-  auto& D = e->drain;
-  const std::string w(who);
-  auto& R = H.open->mem;
-  if (const int rj = twin_join(e)) return rj;
-  hipStream_t s = e->stream;
-  size_t used = 0;
-  uint8_t* h = nullptr;
-  int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
+// What a standing pass over subtrees (tracker S, open; named S.name in
+// messages) does in front of its kernels: the window's tables, then the input
+// block in P.d_in -- whole, or the entry table alone while S.strip_key stands
+// and `kept` is its shape.  *K: its shape; *n_tree: the tree topics among the
+// standing ones.
+int psamd::down_window_stage(ps_engine* e, Drain::Standing& S, Down::Pass& P, Down::Shape& kept, Down::Shape* Kout,
+                             size_t* n_tree) {
+  const std::string w(S.name);
+  Drain::Sink::Res* Rp = nullptr;
+  int rc = standing_window_begin(e, S, &Rp);
   if (rc) return rc;
+  auto& R = *Rp;
+  hipStream_t s = e->stream;
   DownReq Q;
-  if ((rc = down_plan(e, H.topic.data(), H.topic.size(), who, &Q))) return rc;
+  if ((rc = down_plan(e, S.topic.data(), S.topic.size(), S.name, &Q))) return rc;
   const size_t n = Q.topic.size();
   const uint32_t* const topic = Q.topic.data();
 
   std::vector<uint64_t> key{e->graph_epoch, n, Q.n_lvl, Q.n_work};
   for (size_t i = 0; i < n; ++i) {
-    const DrainTopic& T = D.tab.topics[topic[i]];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, topic[i], &u0);
-    key.push_back(static_cast<uint64_t>(T.flags) << 32 | T.n_pos);
-    key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
+    (void)standing_key_topic(e, topic[i], &key);
     key.push_back(topic[i]);
   }
   Down::Shape& K = *Kout;
@@ -246,18 +222,16 @@ int psamd::down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   uint8_t* hs = nullptr;
-  if (key == H.strip_key) {
+  if (standing_key_stands(S, key)) {
     HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc subtree pass staging");
     aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);
     down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), nullptr, nullptr, &K);
-    if (K.ns != H.kept.ns || K.n_verdicts != H.kept.n_verdicts || K.n_nodes != H.kept.n_nodes || K.o_strips != H.kept.o_strips)
+    if (K.ns != kept.ns || K.n_verdicts != kept.n_verdicts || K.n_nodes != kept.n_nodes || K.o_strips != kept.o_strips)
       return e->fail(PS_E_STATE, w + ": the kept strips are not the window's");
-    K.bytes = H.kept.bytes;
-    K.launch = H.kept.launch;
-    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, (n + 1) * sizeof(DownEntry), hipMemcpyHostToDevice, s),
-            "upload subtree pass entries");
+    K.bytes = kept.bytes;
+    K.launch = kept.launch;
+    HIP_TRY(hipMemcpyAsync(P.d_in.p, hs, (n + 1) * sizeof(DownEntry), hipMemcpyHostToDevice, s), "upload subtree pass entries");
   } else {
-    H.strip_key.clear();
     size_t o = 0;
     uint64_t strips_max = 0;
     (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
@@ -268,32 +242,19 @@ int psamd::down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape
     down_entries(e, Q, ae.data(), A, reinterpret_cast<DownEntry*>(hs), reinterpret_cast<uint32_t*>(hs + K.o_lvl),
                  reinterpret_cast<DownWork*>(hs + K.o_work), &K);
     K.bytes = K.o_strips + static_cast<size_t>(K.ns) * sizeof(AudStrip);
-    HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc subtree pass strips");
-    HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload subtree pass strips");
-    H.kept = K;
-    H.strip_key = key;
+    HIP_TRY(P.d_in.ensure(K.bytes), "alloc subtree pass strips");
+    HIP_TRY(hipMemcpyAsync(P.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload subtree pass strips");
+    kept = K;
+    S.strip_key = key;
   }
   *n_tree = n;
   return PS_OK;
 }
 
-// ... and behind them: the fence of the row set, the run's event, the counts
-int psamd::down_window_done(ps_engine* e, Down& H, const char* who, size_t n_tree) {
-  hipStream_t s = e->stream;
-  int rc;
-  // classify and the counted rows read the window's row set: the events are
-  // recorded whether or not a row was read
-  if ((rc = pass_fence(e, H.fence, who))) return rc;
-  HIP_TRY(hipEventRecord(H.open->ev, s), "event");
-  H.open->pending = true;
-  H.windows += 1;
-  H.skipped += H.topic.size() - n_tree;  // the mesh topics of this window
-  return PS_OK;
-}
-
 // A blocking call's input block over the named tree topics (none a mesh), cut
-// whole into H.stage; *K: its shape
-int psamd::down_sync_stage(ps_engine* e, Down& H, const uint32_t* topic, size_t n, const char* who, Down::Shape* Kout) {
+// whole into `stage`; *K: its shape
+int psamd::down_sync_stage(ps_engine* e, std::vector<uint8_t>& stage, const uint32_t* topic, size_t n, const char* who,
+                           Down::Shape* Kout) {
   DownReq Q;
   if (const int rc = down_plan(e, topic, n, who, &Q)) return rc;
   Down::Shape& K = *Kout;
@@ -302,8 +263,8 @@ int psamd::down_sync_stage(ps_engine* e, Down& H, const uint32_t* topic, size_t 
   uint64_t strips_max = 0;
   (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
   if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
-  uint8_t* const hs = H.stage.data();
+  stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  uint8_t* const hs = stage.data();
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
@@ -326,6 +287,7 @@ int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* 
     if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_peer_downstream: a mesh topic has no subtrees");
   auto& D = e->drain;
   auto& H = D.down;
+  auto& Ans = H.ans;
   const auto t_host0 = hclock::now();
   int rc = drain_ready(e);
   if (!rc) rc = drain_tables(e);
@@ -336,25 +298,25 @@ int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* 
   const PhaseTimer tm{D.ev_t, s, D.env.timing};
 
   Down::Shape K;
-  if ((rc = down_sync_stage(e, H, topic, n, "downstream", &K))) return rc;
-  uint8_t* const hs = H.stage.data();
+  if ((rc = down_sync_stage(e, Ans.stage, topic, n, "downstream", &K))) return rc;
+  uint8_t* const hs = Ans.stage.data();
   const double host_ms = ms_since(t_host0);
 
   HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc downstream strips");
-  HIP_TRY(H.d_out.ensure(2 * np * 8), "alloc downstream sums");
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, 2 * np * 8), "alloc downstream view");
-  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(Ans.d_out.ensure(2 * np * 8), "alloc downstream sums");
+  HIP_TRY(pinned_ensure(&Ans.h_out, nullptr, &Ans.out_cap, 2 * np * 8), "alloc downstream view");
+  uint64_t* const out = Ans.d_out.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(out, 0, 2 * np * 8, s), "clear downstream sums");
   if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload downstream strips");
   if ((rc = down_pass(e, H.sync, H.sync.d_in.as<uint8_t>(), K, out, out + np, tm, ms))) return rc;
   // one copy: both arrays, or the one that was asked for
   const size_t lo = below_out ? 0 : np, hi = carried_out ? 2 * np : np;
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(hipMemcpyAsync(H.h_out + lo * 8, out + lo, (hi - lo) * 8, hipMemcpyDeviceToHost, s), "read downstream sums");
+  HIP_TRY(hipMemcpyAsync(Ans.h_out + lo * 8, out + lo, (hi - lo) * 8, hipMemcpyDeviceToHost, s), "read downstream sums");
   HIP_TRY(hipStreamSynchronize(s), "sync");
   HIP_TRY(tm.end(ms[3]), "event");
-  if (below_out) std::memcpy(below_out, H.h_out, np * 8);
-  if (carried_out) std::memcpy(carried_out, H.h_out + np * 8, np * 8);
+  if (below_out) std::memcpy(below_out, Ans.h_out, np * 8);
+  if (carried_out) std::memcpy(carried_out, Ans.h_out + np * 8, np * 8);
   if (D.env.timing)
     std::fprintf(stderr,
                  "psamd peer_downstream: topics %zu strips %u nodes %llu row_bytes %llu work %u launches %zu classify_ms %.4f "
@@ -369,60 +331,30 @@ int ps_peer_downstream(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* 
 
 int ps_downstream_track(ps_engine* e, const uint32_t* topic, size_t n) {
   if (!e || (n && !topic)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_downstream_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  auto& H = e->drain.down;
+  if (const int rc = standing_track_check(e, H.st, topic, n)) return rc;
   for (size_t i = 0; i < n; ++i)
     if (hops_child_lists_mesh(e->topics[topic[i]]))
       return e->fail(PS_E_STATE, "ps_downstream_track: a mesh topic has no subtrees");
-  auto& H = e->drain.down;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  // whatever still adds into the totals ends first
-  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  down_settled(H);
-  H.open = nullptr;
-  H.strip_key.clear();
-  H.windows = H.skipped = 0;
-  H.topic.assign(topic, topic + n);
-  H.on = n > 0;
-  if (!H.on) {
-    H.d_acc.release();
-    H.track.d_in.release();
-    H.track.d_verdict.release();
-    H.track.d_exc.release();
-    H.track.d_full.release();
-    H.track.d_scratch.release();
-    return PS_OK;
-  }
-  const size_t bytes = 2 * static_cast<size_t>(e->cfg.n_peers) * 8;
-  HIP_TRY(H.d_acc.ensure(bytes), "alloc downstream totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, e->stream), "clear downstream totals");
-  return PS_OK;
+  if (const int rc = standing_quiesce(e, H.st)) return rc;
+  standing_retrack(H.st, topic, n);
+  auto& P = H.track;
+  return standing_totals(e, H.st, H.d_acc, 2 * static_cast<size_t>(e->cfg.n_peers) * 8,
+                         {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_scratch});
 }
 
 int ps_downstream_take(ps_engine* e, uint64_t* below_out, uint64_t* carried_out, uint64_t* n_windows_out,
                        uint64_t* n_skipped_out) {
   if (!e || !n_windows_out || !n_skipped_out) return PS_E_INVAL;
   auto& H = e->drain.down;
-  if (!H.on) return e->fail(PS_E_NOTREADY, "no downstream audience is tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
+  auto& S = H.st;
   const size_t np = e->cfg.n_peers;
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, 2 * np * 8), "alloc downstream view");
-  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "downstream event");
-  // every pass ran on `stream`: the copy behind them, the clearing behind the
-  // copy and in front of whatever runs next, one wait
-  hipStream_t s = e->stream;
-  HIP_TRY(hipMemcpyAsync(H.h_out, H.d_acc.p, 2 * np * 8, hipMemcpyDeviceToHost, s), "read downstream totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, 2 * np * 8, s), "clear downstream totals");
-  HIP_TRY(hipEventRecord(H.ev_take, s), "event");
-  HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the downstream totals");
-  down_settled(H);
-  if (below_out) std::memcpy(below_out, H.h_out, np * 8);
-  if (carried_out) std::memcpy(carried_out, H.h_out + np * 8, np * 8);
-  *n_windows_out = H.windows;
-  *n_skipped_out = H.skipped;
-  H.windows = H.skipped = 0;
+  if (const int rc = standing_take_totals(e, S, H.d_acc, H.ans, 2 * np * 8)) return rc;
+  if (below_out) std::memcpy(below_out, H.ans.h_out, np * 8);
+  if (carried_out) std::memcpy(carried_out, H.ans.h_out + np * 8, np * 8);
+  *n_windows_out = S.windows;
+  *n_skipped_out = S.skipped;
+  S.windows = S.skipped = 0;
   return PS_OK;
 }
 

@@ -126,12 +126,6 @@ int hops_pass(ps_engine* e, Hops::Pass& P, const uint8_t* din, const Hops::Shape
   return PS_OK;
 }
 
-// every pass enqueued so far is complete: nothing waits for one any more
-void hops_settled(Hops& H) {
-  for (auto& f : H.fence) f.pending = false;
-  for (auto& a : H.arena) a.pending = false;
-}
-
 size_t hops_total_bytes(size_t n) { return 3 * n * kHopsCols * 8; }
 
 }  // namespace
@@ -180,20 +174,7 @@ bool psamd::hops_child_lists_mesh(const TopicHost& T) {
   return false;
 }
 
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::hops_open(ps_engine* e) {
-  auto& H = e->drain.hops;
-  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
-}
-
-void psamd::hops_abort(ps_engine* e) {
-  auto& H = e->drain.hops;
-  if (!H.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  H.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, added to the totals: its tables (built here
 // where nobody has), the entry table -- per window: it carries the window's
@@ -207,26 +188,21 @@ void psamd::hops_abort(ps_engine* e) {
 int psamd::hops_window(ps_engine* e) {
   auto& D = e->drain;
   auto& H = D.hops;
-  if (!H.on || !H.open) return PS_OK;
-  auto& R = H.open->mem;
-  if (const int rj = twin_join(e)) return rj;
-  hipStream_t s = e->stream;
-  size_t used = 0;
-  uint8_t* h = nullptr;
-  int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
+  auto& S = H.st;
+  if (!S.on || !S.open) return PS_OK;
+  Drain::Sink::Res* Rp = nullptr;
+  int rc = standing_window_begin(e, S, &Rp);
   if (rc) return rc;
+  auto& R = *Rp;
+  hipStream_t s = e->stream;
   HopsReq Q;
-  if ((rc = hops_plan(e, H.topic.data(), H.topic.size(), &Q))) return rc;
+  if ((rc = hops_plan(e, S.topic.data(), S.topic.size(), &Q))) return rc;
   const size_t n = Q.topic.size();
   const uint32_t* const topic = Q.topic.data();
 
   std::vector<uint64_t> key{e->graph_epoch, n, Q.n_lvl};
   for (size_t i = 0; i < n; ++i) {
-    const DrainTopic& T = D.tab.topics[topic[i]];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, topic[i], &u0);
-    key.push_back(static_cast<uint64_t>(T.flags) << 32 | T.n_pos);
-    key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
+    (void)standing_key_topic(e, topic[i], &key);
     key.push_back(static_cast<uint64_t>(Q.row[i]) << 32 | topic[i]);
   }
   Hops::Shape K;
@@ -234,7 +210,7 @@ int psamd::hops_window(ps_engine* e) {
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   uint8_t* hs = nullptr;
-  if (key == H.strip_key) {
+  if (standing_key_stands(S, key)) {
     HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc hop staging");
     aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);
     hops_entries(e, Q, ae.data(), A, reinterpret_cast<HopsEntry*>(hs), nullptr, &K);
@@ -243,7 +219,6 @@ int psamd::hops_window(ps_engine* e) {
     K.bytes = H.kept.bytes;
     HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, (n + 1) * sizeof(HopsEntry), hipMemcpyHostToDevice, s), "upload hop entries");
   } else {
-    H.strip_key.clear();
     size_t o = 0;
     uint64_t strips_max = 0;
     (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
@@ -256,21 +231,14 @@ int psamd::hops_window(ps_engine* e) {
     HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc hop strips");
     HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload hop strips");
     H.kept = K;
-    H.strip_key = key;
+    S.strip_key = key;
   }
   const PhaseTimer untimed{D.ev_t, s, false};
   float none[3] = {0, 0, 0};
   uint64_t* const acc = H.d_acc.as<uint64_t>();
-  const size_t rows = H.topic.size() * kHopsCols;
+  const size_t rows = S.topic.size() * kHopsCols;
   if ((rc = hops_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, acc, acc + rows, acc + 2 * rows, untimed, none))) return rc;
-  // classify and the counted rows read the window's row set: the events are
-  // recorded whether or not a row was read
-  if ((rc = pass_fence(e, H.fence, "hops"))) return rc;
-  HIP_TRY(hipEventRecord(H.open->ev, s), "event");
-  H.open->pending = true;
-  H.windows += 1;
-  H.skipped += H.topic.size() - n;  // the mesh topics of this window
-  return PS_OK;
+  return standing_window_done(e, S, S.topic.size() - n);  // the mesh topics of this window
 }
 
 extern "C" {
@@ -287,6 +255,7 @@ int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes
   if (n == 0) return PS_OK;
   auto& D = e->drain;
   auto& H = D.hops;
+  auto& Ans = H.ans;
   const auto t_host0 = hclock::now();
   int rc = drain_ready(e);
   if (!rc) rc = drain_tables(e);
@@ -303,8 +272,8 @@ int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes
   uint64_t strips_max = 0;
   (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
   if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
-  uint8_t* const hs = H.stage.data();
+  Ans.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  uint8_t* const hs = Ans.stage.data();
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   if (!aud_stage(e, topic, n, ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
@@ -315,19 +284,19 @@ int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes
 
   const size_t rows = n * kHopsCols, out_bytes = hops_total_bytes(n);
   HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc hop strips");
-  HIP_TRY(H.d_out.ensure(out_bytes), "alloc hop sums");
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes), "alloc hop view");
-  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(Ans.d_out.ensure(out_bytes), "alloc hop sums");
+  HIP_TRY(pinned_ensure(&Ans.h_out, nullptr, &Ans.out_cap, out_bytes), "alloc hop view");
+  uint64_t* const out = Ans.d_out.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s), "clear hop sums");
   if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload hop strips");
   if ((rc = hops_pass(e, H.sync, H.sync.d_in.as<uint8_t>(), K, out, out + rows, out + 2 * rows, tm, ms))) return rc;
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(hipMemcpyAsync(H.h_out, out, out_bytes, hipMemcpyDeviceToHost, s), "read hop sums");
+  HIP_TRY(hipMemcpyAsync(Ans.h_out, out, out_bytes, hipMemcpyDeviceToHost, s), "read hop sums");
   HIP_TRY(hipStreamSynchronize(s), "sync");
   HIP_TRY(tm.end(ms[3]), "event");
-  if (nodes_out) std::memcpy(nodes_out, H.h_out, rows * 8);
-  if (reached_out) std::memcpy(reached_out, H.h_out + rows * 8, rows * 8);
-  if (deliv_out) std::memcpy(deliv_out, H.h_out + 2 * rows * 8, rows * 8);
+  if (nodes_out) std::memcpy(nodes_out, Ans.h_out, rows * 8);
+  if (reached_out) std::memcpy(reached_out, Ans.h_out + rows * 8, rows * 8);
+  if (deliv_out) std::memcpy(deliv_out, Ans.h_out + 2 * rows * 8, rows * 8);
   if (D.env.timing)
     std::fprintf(stderr,
                  "psamd topic_hops: topics %zu strips %u nodes %llu row_bytes %llu partials %llu classify_ms %.4f hops_ms %.4f "
@@ -341,61 +310,32 @@ int ps_topic_hops(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* nodes
 
 int ps_hops_track(ps_engine* e, const uint32_t* topic, size_t n) {
   if (!e || (n && !topic)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_hops_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  auto& H = e->drain.hops;
+  if (const int rc = standing_track_check(e, H.st, topic, n)) return rc;
   for (size_t i = 0; i < n; ++i)
     if (hops_child_lists_mesh(e->topics[topic[i]]))
       return e->fail(PS_E_STATE, "ps_hops_track: a mesh topic has no hop per node");
-  auto& H = e->drain.hops;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  // whatever still adds into the totals ends first
-  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  hops_settled(H);
-  H.open = nullptr;
-  H.strip_key.clear();
-  H.windows = H.skipped = 0;
-  H.topic.assign(topic, topic + n);
-  H.on = n > 0;
-  if (!H.on) {
-    H.d_acc.release();
-    H.track.d_in.release();
-    H.track.d_verdict.release();
-    H.track.d_exc.release();
-    H.track.d_full.release();
-    H.track.d_part_r.release();
-    H.track.d_part_d.release();
-    return PS_OK;
-  }
-  HIP_TRY(H.d_acc.ensure(hops_total_bytes(n)), "alloc hop totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, hops_total_bytes(n), e->stream), "clear hop totals");
-  return PS_OK;
+  if (const int rc = standing_quiesce(e, H.st)) return rc;
+  standing_retrack(H.st, topic, n);
+  auto& P = H.track;
+  return standing_totals(e, H.st, H.d_acc, hops_total_bytes(n),
+                         {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_part_r, &P.d_part_d});
 }
 
 int ps_hops_take(ps_engine* e, uint64_t* nodes_out, uint64_t* reached_out, uint64_t* deliv_out, uint64_t* n_windows_out,
                  uint64_t* n_skipped_out) {
   if (!e || !n_windows_out || !n_skipped_out) return PS_E_INVAL;
   auto& H = e->drain.hops;
-  if (!H.on) return e->fail(PS_E_NOTREADY, "no hops are tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  const size_t rows = H.topic.size() * kHopsCols, bytes = hops_total_bytes(H.topic.size());
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, bytes), "alloc hop view");
-  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "hop event");
-  // every pass ran on `stream`: the copy behind them, the clearing behind the
-  // copy and in front of whatever runs next, one wait
-  hipStream_t s = e->stream;
-  HIP_TRY(hipMemcpyAsync(H.h_out, H.d_acc.p, bytes, hipMemcpyDeviceToHost, s), "read hop totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, s), "clear hop totals");
-  HIP_TRY(hipEventRecord(H.ev_take, s), "event");
-  HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the hop totals");
-  hops_settled(H);
-  if (nodes_out) std::memcpy(nodes_out, H.h_out, rows * 8);
-  if (reached_out) std::memcpy(reached_out, H.h_out + rows * 8, rows * 8);
-  if (deliv_out) std::memcpy(deliv_out, H.h_out + 2 * rows * 8, rows * 8);
-  *n_windows_out = H.windows;
-  *n_skipped_out = H.skipped;
-  H.windows = H.skipped = 0;
+  auto& S = H.st;
+  const size_t rows = S.topic.size() * kHopsCols;
+  if (const int rc = standing_take_totals(e, S, H.d_acc, H.ans, hops_total_bytes(S.topic.size()))) return rc;
+  const uint8_t* const h = H.ans.h_out;
+  if (nodes_out) std::memcpy(nodes_out, h, rows * 8);
+  if (reached_out) std::memcpy(reached_out, h + rows * 8, rows * 8);
+  if (deliv_out) std::memcpy(deliv_out, h + 2 * rows * 8, rows * 8);
+  *n_windows_out = S.windows;
+  *n_skipped_out = S.skipped;
+  S.windows = S.skipped = 0;
   return PS_OK;
 }
 

@@ -2,6 +2,10 @@
 // drain.hip).  One file per call family:
 //   drain_tables.cpp  per window, not per call: the entry checks, both table
 //                     builds, query resolution, count + scan, pinned staging
+//   drain_standing.cpp  the tracker lifecycle, once for the six ps_*_track /
+//                     ps_*_take families below: a run's
+//                     staging, the front and the back of a window's pass, the
+//                     fence per row set, registering topics, the take of the totals
 //   drain.cpp         ps_drain, ps_drain_begin / ps_drain_end, the slots
 //   drain_shared.cpp  ps_drain_shared, ps_drain_shared_begin / _end (§5.5c, d),
 //                     the shared-list pass and the synchronous list tail
@@ -12,25 +16,25 @@
 //   drain_topics.cpp  ps_drain_topics (§5.5f): a topic's audience as one list
 //                     plus exceptions; ps_drain_topics_begin / _end (§5.5g):
 //                     that answer behind a running batch
-//   drain_load.cpp    ps_peer_load, ps_load_track / ps_load_take and run.cpp's
-//                     hooks (§5.5i): per-peer recv / sent sums from the audience
+//   drain_load.cpp    ps_peer_load, ps_load_track / ps_load_take and its window
+//                     hook (§5.5i): per-peer recv / sent sums from the audience
 //                     pass's strips and verdicts, with buffers of their own
-//   drain_hops.cpp    ps_topic_hops, ps_hops_track / ps_hops_take and run.cpp's
-//                     hooks (§5.5j): per tree topic, nodes / reached / deliv by
+//   drain_hops.cpp    ps_topic_hops, ps_hops_track / ps_hops_take and its window
+//                     hook (§5.5j): per tree topic, nodes / reached / deliv by
 //                     BFS level from the same strips and verdicts and the
 //                     host's level tables, with buffers of their own
 //   drain_downstream.cpp  ps_peer_downstream, ps_downstream_track / _take and
-//                     run.cpp's hooks (§5.5k): per peer, the nodes and window
+//                     its window hook (§5.5k): per peer, the nodes and window
 //                     messages below its nodes, bottom-up over the same level
 //                     tables behind the same strips and verdicts, with buffers
 //                     of their own
-//   drain_cut.cpp     ps_peer_cut, ps_cut_track / _take and run.cpp's hooks
+//   drain_cut.cpp     ps_peer_cut, ps_cut_track / _take and its window hook
 //                     (§5.5l): per peer, what its nodes missed and what was lost
 //                     behind its cut points, over the downstream pass's plan
-//                     (down_plan .. down_window_done below), with buffers of
+//                     (down_plan .. down_window_stage below), with buffers of
 //                     their own
-//   drain_report.cpp  ps_peer_report, ps_report_track / _take and run.cpp's
-//                     hooks (§5.5m): the four answers above from one classify,
+//   drain_report.cpp  ps_peer_report, ps_report_track / _take and its window
+//                     hook (§5.5m): the four answers above from one classify,
 //                     one per-node kernel and one bottom-up sweep, over the hop
 //                     pass's and the downstream pass's plans (hops_plan,
 //                     hops_entries, down_plan .. down_entries below), with
@@ -53,11 +57,11 @@
 //                     down_front below), then a top-down sweep over the same
 //                     levels, records by count / scan / emit or a gather for
 //                     explicit queries; blocking only, with buffers of its own
-//   drain_blame_track.cpp  ps_blame_track / ps_blame_take and run.cpp's hooks
+//   drain_blame_track.cpp  ps_blame_track / ps_blame_take and its window hook
 //                     (§5.5s): that pass behind every window of a run, its
 //                     records appended at a cursor on the device, over the
-//                     downstream pass's window staging (down_window_stage,
-//                     down_window_done below), with buffers of its own
+//                     downstream pass's window staging (down_window_stage
+//                     below), with buffers of its own
 // The state is ps_engine::Drain (engine.hpp), grouped by owner.
 //
 // What the paths rely on, between them and with run.cpp:
@@ -71,12 +75,15 @@
 //    slab k - 1 is copied while slab k is emitted; under timing the copy runs
 //    in line on `stream`.
 //  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
-//    over each row set) and Load::fence (the last standing load pass over
-//    each), Hops::fence (the last standing hop pass) and Downstream::fence
-//    (the last standing downstream pass) and Cut::fence (the last standing
-//    cut pass), Report::fence (the last standing report pass) and
-//    BlameTrack::pass.fence (the last standing blame pass) are read by
-//    drain_fence (run.cpp).
+//    over each row set) and every tracker's Standing::fence (its last standing
+//    pass over each) are read by drain_fence (run.cpp).
+//  - The six trackers keep one Drain::Standing each and go through
+//    drain_standing.cpp for all of its lifecycle; Drain::standing() lists them
+//    in the order run.cpp opens them, runs their *_window hooks
+//    (kStandingWindow) and aborts them, and drain_fence, drain_destroy and
+//    ps_dist_init*'s refusal walk the same list.  No two share an arena or an
+//    event.  A new tracker is a Standing, a *_window function and one row of
+//    that table.
 //  - ps_drain_shared_begin and the sink run one pass over their queries
 //    (shared_stage, shared_caps, shared_pass), each with buffers of its own.
 //  - ps_drain_topics_begin and the audience sink run one pass over their topics
@@ -96,6 +103,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "engine.hpp"
 
@@ -140,10 +148,9 @@ struct PhaseTimer {
 
 hipError_t pinned_ensure(uint8_t** h, uint8_t** d, size_t* cap, size_t need);
 hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out);
-// the standing passes (load, hops): a run's pinned staging, arena[run & 1];
-// the event behind the last pass over the current row set
-int pass_arena_open(ps_engine* e, Drain::PassArena (&arena)[2], uint64_t* runs, Drain::PassArena** open);
-int pass_fence(ps_engine* e, Drain::PassFence (&fence)[2], const char* who);
+inline void release_all(std::initializer_list<DevBuf*> bufs) {
+  for (DevBuf* b : bufs) b->release();
+}
 
 // Where one call stages its input: a slot's pinned h_in, all of it (one call
 // takes once), or a region of a sink result's arena
@@ -272,6 +279,44 @@ int aud_pass(ps_engine* e, const AudBufs& B, const AudEntry* d_entries, const Au
              const AudShape& A, size_t exc_cap, size_t list_cap, uint32_t seg_bound, const AudView& view,
              const PhaseTimer& tm, float* ms, DrainArgs* args, DrainCtl** ctl_out);
 
+// ---- drain_standing.cpp: the tracker lifecycle, once for the six families -----------
+
+// (standing_open / standing_abort, around a run: engine.hpp, beside the window hooks)
+// every pass enqueued so far is complete: nothing waits for one any more
+void standing_settled(Drain::Standing& S);
+void standing_destroy(Drain::Standing& S);  // (ps_destroy)
+// ps_*_track, in this order with the family's own refusals between them: the
+// multi-rank and in-flight refusals and the topic checks; the device, and the
+// end of whatever still adds into the totals; then the new topics in place of
+// the old ones, the counts zeroed, the kept block dropped
+int standing_track_check(ps_engine* e, const Drain::Standing& S, const uint32_t* topic, size_t n);
+int standing_quiesce(ps_engine* e, Drain::Standing& S);
+void standing_retrack(Drain::Standing& S, const uint32_t* topic, size_t n);
+// ... and behind them the totals: cleared on the stream, or released with the
+// standing pass's buffers when nothing is tracked any more
+int standing_totals(ps_engine* e, Drain::Standing& S, DevBuf& d_acc, size_t bytes, std::initializer_list<DevBuf*> pass);
+// ps_*_take: the state checks and the device; the lazily created event; and the
+// whole take of `bytes` of totals into A.h_out -- checks, copy, clearing, one
+// wait, settled.  The caller hands its arrays out and returns and zeroes the counts.
+int standing_take_enter(ps_engine* e, const Drain::Standing& S);
+int standing_take_event(ps_engine* e, Drain::Standing& S);
+int standing_take_totals(ps_engine* e, Drain::Standing& S, DevBuf& d_acc, Drain::Answer& A, size_t bytes);
+// A window's pass (S.on, S.open): the twin joined and the window's tables,
+// *R: the run's staging; ... its kernels ...; then the fence of the row set,
+// the run's event and the counts
+int standing_window_begin(ps_engine* e, Drain::Standing& S, Drain::Sink::Res** R);
+int standing_window_done(ps_engine* e, Drain::Standing& S, size_t n_skipped);
+// the two words every family's strip_key holds per topic -- table flags |
+// n_pos, non-root nodes | node base -- appended; returns the first non-root node
+uint32_t standing_key_topic(ps_engine* e, uint32_t t, std::vector<uint64_t>* key);
+// the block kept on the device is the window's (true), or the key is dropped
+// until the caller has staged the new block and sets it
+inline bool standing_key_stands(Drain::Standing& S, const std::vector<uint64_t>& key) {
+  if (key == S.strip_key) return true;
+  S.strip_key.clear();
+  return false;
+}
+
 // ---- drain_hops.cpp: what the passes over tree levels ask of a topic ---------------
 
 // topic t is a mesh in the last window's node space: it has no levels
@@ -316,12 +361,11 @@ void down_entries(ps_engine* e, const DownReq& R, const AudEntry* ae, const AudS
 // a pass's buffers, k_audience_classify and k_audience_weights over the block `din`
 int down_front(ps_engine* e, Down::Pass& P, const uint8_t* din, const Down::Shape& K, const PhaseTimer& tm, float* ms,
                DownArgs* out);
-// a blocking call's block over the named tree topics, whole, into H.stage
-int down_sync_stage(ps_engine* e, Down& H, const uint32_t* topic, size_t n, const char* who, Down::Shape* K);
-// a standing pass's window around its kernels: the block into H.track.d_in
-// (kept while H.strip_key stands); the fence, the run's event and the counts
-int down_window_stage(ps_engine* e, Down& H, const char* who, Down::Shape* K, size_t* n_tree);
-int down_window_done(ps_engine* e, Down& H, const char* who, size_t n_tree);
-void down_settled(Down& H);
+// a blocking call's block over the named tree topics, whole, into `stage`
+int down_sync_stage(ps_engine* e, std::vector<uint8_t>& stage, const uint32_t* topic, size_t n, const char* who,
+                    Down::Shape* K);
+// the front of a standing subtree pass's window (downstream, cut, blame): the
+// block into P.d_in, kept with its shape while S.strip_key stands
+int down_window_stage(ps_engine* e, Drain::Standing& S, Down::Pass& P, Down::Shape& kept, Down::Shape* K, size_t* n_tree);
 
 }  // namespace psamd

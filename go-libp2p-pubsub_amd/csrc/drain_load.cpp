@@ -70,28 +70,9 @@ int load_pass(ps_engine* e, Load::Pass& P, const uint8_t* din, size_t o_strips, 
   return PS_OK;
 }
 
-// every pass enqueued so far is complete: nothing waits for one any more
-void load_settled(Load& L) {
-  for (auto& f : L.fence) f.pending = false;
-  for (auto& a : L.arena) a.pending = false;
-}
-
 }  // namespace
 
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::load_open(ps_engine* e) {
-  auto& L = e->drain.load;
-  return L.on ? pass_arena_open(e, L.arena, &L.runs, &L.open) : PS_OK;
-}
-
-void psamd::load_abort(ps_engine* e) {
-  auto& L = e->drain.load;
-  if (!L.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  L.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, added to the totals: its tables (built here
 // where nobody has), the entry table -- per window: it carries the window's
@@ -102,39 +83,32 @@ void psamd::load_abort(ps_engine* e) {
 int psamd::load_window(ps_engine* e) {
   auto& D = e->drain;
   auto& L = D.load;
-  if (!L.on || !L.open) return PS_OK;
-  auto& R = L.open->mem;
-  const size_t n = L.topic.size();
-  const uint32_t* const topic = L.topic.data();
-  if (const int rj = twin_join(e)) return rj;
-  // (no drain_ready: the pass reads no host mirror of the node space, so a
-  // GPU-built one is not read back for it)
-  hipStream_t s = e->stream;
-  size_t used = 0;
-  uint8_t* h = nullptr;
-  int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
+  auto& S = L.st;
+  if (!S.on || !S.open) return PS_OK;
+  const size_t n = S.topic.size();
+  const uint32_t* const topic = S.topic.data();
+  Drain::Sink::Res* Rp = nullptr;
+  int rc = standing_window_begin(e, S, &Rp);
   if (rc) return rc;
+  auto& R = *Rp;
+  hipStream_t s = e->stream;
 
   std::vector<uint64_t> key{e->graph_epoch, n};
   for (size_t i = 0; i < n; ++i) {
-    const DrainTopic& T = D.tab.topics[topic[i]];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, topic[i], &u0);
-    key.push_back(static_cast<uint64_t>(T.flags) << 32 | T.n_pos);
-    key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
+    const uint32_t u0 = standing_key_topic(e, topic[i], &key);
     key.push_back(u0);
   }
   const size_t o_strips = align256((n + 1) * sizeof(LoadEntry));
   AudShape A;
   uint8_t* hs = nullptr;
-  if (key == L.strip_key) {
+  if (standing_key_stands(S, key)) {
     HIP_TRY(sink_stage(R, o_strips, &hs), "alloc load staging");
     aud_stage(e, topic, n, reinterpret_cast<AudEntry*>(hs), nullptr, ~0ull, &A);
-    if (A.ns != L.ns || A.n_verdicts != L.n_verdicts) return e->fail(PS_E_STATE, "load: the kept strips are not the window's");
+    if (A.ns != L.kept.ns || A.n_verdicts != L.kept.n_verdicts)
+      return e->fail(PS_E_STATE, "load: the kept strips are not the window's");
     load_entries(e, hs, n);
     HIP_TRY(hipMemcpyAsync(L.track.d_in.p, hs, (n + 1) * sizeof(LoadEntry), hipMemcpyHostToDevice, s), "upload load entries");
   } else {
-    L.strip_key.clear();
     size_t o = 0;
     uint64_t strips_max = 0;
     const size_t bytes = aud_stage_bytes(e, topic, n, &o, &strips_max);
@@ -146,9 +120,8 @@ int psamd::load_window(ps_engine* e) {
     const size_t in_bytes = o_strips + static_cast<size_t>(A.ns) * sizeof(AudStrip);
     HIP_TRY(L.track.d_in.ensure(in_bytes), "alloc load strips");
     HIP_TRY(hipMemcpyAsync(L.track.d_in.p, hs, in_bytes, hipMemcpyHostToDevice, s), "upload load strips");
-    L.ns = A.ns;
-    L.n_verdicts = A.n_verdicts;
-    L.strip_key = key;
+    L.kept = {A.ns, A.n_verdicts};
+    S.strip_key = key;
   }
   const PhaseTimer untimed{D.ev_t, s, false};
   float none[2] = {0, 0};
@@ -156,13 +129,7 @@ int psamd::load_window(ps_engine* e) {
   if ((rc = load_pass(e, L.track, L.track.d_in.as<uint8_t>(), o_strips, n, A.ns, A.n_verdicts, acc, acc + e->cfg.n_peers,
                       untimed, none)))
     return rc;
-  // classify and the counted rows read the window's row set: the events are
-  // recorded whether or not a row was read
-  if ((rc = pass_fence(e, L.fence, "load"))) return rc;
-  HIP_TRY(hipEventRecord(L.open->ev, s), "event");
-  L.open->pending = true;
-  L.windows += 1;
-  return PS_OK;
+  return standing_window_done(e, S, 0);
 }
 
 extern "C" {
@@ -175,6 +142,7 @@ int ps_peer_load(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* recv_o
   if (const int rc = aud_check_topics(e, topic, n)) return rc;
   auto& D = e->drain;
   auto& L = D.load;
+  auto& Ans = L.ans;
   const auto t_host0 = hclock::now();
   int rc = drain_ready(e);
   if (!rc) rc = drain_tables(e);
@@ -188,30 +156,30 @@ int ps_peer_load(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* recv_o
   uint64_t strips_max = 0;
   const size_t bytes = aud_stage_bytes(e, topic, n, &o_strips, &strips_max);
   if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  L.stage.resize(bytes);
+  Ans.stage.resize(bytes);
   AudShape A;
-  if (!aud_stage(e, topic, n, reinterpret_cast<AudEntry*>(L.stage.data()), reinterpret_cast<AudStrip*>(L.stage.data() + o_strips),
-                 strips_max, &A))
+  if (!aud_stage(e, topic, n, reinterpret_cast<AudEntry*>(Ans.stage.data()),
+                 reinterpret_cast<AudStrip*>(Ans.stage.data() + o_strips), strips_max, &A))
     return e->fail(PS_E_STATE, "load: more strips than staged");
-  load_entries(e, L.stage.data(), n);
+  load_entries(e, Ans.stage.data(), n);
   const double host_ms = ms_since(t_host0);
 
   const size_t in_bytes = o_strips + static_cast<size_t>(A.ns) * sizeof(AudStrip);
   HIP_TRY(L.sync.d_in.ensure(in_bytes), "alloc load strips");
-  HIP_TRY(L.d_out.ensure(2 * np * 8), "alloc load sums");
-  HIP_TRY(pinned_ensure(&L.h_out, nullptr, &L.out_cap, 2 * np * 8), "alloc load view");
-  uint64_t* const out = L.d_out.as<uint64_t>();
+  HIP_TRY(Ans.d_out.ensure(2 * np * 8), "alloc load sums");
+  HIP_TRY(pinned_ensure(&Ans.h_out, nullptr, &Ans.out_cap, 2 * np * 8), "alloc load view");
+  uint64_t* const out = Ans.d_out.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(out, 0, 2 * np * 8, s), "clear load sums");
-  if (A.ns) HIP_TRY(hipMemcpyAsync(L.sync.d_in.p, L.stage.data(), in_bytes, hipMemcpyHostToDevice, s), "upload load strips");
+  if (A.ns) HIP_TRY(hipMemcpyAsync(L.sync.d_in.p, Ans.stage.data(), in_bytes, hipMemcpyHostToDevice, s), "upload load strips");
   if ((rc = load_pass(e, L.sync, L.sync.d_in.as<uint8_t>(), o_strips, n, A.ns, A.n_verdicts, out, out + np, tm, ms))) return rc;
   // one copy: both arrays, or the one that was asked for
   const size_t lo = recv_out ? 0 : np, hi = sent_out ? 2 * np : np;
   HIP_TRY(tm.begin(), "event");
-  HIP_TRY(hipMemcpyAsync(L.h_out + lo * 8, out + lo, (hi - lo) * 8, hipMemcpyDeviceToHost, s), "read load sums");
+  HIP_TRY(hipMemcpyAsync(Ans.h_out + lo * 8, out + lo, (hi - lo) * 8, hipMemcpyDeviceToHost, s), "read load sums");
   HIP_TRY(hipStreamSynchronize(s), "sync");
   HIP_TRY(tm.end(ms[2]), "event");
-  if (recv_out) std::memcpy(recv_out, L.h_out, np * 8);
-  if (sent_out) std::memcpy(sent_out, L.h_out + np * 8, np * 8);
+  if (recv_out) std::memcpy(recv_out, Ans.h_out, np * 8);
+  if (sent_out) std::memcpy(sent_out, Ans.h_out + np * 8, np * 8);
   if (D.env.timing)
     std::fprintf(stderr,
                  "psamd peer_load: topics %zu strips %u nodes %llu row_bytes %llu classify_ms %.4f load_ms %.4f copy_ms %.4f "
@@ -225,54 +193,24 @@ int ps_peer_load(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* recv_o
 
 int ps_load_track(ps_engine* e, const uint32_t* topic, size_t n) {
   if (!e || (n && !topic)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_load_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
   auto& L = e->drain.load;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  // whatever still adds into the totals ends first
-  if (L.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  load_settled(L);
-  L.open = nullptr;
-  L.strip_key.clear();
-  L.windows = 0;
-  L.topic.assign(topic, topic + n);
-  L.on = n > 0;
-  if (!L.on) {
-    L.d_acc.release();
-    L.track.d_in.release();
-    L.track.d_verdict.release();
-    L.track.d_exc.release();
-    L.track.d_full.release();
-    return PS_OK;
-  }
-  const size_t bytes = 2 * static_cast<size_t>(e->cfg.n_peers) * 8;
-  HIP_TRY(L.d_acc.ensure(bytes), "alloc load totals");
-  HIP_TRY(hipMemsetAsync(L.d_acc.p, 0, bytes, e->stream), "clear load totals");
-  return PS_OK;
+  if (const int rc = standing_track_check(e, L.st, topic, n)) return rc;
+  if (const int rc = standing_quiesce(e, L.st)) return rc;
+  standing_retrack(L.st, topic, n);
+  auto& P = L.track;
+  return standing_totals(e, L.st, L.d_acc, 2 * static_cast<size_t>(e->cfg.n_peers) * 8,
+                         {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full});
 }
 
 int ps_load_take(ps_engine* e, uint64_t* recv_out, uint64_t* sent_out, uint64_t* n_windows_out) {
   if (!e || !n_windows_out) return PS_E_INVAL;
   auto& L = e->drain.load;
-  if (!L.on) return e->fail(PS_E_NOTREADY, "no load is tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
   const size_t np = e->cfg.n_peers;
-  HIP_TRY(pinned_ensure(&L.h_out, nullptr, &L.out_cap, 2 * np * 8), "alloc load view");
-  if (!L.ev_take) HIP_TRY(hipEventCreateWithFlags(&L.ev_take, hipEventDisableTiming), "load event");
-  // every pass ran on `stream`: the copy behind them, the clearing behind the
-  // copy and in front of whatever runs next, one wait
-  hipStream_t s = e->stream;
-  HIP_TRY(hipMemcpyAsync(L.h_out, L.d_acc.p, 2 * np * 8, hipMemcpyDeviceToHost, s), "read load totals");
-  HIP_TRY(hipMemsetAsync(L.d_acc.p, 0, 2 * np * 8, s), "clear load totals");
-  HIP_TRY(hipEventRecord(L.ev_take, s), "event");
-  HIP_TRY(hipEventSynchronize(L.ev_take), "wait for the load totals");
-  load_settled(L);
-  if (recv_out) std::memcpy(recv_out, L.h_out, np * 8);
-  if (sent_out) std::memcpy(sent_out, L.h_out + np * 8, np * 8);
-  *n_windows_out = L.windows;
-  L.windows = 0;
+  if (const int rc = standing_take_totals(e, L.st, L.d_acc, L.ans, 2 * np * 8)) return rc;
+  if (recv_out) std::memcpy(recv_out, L.ans.h_out, np * 8);
+  if (sent_out) std::memcpy(sent_out, L.ans.h_out + np * 8, np * 8);
+  *n_windows_out = L.st.windows;
+  L.st.windows = 0;
   return PS_OK;
 }
 

@@ -241,12 +241,6 @@ int report_pass(ps_engine* e, Report::Pass& P, const uint8_t* din, const Report:
   return PS_OK;
 }
 
-// every pass enqueued so far is complete: nothing waits for one any more
-void report_settled(Report& H) {
-  for (auto& f : H.fence) f.pending = false;
-  for (auto& a : H.arena) a.pending = false;
-}
-
 // the checks both entry points make on `what` and the caller's struct
 bool report_args_ok(uint32_t what, const ps_report* out, size_t out_size, bool need_array) {
   if (!out || out_size != sizeof(ps_report) || what == 0 || (what & ~kReportAll)) return false;
@@ -274,20 +268,7 @@ void report_give(const ps_report& out, uint32_t what, const Report::Out& O, cons
 
 }  // namespace
 
-// ---- the standing pass's run hooks (run.cpp calls them) -------------------------
-
-int psamd::report_open(ps_engine* e) {
-  auto& H = e->drain.report;
-  return H.on ? pass_arena_open(e, H.arena, &H.runs, &H.open) : PS_OK;
-}
-
-void psamd::report_abort(ps_engine* e) {
-  auto& H = e->drain.report;
-  if (!H.open) return;
-  // what the run's windows staged must have left the staging
-  (void)hipStreamSynchronize(e->stream);
-  H.open = nullptr;
-}
+// ---- the standing pass's window hook (run.cpp calls it) --------------------------
 
 // The window just remembered, added to the totals, as the four standing passes
 // add theirs: its tables (built here where nobody has), the three entry tables
@@ -298,26 +279,21 @@ void psamd::report_abort(ps_engine* e) {
 int psamd::report_window(ps_engine* e) {
   auto& D = e->drain;
   auto& H = D.report;
-  if (!H.on || !H.open) return PS_OK;
-  auto& R = H.open->mem;
-  if (const int rj = twin_join(e)) return rj;
-  hipStream_t s = e->stream;
-  size_t used = 0;
-  uint8_t* h = nullptr;
-  int rc = drain_tables_async(e, Staging{nullptr, &R}, 0, false, &used, &h);
+  auto& S = H.st;
+  if (!S.on || !S.open) return PS_OK;
+  Drain::Sink::Res* Rp = nullptr;
+  int rc = standing_window_begin(e, S, &Rp);
   if (rc) return rc;
+  auto& R = *Rp;
+  hipStream_t s = e->stream;
   Req Q;
-  if ((rc = report_plan(e, H.topic.data(), H.topic.size(), H.what, &Q))) return rc;
+  if ((rc = report_plan(e, S.topic.data(), S.topic.size(), H.what, &Q))) return rc;
   const size_t n = Q.order.size();
   const uint32_t* const topic = Q.order.data();
 
   std::vector<uint64_t> key{e->graph_epoch, n, Q.hq.topic.size(), Q.dq.n_lvl, Q.dq.n_work, H.what};
   for (size_t i = 0; i < n; ++i) {
-    const DrainTopic& T = D.tab.topics[topic[i]];
-    uint32_t u0 = 0;
-    const uint32_t nn = aud_nodes(e, topic[i], &u0);
-    key.push_back(static_cast<uint64_t>(T.flags) << 32 | T.n_pos);
-    key.push_back(static_cast<uint64_t>(nn) << 32 | e->last_topics[topic[i]].nbase);
+    const uint32_t u0 = standing_key_topic(e, topic[i], &key);
     key.push_back(static_cast<uint64_t>(u0) << 32 | topic[i]);
     key.push_back(i < Q.hq.row.size() ? Q.hq.row[i] : ~0ull);
   }
@@ -326,7 +302,7 @@ int psamd::report_window(ps_engine* e) {
   std::vector<AudEntry> ae(n + 1);
   AudShape A;
   uint8_t* hs = nullptr;
-  if (key == H.strip_key) {
+  if (standing_key_stands(S, key)) {
     HIP_TRY(sink_stage(R, K.o_lvl, &hs), "alloc report staging");
     aud_stage(e, topic, n, ae.data(), nullptr, ~0ull, &A);
     report_entries(e, Q, ae.data(), A, hs, false, &K);
@@ -337,7 +313,6 @@ int psamd::report_window(ps_engine* e) {
     K.launch = H.kept.launch;
     HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.o_lvl, hipMemcpyHostToDevice, s), "upload report entries");
   } else {
-    H.strip_key.clear();
     size_t o = 0;
     uint64_t strips_max = 0;
     (void)aud_stage_bytes(e, topic, n, &o, &strips_max);
@@ -350,20 +325,14 @@ int psamd::report_window(ps_engine* e) {
     HIP_TRY(H.track.d_in.ensure(K.bytes), "alloc report strips");
     HIP_TRY(hipMemcpyAsync(H.track.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload report strips");
     H.kept = K;
-    H.strip_key = key;
+    S.strip_key = key;
   }
   const PhaseTimer untimed{D.ev_t, s, false};
   float none[4] = {0, 0, 0, 0};
-  const Report::Out O = report_out(e->cfg.n_peers, H.topic.size());
+  const Report::Out O = report_out(e->cfg.n_peers, S.topic.size());
   if ((rc = report_pass(e, H.track, H.track.d_in.as<uint8_t>(), K, H.what, H.d_acc.as<uint64_t>(), O, untimed, none))) return rc;
-  // classify and the counted rows read the window's row set: the events are
-  // recorded whether or not a row was read
-  if ((rc = pass_fence(e, H.fence, "report"))) return rc;
-  HIP_TRY(hipEventRecord(H.open->ev, s), "event");
-  H.open->pending = true;
-  H.windows += 1;
-  if (H.what & kTreeSections) H.skipped += Q.n_mesh;  // the mesh topics of this window
-  return PS_OK;
+  // the mesh topics of this window, where a tree section is selected
+  return standing_window_done(e, S, (H.what & kTreeSections) ? Q.n_mesh : 0);
 }
 
 extern "C" {
@@ -379,6 +348,7 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
       if (hops_is_mesh(e, topic[i])) return e->fail(PS_E_STATE, "ps_peer_report: a mesh topic answers the load section alone");
   auto& D = e->drain;
   auto& H = D.report;
+  auto& Ans = H.ans;
   const auto t_host0 = hclock::now();
   int rc = drain_ready(e);
   if (!rc) rc = drain_tables(e);
@@ -395,8 +365,8 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   uint64_t strips_max = 0;
   (void)aud_stage_bytes(e, Q.order.data(), Q.order.size(), &o, &strips_max);
   if (strips_max >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many rows in one drain");
-  H.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
-  uint8_t* const hs = H.stage.data();
+  Ans.stage.resize(K.o_strips + strips_max * sizeof(AudStrip));
+  uint8_t* const hs = Ans.stage.data();
   std::vector<AudEntry> ae(Q.order.size() + 1);
   AudShape A;
   if (!aud_stage(e, Q.order.data(), Q.order.size(), ae.data(), reinterpret_cast<AudStrip*>(hs + K.o_strips), strips_max, &A))
@@ -408,9 +378,9 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
   const Report::Out O = report_out(e->cfg.n_peers, n);
   const size_t out_bytes = O.off[11] * 8;
   HIP_TRY(H.sync.d_in.ensure(K.bytes), "alloc report strips");
-  HIP_TRY(H.d_out.ensure(out_bytes), "alloc report sums");
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes), "alloc report view");
-  uint64_t* const out = H.d_out.as<uint64_t>();
+  HIP_TRY(Ans.d_out.ensure(out_bytes), "alloc report sums");
+  HIP_TRY(pinned_ensure(&Ans.h_out, nullptr, &Ans.out_cap, out_bytes), "alloc report view");
+  uint64_t* const out = Ans.d_out.as<uint64_t>();
   HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s), "clear report sums");
   if (K.ns) HIP_TRY(hipMemcpyAsync(H.sync.d_in.p, hs, K.bytes, hipMemcpyHostToDevice, s), "upload report strips");
   if ((rc = report_pass(e, H.sync, H.sync.d_in.as<uint8_t>(), K, what, out, O, tm, ms))) return rc;
@@ -425,11 +395,11 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
     }
   HIP_TRY(tm.begin(), "event");
   if (O.off[hi] > O.off[lo])
-    HIP_TRY(hipMemcpyAsync(H.h_out + O.off[lo] * 8, out + O.off[lo], (O.off[hi] - O.off[lo]) * 8, hipMemcpyDeviceToHost, s),
+    HIP_TRY(hipMemcpyAsync(Ans.h_out + O.off[lo] * 8, out + O.off[lo], (O.off[hi] - O.off[lo]) * 8, hipMemcpyDeviceToHost, s),
             "read report sums");
   HIP_TRY(hipStreamSynchronize(s), "sync");
   HIP_TRY(tm.end(ms[4]), "event");
-  report_give(*out_p, what, O, H.h_out);
+  report_give(*out_p, what, O, Ans.h_out);
   if (D.env.timing)
     std::fprintf(stderr,
                  "psamd peer_report: topics %zu what %u strips %u nodes %llu row_bytes %llu partials %llu work %u launches %zu "
@@ -444,59 +414,30 @@ int ps_peer_report(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what,
 
 int ps_report_track(ps_engine* e, const uint32_t* topic, size_t n, uint32_t what) {
   if (!e || (n && !topic) || what == 0 || (what & ~kReportAll)) return PS_E_INVAL;
-  if (e->world > 1) return e->fail(PS_E_STATE, "ps_report_track on a multi-rank engine");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  if (const int rc = aud_check_topics(e, topic, n)) return rc;
+  auto& H = e->drain.report;
+  if (const int rc = standing_track_check(e, H.st, topic, n)) return rc;
   if (what & kTreeSections)
     for (size_t i = 0; i < n; ++i)
       if (hops_child_lists_mesh(e->topics[topic[i]]))
         return e->fail(PS_E_STATE, "ps_report_track: a mesh topic answers the load section alone");
-  auto& H = e->drain.report;
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  // whatever still adds into the totals ends first
-  if (H.runs) HIP_TRY(hipStreamSynchronize(e->stream), "sync");
-  report_settled(H);
-  H.open = nullptr;
-  H.strip_key.clear();
-  H.windows = H.skipped = 0;
-  H.topic.assign(topic, topic + n);
+  if (const int rc = standing_quiesce(e, H.st)) return rc;
+  standing_retrack(H.st, topic, n);
   H.what = what;
-  H.on = n > 0;
-  if (!H.on) {
-    H.d_acc.release();
-    for (psamd::DevBuf* b : {&H.track.d_in, &H.track.d_verdict, &H.track.d_exc, &H.track.d_full, &H.track.d_part_r,
-                             &H.track.d_part_d, &H.track.d_scratch})
-      b->release();
-    return PS_OK;
-  }
-  const size_t bytes = report_out(e->cfg.n_peers, n).off[11] * 8;
-  HIP_TRY(H.d_acc.ensure(bytes), "alloc report totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, e->stream), "clear report totals");
-  return PS_OK;
+  auto& P = H.track;
+  return standing_totals(e, H.st, H.d_acc, report_out(e->cfg.n_peers, n).off[11] * 8,
+                         {&P.d_in, &P.d_verdict, &P.d_exc, &P.d_full, &P.d_part_r, &P.d_part_d, &P.d_scratch});
 }
 
 int ps_report_take(ps_engine* e, const ps_report* out_p, size_t out_size, uint64_t* n_windows_out, uint64_t* n_skipped_out) {
   if (!e || !out_p || out_size != sizeof(ps_report) || !n_windows_out || !n_skipped_out) return PS_E_INVAL;
   auto& H = e->drain.report;
-  if (!H.on) return e->fail(PS_E_NOTREADY, "no report is tracked");
-  if (e->infl_count) return e->fail(PS_E_STATE, "a run in flight: ps_wait first");
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  const Report::Out O = report_out(e->cfg.n_peers, H.topic.size());
-  const size_t bytes = O.off[11] * 8;
-  HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, bytes), "alloc report view");
-  if (!H.ev_take) HIP_TRY(hipEventCreateWithFlags(&H.ev_take, hipEventDisableTiming), "report event");
-  // every pass ran on `stream`: the copy behind them, the clearing behind the
-  // copy and in front of whatever runs next, one wait
-  hipStream_t s = e->stream;
-  HIP_TRY(hipMemcpyAsync(H.h_out, H.d_acc.p, bytes, hipMemcpyDeviceToHost, s), "read report totals");
-  HIP_TRY(hipMemsetAsync(H.d_acc.p, 0, bytes, s), "clear report totals");
-  HIP_TRY(hipEventRecord(H.ev_take, s), "event");
-  HIP_TRY(hipEventSynchronize(H.ev_take), "wait for the report totals");
-  report_settled(H);
-  report_give(*out_p, H.what, O, H.h_out);
-  *n_windows_out = H.windows;
-  *n_skipped_out = H.skipped;
-  H.windows = H.skipped = 0;
+  auto& S = H.st;
+  const Report::Out O = report_out(e->cfg.n_peers, S.topic.size());
+  if (const int rc = standing_take_totals(e, S, H.d_acc, H.ans, O.off[11] * 8)) return rc;
+  report_give(*out_p, H.what, O, H.ans.h_out);
+  *n_windows_out = S.windows;
+  *n_skipped_out = S.skipped;
+  S.windows = S.skipped = 0;
   return PS_OK;
 }
 

@@ -45,50 +45,6 @@ hipError_t sink_stage(Drain::Sink::Res& R, size_t bytes, uint8_t** out) {
   return hipSuccess;
 }
 
-// ---- what the standing passes share (ps_load_track, ps_hops_track, ps_downstream_track) --
-
-// The last pass over the window's rows on `stream` (run.cpp: drain_fence),
-// recorded behind it: the entry of this row set, else one whose row set is gone
-int pass_fence(ps_engine* e, Drain::PassFence (&fence)[2], const char* who) {
-  Drain::PassFence* F = nullptr;
-  for (auto& f : fence)
-    if (f.seen == e->rows.seen.p) F = &f;
-  for (auto& f : fence)
-    if (!F && (!f.seen || f.seen != e->rows_other.seen.p)) F = &f;
-  if (!F) return e->fail(PS_E_STATE, std::string(who) + ": no fence entry for the row set");
-  if (!F->ev) HIP_TRY(hipEventCreateWithFlags(&F->ev, kStreamEvent), "pass event");
-  HIP_TRY(hipEventRecord(F->ev, e->stream), "event");
-  F->seen = e->rows.seen.p;
-  F->pending = true;
-  return PS_OK;
-}
-
-// A run's pinned staging for a standing pass: run k takes arena[k & 1], folded
-// into one chunk where the windows of its last run outgrew it
-int pass_arena_open(ps_engine* e, Drain::PassArena (&arena)[2], uint64_t* runs, Drain::PassArena** open) {
-  HIP_TRY(hipSetDevice(e->cfg.device), "hipSetDevice");
-  auto& A = arena[(*runs)++ & 1];
-  // the arena's last run lies two back: its passes have left the staging, or do so soon
-  if (A.pending) HIP_TRY(hipEventSynchronize(A.ev), "wait for a standing pass");
-  A.pending = false;
-  auto& R = A.mem;
-  if (R.arena.size() > 1) {
-    size_t cap = 0;
-    for (auto& c : R.arena) {
-      cap += c.cap;
-      (void)hipHostFree(c.h);
-    }
-    R.arena.clear();
-    uint8_t* h = nullptr;
-    R.arena_used = 0;
-    HIP_TRY(sink_stage(R, cap, &h), "alloc pass staging");
-  }
-  R.arena_used = 0;
-  if (!A.ev) HIP_TRY(hipEventCreateWithFlags(&A.ev, hipEventDisableTiming), "pass event");
-  *open = &A;
-  return PS_OK;
-}
-
 // What every entry point needs after its own state checks: the node-space
 // mirrors (the peer maps read them), the drain's stream and events
 int drain_ready(ps_engine* e) {
@@ -491,40 +447,9 @@ void drain_destroy(ps_engine* e) {
     for (uint8_t* h : {sl.h_in, sl.h_res})
       if (h) (void)hipHostFree(h);
   if (D.aud.h_ids) (void)hipHostFree(D.aud.h_ids);
-  if (D.load.h_out) (void)hipHostFree(D.load.h_out);
-  for (auto& a : D.load.arena) {
-    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
-    if (a.ev) (void)hipEventDestroy(a.ev);
-  }
-  for (auto& f : D.load.fence)
-    if (f.ev) (void)hipEventDestroy(f.ev);
-  if (D.load.ev_take) (void)hipEventDestroy(D.load.ev_take);
-  if (D.hops.h_out) (void)hipHostFree(D.hops.h_out);
-  for (auto& a : D.hops.arena) {
-    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
-    if (a.ev) (void)hipEventDestroy(a.ev);
-  }
-  for (auto& f : D.hops.fence)
-    if (f.ev) (void)hipEventDestroy(f.ev);
-  if (D.hops.ev_take) (void)hipEventDestroy(D.hops.ev_take);
-  for (auto* H : {&D.down, &D.cut, &D.blame_trk.pass}) {
-    if (H->h_out) (void)hipHostFree(H->h_out);
-    for (auto& a : H->arena) {
-      for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
-      if (a.ev) (void)hipEventDestroy(a.ev);
-    }
-    for (auto& f : H->fence)
-      if (f.ev) (void)hipEventDestroy(f.ev);
-    if (H->ev_take) (void)hipEventDestroy(H->ev_take);
-  }
-  if (D.report.h_out) (void)hipHostFree(D.report.h_out);
-  for (auto& a : D.report.arena) {
-    for (auto& c : a.mem.arena) (void)hipHostFree(c.h);
-    if (a.ev) (void)hipEventDestroy(a.ev);
-  }
-  for (auto& f : D.report.fence)
-    if (f.ev) (void)hipEventDestroy(f.ev);
-  if (D.report.ev_take) (void)hipEventDestroy(D.report.ev_take);
+  for (auto* S : D.standing()) standing_destroy(*S);
+  for (auto* A : {&D.load.ans, &D.hops.ans, &D.down.ans, &D.cut.ans, &D.report.ans})
+    if (A->h_out) (void)hipHostFree(A->h_out);
   for (uint8_t* h : {D.dist.h_out, D.dist.h_off, D.dist.h_rec})
     if (h) (void)hipHostFree(h);
   if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);

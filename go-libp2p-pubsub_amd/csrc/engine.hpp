@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <chrono>
 #include <cstdlib>
 #include <cstdint>
@@ -743,8 +744,8 @@ struct ps_engine {
       size_t strip_bytes = 0;  // PSAMD_DRAIN_TIMING: the bytes the open run's windows uploaded for them
     } sink;
 
-    // What the standing passes behind a run's windows (ps_load_track,
-    // ps_hops_track) keep alike (drain_tables.cpp: pass_arena_open, pass_fence).
+    // What the standing passes behind a run's windows keep alike
+    // (drain_standing.cpp).
     // Pinned staging, one arena per run in turn (run k: arena[k & 1]): every
     // window of the run takes a region of its own, and the arena is reused
     // once the last pass of the run two before is complete (ev)
@@ -760,6 +761,36 @@ struct ps_engine {
       hipEvent_t ev = nullptr;
       bool pending = false;
     };
+    // One tracker (ps_*_track / ps_*_take): the standing topics, the counts
+    // since the last take or track call, and what orders its passes against
+    // the runs around them.  Every family owns one; none shares an arena or an
+    // event with another, since each pass may still be pending when the next
+    // run opens.
+    struct Standing {
+      const char* name;  // in messages: load, hops, downstream, cut, report, blame
+      bool on = false;
+      std::vector<uint32_t> topic;
+      // windows; (mesh topic, window) pairs left out of the tree answers
+      uint64_t windows = 0, skipped = 0;
+      // the pass's input block stays on the device while what it is cut from
+      // stays: graph_epoch, each standing topic's table shape and node range,
+      // and what the family adds (standing_key_topic)
+      std::vector<uint64_t> strip_key;
+      PassArena arena[2];
+      uint64_t runs = 0;
+      PassArena* open = nullptr;  // the run being enqueued
+      PassFence fence[2];
+      hipEvent_t ev_take = nullptr;
+    };
+    // A blocking call's answer (ps_peer_load and its like): the sums on the
+    // device, the staged input block, the pinned copy handed out -- the
+    // family's take hands its totals out through the same pinned copy
+    struct Answer {
+      psamd::DevBuf d_out;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
+      uint8_t* h_out = nullptr;
+      size_t out_cap = 0;
+    };
 
     // ps_peer_load / ps_load_track / ps_load_take (host code:
     // drain_load.cpp): per-peer recv / sent sums from the audience pass's
@@ -772,31 +803,16 @@ struct ps_engine {
       struct Pass {
         psamd::DevBuf d_in, d_verdict, d_exc, d_full;
       };
-      // ps_peer_load: its pass, recv | sent on the device, their pinned copy
-      Pass sync;
-      psamd::DevBuf d_out;
-      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
-      uint8_t* h_out = nullptr;
-      size_t out_cap = 0;
-      // ps_load_track: the standing topics and the totals since the last take
-      // or track call, recv | sent in peer space
-      bool on = false;
-      std::vector<uint32_t> topic;
-      Pass track;
-      psamd::DevBuf d_acc;
-      uint64_t windows = 0;  // windows counted since the last take or track call
-      // the entries and strips on the device while what they are cut from
-      // stays (graph_epoch, each standing topic's table shape, node range and
-      // window messages)
-      std::vector<uint64_t> strip_key;
-      uint32_t ns = 0;
-      uint64_t n_verdicts = 0;
-      // pinned staging per run and the last pass per row set (PassArena, PassFence)
-      PassArena arena[2];
-      uint64_t runs = 0;
-      PassArena* open = nullptr;  // the run being enqueued
-      PassFence fence[2];
-      hipEvent_t ev_take = nullptr;
+      // what the grids and buffers of a pass are sized by
+      struct Shape {
+        uint32_t ns = 0;
+        uint64_t n_verdicts = 0;
+      };
+      Pass sync, track;  // ps_peer_load's, the standing pass's
+      Answer ans;        // recv | sent in peer space
+      Standing st{"load"};
+      psamd::DevBuf d_acc;  // the totals, recv | sent in peer space
+      Shape kept;           // the block on the device (st.strip_key)
     } load;
 
     // ps_topic_hops / ps_hops_track / ps_hops_take (host
@@ -819,30 +835,11 @@ struct ps_engine {
         uint32_t ns = 0, max_cols = 0;
         uint64_t n_verdicts = 0, n_parts = 0, row_bytes = 0;
       };
-      // ps_topic_hops: its pass, nodes | reached | deliv on the device, their pinned copy
-      Pass sync;
-      psamd::DevBuf d_out;
-      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
-      uint8_t* h_out = nullptr;
-      size_t out_cap = 0;
-      // ps_hops_track: the standing topics and the totals since the last take
-      // or track call, nodes | reached | deliv, [n][PS_MAX_ROUNDS] each by
-      // request position
-      bool on = false;
-      std::vector<uint32_t> topic;
-      Pass track;
-      psamd::DevBuf d_acc;
-      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out, since the last take or track call
-      // the levels and strips on the device while what they are cut from
-      // stays (graph_epoch, each standing topic's table shape and node range)
-      std::vector<uint64_t> strip_key;
-      Shape kept;
-      // pinned staging per run and the last pass per row set (PassArena, PassFence)
-      PassArena arena[2];
-      uint64_t runs = 0;
-      PassArena* open = nullptr;  // the run being enqueued
-      PassFence fence[2];
-      hipEvent_t ev_take = nullptr;
+      Pass sync, track;  // ps_topic_hops's, the standing pass's
+      Answer ans;        // nodes | reached | deliv, [n][PS_MAX_ROUNDS] each by request position
+      Standing st{"hops"};
+      psamd::DevBuf d_acc;  // the totals, laid out as the answer
+      Shape kept;           // the block on the device (st.strip_key)
     } hops;
 
     // ps_peer_downstream / ps_downstream_track / ps_downstream_take (DESIGN.md
@@ -870,42 +867,25 @@ struct ps_engine {
         uint64_t n_verdicts = 0, n_nodes = 0, row_bytes = 0;
         std::vector<uint32_t> launch;
       };
-      // ps_peer_downstream: its pass, below | carried on the device, their pinned copy
-      Pass sync;
-      psamd::DevBuf d_out;
-      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
-      uint8_t* h_out = nullptr;
-      size_t out_cap = 0;
-      // ps_downstream_track: the standing topics and the totals since the last
-      // take or track call, below | carried in peer space
-      bool on = false;
-      std::vector<uint32_t> topic;
-      Pass track;
-      psamd::DevBuf d_acc;
-      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out, since the last take or track call
-      // the levels, work list and strips on the device while what they are cut
-      // from stays (graph_epoch, each standing topic's table shape and node range)
-      std::vector<uint64_t> strip_key;
-      Shape kept;
-      // pinned staging per run and the last pass per row set (PassArena, PassFence)
-      PassArena arena[2];
-      uint64_t runs = 0;
-      PassArena* open = nullptr;  // the run being enqueued
-      PassFence fence[2];
-      hipEvent_t ev_take = nullptr;
-    } down;
+      explicit Downstream(const char* name) : st{name} {}
+      Pass sync, track;  // ps_peer_downstream's, the standing pass's
+      Answer ans;        // below | carried in peer space
+      Standing st;
+      psamd::DevBuf d_acc;  // the totals, laid out as the answer
+      Shape kept;           // the block on the device (st.strip_key)
+    } down{"downstream"};
 
     // ps_peer_cut / ps_cut_track / ps_cut_take (host code:
     // drain_cut.cpp): per peer, what its nodes missed, and for its cut points
     // -- nodes that lack messages under a full parent -- their number, the
     // nodes behind them and the deliveries lost at and behind them:
     // k_audience_missed behind k_audience_weights, then k_cut_level per BFS
-    // level and k_cut_top over the downstream pass's plan.  The state has the
-    // downstream pass's shape, field for field, with four arrays where that
-    // holds two (missed | cuts | orphaned | lost in d_out and d_acc); it
-    // shares no buffer with it.
+    // level and k_cut_top over the downstream pass's plan.  The alias stays:
+    // the state has the downstream pass's shape, member for member, with four
+    // arrays where that holds two (missed | cuts | orphaned | lost in the
+    // answer and the totals); it shares no buffer with it.
     using Cut = Downstream;
-    Cut cut;
+    Cut cut{"cut"};
 
     // ps_peer_report / ps_report_track / ps_report_take (host
     // code: drain_report.cpp): the four answers above from one pass --
@@ -936,29 +916,12 @@ struct ps_engine {
       struct Out {
         size_t off[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
       };
-      // ps_peer_report: its pass, the cleared output block, its pinned copy
-      Pass sync;
-      psamd::DevBuf d_out;
-      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
-      uint8_t* h_out = nullptr;
-      size_t out_cap = 0;
-      // ps_report_track: the standing topics and sections, the totals since the
-      // last take or track call (the output block's layout over the standing topics)
-      bool on = false;
-      uint32_t what = 0;
-      std::vector<uint32_t> topic;
-      Pass track;
-      psamd::DevBuf d_acc;
-      uint64_t windows = 0, skipped = 0;  // windows; (mesh topic, window) pairs left out of the tree sections
-      // the levels, work list and strips on the device while what they are cut from stays
-      std::vector<uint64_t> strip_key;
-      Shape kept;
-      // pinned staging per run and the last pass per row set (PassArena, PassFence)
-      PassArena arena[2];
-      uint64_t runs = 0;
-      PassArena* open = nullptr;  // the run being enqueued
-      PassFence fence[2];
-      hipEvent_t ev_take = nullptr;
+      Pass sync, track;  // ps_peer_report's, the standing pass's
+      Answer ans;        // the cleared output block
+      Standing st{"report"};
+      uint32_t what = 0;    // the standing sections
+      psamd::DevBuf d_acc;  // the totals: the output block's layout over the standing topics
+      Shape kept;           // the block on the device (st.strip_key)
     } report;
 
     // ps_dist_report (host code: drain_dist.cpp): a rank's
@@ -1012,10 +975,10 @@ struct ps_engine {
     // then k_blame_count, the scan and k_blame_emit into records, or
     // k_blame_gather for explicit queries.  Blocking only; buffers of its own.
     struct Blame {
-      // the front's buffers (plan.sync) and the staged input block
-      // (plan.stage), as down_sync_stage and down_front take them: nothing
-      // else of the downstream pass's shape is used
-      Downstream plan;
+      // the front's buffers and the staged input block, as down_front and
+      // down_sync_stage take them
+      Downstream::Pass front;
+      std::vector<uint8_t> stage;  // (the upload is waited for in the call)
       // the sweep's words cut_node | cut_level, a word per node each; the
       // strips' record counts, their exclusive sum and its temporary; the
       // entries' record offsets; the record arrays the call was asked for
@@ -1035,10 +998,11 @@ struct ps_engine {
     // k_blame_track_emit behind the blocking call's front, sweep, count and
     // scan.  Nothing here is the blocking call's or another tracker's.
     struct BlameTrack {
-      // the standing topics, the pass's buffers (pass.track), the kept strips,
-      // the arenas, the fences and the counts, as the other subtree trackers
-      // keep theirs; sync, d_out, d_acc, stage and h_out stay unused
-      Downstream pass;
+      // the tracker, the pass's buffers and the block kept on the device, as
+      // the other subtree trackers keep theirs (down_window_stage)
+      Standing st{"blame"};
+      Downstream::Pass track;
+      Downstream::Shape kept;
       size_t rec_cap = 0;  // the caller's (zero: the engine's, summed as the windows come)
       uint64_t cap = 0;    // the cap in effect as far as the last window
       // the sweep's words, the strips' record counts, their exclusive sum and
@@ -1052,6 +1016,11 @@ struct ps_engine {
       size_t cur_cap = 0, off_cap = 0, view_cap = 0;
       hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around a window's phases
     } blame_trk;
+
+    // the six trackers, in the order run.cpp's hooks run them behind the sink
+    std::array<Standing*, 6> standing() {
+      return {&load.st, &hops.st, &down.st, &cut.st, &report.st, &blame_trk.st};
+    }
   } drain;
 
   // The slot tables of ps_dist_report's cross-rank sweep (graph.cpp
@@ -1207,38 +1176,20 @@ int sink_open(ps_engine* e);
 int sink_window(ps_engine* e);
 int sink_close(ps_engine* e);
 void sink_abort(ps_engine* e);
-// drain_load.cpp, the standing load pass (ps_load_track; all no-ops while
-// nothing is tracked).  A run opens it (its pinned staging), calls load_window
-// behind every window it remembered, where it calls sink_window, and
-// load_abort when it fails.
-int load_open(ps_engine* e);
+// The standing passes' window hooks (ps_*_track; each a no-op while nothing
+// is tracked or no run is open), each in its family's file.  run.cpp calls them
+// behind every window it remembered, behind sink_window and in this order.
 int load_window(ps_engine* e);
-void load_abort(ps_engine* e);
-// drain_hops.cpp, the standing hop pass (ps_hops_track; all no-ops while
-// nothing is tracked): called where the load pass's hooks are
-int hops_open(ps_engine* e);
 int hops_window(ps_engine* e);
-void hops_abort(ps_engine* e);
-// drain_downstream.cpp, the standing downstream pass (ps_downstream_track; all
-// no-ops while nothing is tracked): called where the hop pass's hooks are
-int downstream_open(ps_engine* e);
 int downstream_window(ps_engine* e);
-void downstream_abort(ps_engine* e);
-// drain_cut.cpp, the standing cut pass (ps_cut_track; all no-ops while nothing
-// is tracked): called where the downstream pass's hooks are
-int cut_open(ps_engine* e);
 int cut_window(ps_engine* e);
-void cut_abort(ps_engine* e);
-// drain_report.cpp, the standing report pass (ps_report_track; all no-ops while
-// nothing is tracked): called where the cut pass's hooks are
-int report_open(ps_engine* e);
 int report_window(ps_engine* e);
-void report_abort(ps_engine* e);
-// drain_blame_track.cpp, the standing blame pass (ps_blame_track; all no-ops
-// while nothing is tracked): called where the report pass's hooks are
-int blame_open(ps_engine* e);
 int blame_window(ps_engine* e);
-void blame_abort(ps_engine* e);
+// drain_standing.cpp: around a run, over Drain::standing(), where sink_open and
+// sink_abort are called: the run's pinned staging of a tracker (a no-op while
+// nothing is tracked); a failed run gives it up
+int standing_open(ps_engine* e, ps_engine::Drain::Standing& S);
+void standing_abort(ps_engine* e, ps_engine::Drain::Standing& S);
 
 // The last window's messages of topic t, in window-slot order (slot li = the
 // topic's rank last_lo + li): their run indices, a slice of run_sorted

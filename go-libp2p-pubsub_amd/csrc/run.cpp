@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iterator>
 #include <thread>
 
 #include "engine.hpp"
@@ -185,24 +186,11 @@ int drain_fence(ps_engine* e, hipStream_t s) {
   const auto& K = e->drain.sink;
   for (const auto& F : K.fence)
     if (F.run > K.runs_done && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending sink drain");
-  // ... and the standing load pass's (ps_load_track): the last one over this row set
-  for (const auto& F : e->drain.load.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending load pass");
-  // ... and the standing hop pass's (ps_hops_track)
-  for (const auto& F : e->drain.hops.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending hop pass");
-  // ... and the standing downstream pass's (ps_downstream_track)
-  for (const auto& F : e->drain.down.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending downstream pass");
-  // ... and the standing cut pass's (ps_cut_track)
-  for (const auto& F : e->drain.cut.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending cut pass");
-  // ... and the standing report pass's (ps_report_track)
-  for (const auto& F : e->drain.report.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending report pass");
-  // ... and the standing blame pass's (ps_blame_track)
-  for (const auto& F : e->drain.blame_trk.pass.fence)
-    if (F.pending && F.seen == e->rows.seen.p) HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), "wait for a pending blame pass");
+  // ... and the trackers' standing passes (ps_*_track): each one's last over this row set
+  for (const auto* S : e->drain.standing())
+    for (const auto& F : S->fence)
+      if (F.pending && F.seen == e->rows.seen.p)
+        HIP_TRY(hipStreamWaitEvent(s, F.ev, 0), (std::string("wait for a pending ") + S->name + " pass").c_str());
   return PS_OK;
 }
 
@@ -1446,6 +1434,10 @@ int run_window(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<
   return WindowRun{e, msgs, win, st}.run();
 }
 
+// the trackers' passes behind a remembered window, in Drain::standing()'s order
+constexpr int (*kStandingWindow[])(ps_engine*) = {load_window, hops_window,   downstream_window,
+                                                  cut_window,  report_window, blame_window};
+
 // Messages of one phase (per topic, a slice of the run's topic-sorted index
 // array), split into windows of at most msg_window messages per topic.
 int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<WinSlice>& per, ps_stats* st) {
@@ -1465,9 +1457,10 @@ int run_phase(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<W
     int rc = run_window(e, msgs, win, st);
     e->defer_last = false;
     // (the window that was remembered: after a k_flood timeout, its re-run)
-    if (!rc && e->window_seq != seq0 && !(rc = sink_window(e)) && !(rc = load_window(e)) && !(rc = hops_window(e)) &&
-        !(rc = downstream_window(e)) && !(rc = cut_window(e)) && !(rc = report_window(e)))
-      rc = blame_window(e);
+    if (!rc && e->window_seq != seq0) {
+      rc = sink_window(e);
+      for (size_t i = 0; !rc && i < std::size(kStandingWindow); ++i) rc = kStandingWindow[i](e);
+    }
     if (rc) return rc;
   }
   return PS_OK;
@@ -1583,24 +1576,18 @@ int run_windows(ps_engine* e, ps_stats* stp, bool may_defer);
 
 // The run with the sink's result around it (ps_sink_set; nothing while none
 // is set): refused before the pending messages are touched, opened, closed
-// behind the last window, given up when the run fails.  And with the standing
-// load pass's, the standing hop pass's and the standing downstream pass's
-// staging around it (ps_load_track, ps_hops_track, ps_downstream_track;
-// nothing while none is set).
+// behind the last window, given up when the run fails.  And with the
+// trackers' staging around it (ps_*_track; nothing while none is set), opened
+// and given up in the hooks' order.
 int run_body(ps_engine* e, ps_stats* stp, bool may_defer) {
   int rc = sink_precheck(e);
   if (rc || (rc = sink_open(e))) return rc;
-  if (!(rc = load_open(e)) && !(rc = hops_open(e)) && !(rc = downstream_open(e)) && !(rc = cut_open(e)) &&
-      !(rc = report_open(e)) && !(rc = blame_open(e)) && !(rc = run_windows(e, stp, may_defer)))
-    rc = sink_close(e);
+  const auto trackers = e->drain.standing();
+  for (size_t i = 0; !rc && i < trackers.size(); ++i) rc = standing_open(e, *trackers[i]);
+  if (!rc && !(rc = run_windows(e, stp, may_defer))) rc = sink_close(e);
   if (rc) {
     sink_abort(e);
-    load_abort(e);
-    hops_abort(e);
-    downstream_abort(e);
-    cut_abort(e);
-    report_abort(e);
-    blame_abort(e);
+    for (auto* S : trackers) standing_abort(e, *S);
   }
   return rc;
 }
