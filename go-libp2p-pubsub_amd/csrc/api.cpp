@@ -165,6 +165,7 @@ static void read_switches(ps_engine* e) {
   if (const char* v = std::getenv("PSAMD_DRAIN_SHARED")) d.share = std::strcmp(v, "private") != 0;
   if (const char* v = std::getenv("PSAMD_LOAD_COUNT")) d.load_rows = std::strcmp(v, "rows") == 0;
   d.spread_wide = env_u32("PSAMD_SPREAD_WIDE", 0, 1 << 30, d.spread_wide);
+  d.spread_track_levels = env_u32("PSAMD_SPREAD_TRACK_LEVELS", 0, kAny, d.spread_track_levels);
   s.twin = env_flag("PSAMD_TWIN", s.twin);
   s.expand_opts = env_flag("PSAMD_NARROW", true) ? 0u : kExpandNoNarrow;
   s.chain_words_lead = env_u32("PSAMD_CHAIN_WORDS_LEAD", 0, 1 << 20, s.chain_words_lead);

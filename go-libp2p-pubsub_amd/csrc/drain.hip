@@ -93,6 +93,9 @@
 //                         a hop per forwarder
 //   k_spread_sum          the hop words into reached / deliv per (entry, column)
 //   k_spread_dup          copies - recv per peer
+// and, for ps_spread_track (§5.5t), that pass behind every window of a run:
+//   k_spread_track_close  behind the window's level launches: a frontier left
+//                         over counts the window as truncated; the counts zeroed
 // A segment is kDrainSegBits positions of one query's row (kernels.hpp,
 // DrainTopic): lane l of its wave owns lane word l.
 #include <hipcub/hipcub.hpp>
@@ -2130,6 +2133,19 @@ __global__ __launch_bounds__(kSpreadBlock) void k_spread_dup(SpreadArgs g) {
   if (p < g.n_peers) g.dup[p] = g.copies[p] - g.recv[p];
 }
 
+// ---- the spread pass behind every window (ps_spread_track) ------------------------
+
+// One thread, behind a tracked window's last level launch: the frontier the
+// next launch would have read still holds items -- the window is counted as
+// truncated --, and the three counts stand at zero for the next window.
+__global__ __launch_bounds__(kWave) void k_spread_track_close(uint32_t* cnt, uint32_t next, unsigned long long* truncated) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  if (cnt[next % 3] != 0) atomicAdd(truncated, 1ull);
+  cnt[0] = 0;
+  cnt[1] = 0;
+  cnt[2] = 0;
+}
+
 // ---- the audience's totals and lists on the device (ps_drain_topics_begin) ---
 // What the host loop of ps_drain_topics does between its waits.
 
@@ -2890,6 +2906,12 @@ hipError_t launch_spread_sum(const SpreadArgs& g, hipStream_t s) {
   if (g.n_strips == 0 || g.n == 0) return hipSuccess;
   const uint32_t per = kAudBlock / kWave;
   hipLaunchKernelGGL(k_spread_sum, dim3((g.n_strips + per - 1) / per), dim3(kAudBlock), 0, s, g);
+  return hipGetLastError();
+}
+
+hipError_t launch_spread_track_close(uint32_t* cnt, uint32_t n_levels, uint64_t* truncated, hipStream_t s) {
+  hipLaunchKernelGGL(k_spread_track_close, dim3(1), dim3(kWave), 0, s, cnt, n_levels % 3,
+                     reinterpret_cast<unsigned long long*>(truncated));
   return hipGetLastError();
 }
 

@@ -2,7 +2,7 @@
 // drain.hip).  One file per call family:
 //   drain_tables.cpp  per window, not per call: the entry checks, both table
 //                     builds, query resolution, count + scan, pinned staging
-//   drain_standing.cpp  the tracker lifecycle, once for the six ps_*_track /
+//   drain_standing.cpp  the tracker lifecycle, once for the seven ps_*_track /
 //                     ps_*_take families below: a run's
 //                     staging, the front and the back of a window's pass, the
 //                     fence per row set, registering topics, the take of the totals
@@ -50,7 +50,14 @@
 //   drain_spread.cpp ps_topic_spread (§5.5p): hops and duplicate copies for meshes
 //                     and trees alike -- the audience pass's strips and classify,
 //                     then a frontier BFS over the node space's child lists, one
-//                     launch per level; blocking only, with buffers of its own
+//                     launch per level; blocking, with buffers of its own; the
+//                     entry table and the kernels' arguments for its tracker too
+//                     (spread_entries .. spread_args below)
+//   drain_spread_track.cpp  ps_spread_track / ps_spread_take and its window hook
+//                     (§5.5t): that pass behind every window of a run, meshes
+//                     and trees alike -- the window's last round + 1 level
+//                     launches enqueued whole, k_spread_track_close behind them
+//                     -- into totals, with buffers of its own
 //   drain_blame.cpp   ps_topic_blame, ps_blame (§5.5q): each node that lacks
 //                     messages with the cut point it hangs behind -- the
 //                     downstream pass's plan and front (down_sync_stage,
@@ -77,7 +84,7 @@
 //  - Slot::seen / emit_pending / ev_emit, Sink::fence (the last sink emit
 //    over each row set) and every tracker's Standing::fence (its last standing
 //    pass over each) are read by drain_fence (run.cpp).
-//  - The six trackers keep one Drain::Standing each and go through
+//  - The seven trackers keep one Drain::Standing each and go through
 //    drain_standing.cpp for all of its lifecycle; Drain::standing() lists them
 //    in the order run.cpp opens them, runs their *_window hooks
 //    (kStandingWindow) and aborts them, and drain_fence, drain_destroy and
@@ -279,7 +286,7 @@ int aud_pass(ps_engine* e, const AudBufs& B, const AudEntry* d_entries, const Au
              const AudShape& A, size_t exc_cap, size_t list_cap, uint32_t seg_bound, const AudView& view,
              const PhaseTimer& tm, float* ms, DrainArgs* args, DrainCtl** ctl_out);
 
-// ---- drain_standing.cpp: the tracker lifecycle, once for the six families -----------
+// ---- drain_standing.cpp: the tracker lifecycle, once for the seven families ---------
 
 // (standing_open / standing_abort, around a run: engine.hpp, beside the window hooks)
 // every pass enqueued so far is complete: nothing waits for one any more
@@ -367,5 +374,48 @@ int down_sync_stage(ps_engine* e, std::vector<uint8_t>& stage, const uint32_t* t
 // the front of a standing subtree pass's window (downstream, cut, blame): the
 // block into P.d_in, kept with its shape while S.strip_key stands
 int down_window_stage(ps_engine* e, Drain::Standing& S, Down::Pass& P, Down::Shape& kept, Down::Shape* K, size_t* n_tree);
+
+// ---- drain_spread.cpp: what the blocking spread and its tracker share ----------------
+
+constexpr uint32_t kSpreadGridMax = 2048;  // blocks of a level launch at most
+constexpr size_t kSpreadCntBytes = 256;    // the three counts in front of the queues
+
+// the output block in 64-bit words: reached | deliv | unreached | holders |
+// visited, then in peer space recv | copies | dup
+struct SpreadOut {
+  size_t reached, deliv, unreached, holders, visited, recv, copies, dup, words;
+  SpreadOut(size_t n, size_t np) {
+    reached = 0;
+    deliv = n * kHopsCols;
+    unreached = 2 * n * kHopsCols;
+    holders = unreached + n;
+    visited = holders + n;
+    recv = visited + n;
+    copies = recv + np;
+    dup = copies + np;
+    words = dup + np;
+  }
+};
+// what the entry table comes to: the words of k / hop, the first frontier, the meshes among it
+struct SpreadPlan {
+  uint64_t n_nodes = 0;
+  uint32_t n_roots = 0, n_mesh = 0;
+};
+// aud_stage's entries [n + 1] as the spread pass's, into se [n + 1]; the roots
+// of the topics that take part -- the first frontier -- into roots [n]
+void spread_entries(ps_engine* e, const uint32_t* topic, size_t n, const AudEntry* ae, const AudShape& A, SpreadEntry* se,
+                    SpreadItem* roots, SpreadPlan* P);
+// a pass's buffers but its input block, sized for the plan
+int spread_ensure(ps_engine* e, Drain::Spread::Pass& B, const AudShape& A, const SpreadPlan& P);
+// the kernels' arguments over a pass's buffers (entries | strips from o_strips
+// in B.d_in), adding into the block `out`; n_edges: what an index into the
+// child lists is checked against
+SpreadArgs spread_args(ps_engine* e, const Drain::Spread::Pass& B, size_t o_strips, size_t n, const AudShape& A,
+                       const SpreadPlan& P, uint32_t n_edges, uint64_t* out, const SpreadOut& O);
+// classify's arguments over the same buffers
+AudArgs spread_classify_args(ps_engine* e, const SpreadArgs& p, const Drain::Spread::Pass& B);
+inline uint32_t spread_level_blocks(const SpreadPlan& P) {
+  return std::min<uint32_t>(std::max<uint32_t>(ceil_div(P.n_nodes, 256), 1), kSpreadGridMax);
+}
 
 }  // namespace psamd

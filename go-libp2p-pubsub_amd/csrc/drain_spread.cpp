@@ -9,7 +9,9 @@
 // BFS over the node space's child lists, one k_spread_level launch per level:
 // where the levels end is the device's to know, so the host reads the frontier
 // count between batches of launches.  k_spread_sum and k_spread_dup close the
-// pass.  Buffers of its own; nothing here is another family's.
+// pass.  Buffers of its own; nothing here is another family's.  The entry
+// table and the kernels' arguments are built by functions the tracker
+// (drain_spread_track.cpp) calls too, over its own buffers.
 #include "drain_impl.hpp"
 
 using namespace psamd;
@@ -20,25 +22,6 @@ static_assert(sizeof(SpreadEntry) == 32, "SpreadEntry is uploaded as laid out he
 static_assert(kHopsCols == PS_MAX_ROUNDS, "a column per round of ps_stats");
 
 constexpr uint32_t kSpreadBatch0 = 8, kSpreadBatchMax = 64;  // level launches between two reads of the frontier count
-constexpr uint32_t kSpreadGridMax = 2048;                     // blocks of a level launch at most
-constexpr size_t kSpreadCntBytes = 256;                       // the three counts in front of the queues
-
-// the output block in 64-bit words: reached | deliv | unreached | holders |
-// visited, then in peer space recv | copies | dup
-struct SpreadOut {
-  size_t reached, deliv, unreached, holders, visited, recv, copies, dup, words;
-  SpreadOut(size_t n, size_t np) {
-    reached = 0;
-    deliv = n * kHopsCols;
-    unreached = 2 * n * kHopsCols;
-    holders = unreached + n;
-    visited = holders + n;
-    recv = visited + n;
-    copies = recv + np;
-    dup = copies + np;
-    words = dup + np;
-  }
-};
 
 // a topic takes part: it had messages in the window and its root is a node
 bool spread_active(const ps_engine* e, uint32_t t) {
@@ -47,6 +30,82 @@ bool spread_active(const ps_engine* e, uint32_t t) {
 }
 
 }  // namespace
+
+// ---- what the blocking call and the tracker share (drain_impl.hpp) -----------------
+
+void psamd::spread_entries(ps_engine* e, const uint32_t* topic, size_t n, const AudEntry* ae, const AudShape& A,
+                           SpreadEntry* se, SpreadItem* roots, SpreadPlan* P) {
+  uint64_t n_nodes = 0;
+  uint32_t n_roots = 0, n_mesh = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t t = topic[i];
+    const TopicDev& d = e->last_topics[t];
+    SpreadEntry E{t, ae[i].strip0, 0, d.nbase, 0, static_cast<uint32_t>(n_nodes), hops_is_mesh(e, t) ? 1u : 0u, 0};
+    if (spread_active(e, t)) {
+      E.c_t = e->last_cnt[t];
+      E.nn = d.n_nodes;
+      n_nodes += d.n_nodes;
+      roots[n_roots++] = SpreadItem{static_cast<uint32_t>(i), 0};
+      n_mesh += E.mesh;
+    }
+    se[i] = E;
+  }
+  se[n] = SpreadEntry{0, A.ns, 0, 0, 0, static_cast<uint32_t>(n_nodes), 0, 0};
+  *P = SpreadPlan{n_nodes, n_roots, n_mesh};
+}
+
+int psamd::spread_ensure(ps_engine* e, Drain::Spread::Pass& B, const AudShape& A, const SpreadPlan& P) {
+  HIP_TRY(B.d_verdict.ensure(A.n_verdicts), "alloc spread verdicts");
+  HIP_TRY(B.d_exc.ensure((static_cast<size_t>(A.ns) + 1) * 8), "alloc spread counts");
+  HIP_TRY(B.d_full.ensure(static_cast<size_t>(A.ns) * 4), "alloc spread counts");
+  HIP_TRY(B.d_scratch.ensure(2 * P.n_nodes * 4), "alloc spread words");
+  HIP_TRY(B.d_queue.ensure(kSpreadCntBytes + 2 * P.n_nodes * sizeof(SpreadItem)), "alloc spread queues");
+  return PS_OK;
+}
+
+SpreadArgs psamd::spread_args(ps_engine* e, const Drain::Spread::Pass& B, size_t o_strips, size_t n, const AudShape& A,
+                              const SpreadPlan& P, uint32_t n_edges, uint64_t* out, const SpreadOut& O) {
+  const auto& D = e->drain;
+  SpreadArgs p{};
+  p.strips = reinterpret_cast<const AudStrip*>(B.d_in.as<uint8_t>() + o_strips);
+  p.n_strips = A.ns;
+  p.entries = B.d_in.as<SpreadEntry>();
+  p.n = static_cast<uint32_t>(n);
+  p.verdict = B.d_verdict.as<uint8_t>();
+  p.n_exc = B.d_exc.as<uint64_t>();
+  p.count_rows = D.env.load_rows;
+  p.wide = D.env.spread_wide;
+  p.node_peer = e->d_node_peer.as<uint32_t>();
+  p.row_ptr = e->d_row_ptr.as<uint32_t>();
+  p.col = e->d_col.as<uint32_t>();
+  p.n_edges = n_edges;
+  p.n_peers = e->cfg.n_peers;
+  p.k = B.d_scratch.as<uint32_t>();
+  p.hop = p.k + P.n_nodes;
+  p.cnt = B.d_queue.as<uint32_t>();
+  p.queue = reinterpret_cast<SpreadItem*>(B.d_queue.as<uint8_t>() + kSpreadCntBytes);
+  p.q_cap = static_cast<uint32_t>(P.n_nodes);
+  p.reached = out + O.reached;
+  p.deliv = out + O.deliv;
+  p.unreached = out + O.unreached;
+  p.holders = out + O.holders;
+  p.visited = out + O.visited;
+  p.recv = out + O.recv;
+  p.copies = out + O.copies;
+  p.dup = out + O.dup;
+  return p;
+}
+
+AudArgs psamd::spread_classify_args(ps_engine* e, const SpreadArgs& p, const Drain::Spread::Pass& B) {
+  AudArgs g{};
+  g.strips = p.strips;
+  g.n_strips = p.n_strips;
+  g.share = e->drain.env.share;
+  g.verdict = B.d_verdict.as<uint8_t>();
+  g.n_exc = B.d_exc.as<uint64_t>();
+  g.n_full = B.d_full.as<uint32_t>();
+  return g;
+}
 
 extern "C" {
 
@@ -89,38 +148,21 @@ int ps_topic_spread(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* rea
     return e->fail(PS_E_STATE, "spread: more strips than staged");
   // the entries, the roots as the first frontier behind its count
   SpreadEntry* const se = reinterpret_cast<SpreadEntry*>(hs);
-  uint64_t n_nodes = 0;
-  uint32_t n_roots = 0, n_mesh = 0;
   H.seed.assign(kSpreadCntBytes + n * sizeof(SpreadItem), 0);
-  SpreadItem* const roots = reinterpret_cast<SpreadItem*>(H.seed.data() + kSpreadCntBytes);
-  for (size_t i = 0; i < n; ++i) {
-    const uint32_t t = topic[i];
-    const TopicDev& d = e->last_topics[t];
-    SpreadEntry E{t, ae[i].strip0, 0, d.nbase, 0, static_cast<uint32_t>(n_nodes), hops_is_mesh(e, t) ? 1u : 0u, 0};
-    if (spread_active(e, t)) {
-      E.c_t = e->last_cnt[t];
-      E.nn = d.n_nodes;
-      n_nodes += d.n_nodes;
-      roots[n_roots++] = SpreadItem{static_cast<uint32_t>(i), 0};
-      n_mesh += E.mesh;
-    }
-    se[i] = E;
-  }
-  se[n] = SpreadEntry{0, A.ns, 0, 0, 0, static_cast<uint32_t>(n_nodes), 0, 0};
+  SpreadPlan P;
+  spread_entries(e, topic, n, ae.data(), A, se, reinterpret_cast<SpreadItem*>(H.seed.data() + kSpreadCntBytes), &P);
+  const uint64_t n_nodes = P.n_nodes;
+  const uint32_t n_roots = P.n_roots, n_mesh = P.n_mesh;
   if (n_nodes >= kDrainRowLimit) return e->fail(PS_E_RANGE, "too many nodes in one spread");
   std::memcpy(H.seed.data(), &n_roots, 4);
-  const uint32_t q_cap = static_cast<uint32_t>(n_nodes);
   const double host_ms = ms_since(t_host0);
 
   const SpreadOut O(n, np);
   const size_t in_bytes = o_strips + static_cast<size_t>(A.ns) * sizeof(AudStrip);
   const size_t out_bytes = O.words * 8;
-  HIP_TRY(H.d_in.ensure(in_bytes), "alloc spread strips");
-  HIP_TRY(H.d_verdict.ensure(A.n_verdicts), "alloc spread verdicts");
-  HIP_TRY(H.d_exc.ensure((static_cast<size_t>(A.ns) + 1) * 8), "alloc spread counts");
-  HIP_TRY(H.d_full.ensure(static_cast<size_t>(A.ns) * 4), "alloc spread counts");
-  HIP_TRY(H.d_scratch.ensure(2 * n_nodes * 4), "alloc spread words");
-  HIP_TRY(H.d_queue.ensure(kSpreadCntBytes + 2 * n_nodes * sizeof(SpreadItem)), "alloc spread queues");
+  auto& B = H.pass;
+  HIP_TRY(B.d_in.ensure(in_bytes), "alloc spread strips");
+  if (const int rc2 = spread_ensure(e, B, A, P)) return rc2;
   HIP_TRY(H.d_out.ensure(out_bytes), "alloc spread sums");
   // (the frontier count lands behind the output block's copy)
   HIP_TRY(pinned_ensure(&H.h_out, nullptr, &H.out_cap, out_bytes + 8), "alloc spread view");
@@ -128,51 +170,19 @@ int ps_topic_spread(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* rea
   HIP_TRY(hipMemsetAsync(out, 0, out_bytes, s), "clear spread sums");
   uint32_t launches = 0;  // level launches: the levels, and what the last batch ran past them
   if (n_roots) {
-    HIP_TRY(hipMemcpyAsync(H.d_in.p, hs, in_bytes, hipMemcpyHostToDevice, s), "upload spread strips");
-    HIP_TRY(hipMemcpyAsync(H.d_queue.p, H.seed.data(), kSpreadCntBytes + n_roots * sizeof(SpreadItem), hipMemcpyHostToDevice, s),
+    HIP_TRY(hipMemcpyAsync(B.d_in.p, hs, in_bytes, hipMemcpyHostToDevice, s), "upload spread strips");
+    HIP_TRY(hipMemcpyAsync(B.d_queue.p, H.seed.data(), kSpreadCntBytes + n_roots * sizeof(SpreadItem), hipMemcpyHostToDevice, s),
             "upload spread roots");
     // the hop words: none
-    HIP_TRY(hipMemsetAsync(H.d_scratch.as<uint32_t>() + n_nodes, 0xFF, n_nodes * 4, s), "clear spread hops");
+    HIP_TRY(hipMemsetAsync(B.d_scratch.as<uint32_t>() + n_nodes, 0xFF, n_nodes * 4, s), "clear spread hops");
     const DrainArgs a = drain_args(e, D.tab);
-    AudArgs g{};
-    g.strips = reinterpret_cast<const AudStrip*>(H.d_in.as<uint8_t>() + o_strips);
-    g.n_strips = A.ns;
-    g.share = D.env.share;
-    g.verdict = H.d_verdict.as<uint8_t>();
-    g.n_exc = H.d_exc.as<uint64_t>();
-    g.n_full = H.d_full.as<uint32_t>();
+    const SpreadArgs p = spread_args(e, B, o_strips, n, A, P, e->row_ptr.empty() ? 0u : e->row_ptr.back(), out, O);
+    const AudArgs g = spread_classify_args(e, p, B);
     if (A.ns) {
       HIP_TRY(tm.begin(), "event");
       HIP_TRY(launch_audience_classify(a, g, s), "k_audience_classify");
       HIP_TRY(tm.end(ms[0]), "event");
     }
-    SpreadArgs p{};
-    p.strips = g.strips;
-    p.n_strips = A.ns;
-    p.entries = H.d_in.as<SpreadEntry>();
-    p.n = static_cast<uint32_t>(n);
-    p.verdict = g.verdict;
-    p.n_exc = g.n_exc;
-    p.count_rows = D.env.load_rows;
-    p.wide = D.env.spread_wide;
-    p.node_peer = e->d_node_peer.as<uint32_t>();
-    p.row_ptr = e->d_row_ptr.as<uint32_t>();
-    p.col = e->d_col.as<uint32_t>();
-    p.n_edges = e->row_ptr.empty() ? 0u : e->row_ptr.back();
-    p.n_peers = static_cast<uint32_t>(np);
-    p.k = H.d_scratch.as<uint32_t>();
-    p.hop = p.k + n_nodes;
-    p.cnt = H.d_queue.as<uint32_t>();
-    p.queue = reinterpret_cast<SpreadItem*>(H.d_queue.as<uint8_t>() + kSpreadCntBytes);
-    p.q_cap = q_cap;
-    p.reached = out + O.reached;
-    p.deliv = out + O.deliv;
-    p.unreached = out + O.unreached;
-    p.holders = out + O.holders;
-    p.visited = out + O.visited;
-    p.recv = out + O.recv;
-    p.copies = out + O.copies;
-    p.dup = out + O.dup;
     HIP_TRY(tm.begin(), "event");
     HIP_TRY(launch_spread_nodes(a, p, s), "k_spread_nodes");
     // (a mesh's node space may hold a peer twice: its unreached nodes are counted from the child entries)
@@ -182,7 +192,7 @@ int ps_topic_spread(ps_engine* e, const uint32_t* topic, size_t n, uint64_t* rea
     // next launch would read.  A launch over an empty frontier leaves the next
     // one empty, so the levels end at the first zero read; a forwarder enters a
     // frontier once, so there are fewer frontiers than nodes.
-    const uint32_t blocks = std::min<uint32_t>(std::max<uint32_t>(ceil_div(n_nodes, 256), 1), kSpreadGridMax);
+    const uint32_t blocks = spread_level_blocks(P);
     uint32_t* const h_cnt = reinterpret_cast<uint32_t*>(H.h_out + out_bytes);
     uint32_t batch = kSpreadBatch0;
     for (bool more = true; more;) {

@@ -1,7 +1,7 @@
-// drain_standing.cpp -- what the six trackers share (drain_impl.hpp; DESIGN.md
+// drain_standing.cpp -- what the seven trackers share (drain_impl.hpp; DESIGN.md
 // §5.5i "The tracker lifecycle"): ps_load_track, ps_hops_track,
-// ps_downstream_track, ps_cut_track, ps_report_track and ps_blame_track each
-// keep one Drain::Standing, and everything that does not depend on what a
+// ps_downstream_track, ps_cut_track, ps_report_track, ps_blame_track and
+// ps_spread_track each keep one Drain::Standing, and everything that does not depend on what a
 // family computes goes through here -- registering topics, a run's pinned
 // staging, the front and the back of a window's pass, the take of the totals.
 // A family's own file holds its kernels' pass, its input block and its key's

@@ -448,8 +448,10 @@ void drain_destroy(ps_engine* e) {
       if (h) (void)hipHostFree(h);
   if (D.aud.h_ids) (void)hipHostFree(D.aud.h_ids);
   for (auto* S : D.standing()) standing_destroy(*S);
-  for (auto* A : {&D.load.ans, &D.hops.ans, &D.down.ans, &D.cut.ans, &D.report.ans})
+  for (auto* A : {&D.load.ans, &D.hops.ans, &D.down.ans, &D.cut.ans, &D.report.ans, &D.spread_trk.ans})
     if (A->h_out) (void)hipHostFree(A->h_out);
+  for (hipEvent_t ev : D.spread_trk.ev_t)
+    if (ev) (void)hipEventDestroy(ev);
   for (uint8_t* h : {D.dist.h_out, D.dist.h_off, D.dist.h_rec})
     if (h) (void)hipHostFree(h);
   if (D.spread.h_out) (void)hipHostFree(D.spread.h_out);

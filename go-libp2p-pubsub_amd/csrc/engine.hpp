@@ -510,6 +510,9 @@ struct ps_engine {
   std::vector<std::vector<psamd::StartGroup>> last_groups;  // topic -> the last window's start groups
   std::vector<psamd::TopicDev> last_topics;
   bool have_window = false;
+  // the last window's last round (WindowRun::r; a deferred window's RunSlot::r):
+  // no hop ps_spread_track's pass can report lies beyond it
+  uint32_t last_rounds = 0;
   std::map<uint32_t, std::vector<uint32_t>> peer_node;  // topic -> peer -> node (peer_node_map)
   std::vector<uint64_t> peer_node_epoch;                 // graph_epoch each map was built for
   uint64_t window_seq = 0;  // bumped whenever last_* change (a new last window)
@@ -608,6 +611,9 @@ struct ps_engine {
       // ps_topic_spread: a frontier node with more child entries than this is walked by its wave, lanes across
       // entries; up to it by its lane alone (A/B: PSAMD_SPREAD_WIDE, 0: every node by the wave)
       uint32_t spread_wide = 16;
+      // ps_spread_track: level launches of a tracked window at most, to show that a truncated BFS is detected
+      // and counted (A/B: PSAMD_SPREAD_TRACK_LEVELS; unset: the window's r + 1)
+      uint32_t spread_track_levels = 0xFFFFFFFFu;
     } env;
 
     hipStream_t copy_stream = nullptr;        // results leave on it, beside whatever `stream` runs next
@@ -767,7 +773,7 @@ struct ps_engine {
     // event with another, since each pass may still be pending when the next
     // run opens.
     struct Standing {
-      const char* name;  // in messages: load, hops, downstream, cut, report, blame
+      const char* name;  // in messages: load, hops, downstream, cut, report, blame, spread
       bool on = false;
       std::vector<uint32_t> topic;
       // windows; (mesh topic, window) pairs left out of the tree answers
@@ -957,10 +963,14 @@ struct ps_engine {
     // child lists, k_spread_sum and k_spread_dup.  Blocking only; buffers of
     // its own.
     struct Spread {
-      // the input block (entries | strips), classify's verdicts and counts,
-      // the per-node words k | hop, the three frontier counts with the two
-      // queues behind them, the cleared output block
-      psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_scratch, d_queue, d_out;
+      // one pass's device buffers: the input block (entries | strips),
+      // classify's verdicts and counts, the per-node words k | hop, the three
+      // frontier counts with the two queues behind them
+      struct Pass {
+        psamd::DevBuf d_in, d_verdict, d_exc, d_full, d_scratch, d_queue;
+      };
+      Pass pass;
+      psamd::DevBuf d_out;  // the cleared output block
       std::vector<uint8_t> stage, seed;  // (the uploads are waited for in the call)
       // the pinned copy of the output block; behind it the frontier count the
       // host reads between batches of level launches
@@ -1017,9 +1027,31 @@ struct ps_engine {
       hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around a window's phases
     } blame_trk;
 
-    // the six trackers, in the order run.cpp's hooks run them behind the sink
-    std::array<Standing*, 6> standing() {
-      return {&load.st, &hops.st, &down.st, &cut.st, &report.st, &blame_trk.st};
+    // ps_spread_track / ps_spread_take (host code:
+    // drain_spread_track.cpp): the spread pass behind every window of a run,
+    // meshes and trees alike -- the blocking call's kernels with the window's
+    // last round + 1 level launches enqueued whole, k_spread_track_close behind
+    // them, adding into totals.  Nothing here is the blocking call's or another
+    // tracker's.
+    struct SpreadTrack {
+      Standing st{"spread"};
+      Spread::Pass track;
+      // what the kept block (st.strip_key) was cut into
+      struct Shape {
+        uint32_t ns = 0;
+        uint64_t n_verdicts = 0;
+      } kept;
+      // the totals: the truncated windows' count, then the blocking call's
+      // output block over the standing topics (dup written by the take)
+      psamd::DevBuf d_acc;
+      Answer ans;  // the pinned copy a take hands out from
+      uint64_t level_launches = 0;  // since the last take or track call (PSAMD_DRAIN_TIMING)
+      hipEvent_t ev_t[2] = {nullptr, nullptr};  // PSAMD_DRAIN_TIMING: around a window's phases
+    } spread_trk;
+
+    // the seven trackers, in the order run.cpp's hooks run them behind the sink
+    std::array<Standing*, 7> standing() {
+      return {&load.st, &hops.st, &down.st, &cut.st, &report.st, &blame_trk.st, &spread_trk.st};
     }
   } drain;
 
@@ -1185,6 +1217,7 @@ int downstream_window(ps_engine* e);
 int cut_window(ps_engine* e);
 int report_window(ps_engine* e);
 int blame_window(ps_engine* e);
+int spread_window(ps_engine* e);
 // drain_standing.cpp: around a run, over Drain::standing(), where sink_open and
 // sink_abort are called: the run's pinned staging of a tracker (a no-op while
 // nothing is tracked); a failed run gives it up

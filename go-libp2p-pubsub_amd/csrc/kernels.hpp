@@ -1495,5 +1495,13 @@ hipError_t launch_spread_unreached(const SpreadArgs& g, hipStream_t s);
 hipError_t launch_spread_level(const SpreadArgs& g, uint32_t level, uint32_t blocks, hipStream_t s);
 hipError_t launch_spread_sum(const SpreadArgs& g, hipStream_t s);
 hipError_t launch_spread_dup(const SpreadArgs& g, hipStream_t s);
+// ps_spread_track: a tracked window enqueues its level
+// launches 0 .. n_levels - 1 whole, with no read of the frontier count between them.
+//   k_spread_track_close  behind the last of them, one thread: the count of the
+//                   frontier launch n_levels would have read, cnt[n_levels % 3];
+//                   not zero: the BFS was cut short, 1 added to *truncated.
+//                   The three counts are left zero.  One writer per word,
+//                   ordered by the stream alone.
+hipError_t launch_spread_track_close(uint32_t* cnt, uint32_t n_levels, uint64_t* truncated, hipStream_t s);
 
 }  // namespace psamd

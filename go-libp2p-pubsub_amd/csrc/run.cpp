@@ -1268,6 +1268,7 @@ struct WindowRun {
     e->last_pos.swap(L.pos);
     e->last_groups.swap(L.groups);
     e->have_window = true;
+    e->last_rounds = r;
     e->last_slot = slot;
     ++e->window_seq;
   }
@@ -1436,7 +1437,8 @@ int run_window(ps_engine* e, const std::vector<RunMsg>& msgs, const std::vector<
 
 // the trackers' passes behind a remembered window, in Drain::standing()'s order
 constexpr int (*kStandingWindow[])(ps_engine*) = {load_window, hops_window,   downstream_window,
-                                                  cut_window,  report_window, blame_window};
+                                                  cut_window,  report_window, blame_window,
+                                                  spread_window};
 
 // Messages of one phase (per topic, a slice of the run's topic-sorted index
 // array), split into windows of at most msg_window messages per topic.

@@ -210,6 +210,8 @@ PROTOTYPES = [
     ("ps_dist_blame", C.c_int, [_P, _u32p, C.c_size_t, C.POINTER(_u64p), C.POINTER(_u32p), C.POINTER(_u32p),
                                 C.POINTER(_u32p), C.POINTER(_u32p), C.POINTER(_u32p), _u64p]),
     ("ps_topic_spread", C.c_int, [_P, _u32p, C.c_size_t, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
+    ("ps_spread_track", C.c_int, [_P, _u32p, C.c_size_t]),
+    ("ps_spread_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -355,6 +357,7 @@ class Engine:
         self._drain_n = []  # (kind: 0 plain, 1 shared, 2 topics; entries) of the drains begun and not ended
         self._sink_n = 0  # standing queries (sink_set)
         self._hops_n = 0  # standing topics (hops_track): the rows hops_take's arrays hold
+        self._spread_n = 0  # standing topics (spread_track): the rows spread_take's arrays hold
         if plan:
             self.set_plan(**plan)
 
@@ -1062,6 +1065,33 @@ class Engine:
                "unreached": np.zeros(t.size, dtype=np.uint64), "stranded": np.zeros(t.size, dtype=np.uint64),
                "copies": np.empty(self.n_peers, dtype=np.uint64), "dup": np.empty(self.n_peers, dtype=np.uint64)}
         self._check(self._L.ps_topic_spread(self._h, _p(t, C.c_uint32), t.size, *(_p(a, C.c_uint64) for a in out.values())))
+        return out
+
+    def spread_track(self, topics):
+        """Registers standing topics, meshes and trees alike (ps_spread_track):
+        from now on every window of every run adds topic_spread's answer over
+        them into totals on the device (spread_take).  No topic clears the
+        tracking; setting or clearing zeroes the totals."""
+        t = np.ascontiguousarray(topics, dtype=np.uint32)
+        if t.ndim != 1:
+            raise ValueError("topics must be a 1-d array")
+        self._check(self._L.ps_spread_track(self._h, _p(t, C.c_uint32), t.size))
+        self._spread_n = int(t.size)
+
+    def spread_take(self) -> dict:
+        """The totals since the last take or track call (ps_spread_take):
+        topic_spread's six arrays, row i for the i-th standing topic, summed
+        over the windows, with n_windows and n_truncated -- the windows whose
+        BFS was cut short with a frontier left (0 on a healthy engine).  The
+        totals and both counts start again at 0."""
+        n = self._spread_n
+        out = {"reached": np.zeros((n, MAX_ROUNDS), dtype=np.uint64), "deliv": np.zeros((n, MAX_ROUNDS), dtype=np.uint64),
+               "unreached": np.zeros(n, dtype=np.uint64), "stranded": np.zeros(n, dtype=np.uint64),
+               "copies": np.empty(self.n_peers, dtype=np.uint64), "dup": np.empty(self.n_peers, dtype=np.uint64)}
+        nw, nt = C.c_uint64(), C.c_uint64()
+        self._check(self._L.ps_spread_take(self._h, *(_p(a, C.c_uint64) for a in out.values()), C.byref(nw), C.byref(nt)))
+        out["n_windows"] = nw.value
+        out["n_truncated"] = nt.value
         return out
 
     def report_track(self, topics, what: int = REPORT_ALL):

@@ -1131,12 +1131,57 @@ int ps_dist_blame(ps_engine* e, const uint32_t* topic, size_t n,
  * topic named twice; PS_E_RANGE, nothing written, for a topic out of range;
  * PS_E_NOTREADY before any run; PS_E_STATE on a multi-rank engine and for a
  * tree topic that was set anew over another kind since the window.
- *   There is no tracker and no asynchronous form: a window's depth is not
- * known to the host before ps_wait, and the pass launches once per hop. */
+ *   There is no asynchronous form of this call: it reads the frontier count
+ * between batches of level launches to find where the levels end.  The
+ * tracker below needs no such read: behind a window that has been enqueued the
+ * host knows its last round, which bounds every hop. */
 int ps_topic_spread(ps_engine* e, const uint32_t* topic, size_t n,
                     uint64_t* reached_out, uint64_t* deliv_out,      /* [n * PS_MAX_ROUNDS], row i = topic[i] */
                     uint64_t* unreached_out, uint64_t* stranded_out, /* [n] */
                     uint64_t* copies_out, uint64_t* dup_out);        /* [n_peers] */
+/* ps_topic_spread's answer behind every window, summed on the device (one
+ * rank).  ps_spread_track registers n distinct standing
+ * topics, meshes and trees alike -- nothing is refused or skipped for being a
+ * mesh; n == 0 clears the tracking and frees the totals.  PS_E_INVAL for a
+ * NULL engine, n > 0 without topic or a topic named twice; PS_E_RANGE for a
+ * topic out of range; PS_E_STATE with a run in flight or on a multi-rank
+ * engine; after a failure the previous tracking stays.  ps_dist_init* on an
+ * engine that tracks spread returns PS_E_STATE.  Setting or clearing zeroes
+ * the totals.  Independent of both sinks and of the six other trackers: all
+ * may be set at once.
+ *   While it is set, every window of every ps_run / ps_run_async that runs
+ * something enqueues the pass behind itself on the engine's stream; the
+ * window is neither planned nor launched differently, and nothing waits.  A
+ * window ends with its last round r, which the host knows once the window is
+ * enqueued; a node that holds a message received it at some round <= r over a
+ * path of as many forwarders, so no hop lies beyond r and the pass enqueues
+ * level launches 0 .. r whole, then checks on the device that the next
+ * frontier is empty.  Each window adds into totals on the device; per window
+ * and per standing topic the contribution is exactly ps_topic_spread's, on
+ * the node space that window ran on (the PSAMD_LOAD_COUNT=rows seam
+ * applies).  A topic idle in a window adds nothing.  stranded is the sum of
+ * the windows' holders minus the sum of their visited nodes; dup is the sum
+ * of copies minus the sum of recv, modulo 2^64.  The totals are indexed by
+ * request position and survive rebuilds, joins, leaves and drops between
+ * windows.  There is no n_skipped: nothing is skipped.
+ *   ps_spread_take waits once for the passes enqueued so far and copies the
+ * totals since the last take or track call; each array may be NULL, all six
+ * too.  It zeroes the totals in front of whatever runs next and sets
+ * *n_windows_out, and *n_truncated_out to the number of windows whose BFS
+ * still had a frontier left behind its r + 1 launches -- 0 on a healthy
+ * engine, reported and not assumed like stranded; such a window's late nodes
+ * count as stranded and the copies they sent are missing.  Both counts start
+ * again at 0.  PS_E_NOTREADY when nothing is tracked; PS_E_STATE with a run in
+ * flight; PS_E_INVAL for a NULL engine or count pointer.  After a failed run
+ * the totals are unspecified until the next take or track call.
+ *   A/B only (PSAMD_AB=1): PSAMD_SPREAD_TRACK_LEVELS=n caps a tracked window's
+ * level launches at n, to show that truncation is detected and counted. */
+int ps_spread_track(ps_engine* e, const uint32_t* topic, size_t n);
+int ps_spread_take(ps_engine* e,
+                   uint64_t* reached_out, uint64_t* deliv_out,      /* [n_tracked * PS_MAX_ROUNDS], nullable */
+                   uint64_t* unreached_out, uint64_t* stranded_out, /* [n_tracked], nullable */
+                   uint64_t* copies_out, uint64_t* dup_out,         /* [n_peers], nullable */
+                   uint64_t* n_windows_out, uint64_t* n_truncated_out);
 /* Order-independent digest of the final seen state of the last window:
  * sum over (peer, topic, word < message words) of
  * mix64(mix64(peer << 32 | topic << 16 | word) ^ mix64(seen word)); a

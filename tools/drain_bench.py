@@ -202,6 +202,16 @@ walls of ps_topic_spread, ps_peer_load and the same answer derived on the host
 (ps_peer_load's recv, the child lists, a frontier BFS in numpy), --reps
 repetitions alternating in one process, the answers compared array for array.
 Writes DIR/spread_bench.json.
+
+--spread-track: that answer behind every window (ps_spread_track), on
+--spread's own mesh in its random and hub shapes.  Per shape: the device
+phases (PSAMD_DRAIN_TIMING) of a tracked window, of its take and of the
+blocking call, alternating in one process, with the level launches of each;
+then three loops of --steps steps alternating in one process, --reps times:
+(a) the untracked pipelined step, (b) ps_run + ps_topic_spread every step,
+(c) the tracked pipelined step with one ps_spread_take every --take-every
+steps, every take compared array for array with the sum of (b)'s answers.
+Writes DIR/spread_track_bench.json.
 """
 from __future__ import annotations
 
@@ -2796,6 +2806,148 @@ def spread_main(a):
             f.write(json.dumps(res, indent=1) + "\n")
 
 
+SPREAD_NAMES = ("reached", "deliv", "unreached", "stranded", "copies", "dup")
+
+
+def spread_track_main(a):
+    """--spread-track (see the module text).  Writes DIR/spread_track_bench.json."""
+    c = 1024
+    k = max(1, min(a.take_every, a.steps))
+    steps = a.steps // k * k
+    res = {"n_peers": a.spread_peers, "n_msgs": c, "reps": a.reps, "hub": a.spread_hub, "steps": steps, "warmup": a.warmup,
+           "take_every": k, "shapes": {}}
+    batch = np.zeros(c)
+
+    def engine(env, g):
+        for key in ("PSAMD_AB", "PSAMD_DRAIN_TIMING", "PSAMD_SPREAD_WIDE", "PSAMD_SPREAD_TRACK_LEVELS"):
+            os.environ.pop(key, None)
+        os.environ.update(env)
+        eng = PE.Engine(a.spread_peers, 1)
+        for key in env:
+            os.environ.pop(key, None)
+        eng.set_children(0, g[2], g[0], g[1])
+        eng.set_live(g[3])
+        eng.publish(batch)
+        return eng, eng.run()
+
+    def pipelined(eng, n):
+        eng.publish(batch)
+        for i in range(n):
+            eng.run_async()
+            if i + 1 < n:
+                eng.publish(batch)
+            if i:
+                eng.wait()
+        eng.wait()
+
+    def summed(parts):
+        tot = {name: np.zeros_like(parts[0][name]) for name in SPREAD_NAMES}
+        with np.errstate(over="ignore"):
+            for p in parts:
+                for name in SPREAD_NAMES:
+                    tot[name] += p[name]
+        return tot
+
+    def agree(take, parts, what):
+        want = summed(parts)
+        assert take["n_windows"] == len(parts) and take["n_truncated"] == 0, (what, take["n_windows"], take["n_truncated"])
+        for name in SPREAD_NAMES:
+            assert np.array_equal(take[name], want[name]), f"{what}: tracked {name} differs from the sum of ps_topic_spread"
+
+    for shape, hub in (("random", 0), ("hub", a.spread_hub)):
+        g = spread_graph(a.spread_peers, hub, a.seed)
+        row = {"edges": int(g[1].size)}
+        # the device phases: one tracked window, its take and one blocking call, alternating
+        eng, st = engine({"PSAMD_DRAIN_TIMING": "1"}, g)
+        with eng:
+            assert st.windows == 1
+            blocking = eng.topic_spread([0])
+            rows = {"spread_track": [], "spread_take": [], "topic_spread": []}
+            eng.spread_track([0])
+            for _ in range(a.reps + 1):  # (the first pass allocates and uploads the strips)
+                eng.publish(batch)
+                with StderrCapture() as cap:
+                    eng.run()
+                r = phase_line(cap.text, "spread_track")
+                for key in ("strips", "nodes", "row_bytes", "rounds", "level_launches", "staged_bytes", "kept"):
+                    r[key] = int(re.search(rf"psamd spread_track: .*\b{key} (\d+)", cap.text).group(1))
+                rows["spread_track"].append(r)
+                with StderrCapture() as cap:
+                    t = eng.spread_take()
+                agree(t, [blocking], shape + " timed")
+                r = phase_line(cap.text, "spread_take")
+                r["copied_bytes"] = int(re.search(r"copied_bytes (\d+)", cap.text).group(1))
+                rows["spread_take"].append(r)
+                with StderrCapture() as cap:
+                    got = eng.topic_spread([0])
+                r = phase_line(cap.text, "topic_spread")
+                r["level_launches"] = int(re.search(r"psamd topic_spread: .*\blevel_launches (\d+)", cap.text).group(1))
+                rows["topic_spread"].append(r)
+                for name in SPREAD_NAMES:
+                    assert np.array_equal(got[name], blocking[name]), name
+            eng.spread_track([])
+        dev = lambda rs, skip=(): float(np.median([sum(v for q, v in r.items() if q.endswith("_ms") and q not in skip) for r in rs]))
+        row.update(deliveries=int(st.deliveries), duplicates=int(st.duplicates), rounds=int(st.rounds),
+                   depth=int(np.nonzero(blocking["reached"][0])[0].max()), tracked_phases=rows["spread_track"][1:],
+                   take_phases=rows["spread_take"][1:], blocking_phases=rows["topic_spread"][1:])
+        row["tracked_window_device_ms"] = dev(row["tracked_phases"], ("host_ms",))
+        row["blocking_call_device_ms"] = dev(row["blocking_phases"], ("host_strips_ms", "copy_ms"))
+        row["blocking_call_copy_ms"] = float(np.median([r["copy_ms"] for r in row["blocking_phases"]]))
+        row["tracked_level_launches"] = row["tracked_phases"][-1]["level_launches"]
+        row["blocking_level_launches"] = row["blocking_phases"][-1]["level_launches"]
+
+        # the walls: (a) the untracked pipelined step, (b) ps_run + ps_topic_spread every step, (c) tracked, a take every k steps
+        eng, _ = engine({}, g)
+
+        def plain(n):
+            t0 = time.perf_counter()
+            for _ in range(n // k):
+                pipelined(eng, k)
+            return 1e3 * (time.perf_counter() - t0) / n
+
+        def blocking_loop(n):
+            parts = []
+            t0 = time.perf_counter()
+            for _ in range(n):
+                eng.publish(batch)
+                eng.run()
+                parts.append(eng.topic_spread([0]))
+            ms = 1e3 * (time.perf_counter() - t0) / n
+            blocking_loop.parts = parts
+            return ms
+
+        def tracked(n):
+            eng.spread_track([0])
+            takes = []
+            t0 = time.perf_counter()
+            for _ in range(n // k):
+                pipelined(eng, k)
+                takes.append(eng.spread_take())
+            ms = 1e3 * (time.perf_counter() - t0) / n
+            for i, t in enumerate(takes):  # (outside the timed part; (b) ran the same steps just before)
+                agree(t, blocking_loop.parts[i * k:(i + 1) * k], shape)
+            eng.spread_track([])
+            return ms
+
+        modes = {"plain": plain, "run_plus_topic_spread": blocking_loop, "tracked": tracked}
+        with eng:
+            for f in modes.values():
+                f(max(a.warmup // k, 1) * k)
+            ms = {name: [] for name in modes}
+            for _ in range(a.reps):
+                for name, f in modes.items():
+                    ms[name].append(f(steps))
+        med = {name: float(np.median(v)) for name, v in ms.items()}
+        row.update(ms_per_step=ms, median_ms_per_step=med, takes_agree=True, tracked_minus_plain_ms=med["tracked"] - med["plain"],
+                   blocking_loop_over_tracked=med["run_plus_topic_spread"] / med["tracked"])
+        res["shapes"][shape] = row
+    print(json.dumps(res))
+    if a.out:
+        os.makedirs(a.out, exist_ok=True)
+        with open(os.path.join(a.out, "spread_track_bench.json"), "w") as f:
+            f.write(json.dumps(res, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--workload", default="cfg3", choices=sorted(WL.CONFIGS))
@@ -2822,7 +2974,7 @@ def main():
     ap.add_argument("--blame", action="store_true", help="ps_topic_blame against ps_peer_cut and the host derivation")
     ap.add_argument("--blame-track", action="store_true",
                     help="ps_blame_track in the pipelined loop against ps_run + ps_topic_blame every step")
-    ap.add_argument("--take-every", type=int, default=10, help="--blame-track: steps between two ps_blame_take")
+    ap.add_argument("--take-every", type=int, default=10, help="--blame-track, --spread-track: steps between two takes")
     ap.add_argument("--report", action="store_true",
                     help="ps_peer_report against the four calls in sequence; report tracking against the four trackers")
     ap.add_argument("--report-once", action="store_true", help="one step and one ps_peer_report (for a kernel trace)")
@@ -2833,9 +2985,13 @@ def main():
     ap.add_argument("--dist-blame", action="store_true",
                     help="ps_dist_blame against ps_topic_blame on one rank; against ps_dist_cut on 2 and 4 loopback ranks")
     ap.add_argument("--spread", action="store_true", help="ps_topic_spread on a mesh of its own against ps_peer_load and the host derivation")
+    ap.add_argument("--spread-track", action="store_true",
+                    help="ps_spread_track in the pipelined loop against ps_run + ps_topic_spread every step, on --spread's meshes")
     ap.add_argument("--spread-peers", type=int, default=1 << 20)
     ap.add_argument("--spread-hub", type=int, default=4096)
     a = ap.parse_args()
+    if a.spread_track:
+        return spread_track_main(a)
     if a.spread:
         return spread_main(a)
     wl = WL.scaled(a.workload, a.scale) if a.scale != 1.0 else WL.CONFIGS[a.workload]()
