@@ -172,6 +172,11 @@ static void read_switches(ps_engine* e) {
   s.upload_reuse = env_flag("PSAMD_UPLOAD_REUSE", s.upload_reuse);
   s.sig_windows = env_flag("PSAMD_SIG_WINDOWS", s.sig_windows);
   s.fuse_reduce = env_flag("PSAMD_FUSE_REDUCE", s.fuse_reduce);
+  s.chain_fill = env_flag("PSAMD_CHAIN_FILL", s.chain_fill);
+  s.chain_fill_bytes = env_u64("PSAMD_CHAIN_FILL_BYTES", 10, s.chain_fill_bytes);
+  s.chain_fill_row_words = env_u64("PSAMD_CHAIN_FILL_ROW_WORDS", 10, s.chain_fill_row_words);
+  s.chain_fill_waves = env_u32("PSAMD_CHAIN_FILL_WAVES", 0, 32, s.chain_fill_waves);
+  s.chain_fill_piece = env_u32("PSAMD_CHAIN_FILL_PIECE", 16, 1 << 16, s.chain_fill_piece);
   ps_plan_opts o = e->opts;
   o.gpu_build = env_flag("PSAMD_GPU_BUILD", o.gpu_build);
   o.flood = env_flag("PSAMD_FLOOD", o.flood);
@@ -676,6 +681,12 @@ int ps_overlapped_windows(ps_engine* e, uint64_t* count_out) {
   return PS_OK;
 }
 
+int ps_chain_fill_launches(ps_engine* e, uint64_t* count_out) {
+  if (!e || !count_out) return PS_E_INVAL;
+  *count_out = e->chain_fills;
+  return PS_OK;
+}
+
 int ps_seen_digest(ps_engine* e, uint64_t* digest_out) {
   if (!e || !digest_out) return PS_E_INVAL;
   if (!e->have_window) return e->fail(PS_E_NOTREADY, "no completed run");
@@ -1009,6 +1020,27 @@ int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size
         v.insert(v.end(), {c.node_begin, c.node_end, c.topic, c.W, static_cast<uint64_t>(c.row0_hi) << 32 | c.row0_lo,
                            c.w0, c.S, c.levels, c.r0, c.group});
         for (uint32_t f = 0; f <= kChainLevels; ++f) v.push_back(c.first[f]);
+      }
+      break;
+    }
+    case PS_PLAN_FILL: {
+      const PairPlan& P = e->pair;
+      if (index >= P.fill_hi.size() || P.fill_hi[index] <= P.fill_lo[index]) {
+        v = {0};
+        break;
+      }
+      v = {P.fill_hi[index] - P.fill_lo[index], P.fill_np[index], P.fill_blocks[index]};
+      for (uint32_t k = P.fill_lo[index]; k < P.fill_hi[index]; ++k) {
+        const FillSeg& f = P.fill[k];
+        v.insert(v.end(), {f.topic, f.W, f.row0, f.nbase, f.levels, f.piece0, f.blk0, f.pw});
+        for (uint32_t i = 0; i <= kChainLevels; ++i) v.push_back(f.first[i]);
+      }
+      for (uint32_t k = P.fill_lo[index]; k < P.fill_hi[index]; ++k) {
+        const FillSeg& f = P.fill[k];
+        for (uint32_t j = 0, n = fill_seg_pieces(f); j < n; ++j) {
+          const FillPiece p = fill_piece(f, j);
+          v.insert(v.end(), {p.w0, p.nw, p.node0, p.off0});
+        }
       }
       break;
     }

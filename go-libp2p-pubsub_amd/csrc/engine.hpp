@@ -244,6 +244,11 @@ struct PairPlan {
                                          // (chains: whole rows [lo, gsplit), column slices [gsplit, hi))
   std::vector<uint32_t> len;             // round q: rounds of the launch starting at q (0: none)
   std::vector<uint8_t> kind;             // per round: PS_K_*
+  // chain launches run as reach + fill: round q's whole-row chunks [lo, gsplit) as
+  // the segments [fill_lo[q], fill_hi[q]) -- none: the launch stays k_pull_chain's -- with fill_blocks[q]
+  // reach blocks and the pieces [fill_p0[q], fill_p0[q] + fill_np[q]) of the plan's pieces
+  std::vector<FillSeg> fill;
+  std::vector<uint32_t> fill_lo, fill_hi, fill_blocks, fill_p0, fill_np;
 };
 struct FloodPlan {
   std::vector<uint64_t> key;
@@ -345,6 +350,16 @@ struct ps_engine {
     bool upload_reuse = true;  // the upload shadows below (A/B: PSAMD_UPLOAD_REUSE=0)
     uint32_t expand_opts = 0;       // ExpandArgs::opts (A/B only: PSAMD_NARROW=0 -> kExpandNoNarrow)
     uint32_t chain_words_lead = 0;  // A/B only (PSAMD_CHAIN_WORDS_LEAD): opts.chain_words for all but the last launch
+    // chain launches as reach + fill (PSAMD_CHAIN_FILL=0: off): a launch whose whole
+    // rows are at least chain_fill_bytes (PSAMD_CHAIN_FILL_BYTES; 0: every eligible launch) and on
+    // average at least chain_fill_row_words wide (PSAMD_CHAIN_FILL_ROW_WORDS; 0: any width), at most
+    // chain_fill_waves fill waves per CU (PSAMD_CHAIN_FILL_WAVES; 0: no cap), in pieces of about
+    // chain_fill_piece words (PSAMD_CHAIN_FILL_PIECE)
+    bool chain_fill = true;
+    uint32_t chain_fill_piece = psamd::kFillPieceWords;
+    uint64_t chain_fill_bytes = 512ull << 20;
+    uint64_t chain_fill_row_words = psamd::kFillMinRowWords;
+    uint32_t chain_fill_waves = psamd::kFillWaves;
   } env;
   std::vector<hipEvent_t> ev_k;  // pairs around expand launches
   uint32_t n_cus = 256, expand_grid = 2048;
@@ -434,6 +449,8 @@ struct ps_engine {
   std::vector<uint64_t> chain_fail_key;  // a pair plan whose chain ranges overflowed the level tables: no chains
   psamd::DevBuf d_chain_ovf;
   psamd::DevBuf d_chain_meta, d_chain_cnt, d_chain_scan;  // the chunks' node entries (k_chain_meta)
+  psamd::DevBuf d_fill_segs, d_fill_pieces;  // pair.fill and its pieces (uploaded / built with the chain chunks)
+  uint64_t chain_fills = 0;                  // chain launches run as reach + fill (ps_chain_fill_launches)
   // rows of rounds writing at least this much store non-temporally (the MALL
   // cannot hold them for the next launch: reversing launch order and cached
   // stores measured 0-50 % slower, profiles/r03/ab_mall_reverse.txt)
@@ -1090,6 +1107,7 @@ struct ps_engine {
   struct RunSlot {
     Staging stg;
     psamd::DevBuf topics, woff, groups, partials, seeds;  // the per-window tables (upload_shadow keys: stable addresses)
+    psamd::DevBuf fill_pop;  // per topic: set bits of its root row in this window (k_fill_popc)
     hipEvent_t ev_gate = nullptr;
     ps_stats st{};
     bool deferred = false;

@@ -322,6 +322,95 @@ hipError_t launch_pull_chain(const PullArgs& a, const ChainChunk* chunks, uint32
                              hipStream_t s);
 // ChainChunk::p_lo / p_hi from the device node_parent (GPU-built graphs)
 hipError_t launch_chain_parents(ChainChunk* chunks, uint32_t n, const uint32_t* node_parent, hipStream_t s);
+// A chain launch as reach + fill (fill.hip): in a
+// single-start window every reached node's row is its topic root's seeded
+// row, an unreached one's is zeros, and levels d .. d + levels - 1 of a topic
+// are one contiguous id range (BFS numbering), so their rows are one
+// contiguous word range of `seen`.  k_fill_reach decides reach for every node
+// of the launch's levels, stamps generations and adds the chain launch's
+// counters; k_fill_rows then writes each topic's range front to back in
+// line-aligned pieces, one wave each, from the root row in LDS.
+struct FillSeg {  // one topic's whole rows of one chain launch
+  uint64_t row0;  // word offset of the row of the topic's first node (the root: its seeded row in a_cur)
+  uint32_t topic, W;
+  uint32_t nbase, levels;
+  uint32_t first[kChainLevels + 1];  // first node of levels d .. d + levels (node ids)
+  uint32_t piece0;                   // the segment's first piece in its launch
+  uint32_t blk0;                     // ... and its first k_fill_reach block (kFillReachBlock nodes each)
+  uint32_t pw;                       // words per piece: a multiple of kFillLine, at most kFillPieceNodes rows
+};
+static_assert(sizeof(FillSeg) == 64, "four segments per 256-B line");
+struct FillPiece {      // one wave's contiguous words [w0, w0 + nw) of `seen`
+  uint64_t w0, row0;    // row0: the topic root's row
+  uint32_t nw, W;
+  uint32_t node0, off0;  // the node holding word w0, and w0's word within its row
+};
+static_assert(sizeof(FillPiece) == 32, "one scalar load per wave");
+constexpr uint32_t kFillLine = 16;            // words of a 128-B line: pieces start and end on lines
+constexpr uint32_t kFillPieceWords = 2048;    // 16 KB per wave (tools/probe/chain_write_probe.hip)
+constexpr uint32_t kFillPieceNodes = 2048;    // nodes with a word in one piece at most (+ 2: k_fill_rows' LDS bytes)
+constexpr uint32_t kFillWaves = 16;           // resident fill waves per CU at most (profiles/chain_fill/sweep.txt)
+constexpr uint32_t kFillReachBlock = 256;
+// A launch is filled only if its rows average at least this many words.  The reach pass costs per
+// node (cfg3's bulk launch: 24 us for 1.5 M nodes, 16 ns each), the fill gains per byte written
+// (6.0 against 4.9 TB/s: 0.3 ps per row word), which breaks even at 53 words; 128 leaves a margin
+// (cfg4's 16-word rows lose: 0.56 against 0.39 ms/step, profiles/chain_fill/ab.json).
+constexpr uint32_t kFillMinRowWords = 128;
+__host__ __device__ inline uint64_t fill_seg_begin(const FillSeg& s) {
+  return s.row0 + static_cast<uint64_t>(s.first[0] - s.nbase) * s.W;
+}
+__host__ __device__ inline uint64_t fill_seg_end(const FillSeg& s) {
+  return s.row0 + static_cast<uint64_t>(s.first[s.levels] - s.nbase) * s.W;
+}
+// words per piece of rows of W words, for pieces of about `words`
+__host__ __device__ inline uint32_t fill_piece_words(uint32_t W, uint32_t words) {
+  const uint64_t cap = (static_cast<uint64_t>(kFillPieceNodes) * W) & ~static_cast<uint64_t>(kFillLine - 1);
+  const uint32_t w = (words < kFillLine ? kFillLine : words) & ~(kFillLine - 1);
+  return cap < w ? static_cast<uint32_t>(cap < kFillLine ? kFillLine : cap) : w;
+}
+__host__ __device__ inline uint32_t fill_seg_pieces(const FillSeg& s) {
+  const uint64_t wb = fill_seg_begin(s), we = fill_seg_end(s);
+  if (we <= wb) return 0;
+  const uint64_t a = wb & ~static_cast<uint64_t>(kFillLine - 1);
+  return static_cast<uint32_t>((we - a + s.pw - 1) / s.pw);
+}
+// Piece j of a segment: cut at multiples of the piece size from the line
+// holding the segment's first word, so only a segment's first and last
+// pieces have an edge off a line.
+__host__ __device__ inline FillPiece fill_piece(const FillSeg& s, uint32_t j) {
+  const uint64_t wb = fill_seg_begin(s), we = fill_seg_end(s);
+  const uint64_t a = wb & ~static_cast<uint64_t>(kFillLine - 1);
+  const uint64_t b = a + static_cast<uint64_t>(j) * s.pw, e = b + s.pw;
+  FillPiece p;
+  p.w0 = b < wb ? wb : b;
+  p.row0 = s.row0;
+  p.nw = static_cast<uint32_t>((e > we ? we : e) - p.w0);
+  p.W = s.W;
+  const uint64_t rel = p.w0 - s.row0;
+  p.node0 = s.nbase + static_cast<uint32_t>(rel / s.W);
+  p.off0 = static_cast<uint32_t>(rel % s.W);
+  return p;
+}
+struct FillReachArgs {
+  const FillSeg* segs;
+  uint32_t n_segs;
+  const uint32_t* node_parent;
+  const uint8_t* node_flags;
+  uint8_t* gen;
+  uint32_t gen_cur;
+  const uint32_t* pop;  // per topic: the popcount of its root row (k_fill_popc, once per window)
+  uint64_t* partials_r[kChainLevels];
+  uint32_t slot_mod;
+};
+// pieces[] of the launch's segments from segs[] (once per plan, on the device)
+hipError_t launch_fill_pieces(const FillSeg* segs, uint32_t n_segs, FillPiece* pieces, uint32_t n_pieces,
+                              hipStream_t s);
+// pop[topic] of every segment's topic, from its root row in a_cur
+hipError_t launch_fill_popc(const FillSeg* segs, uint32_t n_segs, const uint64_t* a_cur, uint32_t* pop, hipStream_t s);
+hipError_t launch_fill_reach(const FillReachArgs& a, uint32_t n_blocks, hipStream_t s);
+hipError_t launch_fill_rows(const FillPiece* pieces, uint32_t n_pieces, const uint64_t* a_cur, uint64_t* seen,
+                            const uint8_t* gen, uint32_t gen_cur, uint32_t waves_per_cu, hipStream_t s);
+
 constexpr uint32_t kPullSlots = 256;  // partial slots per round of a pull launch
 // k_pull_pair: every wave adds its counters with atomics (no block
 // reduction) into slot wave % kPairSlots.  (4096 slots: no faster than 256,

@@ -470,6 +470,12 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
   PP.hi.assign(rounds + 2, 0);
   PP.gsplit.assign(rounds + 2, 0);
   PP.len.assign(rounds + 2, 0);
+  PP.fill.clear();
+  for (auto* v : {&PP.fill_lo, &PP.fill_hi, &PP.fill_blocks, &PP.fill_p0, &PP.fill_np}) v->assign(rounds + 2, 0);
+  uint32_t fill_pieces = 0;  // pieces of the plan's fill launches so far
+  // reach + fill needs every row of a launch to be its topic root's row or zeros: one
+  // rank, one start round (no start groups, no level-aligned bit groups)
+  const bool fill_ok = e->env.chain_fill && e->world == 1 && !L.multi && !L.aligned && L.max_start == 0;
   const bool gpu = e->gpu_graph;
   std::vector<PullChunk> ghost;
   for (uint32_t q = first + 1; q <= rounds; ++q) {
@@ -518,6 +524,51 @@ bool plan_pair_chunks(ps_engine* e, const WindowLayout& L, uint32_t first) {
       PP.gsplit[q] = static_cast<uint32_t>(PP.chain.size());
       PP.chain.insert(PP.chain.end(), sliced.begin(), sliced.end());
       PP.hi[q] = static_cast<uint32_t>(PP.chain.size());
+      // the launch's whole rows as fill segments: per topic the contiguous node range of its levels
+      // (the same parts, in the same order: address order)
+      if (fill_ok) {
+        const uint32_t s0 = static_cast<uint32_t>(PP.fill.size());
+        uint64_t words = 0, launch_nodes = 0;
+        uint32_t blocks = 0, pieces = 0;
+        bool ok = true;
+        chain_parts(q, len, [&](uint32_t t, uint32_t gi, uint32_t d, uint32_t r0, uint32_t levels) {
+          const TopicHost& T = e->topics[t];
+          const StartGroup& g = L.groups[t][gi];
+          const uint32_t W = block_w(tab[t], g);
+          if (chain_size(T, d, levels, W, words_of(q, len)).S < W) return;  // column slices: the chain's own launch
+          ok = ok && r0 == 0 && g.start == 0 && d >= 1 && T.root_local && !(tab[t].flags & kTopicGroups);
+          FillSeg f{};
+          f.row0 = block_row0(tab[t], g);
+          f.topic = t;
+          f.W = W;
+          f.nbase = T.nbase;
+          f.levels = levels;
+          f.pw = fill_piece_words(W, e->env.chain_fill_piece);
+          for (uint32_t k = 0; k <= levels && k <= kChainLevels; ++k)
+            f.first[k] = T.nbase + (d + k < T.level_off.size() ? T.level_off[d + k] : T.n_nodes);
+          const uint32_t nodes = f.first[levels] - f.first[0];
+          if (nodes == 0) return;
+          f.piece0 = pieces;
+          f.blk0 = blocks;
+          pieces += fill_seg_pieces(f);
+          blocks += (nodes + kFillReachBlock - 1) / kFillReachBlock;
+          words += static_cast<uint64_t>(nodes) * W;
+          launch_nodes += nodes;
+          PP.fill.push_back(f);
+        });
+        // big enough, and rows wide enough on average: the reach pass costs per node, the fill gains per byte
+        if (ok && words * 8 >= e->env.chain_fill_bytes && words >= e->env.chain_fill_row_words * launch_nodes &&
+            PP.fill.size() > s0) {
+          PP.fill_lo[q] = s0;
+          PP.fill_hi[q] = static_cast<uint32_t>(PP.fill.size());
+          PP.fill_blocks[q] = blocks;
+          PP.fill_p0[q] = fill_pieces;
+          PP.fill_np[q] = pieces;
+          fill_pieces += pieces;
+        } else {
+          PP.fill.resize(s0);
+        }
+      }
       q += len - 1;
       continue;
     }

@@ -101,6 +101,23 @@ int upload_pair(ps_engine* e, bool* overflow) {
                               e->d_node_flags.as<uint8_t>(), e->d_chain_cnt.as<uint32_t>(), nullptr, 0,
                               e->d_chain_meta.as<uint32_t>(), true, e->stream),
             "chain entries");
+    // the launches that run as reach + fill: their segments, and the pieces cut from them on the device
+    const auto& F = e->pair.fill;
+    if (!F.empty()) {
+      uint32_t np = 0;
+      for (size_t q = 0; q < e->pair.fill_np.size(); ++q) np += e->pair.fill_np[q];
+      HIP_TRY(e->d_fill_segs.ensure(F.size() * sizeof(FillSeg)), "alloc fill segments");
+      HIP_TRY(e->d_fill_pieces.ensure(std::max<size_t>(np, 1) * sizeof(FillPiece)), "alloc fill pieces");
+      HIP_TRY(hipMemcpyAsync(e->d_fill_segs.p, F.data(), F.size() * sizeof(FillSeg), hipMemcpyHostToDevice, e->stream),
+              "upload fill segments");
+      for (size_t q = 0; q < e->pair.fill_np.size(); ++q)
+        if (e->pair.fill_hi[q] > e->pair.fill_lo[q])
+          HIP_TRY(launch_fill_pieces(e->d_fill_segs.as<FillSeg>() + e->pair.fill_lo[q],
+                                     e->pair.fill_hi[q] - e->pair.fill_lo[q],
+                                     e->d_fill_pieces.as<FillPiece>() + e->pair.fill_p0[q], e->pair.fill_np[q],
+                                     e->stream),
+                  "fill pieces");
+    }
   }
   e->pair_up = e->pair.version;
   return PS_OK;
@@ -355,6 +372,7 @@ struct WindowRun {
   bool zero_copy = false;  // N ranks: the ghost-fed nodes read their sources' regions in place
   std::vector<const uint8_t*> peer_region;
   bool gate_done = false, reach_a_done = false;
+  bool fill_pop_done = false;       // the root rows' set bits of this window are counted (slot->fill_pop)
   bool cprof = false;               // debug: chain launches profiled (PSAMD_CHAIN_PROFILE)
   bool host_stats_written = false;  // the reduce wrote the deferred slot's pinned rows
   bool reduce_side = false;         // ... on e->rstream (the window's end event goes there)
@@ -945,9 +963,40 @@ struct WindowRun {
     ++launches;
     uint64_t* const prof = cprof ? e->d_chain_prof.as<uint64_t>() : nullptr;
     pa.prof = prof ? prof + static_cast<size_t>(e->pair.lo[r]) * kChainProf : nullptr;
-    HIP_TRY(launch_pull_chain(pa, e->d_chain.as<ChainChunk>() + e->pair.lo[r], e->pair.gsplit[r] - e->pair.lo[r], r,
-                              record, ntc, false, e->opts.chain_nt, e->opts.chain_waves, s),
-            "pull chain");
+    // reach + fill for the whole rows: the plan holds segments for this launch (one
+    // rank, one start round, big enough), seen rows are lazy, nothing records hops or profiles waves,
+    // and no successor rewrites the root rows while this launch reads them (a window that may be
+    // overlapped alternates row sets)
+    const uint32_t f0 = e->pair.fill_lo[r], f1 = e->pair.fill_hi[r];
+    const bool fill = f1 > f0 && !record && !cprof && !pa.all_current && e->world == 1 && upfront && !xr &&
+                      (!pcap || alt_sets);
+    if (fill) {
+      const FillSeg* const segs = e->d_fill_segs.as<FillSeg>() + f0;
+      if (!fill_pop_done) {  // (the first fill launch of a window holds every later one's topics)
+        HIP_TRY(slot->fill_pop.ensure(std::max<size_t>(nt, 1) * 4), "alloc root row counts");
+        HIP_TRY(launch_fill_popc(segs, f1 - f0, pa.a_cur, slot->fill_pop.as<uint32_t>(), s), "root row counts");
+        fill_pop_done = true;
+      }
+      FillReachArgs fa{};
+      fa.segs = segs;
+      fa.n_segs = f1 - f0;
+      fa.node_parent = pa.node_parent;
+      fa.node_flags = pa.node_flags;
+      fa.gen = pa.gen;
+      fa.gen_cur = pa.gen_cur;
+      fa.pop = slot->fill_pop.as<uint32_t>();
+      for (uint32_t k = 0; k < kChainLevels; ++k) fa.partials_r[k] = pa.partials_r[k];
+      fa.slot_mod = e->woff_host[r + 1] - e->woff_host[r];  // (the launch's slots per round: its chunks, at most kPairSlots)
+      HIP_TRY(launch_fill_reach(fa, e->pair.fill_blocks[r], s), "fill reach");
+      HIP_TRY(launch_fill_rows(e->d_fill_pieces.as<FillPiece>() + e->pair.fill_p0[r], e->pair.fill_np[r], pa.a_cur,
+                               pa.seen, pa.gen, pa.gen_cur, e->env.chain_fill_waves, s),
+              "fill rows");
+      ++e->chain_fills;
+    } else {
+      HIP_TRY(launch_pull_chain(pa, e->d_chain.as<ChainChunk>() + e->pair.lo[r], e->pair.gsplit[r] - e->pair.lo[r], r,
+                                record, ntc, false, e->opts.chain_nt, e->opts.chain_waves, s),
+              "pull chain");
+    }
     pa.prof = prof ? prof + static_cast<size_t>(e->pair.gsplit[r]) * kChainProf : nullptr;
     HIP_TRY(launch_pull_chain(pa, e->d_chain.as<ChainChunk>() + e->pair.gsplit[r], e->pair.hi[r] - e->pair.gsplit[r],
                               r, record, ntc, true, e->opts.chain_nt, e->opts.chain_waves, s),

@@ -214,6 +214,7 @@ PROTOTYPES = [
     ("ps_spread_take", C.c_int, [_P, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p]),
     ("ps_seen_digest", C.c_int, [_P, _u64p]),
     ("ps_overlapped_windows", C.c_int, [_P, _u64p]),
+    ("ps_chain_fill_launches", C.c_int, [_P, _u64p]),
     ("ps_msg_encode", C.c_int, [C.POINTER(MessageC), C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("ps_msg_decode", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(MessageBuf), C.POINTER(C.c_size_t)]),
     ("ps_dist_unique_id", C.c_int, [C.POINTER(C.c_uint8)]),
@@ -1141,6 +1142,12 @@ class Engine:
         """Pipelined windows whose prefix ran beside the previous window."""
         d = C.c_uint64()
         self._check(self._L.ps_overlapped_windows(self._h, C.byref(d)))
+        return d.value
+
+    def chain_fill_launches(self) -> int:
+        """Chain launch slots whose whole rows were written by reach + fill."""
+        d = C.c_uint64()
+        self._check(self._L.ps_chain_fill_launches(self._h, C.byref(d)))
         return d.value
 
     # multi-GPU

@@ -12,7 +12,7 @@ LIB = os.path.join(LIBDIR, "libpsengine.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "pull.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp",
+SOURCES = ["kernels.hip", "pull.hip", "fill.hip", "flood.hip", "gbuild.hip", "drain.hip", "graph.cpp", "plan.cpp", "run.cpp", "api.cpp",
            "drain_tables.cpp", "drain_standing.cpp", "drain.cpp", "drain_shared.cpp", "drain_sink.cpp", "drain_topics.cpp",
            "drain_load.cpp", "drain_hops.cpp", "drain_downstream.cpp", "drain_cut.cpp", "drain_report.cpp",
            "drain_dist.cpp", "drain_spread.cpp", "drain_blame.cpp", "drain_blame_track.cpp", "drain_spread_track.cpp",

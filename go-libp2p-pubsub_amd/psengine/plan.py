@@ -11,7 +11,9 @@ from . import (DistConfig, EngineError, G_BUILD, G_TOPIC, PART_PEER, PlanOpts, _
                graph_get, graph_topic, load)
 
 (INFO, NODES, PARENT, GHOST_REF, TOPIC, LAYOUT, ROUND_KIND, PULL, PAIR, XCHG, SEGS, SHIP, PACK, CHAIN,
- SCHEDULE) = range(15)
+ SCHEDULE, FILL) = range(16)
+FILL_FIELDS = ("topic", "W", "row0", "nbase", "levels", "piece0", "blk0", "pw")
+FILL_PIECE_FIELDS = ("w0", "nw", "node0", "off0")
 CHAIN_FIELDS = ("node_begin", "node_end", "topic", "W", "row0", "w0", "S", "levels", "r0", "group")
 CHAIN_LEVELS = 6  # kChainLevels
 CHUNK_FIELDS = ("node_begin", "node_end", "topic", "W", "row0", "e_lo", "e_hi", "gin", "gout", "group",
@@ -192,3 +194,21 @@ class Plan:
             c["first"] = [int(x) for x in row[len(CHAIN_FIELDS):]]
             out.append(c)
         return n, out
+
+    def fill(self, q: int):
+        """(reach blocks, [segment dicts], [piece dicts]) of the chain launch starting at round q when it
+        runs as reach + fill (PS_PLAN_FILL); (0, [], []): it has no fill segments."""
+        v = self.get(FILL, q).astype(np.int64)
+        ns = int(v[0])
+        if ns == 0:
+            return 0, [], []
+        n_pieces, blocks = int(v[1]), int(v[2])
+        per = len(FILL_FIELDS) + CHAIN_LEVELS + 1
+        segs = []
+        for row in v[3:3 + ns * per].reshape(ns, per):
+            f = dict(zip(FILL_FIELDS, (int(x) for x in row[:len(FILL_FIELDS)])))
+            f["first"] = [int(x) for x in row[len(FILL_FIELDS):]]
+            segs.append(f)
+        body = v[3 + ns * per:].reshape(n_pieces, len(FILL_PIECE_FIELDS))
+        pieces = [dict(zip(FILL_PIECE_FIELDS, (int(x) for x in row))) for row in body]
+        return blocks, segs, pieces

@@ -134,6 +134,9 @@ typedef struct ps_stats {
 #define PS_K_PAIR 3u    /* k_pull_pair: this round and the next in one launch   */
 #define PS_K_PAIR2 4u   /* k_pull_pair: the second round of the launch above    */
 #define PS_K_EXPAND 5u  /* k_expand (compaction mode)                          */
+/* PS_K_CHAIN names the plan's launch slot: k_pull_chain, or -- a bulk launch
+ * of a single-start window on one rank -- k_fill_reach + k_fill_rows for its
+ * whole rows (ps_chain_fill_launches counts those) */
 #define PS_K_CHAIN 6u   /* k_pull_chain: this round and the next 2-3 in one launch */
 #define PS_K_CHAIN2 7u  /* k_pull_chain: a later round of the launch above      */
 
@@ -1192,6 +1195,11 @@ int ps_seen_digest(ps_engine* e, uint64_t* digest_out);
  * previous window's last launches (no reference
  * counterpart: a scheduling diagnostic). */
 int ps_overlapped_windows(ps_engine* e, uint64_t* count_out);
+
+/* Chain launch slots (PS_K_CHAIN rounds) whose whole rows were written as a
+ * reach pass plus a fill from the topic roots' rows instead of by the chain
+ * kernel (a scheduling diagnostic, as above). */
+int ps_chain_fill_launches(ps_engine* e, uint64_t* count_out);
 
 /* ---- multi-GPU: one engine (process) per GPU --------------------------------
  * Every rank creates the same topics and memberships and publishes the same

@@ -61,6 +61,12 @@ int ps_plan_window(ps_engine* e, const uint32_t* topic_of_msg, const uint32_t* s
                                  desc[nd]     (first slot, end slot, stride) per reduce row: rounds
                                               0..planned+1, then one row per reach row
                                  seed_off[ns] per start round 0..latest+1: seeds before that round */
+#define PS_PLAN_FILL 15       /* index = round: the chain launch starting there as reach + fill (DESIGN.md
+                                 5.1d).  0 alone: the launch has no fill segments.  Else segments ns, pieces
+                                 np, reach blocks; then per segment 15 values: topic, W, row0, nbase, levels,
+                                 first piece, first reach block, words per piece, first[0..6]; then per
+                                 piece 4 values, in launch order: first word, words, the node holding the
+                                 first word, that word's offset in the node's row */
 int ps_plan_get(ps_engine* e, uint32_t what, uint32_t index, uint64_t* out, size_t cap, size_t* n_out);
 
 /* ps_graph_get(what, index): the node space itself and which

@@ -8,7 +8,7 @@ N=$1; shift
 P=go-libp2p-pubsub_amd
 O=$P/lib/obj_$N
 mkdir -p $O
-SRC="kernels.hip pull.hip flood.hip gbuild.hip drain.hip graph.cpp plan.cpp run.cpp api.cpp drain_tables.cpp drain_standing.cpp drain.cpp drain_shared.cpp drain_sink.cpp drain_topics.cpp drain_load.cpp drain_hops.cpp drain_downstream.cpp drain_cut.cpp drain_report.cpp drain_dist.cpp drain_spread.cpp drain_blame.cpp drain_blame_track.cpp drain_spread_track.cpp tree.cpp dist.cpp codec.cpp pubsub.cpp"
+SRC="kernels.hip pull.hip fill.hip flood.hip gbuild.hip drain.hip graph.cpp plan.cpp run.cpp api.cpp drain_tables.cpp drain_standing.cpp drain.cpp drain_shared.cpp drain_sink.cpp drain_topics.cpp drain_load.cpp drain_hops.cpp drain_downstream.cpp drain_cut.cpp drain_report.cpp drain_dist.cpp drain_spread.cpp drain_blame.cpp drain_blame_track.cpp drain_spread_track.cpp tree.cpp dist.cpp codec.cpp pubsub.cpp"
 for f in $SRC; do
   /opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -Wall -Iinclude -I$P/csrc "$@" -c $P/csrc/$f -o $O/$f.o &
 done
